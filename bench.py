@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- query-positions/sec of the windowed k-mer conservation sweep on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1 either way: `python bench.py --gpus N ...` starts its own ranks -- one child
      `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, whose one JSON line and exit
      code it relays -- or start it under torch.distributed.run yourself; see launch_ranks())
@@ -85,7 +85,14 @@ def parse():
                          "headline kernel in the trace is then the headline workload)")
     ap.add_argument("--cpu-sample", type=int, default=100_000_000,
                     help="positions of the window the 1-core CPU baseline is timed on (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the last one as DIR/<name>.npy (float32 / float64; "
+                         "at most 64 MB in all, a fixed sample of the positions when the result is larger): two builds "
+                         "run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def visible_gpus():
@@ -217,6 +224,51 @@ def gathered_sample_vs_oracle(R, G, steps):
     return res
 
 
+DUMP_BYTES = 64_000_000           # --dump-outputs: everything it writes together, .npy headers included
+
+
+def timed_result(R, G, steps):
+    """The arrays the last timed step handed its caller, still on the device, in position order: N = 1 the result buffer;
+    N > 1 (rank 0) the gathered result -- rank 0's own share of its window, then every peer's slice."""
+    last = (steps - 1) % R.nbuf
+    if not R.multi:
+        return [R.outs[last]]
+    return [R.outs[last][:R.qe_mine - R.qs]] + [G.decoded[last][g] if G.coded else G.roots[last][g].view(R.dtype).reshape(R.shape)
+                                               for g in range(1, R.world)]
+
+
+def dump_outputs(R, pieces, out_dir):
+    """--dump-outputs: `pieces` (timed_result) as one array per query kind -- conservation counts as float32, membership
+    words (uint32, one row of W words per position) as float64, both exact.  Within DUMP_BYTES the whole result; past
+    that one position per equal stratum of the result, drawn with a fixed seed: the same arguments give the same
+    positions in every build.  Returns the entry for the JSON line."""
+    import numpy as np
+    import torch
+    name, ftype = ("membership", np.float64) if R.membership else ("conservation", np.float32)
+    per_pos = int(np.prod(pieces[0].shape[1:], dtype=np.int64)) * np.dtype(ftype).itemsize
+    total = sum(int(p.shape[0]) for p in pieces)
+    n = min(total, (DUMP_BYTES - 4096) // per_pos)
+    if n == total:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        lo = np.arange(n, dtype=np.int64) * total // n
+        hi = np.arange(1, n + 1, dtype=np.int64) * total // n
+        idx = lo + (np.random.default_rng(0).random(n) * (hi - lo)).astype(np.int64)
+    parts, off = [], 0
+    for p in pieces:
+        m = int(p.shape[0])
+        a, b = np.searchsorted(idx, [off, off + m])
+        sel = torch.from_numpy(idx[a:b] - off).to(p.device)
+        h = p.index_select(0, sel).cpu().numpy()
+        parts.append(h.view(np.uint32) if R.membership else h.view(np.uint8 if R.narrow else np.uint16))
+        off += m
+    out = np.concatenate(parts).astype(ftype)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), out)
+    return {"dir": out_dir, "files": {name + ".npy": list(out.shape)}, "dtype": np.dtype(ftype).name, "positions": total,
+            "sample": None if n == total else f"{n} positions, one per equal stratum of the result, drawn with seed 0"}
+
+
 def main():
     args = parse()
     rc = launch_ranks(args, sys.argv[1:])
@@ -293,6 +345,9 @@ def main():
     # ---- end of the timed region ------------------------------------------------------------------------------
     ix.check(stream.cuda_stream)
     out = R.outs[(args.steps - 1) % R.nbuf]
+    dumped = None
+    if args.dump_outputs and rank == 0:     # (before per_step below launches into the same buffer again)
+        dumped = dump_outputs(R, timed_result(R, G, args.steps), args.dump_outputs)
     # per-step spread (and, N > 1, the sweep's own time): K more sweeps with an event pair each
     per = R.per_step(lambda: R.launch(R.outs[args.steps % R.nbuf]), args.steps)
     kern_ms = float(np.mean(per)) if multi else ev[0].elapsed_time(ev[1]) / args.steps
@@ -319,6 +374,8 @@ def main():
             "roofline": bench_legs.roofline_entry(R, kern_ms, per, b_alg),
         }
         bench_legs.attach_traffic(R, res, b_alg)
+        if dumped:
+            res["dump_outputs"] = dumped
         if multi:
             # what the same run delivers when the result slices stay on their GPUs (no root):
             # every rank's sweep time from its own HIP events, slowest rank counts

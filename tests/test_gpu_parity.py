@@ -1345,18 +1345,12 @@ def test_cli_sharded_path_single_rank(memo, tmp_path):
         argv = [sys.executable, exe, "query", "-b", os.path.join(G.GOLD, c["index"]), "-n", str(c["n"]), "-k", str(c["k"]),
                 "-r", c["region"], "-o", str(out)] + (["-m"] if c["membership"] else [])
         import socket
-        for attempt in range(2):
-            with socket.socket() as sk:
-                sk.bind(("127.0.0.1", 0))
-                port = sk.getsockname()[1]
-            r = subprocess.run(argv, capture_output=True,
-                               env=dict(os.environ, MEMO_FORCE_SHARDED="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)))
-            err = r.stderr.decode(errors="replace")
-            # (one run of the round-6 tier failed here and passed on the next two boxes: a rendezvous that does not come up --
-            # the port taken between our bind and the child's, RCCL's bootstrap -- is tried once more; anything else fails at once)
-            if r.returncode == 0 or not any(w in err for w in ("NCCL", "RCCL", "Address already in use", "Connection", "rendezvous", "store")):
-                break
-        assert r.returncode == 0, (name, err[-3000:])
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        r = subprocess.run(argv, capture_output=True,
+                           env=dict(os.environ, MEMO_FORCE_SHARDED="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)))
+        assert r.returncode == 0, (name, r.stderr.decode(errors="replace")[-3000:])
         assert G.sha(out.read_bytes()) == c["sha256"]
 
 
@@ -1747,16 +1741,17 @@ def test_queries_of_one_index_on_several_streams(memo, oracle):
                                                      (2, "c4", []), (2, "c3", ["--root-weight", "0.3"]),
                                                      (2, "c5", []), (2, "c5", ["--k", "21"]), (2, "c5", ["--plain-gather"]),
                                                      (2, "c5", ["--k", "101", "--coding", "runs"]),
-                                                     (8, "c5", ["--k", "21"]), (8, "c3", [])])
-def test_bench_two_ranks_on_one_gpu(n_ranks, workload, extra):
+                                                     (4, "c5", ["--k", "21"]), (4, "c3", [])])
+def test_bench_two_ranks_on_one_gpu(n_ranks, workload, extra, tmp_path):
     """`python bench.py --gpus N` as the driver spells it, with N > 1 RANKS for the first time on this pool's one-GPU boxes:
     RCCL refuses two ranks on a device, so the ranks share GPU 0 (MEMO_BENCH_ONE_DEVICE=1) and gloo carries the bytes through
     host memory (MEMO_BENCH_BACKEND=gloo; bench.py marks the line "test_transport").  Everything else is the N > 1 path as
     an 8-GPU node runs it: self-launch through torch.distributed.run, link probe, coding choice from the ranks' statistics,
     root weight, double-buffered send / receive per step, decode on rank 0, the gathered slice of the last rank against the
-    oracle, every slice complete, one JSON line.  Round 5: the same with EIGHT ranks -- what the first contact with an 8-GPU node runs:
-    seven receives and ONE decode launch for seven slices per step (memo_transport_runs_unpack_many_dev), a root weight chosen for
-    seven peers; eight config-5 shards on the dense rows share the one GPU (they build their indexes one after the other)."""
+    oracle, every slice complete, one JSON line.  The same with FOUR ranks -- the most that share the GPU with this test process
+    while at most six processes hold it open -- is what an 8-GPU node runs with more peers: three receives and ONE decode launch
+    for three slices per step (memo_transport_runs_unpack_many_dev), a root weight chosen for three peers; four config-5 shards on
+    the dense rows share the one GPU (they build their indexes one after the other)."""
     import json
     import subprocess
     import sys
@@ -1766,7 +1761,8 @@ def test_bench_two_ranks_on_one_gpu(n_ranks, workload, extra):
         env.pop(v, None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n_ranks), "--steps", steps, "--warmup", warm,
-                        "--workload", workload] + extra, capture_output=True, text=True, env=env, timeout=1800)
+                        "--workload", workload, "--dump-outputs", str(tmp_path)] + extra, capture_output=True, text=True, env=env,
+                       timeout=1800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -1777,6 +1773,12 @@ def test_bench_two_ranks_on_one_gpu(n_ranks, workload, extra):
     assert j["gather_parity_sample"].get("every_slice_complete", True) is True
     assert j["link_GBs_measured"] and j["link_probe"]["bytes_per_rank"] > 0
     assert j["value"] > 0 and j["config"]["gather_payload"]
+    # --dump-outputs: rank 0 wrote the gathered result of the last timed step -- every position a step computes, or a sample
+    (name, shape), = j["dump_outputs"]["files"].items()
+    dumped = np.load(tmp_path / name)
+    assert list(dumped.shape) == shape and os.path.getsize(tmp_path / name) <= 64_000_000
+    assert j["dump_outputs"]["positions"] == round(j["value"] * j["ms_per_step"] * 1e-3)
+    assert (j["dump_outputs"]["sample"] is None) == (len(dumped) == j["dump_outputs"]["positions"])
     if workload == "c5":      # BASELINE's multi-GPU config: uint16 slices -- coded by the runs coding unless plain was asked for
         assert j["config"]["result_bytes_per_position"] == 2
         if "--plain-gather" in extra:
@@ -1800,11 +1802,11 @@ def test_bench_two_ranks_on_one_gpu(n_ranks, workload, extra):
         assert c5["expected_from_model"]["coding"] == c5["coding"]
     else:
         assert "config5" not in j
-    if n_ranks == 8:          # all seven peers' slices were received and decoded, and the choice was made for seven peers
+    if n_ranks == 4:          # all three peers' slices were received and decoded, and the choice was made for three peers
         choice = j["config"]["gather_coding_choice"]
         assert choice["candidates"]["runs"]["decode_ms_all_slices_one_launch"] is not None
         assert choice["picked"] == "runs" or workload == "c3", choice["picked"]
-        assert 0 < choice["root_weight"] <= 1 and len({r["rank"] for r in j["ranks_seen"]["ranks"]}) == 8
+        assert 0 < choice["root_weight"] <= 1 and len({r["rank"] for r in j["ranks_seen"]["ranks"]}) == 4
 
 
 def test_no_room_on_the_device_for_views_and_tile_tables(memo, oracle, ab):

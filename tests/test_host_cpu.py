@@ -546,6 +546,34 @@ def test_bench_parent_does_not_touch_the_gpu_stack(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: the whole result while it fits the budget, else one position per equal stratum with a fixed seed
+    (the same positions however the result is split into pieces); every value exact (uint8 / uint16 counts as float32,
+    uint32 membership words as float64); the file within the budget."""
+    import types
+    import torch
+    import bench
+    rng = np.random.default_rng(5)
+    cons = rng.integers(0, 256, 100_000).astype(np.uint8)
+    e = bench.dump_outputs(types.SimpleNamespace(membership=False, narrow=True), [torch.from_numpy(cons)], str(tmp_path / "a"))
+    got = np.load(tmp_path / "a" / "conservation.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, cons) and e["sample"] is None and e["positions"] == 100_000
+    memb = rng.integers(0, 2 ** 32, (5000, 3), dtype=np.uint64).astype(np.uint32)
+    bench.dump_outputs(types.SimpleNamespace(membership=True, narrow=False), [torch.from_numpy(memb.view(np.int32))], str(tmp_path / "m"))
+    got = np.load(tmp_path / "m" / "membership.npy")
+    assert got.dtype == np.float64 and got.shape == (5000, 3) and np.array_equal(got.astype(np.uint32), memb)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 4 * 1000)
+    wide = rng.integers(0, 65536, 100_000).astype(np.uint16)
+    R = types.SimpleNamespace(membership=False, narrow=False)
+    e = bench.dump_outputs(R, [torch.from_numpy(wide[:30_001].view(np.int16)), torch.from_numpy(wide[30_001:].view(np.int16))],
+                           str(tmp_path / "b"))
+    bench.dump_outputs(R, [torch.from_numpy(wide.view(np.int16))], str(tmp_path / "c"))
+    b, c = (np.load(tmp_path / d / "conservation.npy") for d in "bc")
+    assert len(b) == 1000 and e["sample"] and e["positions"] == 100_000 and np.array_equal(b, c)
+    assert all(v in wide[i * 100:(i + 1) * 100] for i, v in enumerate(b.astype(np.uint16)))
+    assert os.path.getsize(tmp_path / "b" / "conservation.npy") <= bench.DUMP_BYTES
+
+
 def _device_disassembly(obj, tmp_path):
     """gfx950 disassembly of the device code inside a hipcc object file"""
     import shutil

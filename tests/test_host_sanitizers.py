@@ -3,6 +3,8 @@ available on this pool).  Covers the C oracle and the product's host C++ (text e
 parser), each built on its own with gcc -fsanitize and driven from a child process that preloads
 libasan."""
 import os
+import platform
+import shutil
 import subprocess
 import sys
 import textwrap
@@ -95,7 +97,14 @@ def test_host_packer_under_sanitizers(tmp_path, sanitizer):
                            os.path.join(ROOT, "tests", "host_stub.cpp"),
                            os.path.join(ROOT, "memo_amd", "csrc", "memo_hostcore.cpp"), "-o", exe])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", TSAN_OPTIONS="halt_on_error=1", MEMO_HOST_THREADS="6")
+    cmd = [exe]
+    # ThreadSanitizer wants the program and its libraries inside its fixed memory map; on kernels that randomise mmap with
+    # more bits they can land outside it ("FATAL: ThreadSanitizer: unexpected memory mapping").  So the TSan child runs
+    # with address randomisation off for itself alone (setarch -R), where that personality may be set.
+    no_aslr = ["setarch", platform.machine(), "-R"]
+    if sanitizer == "thread" and shutil.which("setarch") and subprocess.run(no_aslr + ["true"], capture_output=True).returncode == 0:
+        cmd = no_aslr + cmd
     for simd in ("2", "1", "0"):     # the row pass: the hand-written AVX-512 packers, the compiler's AVX2 instance (where the CPU has them), the plain one
-        r = subprocess.run([exe], capture_output=True, text=True, env=dict(env, MEMO_HOST_SIMD=simd), timeout=600)
+        r = subprocess.run(cmd, capture_output=True, text=True, env=dict(env, MEMO_HOST_SIMD=simd), timeout=600)
         assert r.returncode == 0 and "hostcore ok" in r.stdout, (simd, (r.stdout + r.stderr)[-3000:])
         assert "WARNING: ThreadSanitizer" not in r.stderr and "runtime error" not in r.stderr, (simd, r.stderr[-3000:])
