@@ -27,6 +27,9 @@ int memo_dap_push(memo_dap_t *h, const int32_t *lcp, int64_t positions, uint64_t
 int memo_dap_fetch(memo_dap_t *h, int32_t *rec, int64_t *start, int64_t *end, int32_t *annot);
 int memo_dap_finish(memo_dap_t *h, int32_t *rec, int64_t *start, int64_t *end, int32_t *annot,
                     uint64_t *out_rows);
+/* the same, with the DAP already on the handle's device (dev_lcp: int32 [positions][columns] in HBM, e.g. the
+ * matrix of a memo_ms_t -- memo_ms_push_dap is that call) */
+int memo_dap_push_dev(memo_dap_t *h, const int32_t *dev_lcp, int64_t positions, uint64_t *out_rows);
 void memo_dap_destroy(memo_dap_t *h);
 /* host-side parser for the DAP text (whitespace-separated decimal integers), multi-threaded.
  * Returns how many integers the text holds (they are written only when cap is enough), -1 on a
@@ -36,6 +39,30 @@ int64_t memo_parse_ints(const char *text, size_t len, int64_t *out, size_t cap);
  * NUL-terminated strings back to back.  Returns the bytes needed; writes only if they fit. */
 size_t memo_emit_bed(const int32_t *rec, const int64_t *start, const int64_t *end, const int32_t *annot,
                      uint64_t rows, const char *names, int32_t nrec, char *buf, size_t cap);
+
+/* ---- matching statistics: the MONI stage of `memo index` (src/index.sh:57-80) --------------------------
+ * MS_g[p] = the longest l such that pivot record R[p, p + l) is a substring of genome g's text (its records
+ * and their reverse complements, separated by NUL bytes, which no pivot byte can equal); a match never runs
+ * past the end of its pivot record.  Bytes compare exactly.
+ * memo_ms_create: the pivot (rec_begin[nrec] bytes, no NUL; records 1 .. 2^30-1 long) and an int32 DAP matrix
+ *   [positions][columns] of zeros, resident on `device` (refused when it does not fit in its free memory).
+ *   chunk: pivot positions per walk thread (<= 0: the default).
+ * memo_ms_add_genome: builds the suffix array, LCP and min hierarchy of `text` (n < 2^31 - 1 bytes) on the
+ *   device and writes the genome's MS into DAP column `column`.  One genome at a time; buffers are reused.
+ * memo_ms_fetch: host copy of DAP rows [first, first + positions).
+ * memo_ms_push_dap: memo_dap_push_dev of those rows (same device, same column count).
+ * memo_ms_timings: device milliseconds so far of {suffix arrays, LCP + hierarchy, walks}.
+ * memo_suffix_array: the suffix array of text[0, n) on `device` into sa_out (n int32); a suffix that is a
+ *   prefix of another sorts first. */
+typedef struct memo_ms memo_ms_t;
+int memo_ms_create(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec, int32_t columns, int64_t chunk,
+                   int32_t device, memo_ms_t **out);
+int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t column);
+int memo_ms_fetch(memo_ms_t *h, int64_t first, int64_t positions, int32_t *out);
+int memo_ms_push_dap(memo_ms_t *h, memo_dap_t *dap, int64_t first, int64_t positions, uint64_t *out_rows);
+int memo_ms_timings(memo_ms_t *h, float *out3);
+void memo_ms_destroy(memo_ms_t *h);
+int memo_suffix_array(const uint8_t *text, int64_t n, int32_t *sa_out, int32_t device);
 
 
 #ifdef __cplusplus

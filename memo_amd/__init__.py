@@ -10,6 +10,8 @@ Layout (only what the path needs):
   _fastquery.py    `memo query` answered from that cache with nothing but ctypes (no NumPy import)
   synth.py         the synthetic pangenome workloads of BASELINE.json
   shard.py         window sharding across ranks + gather (torch.distributed)
+  dap_to_bed.py    DAP -> index rows on the GPU -> BED text or Parquet
+  build_index.py   `memo index`: FASTA genomes -> matching statistics on the GPU -> Parquet index
 
 Attributes are loaded on first use (PEP 562), so that `import memo_amd._fastquery` -- the CLI's cache-hit
 path -- does not pay for NumPy.
@@ -30,7 +32,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "dap_to_bed", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

@@ -108,7 +108,15 @@ SYMBOLS = {
     "memo_dap_push": (C.c_int, [_P, _P, _I64, C.POINTER(_U64)]),
     "memo_dap_fetch": (C.c_int, [_P, _P, _P, _P, _P]),
     "memo_dap_finish": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(_U64)]),
+    "memo_dap_push_dev": (C.c_int, [_P, _P, _I64, C.POINTER(_U64)]),
     "memo_dap_destroy": (None, [_P]),
+    "memo_ms_create": (C.c_int, [_P, _P, _I32, _I32, _I64, _I32, C.POINTER(_P)]),
+    "memo_ms_add_genome": (C.c_int, [_P, _P, _I64, _I32]),
+    "memo_ms_fetch": (C.c_int, [_P, _I64, _I64, _P]),
+    "memo_ms_push_dap": (C.c_int, [_P, _P, _I64, _I64, C.POINTER(_U64)]),
+    "memo_ms_timings": (C.c_int, [_P, _P]),
+    "memo_ms_destroy": (None, [_P]),
+    "memo_suffix_array": (C.c_int, [_P, _I64, _P, _I32]),
     "memo_parse_ints": (C.c_int64, [_P, _SZ, _P, _SZ]),
     "memo_emit_bed": (_SZ, [_P, _P, _P, _P, _U64, _P, _I32, _P, _SZ]),
     "memo_transport_runs_bytes": (_SZ, [_I64, C.c_uint32]),

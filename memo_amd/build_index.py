@@ -1,0 +1,250 @@
+#!/usr/bin/env python3
+"""`memo index`: FASTA genomes -> matching statistics on the GPU -> MEMO index rows -> Parquet, in one command.
+
+    memo index -g genome_list.txt -o work -p test [-m]
+
+Same command line, usage text and progress lines as the reference's src/index.sh, which builds the matching
+statistics (MS) with MONI, genome by genome on the host.  Here every stage runs on the device:
+
+  1. FASTA -> bytes (host, this module): a record's name is the first word after '>'; its sequence lines are
+     joined with all whitespace removed and upper-cased.  The first genome of the list is the pivot; its record
+     names and offsets take the place of the .fai that `samtools faidx` writes (index.sh:55-56).
+  2. genome g's text (index.sh:63-65): S_1 $ S_2 $ ... S_s $ rc(S_1) $ ... rc(S_s) $, with $ a NUL byte (no
+     pivot byte can be NUL: such input is refused) and rc the reverse complement of `samtools faidx -i`
+     (A-T, C-G, R-Y, K-M, B-V, D-H swap, every other byte stays).
+  3. MS of every pivot position against every genome text (memo_ms_*, memo_amd/csrc/memo_ms.hip: suffix array,
+     LCP, MS walk), straight into the DAP matrix [positions][genomes - 1] in HBM (index.sh:83).
+  4. DAP -> index rows on the device (memo_dap_push_dev; --mem --overlap, plus --order for the conservation
+     index: index.sh:86-103) -> DIR/PREFIX.parquet (f0 utf8, f1 f2 f3 int64, ZSTD: parquet_compress_bed.py).
+
+Not written, by design: MONI's *.w_rc* files, dap.txt, PREFIX.bed and the pivot's .fai.  Nothing downstream
+reads them.
+
+Refused with a message (never a wrong result): gzip input, a NUL byte, a pivot record of length 0, a pivot
+record of 2^30 positions or more, a genome text of 2^31 - 1 bytes or more, more than 4096 genomes besides the
+pivot, a DAP matrix that does not fit in the device's free memory.
+"""
+import ctypes as C
+import getopt
+import os
+import sys
+import time
+
+import numpy as np
+
+from ._lib import MemoError, check, lib
+
+USAGE = """
+omem index - index overlap order MEMs from a document array profile
+Usage: omem index [options]
+
+Basic options:
+  -g [FILE]              document list
+  -o [FILE]              output directory ['.']
+  -p [FILE]              output file prefix
+  -m                     make membership index
+
+"""
+
+SEPARATOR = b"\0"
+_WHITESPACE = b" \t\r\n\v\f"
+# samtools faidx -i: the IUPAC complement; every other byte (N, S, W, ...) is its own complement
+_COMPLEMENT = bytes.maketrans(b"ACGTRYKMBVDH", b"TGCAYRMKVBHD")
+MAX_RECORD = (1 << 30) - 1        # memo_dap: positions of one pivot record
+MAX_TEXT = (1 << 31) - 2          # memo_ms: int32 suffix array of one genome text
+MAX_COLUMNS = 4096                # memo_dap: genomes besides the pivot
+
+
+class FastaError(ValueError):
+    """input that `memo index` refuses rather than index wrongly"""
+
+
+def parse_fasta(data, path="<fasta>"):
+    """[(name, sequence bytes)] of a FASTA file's bytes: name = first whitespace-delimited word after '>',
+    sequence = the record's lines joined, all whitespace removed, upper-cased"""
+    if data[:2] == b"\x1f\x8b":
+        raise FastaError(f"{path}: gzip-compressed FASTA is not supported; decompress it first")
+    if SEPARATOR in data:
+        raise FastaError(f"{path}: holds a NUL byte")
+    parts = (b"\n" + data).split(b"\n>")
+    if parts[0].strip():
+        raise FastaError(f"{path}: not FASTA (text before the first '>' header)")
+    records = []
+    for part in parts[1:]:
+        header, _, body = part.partition(b"\n")
+        words = header.split()
+        name = words[0].decode("utf-8", "replace") if words else ""
+        records.append((name, body.translate(None, _WHITESPACE).upper()))
+    return records
+
+
+def read_fasta(path):
+    with open(path, "rb") as fh:
+        return parse_fasta(fh.read(), path)
+
+
+def revcomp(seq):
+    """reverse complement as `samtools faidx -i` writes it"""
+    return seq.translate(_COMPLEMENT)[::-1]
+
+
+def genome_text(seqs):
+    """S_1 $ ... S_s $ rc(S_1) $ ... rc(S_s) $ (index.sh:63-65), $ = NUL"""
+    if not seqs:
+        return b""
+    return SEPARATOR.join(list(seqs) + [revcomp(s) for s in seqs]) + SEPARATOR
+
+
+def pivot_layout(records, path="<pivot>"):
+    """(names, concatenated bytes, int64 record offsets [nrec + 1]) -- what the .fai gave dap_to_bed.py"""
+    if not records:
+        raise FastaError(f"{path}: the pivot has no records")
+    for name, seq in records:
+        if not seq:
+            raise FastaError(f"{path}: pivot record '{name}' has length 0")
+        if len(seq) > MAX_RECORD:
+            raise FastaError(f"{path}: pivot record '{name}' has {len(seq)} positions (the limit is {MAX_RECORD})")
+    rec_begin = np.zeros(len(records) + 1, np.int64)
+    rec_begin[1:] = np.cumsum([len(s) for _, s in records])
+    return [n for n, _ in records], b"".join(s for _, s in records), rec_begin
+
+
+class MatchingStatistics:
+    """The DAP matrix int32 [positions][columns] of one pivot, resident on `device` (memo_ms_*)."""
+
+    def __init__(self, pivot, rec_begin, columns, device=0, chunk=0):
+        self._h = C.c_void_p()
+        self.rec_begin = np.ascontiguousarray(rec_begin, np.int64)
+        self.positions = int(self.rec_begin[-1])
+        self.columns = columns
+        self._pivot = bytes(pivot)
+        if len(self._pivot) != self.positions:
+            raise ValueError(f"pivot has {len(self._pivot)} bytes, its records {self.positions}")
+        check(lib().memo_ms_create(self._pivot, self.rec_begin.ctypes.data, len(self.rec_begin) - 1, columns,
+                                   int(chunk), device, C.byref(self._h)))
+
+    def add(self, text, column):
+        """matching statistics of the pivot against one genome text, into DAP column `column`"""
+        if len(text) > MAX_TEXT:
+            raise MemoError(-1, f"genome text of {len(text)} bytes: the limit is {MAX_TEXT}")
+        check(lib().memo_ms_add_genome(self._h, bytes(text), len(text), column))
+
+    def fetch(self, first=0, positions=None):
+        positions = self.positions - first if positions is None else positions
+        out = np.empty((positions, self.columns), np.int32)
+        check(lib().memo_ms_fetch(self._h, first, positions, out.ctypes.data))
+        return out
+
+    def timings(self):
+        """device milliseconds so far: suffix arrays, LCP + hierarchy, MS walks"""
+        t = (C.c_float * 3)()
+        check(lib().memo_ms_timings(self._h, t))
+        return {"sa_ms": t[0], "lcp_ms": t[1], "walk_ms": t[2]}
+
+    def close(self):
+        if self._h:
+            lib().memo_ms_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def matching_statistics(pivot, genomes, device=0, chunk=0):
+    """MS matrix int32 [pivot positions][len(genomes)] of pivot records (list of bytes) against genomes (each a
+    list of record bytes), by the rule in the module docstring"""
+    _, seq, rec_begin = pivot_layout([(str(i), s) for i, s in enumerate(pivot)])
+    with MatchingStatistics(seq, rec_begin, len(genomes), device, chunk) as ms:
+        for c, recs in enumerate(genomes):
+            ms.add(genome_text(recs), c)
+        return ms.fetch()
+
+
+def read_genome_list(path):
+    if not path:
+        raise FastaError("no genome list: give one with -g")
+    try:
+        with open(path) as fh:
+            paths = [ln.strip() for ln in fh if ln.strip()]
+    except OSError as exc:
+        raise FastaError(f"cannot read the genome list {path}: {exc.strerror}") from None
+    if len(paths) < 2:
+        raise FastaError(f"{path}: needs the pivot and at least one more genome")
+    if len(paths) - 1 > MAX_COLUMNS:
+        raise FastaError(f"{path}: {len(paths) - 1} genomes besides the pivot (the limit is {MAX_COLUMNS})")
+    return paths
+
+
+def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log=print, keep_ms=False):
+    """index.sh end to end; returns per-stage seconds (and the MS matrix when keep_ms)"""
+    from .dap_to_bed import DapConverter, write_parquet
+    t0 = time.perf_counter()
+    paths = read_genome_list(genome_list)
+    names, pivot, rec_begin = pivot_layout(read_fasta(paths[0]), paths[0])
+    stats = {"positions": int(rec_begin[-1]), "genomes": len(paths), "read_s": 0.0}
+    stats["read_s"] += time.perf_counter() - t0
+    out_path = os.path.join(out_dir, prefix + ".parquet")
+    os.makedirs(out_dir or ".", exist_ok=True)
+    with MatchingStatistics(pivot, rec_begin, len(paths) - 1, device, chunk) as ms:
+        t1 = time.perf_counter()
+        for c, path in enumerate(paths[1:]):
+            tr = time.perf_counter()
+            text = genome_text([s for _, s in read_fasta(path)])
+            stats["read_s"] += time.perf_counter() - tr
+            log(f"Finding MS between pivot and {os.path.basename(path)}")
+            ms.add(text, c)
+        stats["ms_s"] = time.perf_counter() - t1
+        stats.update(ms.timings())
+        if keep_ms:
+            stats["ms"] = ms.fetch()
+        log("Making membership index" if membership else "Making conservation index")
+        t2 = time.perf_counter()
+        batches = []
+        npos, C_ = ms.positions, ms.columns
+        block = max(1024, (64 << 20) // C_)
+        with DapConverter(C_, rec_begin, not membership, True, device) as conv:
+            for first in range(0, npos, block):
+                batches.append(conv.push_ms(ms, first, min(block, npos - first)))
+            batches.append(conv.finish())
+        stats["dap_to_rows_s"] = time.perf_counter() - t2
+    log("Compressing index.")
+    t3 = time.perf_counter()
+    rows = write_parquet(out_path, ((names, b) for b in batches))
+    stats["parquet_s"] = time.perf_counter() - t3
+    stats["rows"] = rows
+    stats["total_s"] = time.perf_counter() - t0
+    log("DONE")
+    return stats
+
+
+def main(argv):
+    """bin/memo index [options]; exit statuses and usage handling of index.sh"""
+    if not argv or argv[0] == "-h":
+        sys.stdout.write(USAGE)
+        sys.exit(0)
+    try:
+        opts, _ = getopt.getopt(argv, "g:o:p:m")
+    except getopt.GetoptError as exc:               # bash getopts: message on stderr, then usage, exit 0
+        what = "option requires an argument" if "requires argument" in exc.msg else "illegal option"
+        sys.stderr.write(f"{sys.argv[0]}: {what} -- {exc.opt}\n")
+        sys.stdout.write(USAGE)
+        sys.exit(0)
+    val = {"-o": "."}                                # index.sh:6
+    for o, a in opts:
+        val[o] = a
+    try:
+        if not val.get("-p"):
+            raise FastaError("no output prefix: give one with -p")
+        read_genome_list(val.get("-g", ""))          # refuse before the device is touched
+        build_index(val["-g"], val["-o"], val["-p"], "-m" in val, int(os.environ.get("MEMO_DEVICE", "0")),
+                    log=lambda s: print(s, flush=True))
+    except (FastaError, MemoError) as exc:
+        sys.stderr.write(f"memo index: {exc}\n")
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

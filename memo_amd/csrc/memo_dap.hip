@@ -226,6 +226,76 @@ struct memo_dap {
     uint64_t n_out = 0;
 };
 
+void memo::dap_shape(const memo_dap_t *h, int *device, int *columns) {
+    *device = h->device;
+    *columns = h->C;
+}
+
+// the rows come from the host (memo_dap_push) or from a device matrix on the handle's device (memo_dap_push_dev)
+static int dap_push(memo_dap_t *h, const int32_t *lcp, int64_t positions, uint64_t *out_rows, hipMemcpyKind kind) {
+    if (!h || !out_rows) return fail(MEMO_EINVAL, "NULL argument");
+    *out_rows = 0;
+    h->n_out = 0;
+    if (positions <= 0) return MEMO_OK;
+    if (!lcp) return fail(MEMO_EINVAL, "lcp is NULL");
+    if (h->g + positions > h->total)
+        return fail(MEMO_EINVAL, "DAP has more rows than the .fai has positions (%lld > %lld)",
+                    (long long)(h->g + positions), (long long)h->total);
+    DeviceGuard guard(h->device);
+    hipStream_t st = nullptr;
+    const int C = h->C;
+    const int64_t npos = positions, nseg = (npos + kSeg - 1) / kSeg, nslots = 2 * npos;
+    int rc;
+    if ((rc = h->M.ensure((size_t)npos * C)) || (rc = h->E.ensure((size_t)nslots * C)) ||
+        (rc = h->rec.ensure((size_t)npos)) || (rc = h->rel.ensure((size_t)npos)) || (rc = h->len.ensure((size_t)npos)) ||
+        (rc = h->seg_last.ensure((size_t)nseg * C)) || (rc = h->carry_in.ensure((size_t)nseg * C)) ||
+        (rc = h->counts.ensure((size_t)nslots + 1)) || (rc = h->offsets.ensure((size_t)nslots + 1)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(h->M.p, lcp, (size_t)npos * C * sizeof(int32_t), kind, st));
+    hipLaunchKernelGGL(locate_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, st, h->rec_begin.p, h->nrec,
+                       h->g, npos, h->rec.p, h->rel.p, h->len.p);
+    if (h->order && C > 1) {
+        int p2 = 1;
+        while (p2 < C) p2 <<= 1;
+        const int threads = p2 / 2 < 64 ? 64 : (p2 / 2 > 1024 ? 1024 : p2 / 2);
+        hipLaunchKernelGGL(sort_rows_kernel, dim3((unsigned)npos), dim3(threads), (size_t)p2 * sizeof(int32_t), st,
+                           h->M.p, npos, C, p2);
+    }
+    const ScanArgs A{h->M.p, h->carry_row.p, h->rel.p, h->len.p, npos, C, h->overlap};
+    const int threads = C <= 64 ? 64 : (C <= 128 ? 128 : 256);
+    hipLaunchKernelGGL(segment_summary_kernel, dim3((unsigned)nseg), dim3(threads), 0, st, A, h->seg_last.p);
+    hipLaunchKernelGGL(carry_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, A, h->seg_last.p, nseg,
+                       h->carry_in.p, h->prev_end.p, h->carry_row_next.p);
+    hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nseg), dim3(threads), 0, st, A, h->carry_in.p, h->E.p);
+    hipLaunchKernelGGL(count_kernel, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, st, h->E.p, nslots, C,
+                       h->counts.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(h->counts.p + nslots, 0, sizeof(uint64_t), st));  // scanned too: offsets[nslots] = total
+    size_t tmp = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, h->counts.p, h->offsets.p, (uint64_t)0, (size_t)nslots + 1,
+                                    rocprim::plus<uint64_t>(), st));
+    if ((rc = h->scan_tmp.ensure(tmp ? tmp : 16))) return rc;
+    HIP_TRY(rocprim::exclusive_scan(h->scan_tmp.p, tmp, h->counts.p, h->offsets.p, (uint64_t)0, (size_t)nslots + 1,
+                                    rocprim::plus<uint64_t>(), st));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, h->offsets.p + nslots, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = h->o_rec.ensure((size_t)total)) || (rc = h->o_annot.ensure((size_t)total)) ||
+        (rc = h->o_start.ensure((size_t)total)) || (rc = h->o_end.ensure((size_t)total)))
+        return rc;
+    if (total)
+        hipLaunchKernelGGL(write_kernel, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, st, h->E.p, nslots, C,
+                           h->offsets.p, h->rec.p, h->rel.p, h->len.p, h->o_rec.p, h->o_start.p, h->o_end.p,
+                           h->o_annot.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    std::swap(h->carry_row, h->carry_row_next);
+    h->g += npos;
+    h->n_out = total;
+    *out_rows = total;
+    return MEMO_OK;
+}
+
 extern "C" {
 
 void memo_dap_destroy(memo_dap_t *h) {
@@ -277,67 +347,11 @@ int memo_dap_create(int32_t columns, const int64_t *rec_begin, int32_t nrec, int
 }
 
 int memo_dap_push(memo_dap_t *h, const int32_t *lcp, int64_t positions, uint64_t *out_rows) {
-    if (!h || !out_rows) return fail(MEMO_EINVAL, "NULL argument");
-    *out_rows = 0;
-    h->n_out = 0;
-    if (positions <= 0) return MEMO_OK;
-    if (!lcp) return fail(MEMO_EINVAL, "lcp is NULL");
-    if (h->g + positions > h->total)
-        return fail(MEMO_EINVAL, "DAP has more rows than the .fai has positions (%lld > %lld)",
-                    (long long)(h->g + positions), (long long)h->total);
-    DeviceGuard guard(h->device);
-    hipStream_t st = nullptr;
-    const int C = h->C;
-    const int64_t npos = positions, nseg = (npos + kSeg - 1) / kSeg, nslots = 2 * npos;
-    int rc;
-    if ((rc = h->M.ensure((size_t)npos * C)) || (rc = h->E.ensure((size_t)nslots * C)) ||
-        (rc = h->rec.ensure((size_t)npos)) || (rc = h->rel.ensure((size_t)npos)) || (rc = h->len.ensure((size_t)npos)) ||
-        (rc = h->seg_last.ensure((size_t)nseg * C)) || (rc = h->carry_in.ensure((size_t)nseg * C)) ||
-        (rc = h->counts.ensure((size_t)nslots + 1)) || (rc = h->offsets.ensure((size_t)nslots + 1)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(h->M.p, lcp, (size_t)npos * C * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(locate_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, st, h->rec_begin.p, h->nrec,
-                       h->g, npos, h->rec.p, h->rel.p, h->len.p);
-    if (h->order && C > 1) {
-        int p2 = 1;
-        while (p2 < C) p2 <<= 1;
-        const int threads = p2 / 2 < 64 ? 64 : (p2 / 2 > 1024 ? 1024 : p2 / 2);
-        hipLaunchKernelGGL(sort_rows_kernel, dim3((unsigned)npos), dim3(threads), (size_t)p2 * sizeof(int32_t), st,
-                           h->M.p, npos, C, p2);
-    }
-    const ScanArgs A{h->M.p, h->carry_row.p, h->rel.p, h->len.p, npos, C, h->overlap};
-    const int threads = C <= 64 ? 64 : (C <= 128 ? 128 : 256);
-    hipLaunchKernelGGL(segment_summary_kernel, dim3((unsigned)nseg), dim3(threads), 0, st, A, h->seg_last.p);
-    hipLaunchKernelGGL(carry_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, A, h->seg_last.p, nseg,
-                       h->carry_in.p, h->prev_end.p, h->carry_row_next.p);
-    hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nseg), dim3(threads), 0, st, A, h->carry_in.p, h->E.p);
-    hipLaunchKernelGGL(count_kernel, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, st, h->E.p, nslots, C,
-                       h->counts.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(h->counts.p + nslots, 0, sizeof(uint64_t), st));  // scanned too: offsets[nslots] = total
-    size_t tmp = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, h->counts.p, h->offsets.p, (uint64_t)0, (size_t)nslots + 1,
-                                    rocprim::plus<uint64_t>(), st));
-    if ((rc = h->scan_tmp.ensure(tmp ? tmp : 16))) return rc;
-    HIP_TRY(rocprim::exclusive_scan(h->scan_tmp.p, tmp, h->counts.p, h->offsets.p, (uint64_t)0, (size_t)nslots + 1,
-                                    rocprim::plus<uint64_t>(), st));
-    uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, h->offsets.p + nslots, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = h->o_rec.ensure((size_t)total)) || (rc = h->o_annot.ensure((size_t)total)) ||
-        (rc = h->o_start.ensure((size_t)total)) || (rc = h->o_end.ensure((size_t)total)))
-        return rc;
-    if (total)
-        hipLaunchKernelGGL(write_kernel, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, st, h->E.p, nslots, C,
-                           h->offsets.p, h->rec.p, h->rel.p, h->len.p, h->o_rec.p, h->o_start.p, h->o_end.p,
-                           h->o_annot.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    std::swap(h->carry_row, h->carry_row_next);
-    h->g += npos;
-    h->n_out = total;
-    *out_rows = total;
-    return MEMO_OK;
+    return dap_push(h, lcp, positions, out_rows, hipMemcpyHostToDevice);
+}
+
+int memo_dap_push_dev(memo_dap_t *h, const int32_t *dev_lcp, int64_t positions, uint64_t *out_rows) {
+    return dap_push(h, dev_lcp, positions, out_rows, hipMemcpyDeviceToDevice);
 }
 
 int memo_dap_fetch(memo_dap_t *h, int32_t *rec, int64_t *start, int64_t *end, int32_t *annot) {

@@ -1,0 +1,703 @@
+// memo_ms.hip -- matching statistics of a pivot against genome texts, on the GPU: the stage of `memo index`
+// that the reference hands to MONI (src/index.sh:57-80).  One genome at a time:
+//
+//   suffix array      prefix doubling.  The first sort is on a packed prefix of several characters (the text's
+//                     alphabet remapped to the fewest bits); every later round sorts (rank[i], rank[i + h]) as one
+//                     64-bit key with rocPRIM's radix sort, and only the suffixes whose group is not yet a singleton
+//                     take part.  A head-flag max-scan re-ranks; ranks are "SA position of the group's head + 1", so
+//                     finished groups never move.  At most ceil(log2 n) + 2 rounds (host-bounded).
+//   ISA, PLCP, LCP    Kärkkäinen-Manzini-Puglisi: PLCP[i] >= PLCP[i-1] - 1, chunk-parallel (every chunk starts its
+//                     first position from 0), 8 bytes per compare; LCP[x] = PLCP[SA[x]].
+//   min hierarchy     64-ary minima over LCP: "nearest y left / right of x with LCP[y] < t" in a bounded number of
+//                     64-entry block scans (2 per level).
+//   MS walk           one thread per chunk of pivot positions inside one record, carrying the SA interval of
+//                     P[i, i + l): extend by two binary searches on T[SA[y] + l] (direct comparison once the
+//                     interval is one suffix), record MS[i] = l, advance through x = ISA[SA[lo] + 1] and the maximal
+//                     range around x with LCP >= l - 1.  Exact from any start, so chunks need no fix-up.
+//
+// MS columns are written straight into a device DAP matrix int32 [positions][columns] that memo_dap_push_dev
+// (memo_dap.hip) consumes in place.  Bad input sets a device error word that the host turns into an error;
+// nothing traps or spins.  rocPRIM lives in this translation unit only (its headers compile slowly).
+#include <cstring>  // rocprim's texture iterator calls memset without including it
+
+#include <rocprim/rocprim.hpp>
+
+#include <new>
+#include <vector>
+
+#include "memo_common.h"
+
+using namespace memo;
+
+namespace {
+
+constexpr int kPad = 64;          // zero bytes behind the text and the pivot: the 8-byte loads stay inside
+constexpr int kFanout = 64;       // min hierarchy: entries per block
+constexpr int kMaxLevels = 8;     // 64^6 > 2^31: six levels above LCP at most
+constexpr int kLcpChunk = 256;    // text positions per PLCP thread
+constexpr int kErrSearch = 1;     // device error bits: a hierarchy search ran off its levels
+constexpr int kErrWalk = 2;       //   an MS walk loop hit its bound
+constexpr int kErrIsa = 4;        //   an advance step found no successor suffix
+constexpr int kBlock = 256;
+
+unsigned grid_for(int64_t n, int block = kBlock) {  // n < 2^31: at most 2^23 blocks
+    const int64_t g = (n + block - 1) / block;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+
+// 8 bytes starting at byte p (little-endian: byte p is the low byte); two aligned loads and a funnel shift
+__device__ __forceinline__ uint64_t load8(const uint8_t *T, int64_t p) {
+    const uint64_t *w = reinterpret_cast<const uint64_t *>(T) + (p >> 3);
+    const int s = (int)(p & 7) * 8;
+    const uint64_t lo = w[0];
+    return s ? (lo >> s) | (w[1] << (64 - s)) : lo;
+}
+
+// common prefix of A[a, a + lim) and B[b, b + lim), 8 bytes per step; the buffers are padded by kPad
+__device__ __forceinline__ int64_t common_prefix(const uint8_t *A, int64_t a, const uint8_t *B, int64_t b, int64_t lim) {
+    int64_t l = 0;
+    for (int64_t step = 0; step <= (lim >> 3) && l < lim; ++step) {
+        const uint64_t x = load8(A, a + l) ^ load8(B, b + l);
+        if (x) {
+            l += __builtin_ctzll(x) >> 3;
+            break;
+        }
+        l += 8;
+    }
+    return l < lim ? l : lim;
+}
+
+// ---- suffix array ------------------------------------------------------------------------------------
+
+__global__ void histogram_kernel(const uint8_t *T, int64_t n, uint32_t *hist) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        atomicAdd(&h[T[i]], 1u);
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+
+struct CharCodes {
+    uint16_t code[256];  // 1 .. sigma (sigma <= 256); 0 = past the end of the text
+};
+
+// round 0: every suffix, keyed by its first `cpk` characters at `bits` bits each
+__global__ void __launch_bounds__(kBlock) prefix_key_kernel(const uint8_t *T, int64_t n, CharCodes cc, int bits, int cpk,
+                                                            uint64_t *key, int32_t *suf, int32_t *pos) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t k = 0;
+    for (int j = 0; j < cpk; ++j) k = (k << bits) | (i + j < n ? cc.code[T[i + j]] : 0);
+    key[i] = k;
+    suf[i] = (int32_t)i;
+    pos[i] = (int32_t)i;
+}
+
+// later rounds: (rank[s], rank[s + h]) of the active suffixes; rank 0 = past the end
+__global__ void __launch_bounds__(kBlock) pair_key_kernel(const int32_t *rank, const int32_t *suf, int64_t m, int64_t n, int64_t h,
+                                                          int bits, uint64_t *key) {
+    const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int64_t s = suf[j];
+    const uint64_t r2 = s + h < n ? (uint64_t)rank[s + h] : 0;
+    key[j] = ((uint64_t)rank[s] << bits) | r2;
+}
+
+// after the sort: place the suffixes, flag the group heads (value = SA position + 1 of the head)
+__global__ void __launch_bounds__(kBlock) place_kernel(const uint64_t *key, const int32_t *suf, const int32_t *pos, int64_t m,
+                                                       int32_t *SA, int32_t *head) {
+    const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    SA[pos[j]] = suf[j];
+    head[j] = (j == 0 || key[j] != key[j - 1]) ? pos[j] + 1 : 0;
+}
+
+// after the max-scan: new ranks; a suffix stays active unless its group is a singleton
+__global__ void __launch_bounds__(kBlock) rerank_kernel(const int32_t *head, const int32_t *grp, const int32_t *suf, int64_t m,
+                                                        int32_t *rank, int32_t *keep) {
+    const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    rank[suf[j]] = grp[j];
+    const bool single = head[j] != 0 && (j + 1 == m || head[j + 1] != 0);
+    keep[j] = single ? 0 : 1;
+}
+
+__global__ void __launch_bounds__(kBlock) compact_kernel(const int32_t *keep, const int32_t *off, const int32_t *suf, const int32_t *pos,
+                                                         int64_t m, int32_t *suf_out, int32_t *pos_out) {
+    const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (j >= m || !keep[j]) return;
+    suf_out[off[j]] = suf[j];
+    pos_out[off[j]] = pos[j];
+}
+
+// ---- ISA, PLCP, LCP, hierarchy ----------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kBlock) isa_phi_kernel(const int32_t *SA, int64_t n, int32_t *isa, int32_t *phi) {
+    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (x >= n) return;
+    const int32_t s = SA[x];
+    isa[s] = (int32_t)x;
+    phi[s] = x ? SA[x - 1] : -1;
+}
+
+// PLCP over text positions [c * kLcpChunk, (c + 1) * kLcpChunk): the first from 0, the rest from the previous - 1
+__global__ void __launch_bounds__(kBlock) plcp_kernel(const uint8_t *T, int64_t n, const int32_t *phi, int32_t *plcp) {
+    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const int64_t i0 = c * kLcpChunk;
+    if (i0 >= n) return;
+    const int64_t i1 = i0 + kLcpChunk < n ? i0 + kLcpChunk : n;
+    int64_t l = 0;
+    for (int64_t i = i0; i < i1; ++i) {
+        const int64_t j = phi[i];
+        if (j < 0) {
+            l = 0;
+        } else {
+            const int64_t lim = n - (i > j ? i : j);
+            if (l > lim) l = lim;
+            l += common_prefix(T, i + l, T, j + l, lim - l);
+        }
+        plcp[i] = (int32_t)l;
+        if (l > 0) --l;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) lcp_kernel(const int32_t *SA, const int32_t *plcp, int64_t n, int32_t *lcp) {
+    const int64_t x = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (x >= n) return;
+    lcp[x] = x ? plcp[SA[x]] : 0;
+}
+
+__global__ void __launch_bounds__(kBlock) block_min_kernel(const int32_t *src, int64_t n_src, int32_t *dst, int64_t n_dst) {
+    const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (e >= n_dst) return;
+    const int64_t a = e * kFanout, b = a + kFanout < n_src ? a + kFanout : n_src;
+    int32_t m = INT32_MAX;
+    for (int64_t y = a; y < b; ++y) m = src[y] < m ? src[y] : m;
+    dst[e] = m;
+}
+
+struct Hierarchy {
+    const int32_t *lv[kMaxLevels];  // lv[0] = LCP
+    int64_t size[kMaxLevels];
+    int levels;
+};
+
+// nearest y <= x with LCP[y] < t, or -1
+__device__ int64_t search_left(const Hierarchy &H, int64_t x, int32_t t, int *err) {
+    int k = 0;
+    int64_t pos = x, found = -1;
+    for (; k < H.levels; ++k) {
+        const int64_t g0 = pos & ~(int64_t)(kFanout - 1);
+        for (int64_t y = pos; y >= g0; --y)
+            if (H.lv[k][y] < t) {
+                found = y;
+                break;
+            }
+        if (found >= 0 || g0 == 0) break;
+        pos = (g0 / kFanout) - 1;
+    }
+    if (found < 0) {
+        if (k >= H.levels) *err |= kErrSearch;
+        return -1;
+    }
+    for (; k > 0; --k) {  // descend: the rightmost child whose minimum is < t
+        const int64_t c0 = found * kFanout;
+        int64_t c = c0 + kFanout - 1 < H.size[k - 1] ? c0 + kFanout - 1 : H.size[k - 1] - 1;
+        for (; c > c0 && H.lv[k - 1][c] >= t; --c) {
+        }
+        found = c;
+    }
+    return found;
+}
+
+// nearest y >= x with LCP[y] < t, or n
+__device__ int64_t search_right(const Hierarchy &H, int64_t x, int32_t t, int *err) {
+    if (x >= H.size[0]) return H.size[0];
+    int k = 0;
+    int64_t pos = x, found = -1;
+    for (; k < H.levels; ++k) {
+        const int64_t end = (pos | (kFanout - 1)) < H.size[k] - 1 ? (pos | (kFanout - 1)) : H.size[k] - 1;
+        for (int64_t y = pos; y <= end; ++y)
+            if (H.lv[k][y] < t) {
+                found = y;
+                break;
+            }
+        if (found >= 0 || end == H.size[k] - 1) break;
+        pos = end / kFanout + 1;
+    }
+    if (found < 0) {
+        if (k >= H.levels) *err |= kErrSearch;
+        return H.size[0];
+    }
+    for (; k > 0; --k) {  // descend: the leftmost child whose minimum is < t
+        int64_t c = found * kFanout;
+        const int64_t c1 = c + kFanout - 1 < H.size[k - 1] ? c + kFanout - 1 : H.size[k - 1] - 1;
+        for (; c < c1 && H.lv[k - 1][c] >= t; ++c) {
+        }
+        found = c;
+    }
+    return found;
+}
+
+// ---- the walk ------------------------------------------------------------------------------------------
+
+struct WalkArgs {
+    const uint8_t *T;         // genome text (+ kPad zeros)
+    const int32_t *SA, *ISA;
+    Hierarchy H;
+    int64_t n;
+    const uint8_t *P;         // pivot (+ kPad zeros)
+    const int64_t *rec_begin; // nrec + 1
+    const int64_t *chunk_begin;  // nrec + 1: first walk chunk of each record
+    int nrec;
+    int64_t chunk;            // positions per walk chunk
+    int64_t nchunks;
+    int32_t *M;               // DAP [positions][C]
+    int C, col;
+    int *err;
+};
+
+// T[SA[y] + l] as a signed value; -1 past the end of the text (sorts first)
+__device__ __forceinline__ int char_at(const WalkArgs &A, int64_t y, int64_t l) {
+    const int64_t p = (int64_t)A.SA[y] + l;
+    return p < A.n ? (int)A.T[p] : -1;
+}
+
+__global__ void __launch_bounds__(kBlock) ms_walk_kernel(const WalkArgs A) {
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t >= A.nchunks) return;
+    int lo_r = 0, hi_r = A.nrec;  // record of this chunk: last r with chunk_begin[r] <= t
+    while (hi_r - lo_r > 1) {
+        const int mid = (lo_r + hi_r) >> 1;
+        if (A.chunk_begin[mid] <= t) lo_r = mid; else hi_r = mid;
+    }
+    const int64_t rb = A.rec_begin[lo_r], re = A.rec_begin[lo_r + 1];
+    const int64_t i0 = rb + (t - A.chunk_begin[lo_r]) * A.chunk;
+    const int64_t i1 = i0 + A.chunk < re ? i0 + A.chunk : re;
+    const int64_t n = A.n;
+    int err = 0;
+    int64_t lo = 0, hi = n - 1, l = 0;  // SA interval of P[i, i + l)
+    for (int64_t i = i0; i < i1; ++i) {
+        // extend
+        for (int64_t step = 0; i + l < re; ++step) {
+            if (step > re - rb) {
+                err |= kErrWalk;
+                break;
+            }
+            if (lo == hi) {  // one suffix left: compare directly
+                const int64_t s = A.SA[lo];
+                const int64_t lim = (re - i < n - s ? re - i : n - s);
+                if (l < lim) l += common_prefix(A.T, s + l, A.P, i + l, lim - l);
+                break;
+            }
+            const int c = A.P[i + l];
+            int64_t a = lo, b = hi + 1;  // first y in [lo, hi] with char >= c
+            for (int k = 0; k < 33 && a < b; ++k) {
+                const int64_t mid = (a + b) >> 1;
+                if (char_at(A, mid, l) < c) a = mid + 1; else b = mid;
+            }
+            if (a > hi || char_at(A, a, l) != c) break;  // P[i, i + l] occurs nowhere
+            int64_t a2 = a, b2 = hi + 1;                  // first y in [a, hi] with char > c
+            for (int k = 0; k < 33 && a2 < b2; ++k) {
+                const int64_t mid = (a2 + b2) >> 1;
+                if (char_at(A, mid, l) <= c) a2 = mid + 1; else b2 = mid;
+            }
+            lo = a;
+            hi = a2 - 1;
+            ++l;
+        }
+        A.M[(i) * (int64_t)A.C + A.col] = (int32_t)l;
+        // advance: P[i + 1, i + l) is the suffix after SA[lo], less its first character
+        if (l > 1) {
+            const int64_t s1 = (int64_t)A.SA[lo] + 1;
+            if (s1 >= n) {
+                err |= kErrIsa;
+                l = 0;
+                lo = 0;
+                hi = n - 1;
+                continue;
+            }
+            const int64_t x = A.ISA[s1];
+            --l;
+            const int64_t y0 = search_left(A.H, x, (int32_t)l, &err);
+            const int64_t y1 = search_right(A.H, x + 1, (int32_t)l, &err);
+            lo = y0 < 0 ? 0 : y0;
+            hi = y1 - 1;
+        } else {
+            l = 0;
+            lo = 0;
+            hi = n - 1;
+        }
+    }
+    if (err) atomicOr(A.err, err);
+}
+
+template <typename T>
+struct DevBuf {  // device buffer that only ever grows
+    T *p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t need) {
+        if (need <= cap) return MEMO_OK;
+        (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(hipMalloc(&p, need * sizeof(T)));
+        cap = need;
+        return MEMO_OK;
+    }
+    void release() {
+        (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+int bits_for(uint64_t v) {  // bits to hold 0 .. v
+    int b = 1;
+    while (b < 64 && (v >> b)) ++b;
+    return b;
+}
+
+// the suffix array of T[0, n) (device; T padded by kPad) into SA; the rest is scratch that the caller keeps
+struct SaWork {
+    DevBuf<uint64_t> key, key2;
+    DevBuf<int32_t> suf, suf2, pos, pos2, rank, head, grp;
+    DevBuf<uint32_t> hist;
+    DevBuf<char> tmp;
+    void release() {
+        key.release(); key2.release(); suf.release(); suf2.release(); pos.release(); pos2.release();
+        rank.release(); head.release(); grp.release(); hist.release(); tmp.release();
+    }
+};
+
+int build_sa(const uint8_t *dT, int64_t n, int32_t *dSA, SaWork &W, hipStream_t st) {
+    int rc;
+    const size_t m1 = (size_t)n + 1;
+    if ((rc = W.key.ensure(m1)) || (rc = W.key2.ensure(m1)) || (rc = W.suf.ensure(m1)) || (rc = W.suf2.ensure(m1)) ||
+        (rc = W.pos.ensure(m1)) || (rc = W.pos2.ensure(m1)) || (rc = W.rank.ensure(m1)) || (rc = W.head.ensure(m1)) ||
+        (rc = W.grp.ensure(m1)) || (rc = W.hist.ensure(256)))
+        return rc;
+    // the text's alphabet, remapped to 1 .. sigma
+    HIP_TRY(hipMemsetAsync(W.hist.p, 0, 256 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(histogram_kernel, dim3(grid_for(n) < 1024 ? grid_for(n) : 1024), dim3(256), 0, st, dT, n, W.hist.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t hist[256];
+    HIP_TRY(hipMemcpyAsync(hist, W.hist.p, sizeof(hist), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    CharCodes cc;
+    int sigma = 0;
+    for (int c = 0; c < 256; ++c) cc.code[c] = hist[c] ? (uint16_t)++sigma : 0;
+    const int cbits = bits_for((uint64_t)sigma);
+    const int cpk = 64 / cbits;
+    // scratch of the radix sort: the largest it will need (the first round sorts all n)
+    size_t tmp_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, W.key.p, W.key2.p, W.suf.p, W.suf2.p, (size_t)n, 0, 64, st));
+    size_t scan_bytes = 0;
+    HIP_TRY(rocprim::inclusive_scan(nullptr, scan_bytes, W.head.p, W.grp.p, (size_t)n, rocprim::maximum<int32_t>(), st));
+    tmp_bytes = tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, W.head.p, W.grp.p, (int32_t)0, (size_t)n, rocprim::plus<int32_t>(), st));
+    tmp_bytes = tmp_bytes > scan_bytes ? tmp_bytes : scan_bytes;
+    if ((rc = W.tmp.ensure(tmp_bytes ? tmp_bytes : 16))) return rc;
+
+    hipLaunchKernelGGL(prefix_key_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, dT, n, cc, cbits, cpk, W.key.p, W.suf.p, W.pos.p);
+    HIP_TRY(hipGetLastError());
+    const int rbits = bits_for((uint64_t)n);  // ranks 0 .. n
+    int64_t m = n, h = cpk;
+    int end_bit = cpk * cbits;
+    const int max_rounds = bits_for((uint64_t)n) + 2;  // h grows from >= 1 by doubling: ceil(log2 n) rounds suffice
+    for (int round = 0; m > 0; ++round) {
+        if (round > max_rounds) return fail(MEMO_EHIP, "suffix array: not done after %d doubling rounds", round);
+        if (round > 0) {
+            hipLaunchKernelGGL(pair_key_kernel, dim3(grid_for(m)), dim3(kBlock), 0, st, W.rank.p, W.suf.p, m, n, h, rbits, W.key.p);
+            HIP_TRY(hipGetLastError());
+            h *= 2;
+            end_bit = 2 * rbits;
+        }
+        size_t tb = W.tmp.cap;
+        HIP_TRY(rocprim::radix_sort_pairs(W.tmp.p, tb, W.key.p, W.key2.p, W.suf.p, W.suf2.p, (size_t)m, 0, end_bit, st));
+        // sorted keys in key2, suffixes in suf2; pos (the ascending SA slots of the active suffixes) stays as it was
+        hipLaunchKernelGGL(place_kernel, dim3(grid_for(m)), dim3(kBlock), 0, st, W.key2.p, W.suf2.p, W.pos.p, m, dSA, W.head.p);
+        HIP_TRY(hipGetLastError());
+        tb = W.tmp.cap;
+        HIP_TRY(rocprim::inclusive_scan(W.tmp.p, tb, W.head.p, W.grp.p, (size_t)m, rocprim::maximum<int32_t>(), st));
+        int32_t *keep = W.suf.p;  // free since the sort
+        hipLaunchKernelGGL(rerank_kernel, dim3(grid_for(m)), dim3(kBlock), 0, st, W.head.p, W.grp.p, W.suf2.p, m, W.rank.p, keep);
+        HIP_TRY(hipGetLastError());
+        int32_t *off = W.head.p;  // free since the re-rank
+        tb = W.tmp.cap;
+        HIP_TRY(rocprim::exclusive_scan(W.tmp.p, tb, keep, off, (int32_t)0, (size_t)m, rocprim::plus<int32_t>(), st));
+        int32_t last_off = 0, last_keep = 0;
+        HIP_TRY(hipMemcpyAsync(&last_off, off + m - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&last_keep, keep + m - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        // the survivors: suffixes into pos2, slots into grp (free since the re-rank); then they become suf / pos
+        hipLaunchKernelGGL(compact_kernel, dim3(grid_for(m)), dim3(kBlock), 0, st, keep, off, W.suf2.p, W.pos.p, m, W.pos2.p, W.grp.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        m = (int64_t)last_off + last_keep;
+        std::swap(W.suf, W.pos2);
+        std::swap(W.pos, W.grp);
+    }
+    return MEMO_OK;
+}
+
+}  // namespace
+
+struct memo_ms {
+    int device = 0, C = 0, nrec = 0;
+    int64_t npos = 0;
+    int64_t chunk = 0;
+    std::vector<int64_t> h_rec_begin;
+    DevBuf<uint8_t> P, T;
+    DevBuf<int64_t> rec_begin, chunk_begin;
+    DevBuf<int32_t> M, SA, ISA, LCP, levels;
+    DevBuf<int> err;
+    SaWork W;
+    float ms_sa = 0.f, ms_lcp = 0.f, ms_walk = 0.f;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+namespace {
+
+void release(memo_ms *h) {
+    h->P.release(); h->T.release(); h->rec_begin.release(); h->chunk_begin.release();
+    h->M.release(); h->SA.release(); h->ISA.release(); h->LCP.release(); h->levels.release(); h->err.release();
+    h->W.release();
+    for (auto &e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+}
+
+int upload_padded(DevBuf<uint8_t> &buf, const uint8_t *src, int64_t n, hipStream_t st) {
+    int rc = buf.ensure((size_t)n + kPad);
+    if (rc) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(buf.p, src, (size_t)n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(buf.p + n, 0, kPad, st));
+    return MEMO_OK;
+}
+
+// device bytes a genome text of n characters needs while its suffix array is built (SaWork + SA + text)
+uint64_t sa_bytes(int64_t n) { return (uint64_t)n * (8 + 8 + 4 * 9 + 4) + (uint64_t)n / 4 + (64u << 20); }
+
+int fits(int64_t need, const char *what) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if ((uint64_t)need > (uint64_t)free_b)
+        return fail(MEMO_EINVAL, "%s needs %.2f GB of device memory, %.2f GB are free (of %.2f GB)", what, need / 1e9,
+                    free_b / 1e9, total_b / 1e9);
+    return MEMO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int memo_suffix_array(const uint8_t *text, int64_t n, int32_t *sa_out, int32_t device) {
+    if (n < 0 || n >= ((int64_t)1 << 31) - 1) return fail(MEMO_EINVAL, "text length %lld outside [0, 2^31 - 1)", (long long)n);
+    if (n == 0) return MEMO_OK;
+    if (!text || !sa_out) return fail(MEMO_EINVAL, "NULL argument");
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    int rc = fits((int64_t)sa_bytes(n), "the suffix array");
+    if (rc) return rc;
+    DevBuf<uint8_t> T;
+    DevBuf<int32_t> SA;
+    SaWork W;
+    hipStream_t st = nullptr;
+    rc = upload_padded(T, text, n, st);
+    if (!rc) rc = SA.ensure((size_t)n);
+    if (!rc) rc = build_sa(T.p, n, SA.p, W, st);
+    if (!rc && hipMemcpy(sa_out, SA.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(MEMO_EHIP, "memo_suffix_array: copy back failed");
+    T.release();
+    SA.release();
+    W.release();
+    return rc;
+}
+
+void memo_ms_destroy(memo_ms_t *h) {
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    release(h);
+    delete h;
+}
+
+int memo_ms_create(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec, int32_t columns, int64_t chunk,
+                   int32_t device, memo_ms_t **out) {
+    if (!out) return fail(MEMO_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (columns < 1 || columns > 4096) return fail(MEMO_EINVAL, "columns must be in [1, 4096], got %d", columns);
+    if (nrec < 1 || !rec_begin) return fail(MEMO_EINVAL, "need at least one pivot record");
+    if (rec_begin[0] != 0) return fail(MEMO_EINVAL, "rec_begin[0] must be 0");
+    for (int r = 0; r < nrec; ++r) {
+        const int64_t L = rec_begin[r + 1] - rec_begin[r];
+        if (L < 1 || L >= ((int64_t)1 << 30))
+            return fail(MEMO_EINVAL, "pivot record %d has length %lld (need 1 .. 2^30-1)", r, (long long)L);
+    }
+    const int64_t npos = rec_begin[nrec];
+    if (npos >= ((int64_t)1 << 40)) return fail(MEMO_EINVAL, "pivot of %lld positions is too long", (long long)npos);
+    if (chunk <= 0) chunk = 128;
+    if (chunk > ((int64_t)1 << 30)) return fail(MEMO_EINVAL, "walk chunk %lld too long", (long long)chunk);
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    // the DAP matrix stays resident; every genome's working set comes on top of it
+    const int64_t dap_bytes = npos * (int64_t)columns * 4;
+    int rc = fits(dap_bytes + npos + (int64_t)(sa_bytes(1 << 20)), "the DAP matrix");
+    if (rc) return rc;
+    if (!pivot) return fail(MEMO_EINVAL, "pivot is NULL");
+    if (memchr(pivot, 0, (size_t)npos)) return fail(MEMO_EINVAL, "the pivot holds a NUL byte");
+    memo_ms *h = new (std::nothrow) memo_ms();
+    if (!h) return fail(MEMO_EHIP, "out of host memory");
+    h->device = device;
+    h->C = columns;
+    h->nrec = nrec;
+    h->npos = npos;
+    h->chunk = chunk;
+    h->h_rec_begin.assign(rec_begin, rec_begin + nrec + 1);
+    std::vector<int64_t> cb(nrec + 1, 0);
+    for (int r = 0; r < nrec; ++r) cb[r + 1] = cb[r] + (rec_begin[r + 1] - rec_begin[r] + chunk - 1) / chunk;
+    hipStream_t st = nullptr;
+    rc = upload_padded(h->P, pivot, npos, st);
+    if (!rc) rc = h->rec_begin.ensure((size_t)nrec + 1);
+    if (!rc) rc = h->chunk_begin.ensure((size_t)nrec + 1);
+    if (!rc) rc = h->M.ensure((size_t)(npos * columns));
+    if (!rc) rc = h->err.ensure(1);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpy(h->rec_begin.p, rec_begin, (nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipMemcpy(h->chunk_begin.p, cb.data(), (nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipMemset(h->M.p, 0, (size_t)(npos * columns) * sizeof(int32_t));
+    for (auto &ev : h->ev)
+        if (!rc && e == hipSuccess) e = hipEventCreate(&ev);
+    if (!rc && e == hipSuccess) e = hipDeviceSynchronize();
+    if (rc || e != hipSuccess) {
+        memo_ms_destroy(h);
+        return rc ? rc : fail(MEMO_EHIP, "memo_ms_create: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return MEMO_OK;
+}
+
+int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t column) {
+    if (!h) return fail(MEMO_EINVAL, "handle is NULL");
+    if (column < 0 || column >= h->C) return fail(MEMO_EINVAL, "column %d outside [0, %d)", column, h->C);
+    if (n < 0 || n >= ((int64_t)1 << 31) - 1)
+        return fail(MEMO_EINVAL, "genome text of %lld characters: the limit is 2^31 - 2 (int32 suffix array)", (long long)n);
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
+    hipStream_t st = nullptr;
+    if (n == 0) {  // an empty genome matches nothing: its column is zero
+        HIP_TRY(hipMemset2D(h->M.p + column, (size_t)h->C * 4, 0, 4, (size_t)h->npos));
+        return MEMO_OK;
+    }
+    if (!text) return fail(MEMO_EINVAL, "text is NULL");
+    // what is not allocated yet must fit (the buffers grow only)
+    const int64_t have = (int64_t)(h->T.cap + (h->SA.cap + h->ISA.cap + h->LCP.cap) * 4 + h->W.key.cap * 16 + h->W.suf.cap * 28);
+    const int64_t need = (int64_t)sa_bytes(n) + n * 12 + n / 8 - have;
+    int rc = need > 0 ? fits(need, "this genome's suffix array and LCP") : MEMO_OK;
+    if (rc) return rc;
+    if ((rc = upload_padded(h->T, text, n, st)) || (rc = h->SA.ensure(n)) || (rc = h->ISA.ensure(n)) ||
+        (rc = h->LCP.ensure(n)))
+        return rc;
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    if ((rc = build_sa(h->T.p, n, h->SA.p, h->W, st))) return rc;
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    // ISA and PHI (PHI in the rank scratch), PLCP (in grp), LCP
+    int32_t *phi = h->W.rank.p, *plcp = h->W.grp.p;
+    hipLaunchKernelGGL(isa_phi_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, h->SA.p, n, h->ISA.p, phi);
+    hipLaunchKernelGGL(plcp_kernel, dim3(grid_for((n + kLcpChunk - 1) / kLcpChunk)), dim3(kBlock), 0, st, h->T.p, n, phi, plcp);
+    hipLaunchKernelGGL(lcp_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, h->SA.p, plcp, n, h->LCP.p);
+    HIP_TRY(hipGetLastError());
+    // the min hierarchy over LCP
+    Hierarchy H{};
+    int64_t sizes[kMaxLevels], offs[kMaxLevels], total = 0;
+    int levels = 1;
+    sizes[0] = n;
+    while (sizes[levels - 1] > 1 && levels < kMaxLevels) {
+        sizes[levels] = (sizes[levels - 1] + kFanout - 1) / kFanout;
+        offs[levels] = total;
+        total += sizes[levels];
+        ++levels;
+    }
+    if ((rc = h->levels.ensure((size_t)(total ? total : 1)))) return rc;
+    H.levels = levels;
+    H.lv[0] = h->LCP.p;
+    H.size[0] = n;
+    for (int k = 1; k < levels; ++k) {
+        H.lv[k] = h->levels.p + offs[k];
+        H.size[k] = sizes[k];
+        hipLaunchKernelGGL(block_min_kernel, dim3(grid_for(sizes[k])), dim3(kBlock), 0, st, H.lv[k - 1], sizes[k - 1],
+                           h->levels.p + offs[k], sizes[k]);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[2], st));
+    // the walk
+    WalkArgs A{};
+    A.T = h->T.p;
+    A.SA = h->SA.p;
+    A.ISA = h->ISA.p;
+    A.H = H;
+    A.n = n;
+    A.P = h->P.p;
+    A.rec_begin = h->rec_begin.p;
+    A.chunk_begin = h->chunk_begin.p;
+    A.nrec = h->nrec;
+    A.chunk = h->chunk;
+    int64_t nchunks = 0;
+    for (int r = 0; r < h->nrec; ++r) nchunks += (h->h_rec_begin[r + 1] - h->h_rec_begin[r] + h->chunk - 1) / h->chunk;
+    A.nchunks = nchunks;
+    A.M = h->M.p;
+    A.C = h->C;
+    A.col = column;
+    A.err = h->err.p;
+    HIP_TRY(hipMemsetAsync(h->err.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(ms_walk_kernel, dim3(grid_for(nchunks)), dim3(kBlock), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], st));
+    int errw = 0;
+    HIP_TRY(hipMemcpyAsync(&errw, h->err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float a = 0, b = 0, c = 0;
+    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
+    h->ms_sa += a;
+    h->ms_lcp += b;
+    h->ms_walk += c;
+    if (errw) return fail(MEMO_EHIP, "matching statistics of column %d: the walk kernel reported error bits 0x%x", column, errw);
+    return MEMO_OK;
+}
+
+int memo_ms_fetch(memo_ms_t *h, int64_t first, int64_t positions, int32_t *out) {
+    if (!h) return fail(MEMO_EINVAL, "handle is NULL");
+    if (first < 0 || positions < 0 || first + positions > h->npos)
+        return fail(MEMO_EINVAL, "positions [%lld, %lld) outside the pivot's %lld", (long long)first,
+                    (long long)(first + positions), (long long)h->npos);
+    if (!positions) return MEMO_OK;
+    if (!out) return fail(MEMO_EINVAL, "out is NULL");
+    DeviceGuard guard(h->device);
+    HIP_TRY(hipMemcpy(out, h->M.p + first * h->C, (size_t)(positions * h->C) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MEMO_OK;
+}
+
+int memo_ms_push_dap(memo_ms_t *h, memo_dap_t *dap, int64_t first, int64_t positions, uint64_t *out_rows) {
+    if (!h || !dap || !out_rows) return fail(MEMO_EINVAL, "NULL argument");
+    if (first < 0 || positions < 0 || first + positions > h->npos)
+        return fail(MEMO_EINVAL, "positions [%lld, %lld) outside the pivot's %lld", (long long)first,
+                    (long long)(first + positions), (long long)h->npos);
+    int dev = -1, cols = 0;
+    dap_shape(dap, &dev, &cols);
+    if (dev != h->device || cols != h->C)
+        return fail(MEMO_EINVAL, "the DAP handle has %d columns on device %d, the matching statistics %d on device %d", cols, dev,
+                    h->C, h->device);
+    return memo_dap_push_dev(dap, h->M.p + first * h->C, positions, out_rows);
+}
+
+int memo_ms_timings(memo_ms_t *h, float *out3) {
+    if (!h || !out3) return fail(MEMO_EINVAL, "NULL argument");
+    out3[0] = h->ms_sa;
+    out3[1] = h->ms_lcp;
+    out3[2] = h->ms_walk;
+    return MEMO_OK;
+}
+
+}  // extern "C"

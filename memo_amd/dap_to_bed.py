@@ -102,6 +102,16 @@ class DapConverter:
             check(lib().memo_dap_fetch(self._h, *[a.ctypes.data for a in out]))
         return out
 
+    def push_ms(self, ms, first, positions):
+        """the same for DAP rows [first, first + positions) of a build_index.MatchingStatistics, read where they
+        lie in device memory (memo_ms_push_dap)"""
+        n = C.c_uint64()
+        check(lib().memo_ms_push_dap(ms._h, self._h, first, positions, C.byref(n)))
+        out = self._bufs(n.value)
+        if n.value:
+            check(lib().memo_dap_fetch(self._h, *[a.ctypes.data for a in out]))
+        return out
+
     def finish(self):
         out = self._bufs(self.columns)
         n = C.c_uint64()
@@ -150,16 +160,25 @@ def convert(dap_path, fai_path, order, overlap, device=0):
             conv.close()
 
 
-def dap_to_parquet(dap_path, fai_path, out_path, order, device=0, codec="ZSTD"):
-    """the index file `memo index` ends with: columns f0 utf8, f1 f2 f3 int64, ZSTD"""
+def write_parquet(out_path, batches, codec="ZSTD"):
+    """(names, (rec, start, end, annot)) row batches -> the index file `memo index` ends with: columns f0 utf8,
+    f1 f2 f3 int64, ZSTD (parquet_compress_bed.py:19-38).  Returns the number of rows."""
     import pyarrow as pa
     import pyarrow.parquet as pq
     schema = pa.schema([("f0", pa.utf8()), ("f1", pa.int64()), ("f2", pa.int64()), ("f3", pa.int64())])
+    rows = 0
     with pq.ParquetWriter(out_path, schema, compression=codec) as w:
-        for names, (rec, start, end, annot) in convert(dap_path, fai_path, order, True, device):
+        for names, (rec, start, end, annot) in batches:
             if len(rec):
                 f0 = pa.DictionaryArray.from_arrays(pa.array(rec, pa.int32()), pa.array(names, pa.utf8())).cast(pa.utf8())
                 w.write_table(pa.table({"f0": f0, "f1": start, "f2": end, "f3": annot.astype(np.int64)}, schema=schema))
+                rows += len(rec)
+    return rows
+
+
+def dap_to_parquet(dap_path, fai_path, out_path, order, device=0, codec="ZSTD"):
+    """the index file `memo index` ends with, from a DAP text and the pivot's .fai"""
+    write_parquet(out_path, convert(dap_path, fai_path, order, True, device), codec)
 
 
 ################################################################################
