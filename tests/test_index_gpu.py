@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+from oracle.ms_oracle import brute_ms as _brute_ms  # tools/make_golden.py's definition
 from tests import golden_util as G
 
 pytestmark = pytest.mark.gpu
@@ -24,22 +25,6 @@ def bi():
     from memo_amd import _lib, build_index
     _lib.lib()
     return build_index
-
-
-def _brute_ms(records, text):
-    """tools/make_golden.py's definition: longest prefix of record[i:] occurring in the text (binary search on the length)"""
-    out = []
-    for rec in records:
-        for i in range(len(rec)):
-            lo, hi = 0, len(rec) - i
-            while lo < hi:
-                mid = (lo + hi + 1) // 2
-                if rec[i:i + mid] in text:
-                    lo = mid
-                else:
-                    hi = mid - 1
-            out.append(lo)
-    return np.array(out, np.int32)
 
 
 # ---- the example walkthrough ------------------------------------------------------------------------------
