@@ -18,7 +18,9 @@ extern "C" {
  * consecutive positions starting at 0, in as many pushes as the caller likes (state carries over);
  * each push produces, on `device`, the (record, start, end, annot) rows the reference would print
  * for those positions, in its order.  rec_begin: nrec + 1 cumulative record offsets of the pivot
- * (from its .fai).  memo_dap_fetch copies the rows of the last push; memo_dap_finish returns the
+ * (from its .fai).  DAP values must lie in [0, 2^31); they are not checked (a negative value gives
+ * undefined rows).  Every such value is exact: MEM ends (start + value, up to 2^30 + 2^31) are
+ * int64.  memo_dap_fetch copies the rows of the last push; memo_dap_finish returns the
  * chr-end rows of a DAP that stops inside a record (at most `columns` rows). */
 typedef struct memo_dap memo_dap_t;
 int memo_dap_create(int32_t columns, const int64_t *rec_begin, int32_t nrec, int32_t sort_order,

@@ -38,6 +38,7 @@ namespace {
 
 constexpr int kNone = -1;   // "no MEM end yet" / "nothing to print"
 constexpr int kSeg = 256;   // rows per scan segment
+constexpr int kSlotBlocks = 1 << 20;  // grid cap of sort (1 row per block) and count/write (4 slots per block)
 
 __global__ void locate_kernel(const int64_t *rec_begin, int nrec, int64_t g0, int64_t npos, int32_t *rec,
                               int32_t *rel, int32_t *len) {
@@ -54,28 +55,31 @@ __global__ void locate_kernel(const int64_t *rec_begin, int nrec, int64_t g0, in
     len[p] = (int32_t)(rec_begin[lo + 1] - rec_begin[lo]);
 }
 
-// one workgroup per row; P2 = columns rounded up to a power of two, padding sorts to the end
+// one workgroup per row (grid-stride over rows); P2 = columns rounded up to a power of two, padding
+// sorts to the end
 __global__ void sort_rows_kernel(int32_t *M, int64_t npos, int C, int P2) {
     extern __shared__ int32_t v[];
-    const int64_t p = blockIdx.x;
-    int32_t *row = M + p * C;
-    for (int i = threadIdx.x; i < P2; i += blockDim.x) v[i] = i < C ? row[i] : INT32_MIN;
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < P2 / 2; t += blockDim.x) {
-                const int i = 2 * t - (t & (j - 1));  // lower index of the pair, bit j clear
-                const int l = i + j;
-                const bool desc = (i & k) == 0;       // this run sorts descending
-                const int32_t a = v[i], b = v[l];
-                if (desc ? a < b : a > b) {
-                    v[i] = b;
-                    v[l] = a;
+    for (int64_t p = blockIdx.x; p < npos; p += gridDim.x) {
+        int32_t *row = M + p * C;
+        for (int i = threadIdx.x; i < P2; i += blockDim.x) v[i] = i < C ? row[i] : INT32_MIN;
+        __syncthreads();
+        for (int k = 2; k <= P2; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int t = threadIdx.x; t < P2 / 2; t += blockDim.x) {
+                    const int i = 2 * t - (t & (j - 1));  // lower index of the pair, bit j clear
+                    const int l = i + j;
+                    const bool desc = (i & k) == 0;       // this run sorts descending
+                    const int32_t a = v[i], b = v[l];
+                    if (desc ? a < b : a > b) {
+                        v[i] = b;
+                        v[l] = a;
+                    }
                 }
+                __syncthreads();
             }
-            __syncthreads();
-        }
-    for (int i = threadIdx.x; i < C; i += blockDim.x) row[i] = v[i];
+        for (int i = threadIdx.x; i < C; i += blockDim.x) row[i] = v[i];
+        __syncthreads();  // v is refilled for the next row
+    }
 }
 
 struct ScanArgs {
@@ -91,14 +95,16 @@ __device__ __forceinline__ int32_t lcp_above(const ScanArgs &A, int64_t p, int c
     return p == 0 ? A.carry_row[c] : A.M[(p - 1) * A.C + c];
 }
 
+// MEM ends are int64: rel + m reaches 2^30 + 2^31 for DAP values in [0, 2^31)
 // pass 1: end of the last MEM that starts inside the segment, per column
-__global__ void segment_summary_kernel(const ScanArgs A, int32_t *seg_last) {
+__global__ void segment_summary_kernel(const ScanArgs A, int64_t *seg_last) {
     const int64_t p0 = blockIdx.x * (int64_t)kSeg, p1 = p0 + kSeg < A.npos ? p0 + kSeg : A.npos;
     for (int c = threadIdx.x; c < A.C; c += blockDim.x) {
-        int32_t above = lcp_above(A, p0, c), last = kNone;
+        int32_t above = lcp_above(A, p0, c);
+        int64_t last = kNone;
         for (int64_t p = p0; p < p1; ++p) {
             const int32_t m = A.M[p * A.C + c];
-            if (A.rel[p] == 0 || above <= m) last = A.rel[p] + m;
+            if (A.rel[p] == 0 || above <= m) last = (int64_t)A.rel[p] + m;
             above = m;
         }
         seg_last[blockIdx.x * (int64_t)A.C + c] = last;
@@ -106,46 +112,48 @@ __global__ void segment_summary_kernel(const ScanArgs A, int32_t *seg_last) {
 }
 
 // pass 2: chain the segments; prev_end carries over to the next chunk, so does the last row
-__global__ void carry_kernel(const ScanArgs A, const int32_t *seg_last, int64_t nseg, int32_t *carry_in,
-                             int32_t *prev_end, int32_t *carry_row_out) {
+__global__ void carry_kernel(const ScanArgs A, const int64_t *seg_last, int64_t nseg, int64_t *carry_in,
+                             int64_t *prev_end, int32_t *carry_row_out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= A.C) return;
-    int32_t carry = prev_end[c];
+    int64_t carry = prev_end[c];
     for (int64_t s = 0; s < nseg; ++s) {
         carry_in[s * A.C + c] = carry;
-        const int32_t l = seg_last[s * A.C + c];
+        const int64_t l = seg_last[s * A.C + c];
         if (l != kNone) carry = l;
     }
     prev_end[c] = carry;
     carry_row_out[c] = A.M[(A.npos - 1) * A.C + c];
 }
 
-// pass 3: E[2p][c] = end of the row printed for (row p, column c) or kNone; E[2p+1][c] = the same
-// for the chr-end pseudo-MEM when p is the last row of its record
-__global__ void emit_kernel(const ScanArgs A, const int32_t *carry_in, int32_t *E) {
+// pass 3: E[2p][c] = end - start of the row printed for (row p, column c) or kNone; E[2p+1][c] = the
+// same for the chr-end pseudo-MEM when p is the last row of its record.  A printed row has
+// 0 <= end - start <= max(m, L) < 2^31, so the difference fits int32 and never equals kNone.
+__global__ void emit_kernel(const ScanArgs A, const int64_t *carry_in, int32_t *E) {
     const int64_t p0 = blockIdx.x * (int64_t)kSeg, p1 = p0 + kSeg < A.npos ? p0 + kSeg : A.npos;
     for (int c = threadIdx.x; c < A.C; c += blockDim.x) {
-        int32_t above = lcp_above(A, p0, c), carry = carry_in[blockIdx.x * (int64_t)A.C + c];
+        int32_t above = lcp_above(A, p0, c);
+        int64_t carry = carry_in[blockIdx.x * (int64_t)A.C + c];
         for (int64_t p = p0; p < p1; ++p) {
             const int32_t m = A.M[p * A.C + c], rel = A.rel[p], L = A.len[p];
             const bool opener = rel == 0;
             int32_t e0 = kNone, e1 = kNone;
             if (opener || above <= m) {  // a MEM starts here: (rel, rel + m)
-                const int32_t cur = rel + m;
+                const int64_t cur = (int64_t)rel + m;
                 if (!A.overlap) {
-                    e0 = cur;
+                    e0 = m;
                 } else if (!opener && carry != kNone) {  // overlap with the previous MEM of the column
-                    const int32_t e = carry < cur ? carry : cur;
-                    if (e >= rel) e0 = e;
+                    const int64_t e = carry < cur ? carry : cur;
+                    if (e >= rel) e0 = (int32_t)(e - rel);
                 }
                 carry = cur;
             }
             if (rel == L - 1) {  // chr end: the pseudo-MEM (L, 2L) through the same printer
                 if (!A.overlap) {
-                    e1 = 2 * L;
+                    e1 = L;
                 } else if (carry != kNone) {
-                    const int32_t e = carry < 2 * L ? carry : 2 * L;
-                    if (e >= L) e1 = e;
+                    const int64_t e = carry < 2 * (int64_t)L ? carry : 2 * (int64_t)L;
+                    if (e >= L) e1 = (int32_t)(e - L);
                 }
             }
             above = m;
@@ -155,40 +163,42 @@ __global__ void emit_kernel(const ScanArgs A, const int32_t *carry_in, int32_t *
     }
 }
 
-// one wave per slot (2 per row): how many rows it prints
+// one wave per slot (2 per row), grid-stride (the grid stays under 2^32 work-items): how many rows it prints
 __global__ void count_kernel(const int32_t *E, int64_t nslots, int C, uint64_t *counts) {
-    const int64_t slot = blockIdx.x * (int64_t)(blockDim.x / 64) + threadIdx.x / 64;
-    if (slot >= nslots) return;
     const int lane = threadIdx.x & 63;
-    unsigned n = 0;
-    for (int c0 = 0; c0 < C; c0 += 64) {
-        const int c = c0 + lane;
-        n += __popcll(__ballot(c < C && E[slot * C + c] != kNone));
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x / 64);
+    for (int64_t slot = blockIdx.x * (int64_t)(blockDim.x / 64) + threadIdx.x / 64; slot < nslots; slot += waves) {
+        unsigned n = 0;
+        for (int c0 = 0; c0 < C; c0 += 64) {
+            const int c = c0 + lane;
+            n += __popcll(__ballot(c < C && E[slot * C + c] != kNone));
+        }
+        if (lane == 0) counts[slot] = n;
     }
-    if (lane == 0) counts[slot] = n;
 }
 
 __global__ void write_kernel(const int32_t *E, int64_t nslots, int C, const uint64_t *offsets,
                              const int32_t *rec, const int32_t *rel, const int32_t *len, int32_t *o_rec,
                              int64_t *o_start, int64_t *o_end, int32_t *o_annot) {
-    const int64_t slot = blockIdx.x * (int64_t)(blockDim.x / 64) + threadIdx.x / 64;
-    if (slot >= nslots) return;
     const int lane = threadIdx.x & 63;
-    const int64_t p = slot >> 1;
-    const int64_t start = (slot & 1) ? len[p] : rel[p];
-    uint64_t at = offsets[slot];
-    for (int c0 = 0; c0 < C; c0 += 64) {
-        const int c = c0 + lane;
-        const int32_t e = c < C ? E[slot * C + c] : kNone;
-        const unsigned long long mask = __ballot(e != kNone);
-        if (e != kNone) {
-            const uint64_t k = at + __popcll(mask & ((1ull << lane) - 1));
-            o_rec[k] = rec[p];
-            o_start[k] = start;
-            o_end[k] = e;
-            o_annot[k] = c + 1;  // annots are 1-based (dap_to_bed.py:113,122)
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x / 64);
+    for (int64_t slot = blockIdx.x * (int64_t)(blockDim.x / 64) + threadIdx.x / 64; slot < nslots; slot += waves) {
+        const int64_t p = slot >> 1;
+        const int64_t start = (slot & 1) ? len[p] : rel[p];
+        uint64_t at = offsets[slot];
+        for (int c0 = 0; c0 < C; c0 += 64) {
+            const int c = c0 + lane;
+            const int32_t e = c < C ? E[slot * C + c] : kNone;
+            const unsigned long long mask = __ballot(e != kNone);
+            if (e != kNone) {
+                const uint64_t k = at + __popcll(mask & ((1ull << lane) - 1));
+                o_rec[k] = rec[p];
+                o_start[k] = start;
+                o_end[k] = start + e;
+                o_annot[k] = c + 1;  // annots are 1-based (dap_to_bed.py:113,122)
+            }
+            at += __popcll(mask);
         }
-        at += __popcll(mask);
     }
 }
 
@@ -215,9 +225,11 @@ struct memo_dap {
     int64_t total = 0;  // rec_begin[nrec]
     DevBuf<int64_t> rec_begin;
     std::vector<int64_t> h_rec_begin;
-    DevBuf<int32_t> carry_row, carry_row_next, prev_end;
+    DevBuf<int32_t> carry_row, carry_row_next;
+    DevBuf<int64_t> prev_end;  // per column: end of its last MEM so far, or kNone
     // per-chunk buffers
-    DevBuf<int32_t> M, E, rec, rel, len, seg_last, carry_in;
+    DevBuf<int32_t> M, E, rec, rel, len;
+    DevBuf<int64_t> seg_last, carry_in;
     DevBuf<uint64_t> counts, offsets;
     DevBuf<char> scan_tmp;
     // rows of the last push
@@ -258,7 +270,7 @@ static int dap_push(memo_dap_t *h, const int32_t *lcp, int64_t positions, uint64
         int p2 = 1;
         while (p2 < C) p2 <<= 1;
         const int threads = p2 / 2 < 64 ? 64 : (p2 / 2 > 1024 ? 1024 : p2 / 2);
-        hipLaunchKernelGGL(sort_rows_kernel, dim3((unsigned)npos), dim3(threads), (size_t)p2 * sizeof(int32_t), st,
+        hipLaunchKernelGGL(sort_rows_kernel, dim3((unsigned)(npos < kSlotBlocks ? npos : kSlotBlocks)), dim3(threads), (size_t)p2 * sizeof(int32_t), st,
                            h->M.p, npos, C, p2);
     }
     const ScanArgs A{h->M.p, h->carry_row.p, h->rel.p, h->len.p, npos, C, h->overlap};
@@ -267,7 +279,8 @@ static int dap_push(memo_dap_t *h, const int32_t *lcp, int64_t positions, uint64
     hipLaunchKernelGGL(carry_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, A, h->seg_last.p, nseg,
                        h->carry_in.p, h->prev_end.p, h->carry_row_next.p);
     hipLaunchKernelGGL(emit_kernel, dim3((unsigned)nseg), dim3(threads), 0, st, A, h->carry_in.p, h->E.p);
-    hipLaunchKernelGGL(count_kernel, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, st, h->E.p, nslots, C,
+    const unsigned slot_blocks = (unsigned)((nslots + 3) / 4 < kSlotBlocks ? (nslots + 3) / 4 : kSlotBlocks);
+    hipLaunchKernelGGL(count_kernel, dim3(slot_blocks), dim3(256), 0, st, h->E.p, nslots, C,
                        h->counts.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(h->counts.p + nslots, 0, sizeof(uint64_t), st));  // scanned too: offsets[nslots] = total
@@ -284,7 +297,7 @@ static int dap_push(memo_dap_t *h, const int32_t *lcp, int64_t positions, uint64
         (rc = h->o_start.ensure((size_t)total)) || (rc = h->o_end.ensure((size_t)total)))
         return rc;
     if (total)
-        hipLaunchKernelGGL(write_kernel, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, st, h->E.p, nslots, C,
+        hipLaunchKernelGGL(write_kernel, dim3(slot_blocks), dim3(256), 0, st, h->E.p, nslots, C,
                            h->offsets.p, h->rec.p, h->rel.p, h->len.p, h->o_rec.p, h->o_start.p, h->o_end.p,
                            h->o_annot.p);
     HIP_TRY(hipGetLastError());
@@ -337,7 +350,7 @@ int memo_dap_create(int32_t columns, const int64_t *rec_begin, int32_t nrec, int
     hipError_t err = hipSuccess;
     if (!rc) err = hipMemcpy(h->rec_begin.p, rec_begin, (size_t)(nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
     if (!rc && err == hipSuccess) err = hipMemset(h->carry_row.p, 0, (size_t)columns * sizeof(int32_t));
-    if (!rc && err == hipSuccess) err = hipMemset(h->prev_end.p, 0xFF, (size_t)columns * sizeof(int32_t));  // kNone
+    if (!rc && err == hipSuccess) err = hipMemset(h->prev_end.p, 0xFF, (size_t)columns * sizeof(int64_t));  // kNone
     if (rc || err != hipSuccess) {
         memo_dap_destroy(h);
         return rc ? rc : fail(MEMO_EHIP, "memo_dap_create: %s", hipGetErrorString(err));
@@ -378,8 +391,8 @@ int memo_dap_finish(memo_dap_t *h, int32_t *rec, int64_t *start, int64_t *end, i
     if (h->h_rec_begin[r + 1] == h->g) return MEMO_OK;  // the last record was complete: already printed
     if (!rec || !start || !end || !annot) return fail(MEMO_EINVAL, "output pointer is NULL");
     DeviceGuard guard(h->device);
-    std::vector<int32_t> pe(h->C);
-    HIP_TRY(hipMemcpy(pe.data(), h->prev_end.p, (size_t)h->C * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<int64_t> pe(h->C);
+    HIP_TRY(hipMemcpy(pe.data(), h->prev_end.p, (size_t)h->C * sizeof(int64_t), hipMemcpyDeviceToHost));
     const int64_t L = h->h_rec_begin[r + 1] - h->h_rec_begin[r];
     uint64_t n = 0;
     for (int c = 0; c < h->C; ++c) {

@@ -88,9 +88,9 @@ class DapConverter:
 
     def push(self, lcp):
         lcp = np.asarray(lcp)
-        if lcp.size and lcp.dtype != np.int32:
-            # matching statistics are lengths inside a record (< 2^30 here): anything else would wrap
-            # silently in the int32 matrix the device works on
+        if lcp.size:
+            # the device reads int32 and takes values in [0, 2^31): a wider value would wrap in the
+            # conversion, and a negative one (int32 included) would print rows the reference does not
             lo, hi = int(lcp.min()), int(lcp.max())
             if lo < 0 or hi >= 2 ** 31:
                 raise ValueError(f"DAP values must lie in [0, 2^31): found {lo if lo < 0 else hi}")
