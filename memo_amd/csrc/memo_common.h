@@ -139,6 +139,7 @@ struct memo_index {
         uint32_t *p3 = nullptr;
         int64_t *boff = nullptr;
         uint64_t rows = 0, padded = 0;
+        uint64_t dead_groups = 0;  // six-row views with places: groups flagged as holding no live row (memo_view.hip: kDeadGroup)
         uint64_t bytes = 0;      // of the rows' allocation (set where a view is installed: a six-row view is (groups + 64) x 16 B, not
                                  //   what its padded row count makes of five-row groups -- ADVICE r05: the budget charged it a fifth too much)
         float build_ms = 0.f;
@@ -159,6 +160,7 @@ struct memo_index {
     uint64_t last_rows_read = 0;  // rows of the row source the last sweep read (info.last_rows_read)
     float last_view_ms = 0.f;     // device time of the view build, when the last sweep's view was built by it (else 0)
     int last_view_placed = 0, last_view_rpg = 5;  // (memo_index_info_t: of the dense rows the last sweep read)
+    double last_view_dead_share = 0;              // ... the share of its groups flagged dead (the sweep skips them where it pays)
     uint64_t max_annot = 0;    // largest annot of the packed rows
     // Sampled histogram of the packed rows' overlap field (min(end - start, 255)): with it the length n = k - 1 -
     // overlap of a row's interval is known in distribution for any k, which is what the choice between the level

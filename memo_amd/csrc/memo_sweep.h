@@ -571,8 +571,11 @@ using SweepKernel = void (*)(const SweepArgs);
 inline int floor_log2(uint32_t v) { return 31 - __builtin_clz(v); }
 int launch_tiles(SweepKernel kernel, SweepArgs &A, int w, int threads, size_t lds, hipStream_t st);
 // memo_sweep_cons3t.hip: the table-driven dense-row sweep; 1 = this query does not fit it
+// live: the row source is a six-row view with dead-group flags, at least kLiveMinShare of its groups flagged (below that a wave's
+// ballots and packing have little to save; profiles/r07_live_rows.txt has the shares measured)
+constexpr double kLiveMinShare = 0.25;
 int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStream_t st, bool annot9 = false, bool all_write = false,
-                  bool six = false);
+                  bool six = false, bool live = false);
 int pick_rows(const memo_index *ix, int32_t k, int &fmt);
 int check_query_args(const memo_index *ix, int64_t qs, int64_t qe, int32_t k, int32_t num_docs,
                      const void *d_out);

@@ -1435,7 +1435,8 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
                 ix->last_rows_read = vrows;
                 if (table) {
                     // the tile's row slice from a table built once per (index, k): memo_sweep_cons3t.hip; 1 = does not fit
-                    const int trc = launch_halo3t(ix, A, tw, (int)sizeof(OutT), st, top9, view_cap == k - 1 && !tune.no_all_write, rpg == 6);
+                    const int trc = launch_halo3t(ix, A, tw, (int)sizeof(OutT), st, top9, view_cap == k - 1 && !tune.no_all_write, rpg == 6,
+                                                  rpg == 6 && ix->last_view_placed && ix->last_view_dead_share >= kLiveMinShare);
                     if (trc < 0) return trc;
                     if (trc == MEMO_OK) {
                         ix->last_sweep = 5;

@@ -69,11 +69,14 @@ __global__ void tile_table_kernel(const int64_t *boff, int64_t nb, int64_t bbase
 // k = 21 -3.4 %, k = 17 -4.5 %, k = 9 -6 % on config 3's views.  Not for tiles of several full batches (config 5: +2 ... +6 %:
 // behind the branches the compiler waits for ALL of a batch's loads before its first piece), hence a template flag the
 // launcher sets from the rows per tile (profiles/r06_headline.txt; masking the dead loads off with EXEC = 0 instead gained nothing).
-template <int NLEV, typename OutT, int T, bool A9 = false, bool AW = false, bool SIX = false, bool SP = false>
+// LIVE (SIX only): the view's groups say which of them hold no live row (memo_view.hip: view_live_kernel) -- a dead group's lane
+// sits out its rows' atomics, a piece without a live group is skipped (memo_sweep_dense.h: live_pieces)
+template <int NLEV, typename OutT, int T, bool A9 = false, bool AW = false, bool SIX = false, bool SP = false, bool LIVE = false>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T == 256 ? 8 : 4, 8)))
 void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     static_assert(!A9 || sizeof(OutT) == 2, "more than 255 genomes: uint16 results");
     static_assert(!(A9 && SIX), "six-row groups hold eight-bit annots");
+    static_assert(!LIVE || SIX, "dead-group flags: six-row views");
     constexpr int SH = A9 ? 23 : 24;  // a cell = order << SH | tie-breaking bits
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     constexpr int NW = T / 64, NL = kStageGroups / T;  // waves; 16-byte groups per lane and batch
@@ -153,7 +156,10 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
         }
         const uint32_t gbase = batch * kStageGroups;
         const uint32_t gleft = g.ng > gbase ? g.ng - gbase : 0;
-        if constexpr (SIX) {
+        if constexpr (SIX && LIVE) {
+            live_pieces<T, NL, AW>(V, lane, wave, gleft, C6);
+            continue;
+        } else if constexpr (SIX) {
             six_pieces<T, NL, AW>(V, lane, wave, gleft, C6);
             continue;
         }
@@ -234,16 +240,21 @@ SweepKernel kernel_of(int nlev, int elem_bytes, bool annot9) {  // (256 .. 511 g
                   : (elem_bytes == 1 ? kernel_for<uint8_t, 256, false, AW, SP>(nlev) : kernel_for<uint16_t, 256, false, AW, SP>(nlev));
 }
 
-template <typename OutT, bool AW, bool SP>
-SweepKernel kernel_six(int nlev) {
+template <typename OutT, bool AW, bool SP, bool LIVE>
+SweepKernel kernel_six_of(int nlev) {
     switch (nlev) {
-        case 1: return (SweepKernel)sweep_conservation_halo3t_kernel<1, OutT, 256, false, AW, true, SP>;
-        case 2: return (SweepKernel)sweep_conservation_halo3t_kernel<2, OutT, 256, false, AW, true, SP>;
-        case 3: return (SweepKernel)sweep_conservation_halo3t_kernel<3, OutT, 256, false, AW, true, SP>;
-        case 4: return (SweepKernel)sweep_conservation_halo3t_kernel<4, OutT, 256, false, AW, true, SP>;
-        case 5: return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, 256, false, AW, true, SP>;
+        case 1: return (SweepKernel)sweep_conservation_halo3t_kernel<1, OutT, 256, false, AW, true, SP, LIVE>;
+        case 2: return (SweepKernel)sweep_conservation_halo3t_kernel<2, OutT, 256, false, AW, true, SP, LIVE>;
+        case 3: return (SweepKernel)sweep_conservation_halo3t_kernel<3, OutT, 256, false, AW, true, SP, LIVE>;
+        case 4: return (SweepKernel)sweep_conservation_halo3t_kernel<4, OutT, 256, false, AW, true, SP, LIVE>;
+        case 5: return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, 256, false, AW, true, SP, LIVE>;
     }
     return nullptr;
+}
+
+template <typename OutT, bool AW, bool SP>
+SweepKernel kernel_six(int nlev, bool live) {
+    return live ? kernel_six_of<OutT, AW, SP, true>(nlev) : kernel_six_of<OutT, AW, SP, false>(nlev);
 }
 
 }  // namespace
@@ -307,7 +318,11 @@ static int tile_table(memo_index *ix, const void *rows_of, const int64_t *boff, 
 
 // Launch the table-driven dense-row sweep if this query fits it (else return 1: the caller takes
 // sweep_conservation_halo3_kernel).  A: filled for the unclipped sweep (hl, w, ls, nlev, ncols); tw = tile width.
-int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStream_t st, bool annot9, bool all_write, bool six) {
+// live: a six-row view whose groups carry the dead-group flag (one built with places)
+int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStream_t st, bool annot9, bool all_write, bool six, bool live) {
+#ifdef MEMO_LIVE_NEVER  // (A/B builds: every group of the view scattered, as before the flags)
+    live = false;
+#endif
     if (annot9 && elem_bytes != 2) return 1;
     if (six && (annot9 || A.nlev > 5 || ix->bshift != 5)) return 1;
     if (!A.p3 || A.ls > kLS || A.nlev < 1 || A.nlev > 6 || A.km1 > 63 || A.qs < 0) return 1;
@@ -347,11 +362,11 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
                           : (all_write ? kernel_of<true, false>(A.nlev, elem_bytes, annot9) : kernel_of<false, false>(A.nlev, elem_bytes, annot9));
     if (six) {
         if (sp)
-            kern = elem_bytes == 1 ? (all_write ? kernel_six<uint8_t, true, true>(A.nlev) : kernel_six<uint8_t, false, true>(A.nlev))
-                                   : (all_write ? kernel_six<uint16_t, true, true>(A.nlev) : kernel_six<uint16_t, false, true>(A.nlev));
+            kern = elem_bytes == 1 ? (all_write ? kernel_six<uint8_t, true, true>(A.nlev, live) : kernel_six<uint8_t, false, true>(A.nlev, live))
+                                   : (all_write ? kernel_six<uint16_t, true, true>(A.nlev, live) : kernel_six<uint16_t, false, true>(A.nlev, live));
         else
-            kern = elem_bytes == 1 ? (all_write ? kernel_six<uint8_t, true, false>(A.nlev) : kernel_six<uint8_t, false, false>(A.nlev))
-                                   : (all_write ? kernel_six<uint16_t, true, false>(A.nlev) : kernel_six<uint16_t, false, false>(A.nlev));
+            kern = elem_bytes == 1 ? (all_write ? kernel_six<uint8_t, true, false>(A.nlev, live) : kernel_six<uint8_t, false, false>(A.nlev, live))
+                                   : (all_write ? kernel_six<uint16_t, true, false>(A.nlev, live) : kernel_six<uint16_t, false, false>(A.nlev, live));
     }
     if (!kern) return 1;
     if (g_prepare_only) return MEMO_OK;  // memo_index_prepare: the table is built, nothing is launched

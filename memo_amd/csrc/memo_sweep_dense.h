@@ -269,7 +269,9 @@ struct SixConst {
 };
 
 // lg: the lane's group number inside the piece's count, left: groups of the slice left at this piece (MASKED: lanes past it do nothing)
-template <bool MASKED, bool AW>
+// ONCE (with MASKED and AW): EXEC is set once for the group's six rows, not in front of each (rows that all write need no test of
+// their own that would reset it)
+template <bool MASKED, bool AW, bool ONCE = false>
 __device__ __forceinline__ void group_rows6(const uint4 &V, const SixConst &C, uint32_t lg, uint32_t left) {
     const uint32_t lo4 = V.x >> 10, d4 = V.y << 14, lo5 = V.w >> 10, d5 = V.z << 14;
     // the cell of the bucket's first position in the tile's arrays: (bucket mod 32) * 32 - tile start, mod 1024
@@ -279,7 +281,9 @@ __device__ __forceinline__ void group_rows6(const uint4 &V, const SixConst &C, u
     MEMO_EXEC_ALL_ONES(C.status);
 #define MEMO_SIX_IN "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w), "v"(lo4), "v"(lo5), "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w), "v"(d4), "v"(d5), \
                     "v"(bias), "s"(C.km1), "s"(C.ls4), "v"(C.top_bit)
-    if constexpr (MASKED && AW) {
+    if constexpr (MASKED && AW && ONCE) {
+        asm volatile(MEMO_ROW6_MASK MEMO_SIX_ROWS("", "", "") MEMO_ROW3_DONE MEMO_G3_OUT : MEMO_SIX_IN, "v"(lg), "s"(left) : "memory", "vcc");
+    } else if constexpr (MASKED && AW) {
         asm volatile(MEMO_SIX_ROWS(MEMO_ROW6_MASK, "", MEMO_ROW3_DONE) MEMO_G3_OUT : MEMO_SIX_IN, "v"(lg), "s"(left) : "memory", "vcc");
     } else if constexpr (MASKED) {
         asm volatile(MEMO_SIX_ROWS(MEMO_ROW6_MASK, MEMO_ROW3_TEST, MEMO_ROW3_DONE) MEMO_G3_OUT : MEMO_SIX_IN, "v"(lg), "s"(left) : "memory", "vcc");
@@ -300,6 +304,28 @@ __device__ __forceinline__ void six_pieces(const uint4 (&V)[NL], int lane, int w
         if (pg + 64u <= gleft) group_rows6<false, AW>(V[J], C, 0, 0);
         else group_rows6<true, AW>(V[J], C, pg + (uint32_t)lane, gleft);
         six_pieces<T, NL, AW, J + 1>(V, lane, wave, gleft, C);
+    }
+}
+
+// ---- LIVE: views whose groups say which of them hold no live row (memo_view.hip: view_live_kernel, kDeadGroup) -----------------
+// A view row that a row of lower order contains at every k never decides a minimum; the view builder puts a bucket's live rows
+// in its first groups and sets kDeadGroup in the first dword of every group without one (most of config 3's at k = 31).
+// The loads stay as they are (the bytes a sweep reads do not change); a dead group's lane sits out its rows' two atomics each, which
+// leaves a quarter of the lanes of a row instruction to spread over the LDS banks, and a piece of 64 dead groups is skipped.
+// (Packing the live groups first was slower both ways it was built: across the tile, staged in level array 0 before its clear
+// with two more barriers, k = 31 -1.5 %, k = 21 +10 %, k = 17 +18 %; inside each wave by ds_permute rotations, no barrier,
+// k = 31 -1.5 %, k = 21 +5 %, k = 17 +14 % -- fuller row instructions meet on the banks again: profiles/r07_live_rows.txt.)
+constexpr uint32_t kDeadGroup = 1u << 20;
+
+// the NL groups of a lane (as six_pieces), the dead ones masked off
+template <int T, int NL, bool AW, int J = 0>
+__device__ __forceinline__ void live_pieces(const uint4 (&V)[NL], int lane, int wave, uint32_t gleft, const SixConst &C) {
+    if constexpr (J < NL) {
+        const uint32_t pg = (uint32_t)(J * T + wave * 64);
+        if (pg >= gleft) return;
+        const bool on = pg + (uint32_t)lane < gleft && !(V[J].x & kDeadGroup);
+        if (__ballot(on)) group_rows6<true, AW, true>(V[J], C, on ? 0u : 1u, 1u);
+        live_pieces<T, NL, AW, J + 1>(V, lane, wave, gleft, C);
     }
 }
 

@@ -219,7 +219,17 @@ struct ViewArgs {
     int km1;                 // the k - 1 whose level arrays the places are chosen for (the class's cap); 0: rows keep their order
     int run_buckets;         // buckets per run (<= kViewRun)
     int stage_rows;          // kept rows the LDS stage holds (kViewCapPlaced / kViewCapPlain)
+    const uint8_t *dead8;    // P = 6 with places: bit i of byte g: source row 5 g + i is contained (view_live_kernel); NULL: none is
+    unsigned long long *dead_groups;  // ... groups flagged kDeadGroup (counted)
 };
+
+// A kept row b = (s, ov, order) covers [s + ov - (k - 1), s) at every k.  A kept row a of strictly LOWER order with s_a >= s_b and
+// s_a + ov_a <= s_b + ov_b covers all of it at every k (k moves both left ends alike), so b never decides a minimum: b is DEAD.
+// (Equal orders: both stay.)  a starts within ov_b < 32 positions of b: in b's bucket or the next (bshift 5: six-row views only).
+// W (group_row) carries the verdict in bit 25 through the stage; a group of six slots that holds no live row has kDeadGroup set in
+// its first dword (a bit group_rows6 does not decode): the sweep skips it (memo_sweep_cons3t.hip: LIVE).
+constexpr uint32_t kDeadRow = 1u << 25;
+constexpr uint32_t kDeadGroup = 1u << 20;
 
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long ballot) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
@@ -258,6 +268,7 @@ __device__ __forceinline__ uint32_t view_load_compact(const ViewArgs &a, const V
             const uint64_t g = g0 + (uint64_t)(64 * u + lane);
             if (g0 + (uint64_t)(64 * u) >= g_hi) break;  // (wave-uniform)
             uint32_t m = g < g_hi ? group_keep(R[u], g, a.rows, a.cap) : 0u;
+            const uint32_t dm = (a.dead8 && g < g_hi) ? (uint32_t)a.dead8[g] << 25 : 0u;  // (bit 25 + i: row i is dead)
             const uint64_t r = 5 * g;  // rows of the group outside [r_lo, r_hi): the first and the last group of the range
             if (r < r_lo) m &= ~((1u << (uint32_t)(r_lo - r)) - 1u);
             if (r + 5 > r_hi) m &= r >= r_hi ? 0u : (1u << (uint32_t)(r_hi - r)) - 1u;
@@ -266,15 +277,15 @@ __device__ __forceinline__ uint32_t view_load_compact(const ViewArgs &a, const V
             uint32_t idx = n + lanes_below(b0) + lanes_below(b1) + lanes_below(b2) + lanes_below(b3) + lanes_below(b4);
             // (no branches: a row that goes is stored to a slot nobody reads -- plain stores of many lanes to one address cost one)
             const uint32_t kNowhere = L.cap + 7u;
-            L.stage[(m & 1u) ? idx : kNowhere] = group_row<0>(R[u]);
+            L.stage[(m & 1u) ? idx : kNowhere] = group_row<0>(R[u]) | ((dm >> 0) & kDeadRow);
             idx += m & 1u;
-            L.stage[(m & 2u) ? idx : kNowhere] = group_row<1>(R[u]);
+            L.stage[(m & 2u) ? idx : kNowhere] = group_row<1>(R[u]) | ((dm >> 1) & kDeadRow);
             idx += (m >> 1) & 1u;
-            L.stage[(m & 4u) ? idx : kNowhere] = group_row<2>(R[u]);
+            L.stage[(m & 4u) ? idx : kNowhere] = group_row<2>(R[u]) | ((dm >> 2) & kDeadRow);
             idx += (m >> 2) & 1u;
-            L.stage[(m & 8u) ? idx : kNowhere] = group_row<3>(R[u]);
+            L.stage[(m & 8u) ? idx : kNowhere] = group_row<3>(R[u]) | ((dm >> 3) & kDeadRow);
             idx += (m >> 3) & 1u;
-            L.stage[(m & 16u) ? idx : kNowhere] = group_row<4>(R[u]);
+            L.stage[(m & 16u) ? idx : kNowhere] = group_row<4>(R[u]) | ((dm >> 4) & kDeadRow);
             n += (uint32_t)(__popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3) + __popcll(b4));
         }
     };
@@ -322,13 +333,19 @@ template <int P>
 __device__ __forceinline__ uint32_t view_emit(const ViewArgs &a, const ViewLds &L, uint64_t gout, uint32_t ns, uint32_t from, bool tail,
                                               int lane) {
     const uint32_t whole = ns / P, all = whole + ((tail && ns % P) ? 1u : 0u);
+    uint32_t flagged = 0;
     for (uint32_t t = (uint32_t)lane; t < all; t += 64) {
         const uint32_t lo = t == 0 ? from : 0u, hi = ns - P * t < (uint32_t)P ? ns - P * t : (uint32_t)P;
         if constexpr (P == 6) {
             uint32_t w[6];
 #pragma unroll
             for (int i = 0; i < 6; ++i) w[i] = L.stage[L.inv[6 * t + i]];
-            a.out[gout + t] = pack_six(w);
+            uint4 g = pack_six(w);
+            if (a.dead8 && (w[0] & w[1] & w[2] & w[3] & w[4] & w[5] & kDeadRow)) {
+                g.x |= kDeadGroup;
+                ++flagged;
+            }
+            a.out[gout + t] = g;
         } else {
             uint32_t w[5];
 #pragma unroll
@@ -345,12 +362,18 @@ __device__ __forceinline__ uint32_t view_emit(const ViewArgs &a, const ViewLds &
             }
         }
     }
+    if (P == 6 && a.dead8) {  // (every lane of the wave is here)
+        for (int off = 32; off; off >>= 1) flagged += (uint32_t)__shfl_xor((int)flagged, off, 64);
+        if (lane == 0 && flagged) atomicAdd(a.dead_groups, (unsigned long long)flagged);
+    }
     return whole;
 }
 
 // lane's bucket: rows stage[off .. off + n) -> inv[bslot + place]: the place of every row among the bucket's slots.
 // P = 5: slot q of the bucket is the view's row vb + q, its place in its group (vb + q) mod 5; P = 6: 6 * ng slots, place q mod 6.
-// The lanes of a wave run this together, a bucket each.
+// The lanes of a wave run this together, a bucket each.  nl: the bucket's first nl rows are its live ones (view_live_kernel; nl = n
+// when there is no verdict) -- P = 6 places them inside the bucket's first ceil(nl / 6) groups, then the dead rows; lastp: the stage
+// slot of the bucket's last row in source order (what the places no row took hold a copy of, as in the view without places).
 //
 // The places (round 4's one-lane-per-bucket kernel, NOTEBOOK.md; the cost model: profiles/r04_lds_atomics.txt, tools/view_order_model.py).  The sweep gives
 // a lane one group, and a wave's i-th row instruction visits place i of 64 consecutive groups: a half-wave's 32 atomics of one
@@ -365,12 +388,12 @@ __device__ __forceinline__ uint32_t view_emit(const ViewArgs &a, const ViewLds &
 // 0.5 % of a sweep, and it was a third of this pass's instructions and a quarter of its LDS.
 template <int P>
 __device__ __forceinline__ void view_place_bucket(const ViewArgs &a, const ViewLds &L, uint32_t off, uint32_t n, uint32_t bslot,
-                                                  uint32_t vb_mod5, int lane) {
+                                                  uint32_t vb_mod5, int lane, uint32_t nl, uint32_t lastp) {
     const uint32_t ng = (n + P - 1) / P;
     const bool colour = a.km1 > 0 && n >= 6 && n <= (uint32_t)(P == 6 ? kColourMax6 : kColourMax5);
     if (!colour) {  // as they come (P = 6: the places the bucket leaves empty hold a copy of its last row)
         if (n)
-            for (uint32_t q = 0; q < (P == 6 ? 6 * ng : n); ++q) L.inv[bslot + q] = (uint16_t)(off + (q < n ? q : n - 1));
+            for (uint32_t q = 0; q < (P == 6 ? 6 * ng : n); ++q) L.inv[bslot + q] = (uint16_t)(q < n ? off + q : lastp);
     }
     if (!__ballot(colour)) return;
     const uint32_t km1 = (uint32_t)a.km1;
@@ -388,6 +411,13 @@ __device__ __forceinline__ void view_place_bucket(const ViewArgs &a, const ViewL
         notfull |= room ? 1u << c : 0u;
     }
     const uint32_t nc = colour ? n : 0u;  // rows this lane places
+    // P = 6: the live rows first, into the first gl groups (every colour's room gl), then the rest (room ng)
+    const uint32_t gl = (nl + 5u) / 6u;
+    uint32_t lim = ng;
+    if (P == 6 && nl < n && nl) {
+        lim = gl;
+        notfull = 0x3Fu;
+    }
     uint8_t *a1p = L.am1 + lane, *a2p = L.am2 + lane, *b1p = L.bm1 + lane, *b2p = L.bm2 + lane;
     uint32_t loads = 0;
     uint32_t w_next = nc ? L.stage[off] : 0u;
@@ -396,6 +426,12 @@ __device__ __forceinline__ void view_place_bucket(const ViewArgs &a, const ViewL
         const bool on = j < nc;
         w_next = j + 1 < nc ? L.stage[off + j + 1] : 0u;  // (a row ahead: the read is in flight under this row's arithmetic)
         if (!on) continue;
+        if (P == 6 && j == nl && lim != ng) {  // (the dead rows: every colour's room is ng again)
+            lim = ng;
+            notfull = 0;
+#pragma unroll
+            for (int c = 0; c < P; ++c) notfull |= ((loads >> (5 * c)) & 31u) < ng ? 1u << c : 0u;
+        }
         const uint32_t ov = w & 63u, s = (w >> 6) & 1023u;
         const uint32_t nn = km1 - ov;  // (>= 1: the view holds the rows whose overlap is below the cap)
         const uint32_t ra = (s - nn) & 31u;                                           // first block: cell start - (k - 1) + overlap
@@ -427,12 +463,65 @@ __device__ __forceinline__ void view_place_bucket(const ViewArgs &a, const ViewL
         b2p[64u * rb] = (uint8_t)(b2 | (b1 & bit));
         b1p[64u * rb] = (uint8_t)(b1 | bit);
         loads += 1u << (5 * c);
-        if (ld + 1u == ((rooms >> (5 * c)) & 31u)) notfull &= ~bit;
+        if (ld + 1u == (P == 6 ? lim : ((rooms >> (5 * c)) & 31u))) notfull &= ~bit;
     }
     if constexpr (P == 6) {  // the places no row took (6 ng - n of them, five at most): a copy of the bucket's last row
         if (nc)
             for (int c = 0; c < 6; ++c)
-                for (uint32_t g = (loads >> (5 * c)) & 31u; g < ng; ++g) L.inv[bslot + 6u * g + (uint32_t)c] = (uint16_t)(off + n - 1);
+                for (uint32_t g = (loads >> (5 * c)) & 31u; g < ng; ++g) L.inv[bslot + 6u * g + (uint32_t)c] = (uint16_t)lastp;
+    }
+}
+
+// source row r of the dense rows as W (group_row)
+__device__ __forceinline__ uint32_t source_row(const uint4 *__restrict__ src, uint64_t r) {
+    const uint4 V = src[r / 5];
+    switch ((uint32_t)(r % 5)) {
+        case 0: return group_row<0>(V);
+        case 1: return group_row<1>(V);
+        case 2: return group_row<2>(V);
+        case 3: return group_row<3>(V);
+    }
+    return group_row<4>(V);
+}
+
+// The dead kept rows (ViewArgs::dead8; bshift 5) -- a wave per bucket b: M[t][j] = the least order of the kept rows of buckets b and
+// b + 1 that start at position t of the two (0 .. 63) with overlap <= j, then a kept row (s, ov, order) of b is dead iff
+// min over d = 0 .. ov of M[s + d][ov - d] < order.  dead: a byte per source group (zeroed), or-ed into as 32-bit words.
+__global__ __launch_bounds__(64) void view_live_kernel(const uint4 *__restrict__ src, const int64_t *__restrict__ boff, int64_t nbuckets,
+                                                       uint32_t cap, uint32_t *__restrict__ dead) {
+    __shared__ uint32_t M[64 * 33];  // (33: a lane's row of the prefix pass on a bank of its own)
+    const int lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < nbuckets; b += gridDim.x) {
+        const uint64_t r0 = (uint64_t)boff[b], r1 = (uint64_t)boff[b + 1], r2 = b + 1 < nbuckets ? (uint64_t)boff[b + 2] : r1;
+        for (int i = lane; i < 64 * 33; i += 64) M[i] = 0xFFFFFFFFu;
+        __syncthreads();
+        for (uint64_t r = r0 + (uint64_t)lane; r < r2; r += 64) {
+            const uint32_t w = source_row(src, r), ov = w & 63u;
+            if (ov < cap) atomicMin(&M[((r < r1 ? 0u : 32u) + ((w >> 6) & 31u)) * 33u + ov], (w >> 16) & 0x1FFu);
+        }
+        __syncthreads();
+        uint32_t m = M[lane * 33];
+        for (int j = 1; j < 32; ++j) {
+            const uint32_t x = M[lane * 33 + j];
+            m = x < m ? x : m;
+            M[lane * 33 + j] = m;
+        }
+        __syncthreads();
+        for (uint64_t r = r0 + (uint64_t)lane; r < r1; r += 64) {
+            const uint32_t w = source_row(src, r), ov = w & 63u;
+            if (ov >= cap) continue;
+            const uint32_t s = (w >> 6) & 31u, order = (w >> 16) & 0x1FFu;
+            uint32_t least = 0xFFFFFFFFu;
+            for (uint32_t d = 0; d <= ov; ++d) {
+                const uint32_t x = M[(s + d) * 33u + ov - d];
+                least = x < least ? x : least;
+            }
+            if (least < order) {
+                const uint64_t g = r / 5;
+                atomicOr(dead + (g >> 2), 1u << (8u * (uint32_t)(g & 3) + (uint32_t)(r - 5 * g)));
+            }
+        }
+        __syncthreads();
     }
 }
 
@@ -495,8 +584,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
                 }
                 if (a.km1 > 0)
                     for (int i = lane; i < 4 * 32 * 64 / 4; i += 64) reinterpret_cast<uint32_t *>(L.am1)[i] = 0;  // (no colour holds a row yet)
+                // the live rows of the lane's bucket to its front (swaps: a row moves only when a live row comes after a dead one --
+                // the last row in source order ends at nl - 1 when live, stays at n - 1 when dead)
+                uint32_t nl = n, lastp = off + (n ? n - 1 : 0);
+                if (P == 6 && a.dead8 && n) {
+                    const bool last_live = !(L.stage[off + n - 1] & kDeadRow);
+                    nl = 0;
+                    for (uint32_t j = 0; j < n; ++j) {
+                        const uint32_t w = L.stage[off + j];
+                        if (w & kDeadRow) continue;
+                        if (j != nl) {
+                            L.stage[off + j] = L.stage[off + nl];
+                            L.stage[off + nl] = w;
+                        }
+                        ++nl;
+                    }
+                    lastp = off + (last_live ? nl - 1 : n - 1);
+                }
                 __syncthreads();
-                view_place_bucket<P>(a, L, off, n, bslot, (uint32_t)(vb % 5), lane);
+                view_place_bucket<P>(a, L, off, n, bslot, (uint32_t)(vb % 5), lane, nl, lastp);
                 __syncthreads();
                 if constexpr (P == 6) {
                     const uint64_t gend = (uint64_t)__shfl((long long)(gq + (ve - vb + 5) / 6), e - 1, 64);
@@ -605,7 +711,7 @@ hipError_t side_alloc(void **p, size_t bytes) {
 // the fused pass (view_build_kernel) are queued on `st`; the call waits for them twice (the kept rows decide the allocation).
 static int dense_view_build(int device, const uint32_t *src_p3, const int64_t *src_boff, uint64_t rows, uint64_t nb, int cap, int min_tenths,
                             hipStream_t st, int rpg, int colour_km1, uint32_t **out_p3, int64_t **out_boff, uint64_t *out_rows,
-                            uint64_t *out_padded) {
+                            uint64_t *out_padded, uint64_t *out_dead = nullptr) {
     *out_p3 = nullptr;
     *out_boff = nullptr;
     if (!rows || rows >= ((uint64_t)1 << 38) || nb < 2) return MEMO_OK;
@@ -615,7 +721,10 @@ static int dense_view_build(int device, const uint32_t *src_p3, const int64_t *s
     // one allocation for everything that goes again: keep bytes, the two scans' arrays
     auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
     const uint64_t o_keep = 0, o_count = o_keep + up(chunks * 64), o_bpre = o_count + up(chunks * 4), o_gcount = o_bpre + up((nblk + 1) * 8),
-                   o_gblock = o_gcount + up(rpg == 6 ? nbk * 4 + 4 : 0), tmp_bytes = o_gblock + up(rpg == 6 ? (nblk6 + 1) * 8 : 0);
+                   o_gblock = o_gcount + up(rpg == 6 ? nbk * 4 + 4 : 0), o_dead = o_gblock + up(rpg == 6 ? (nblk6 + 1) * 8 : 0);
+    const bool live = rpg == 6 && colour_km1 > 0 && cap <= 32;  // (the dead rows: views of six rows with places)
+    const uint64_t o_ndead = o_dead + up(live ? chunks * 64 : 0), tmp_bytes = o_ndead + up(live ? 8 : 0);
+    if (out_dead) *out_dead = 0;
     char *tmp = nullptr;
     uint4 *outg = nullptr;
     int64_t *boffv = nullptr, *boff6 = nullptr;
@@ -669,6 +778,17 @@ static int dense_view_build(int device, const uint32_t *src_p3, const int64_t *s
         a.boff6 = boff6;
         a.cap = (uint32_t)cap;
         a.km1 = colour_km1;
+        a.dead8 = nullptr;
+        a.dead_groups = reinterpret_cast<unsigned long long *>(tmp + o_ndead);
+        uint64_t ndead = 0;
+        if (live) {
+            uint8_t *dead8 = reinterpret_cast<uint8_t *>(tmp + o_dead);
+            err = hipMemsetAsync(dead8, 0, o_ndead + 8 - o_dead, st);  // (the dead bits and their group count)
+            if (err != hipSuccess) { rc = fail(MEMO_EHIP, "dense view: %s", hipGetErrorString(err)); break; }
+            hipLaunchKernelGGL(view_live_kernel, dim3((unsigned)(nbk < 256 * 32 ? nbk : 256 * 32)), dim3(64), 0, st, p3, src_boff, (int64_t)nbk,
+                               (uint32_t)cap, reinterpret_cast<uint32_t *>(dead8));
+            a.dead8 = dead8;
+        }
         // buckets per run: as many as (nearly always) fit the stage whole, so that a run is one piece and every lane has a bucket
         const double per_bucket = (double)total / (double)nbk;
         a.stage_rows = colour_km1 > 0 ? kViewCapPlaced : kViewCapPlain;
@@ -685,8 +805,10 @@ static int dense_view_build(int device, const uint32_t *src_p3, const int64_t *s
         else
             hipLaunchKernelGGL(view_build_kernel<5>, dim3(grid), dim3(64), lds_bytes, st, a);
         err = hipGetLastError();
+        if (err == hipSuccess && live) err = hipMemcpyAsync(&ndead, a.dead_groups, 8, hipMemcpyDeviceToHost, st);
         if (err == hipSuccess) err = hipStreamSynchronize(st);
         if (err != hipSuccess) { rc = fail(MEMO_EHIP, "dense view: %s", hipGetErrorString(err)); break; }
+        if (out_dead) *out_dead = ndead;
         *out_p3 = reinterpret_cast<uint32_t *>(outg);
         *out_boff = rpg == 6 ? boff6 : boffv;
         *out_rows = total;
@@ -1143,6 +1265,7 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint
     if (view_cap) *view_cap = 0;  // (the cap of the view handed out: its rows are exactly those with overlap < cap)
     if (rpg) *rpg = 5;
     ix->last_view_placed = 0;
+    ix->last_view_dead_share = 0;
     ix->last_view_rpg = 5;
     *p3 = ix->p3;
     *boff = ix->boff3 ? ix->boff3 : ix->boff;
@@ -1177,7 +1300,7 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint
         const bool place = can_place && g_prepare_only;  // (asked for: everything at once; a query: first the view)
         const int rc = build_timed(ix, v, st, [&]() {
             return dense_view_build(ix->device, src_p3, src_boff, nsrc, ix->nb, cap, 2, st, rpg_arg, place ? cap : 0, &v.p3, &v.boff, &v.rows,
-                                    &v.padded);
+                                    &v.padded, &v.dead_groups);
         });
         if (rc && rc != kNoRoom) return rc;  // (no room on the device for a view: the sweep reads all the rows)
         v.cap = cap;
@@ -1203,7 +1326,8 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint
         DeviceGuard guard(ix->device);
         memo_index::DenseView nv;
         const int rc = build_timed(ix, nv, st, [&]() {
-            return dense_view_build(ix->device, src_p3, src_boff, nsrc, ix->nb, cap, 0, st, rpg_arg, cap, &nv.p3, &nv.boff, &nv.rows, &nv.padded);
+            return dense_view_build(ix->device, src_p3, src_boff, nsrc, ix->nb, cap, 0, st, rpg_arg, cap, &nv.p3, &nv.boff, &nv.rows, &nv.padded,
+                                    &nv.dead_groups);
         });
         if (rc && rc != kNoRoom) return rc;
         if (rc == kNoRoom || !nv.p3) {  // (no room for the second copy: the view stays as it is; look again much later)
@@ -1233,6 +1357,7 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint
         if (view_cap) *view_cap = v.cap;
         if (rpg) *rpg = six ? 6 : 5;
         ix->last_view_placed = v.placed;
+        ix->last_view_dead_share = six && v.padded ? 6.0 * (double)v.dead_groups / (double)v.padded : 0.0;
         ix->last_view_rpg = six ? 6 : 5;
     }
     return MEMO_OK;
