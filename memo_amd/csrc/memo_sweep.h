@@ -92,21 +92,8 @@ __device__ __forceinline__ void row_slice(const SweepArgs &A, int64_t a, int64_t
     int64_t b1 = lim <= 0 ? 0 : ((lim + ((int64_t)1 << A.bshift) - 1) >> A.bshift) - A.bbase;
     b0 = b0 < 0 ? 0 : (b0 > last ? last : b0);
     b1 = b1 < 0 ? 0 : (b1 > last ? last : b1);
-#ifdef MEMO_SYNTH_LOCATE
-    // diagnostic build only: the bucket table of the synthetic config-3 index in closed form (5 rows per
-    // position, start_i = 1 + i / 5) -- what would the sweep gain if a tile's row slice cost no memory access?
-    (void)last;
-    auto first_row = [&](int64_t pos) { return pos <= 1 ? (int64_t)0 : 5 * (pos - 1); };
-    const int64_t rows_total = A.boff ? (int64_t)MEMO_SYNTH_LOCATE : 0;
-    int64_t q0 = first_row((b0 + A.bbase) << A.bshift), q1 = first_row((b1 + A.bbase) << A.bshift);
-    q0 = q0 > rows_total ? rows_total : q0;
-    q1 = q1 > rows_total ? rows_total : q1;
-    r0 = a <= 0 ? 0 : (uint64_t)q0;
-    r1 = (uint64_t)q1;
-#else
     r0 = a <= 0 ? 0 : (uint64_t)A.boff[b0];  // (rows with a negative start lie before bucket 0)
     r1 = (uint64_t)A.boff[b1];
-#endif
 }
 
 // The branch-free row blocks (v_cmpx ... s_mov_b64 exec, -1) are right only when every lane is enabled on entry, which
@@ -131,17 +118,6 @@ __device__ __forceinline__ int clamp_to_tile(int64_t v, int lo, int hi) {
 // shared pieces of the sweep kernels.  T = threads per workgroup (64 = one wave owns the tile;
 // 256 = four waves share it and meet at workgroup barriers between the phases).
 // ------------------------------------------------------------------------------------------
-#ifndef MEMO_KU
-#define MEMO_KU 4
-#endif
-
-// Level arrays of the conservation sweep are W + kLevelSkew words apart: rows that hit the same
-// position on different levels then fall into different LDS banks.
-#ifndef MEMO_SKEW
-#define MEMO_SKEW 0
-#endif
-constexpr int kLevelSkew = MEMO_SKEW;
-
 struct Tile {
     int64_t a;     // pivot position of tile slot 0
     int x_lo, x_hi;  // slots of the tile that lie inside the window
@@ -191,7 +167,7 @@ __device__ __forceinline__ bool check_col(const SweepArgs &A, int64_t o, int &co
 // the Parquet columns as they are: 3 x int64 per row.  2 rows per lane per column per load
 // (16 B / lane, 1 KiB / wave), U loads of each column in flight per lane.
 struct WideRows {
-    static constexpr int kLoads = MEMO_KU;  // loads of each column in flight per lane
+    static constexpr int kLoads = 4;  // loads of each column in flight per lane
     // `between` runs once, in every thread, before any row is handed to f: the kernels clear their
     // LDS tile there.  PackedRows issues its first batch of loads before it; here (ten batches per
     // tile, HBM-bound) that ordering measured 5 % slower, so the tile is cleared first.
@@ -268,7 +244,7 @@ __device__ __forceinline__ int pin_vgpr(int uniform) {
 template <bool ANNOT16, bool CHECKED, bool W12 = false>
 struct PackedRows {
     static_assert(!(ANNOT16 && W12), "a 12-bit annot rides in the word");
-    static constexpr int kLoads = 2 * MEMO_KU;  // A/B: 8 x 16 B in flight per lane, 5 % over 4
+    static constexpr int kLoads = 8;  // 16-byte loads in flight per lane: 5 % faster than 4
     static constexpr bool kAnnot16 = ANNOT16;
     static constexpr bool kW12 = W12;
     static constexpr int kTopShift = W12 ? 20 : 24;  // where the annot sits when it rides in the word

@@ -15,7 +15,7 @@ template <typename Rows, int W, int U, int T, typename OutT>
 __global__ __launch_bounds__(T) void sweep_conservation_kernel(const SweepArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int tid = threadIdx.x;
-    constexpr int LS = W + kLevelSkew;  // words between level arrays
+    constexpr int LS = W;  // words between level arrays
     Tile t;
 #ifdef MEMO_STAMPS
     unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime();
@@ -100,23 +100,12 @@ __global__ __launch_bounds__(T) void sweep_conservation_kernel(const SweepArgs A
 // (Measured and dropped, profiles/r01_unclipped_scatter.txt: a workgroup walking 2..32 tiles with
 // the next tile's rows in flight under the fold -- 6-17 % slower than one tile per workgroup.)
 // ------------------------------------------------------------------------------------------
-#ifndef MEMO_HALO_WAVES
-#define MEMO_HALO_WAVES 8
-#endif
-// diagnostic builds only (tools/build_variant.sh): bit 0 / 1 = drop the first / second ds_min of a row,
-// 2 = no fold passes, 3 = no clear, 4 = no scatter arithmetic at all (rows are loaded and dropped).
-// Results are wrong with any of them; they size what each phase costs.
-#ifndef MEMO_ABLATE
-#define MEMO_ABLATE 0
-#endif
-
 // every level starts at the sentinel column N (memo_query.py:53-54); under the first loads
 template <int T>
 __device__ __forceinline__ void halo_clear(const SweepArgs &A, uint32_t *lds, uint32_t sent) {
     const uint4 sv = make_uint4(sent, sent, sent, sent);
     uint4 *p = reinterpret_cast<uint4 *>(lds);
-    if (!(MEMO_ABLATE & 8))
-        for (int i = threadIdx.x; i < A.nlev * (A.ls / 4); i += T) p[i] = sv;
+    for (int i = threadIdx.x; i < A.nlev * (A.ls / 4); i += T) p[i] = sv;
     lds_barrier();
 }
 
@@ -126,7 +115,7 @@ template <typename OutT, int T, int TOP>
 __device__ __forceinline__ void halo_fold_store(const SweepArgs &A, const Tile &t, uint32_t *lds) {
     const int LS = A.ls, HL = A.hl, W = A.w;
     const int cells = HL + W;
-    for (int slot = 0; slot + 2 < A.nlev && !(MEMO_ABLATE & 4); ++slot) {  // (the last fold happens in store_conservation)
+    for (int slot = 0; slot + 2 < A.nlev; ++slot) {  // (the last fold happens in store_conservation)
         const int half = 1 << (A.nlev - 2 - slot);
         const uint32_t *hi = lds + slot * LS;
         uint32_t *lo = lds + (slot + 1) * LS;
@@ -216,15 +205,10 @@ __device__ __forceinline__ void halo_fold_store_dpp(const SweepArgs &A, const Ti
     }
 }
 
-#ifndef MEMO_FOLD_REG
-#define MEMO_FOLD_REG 1
-#endif
-#ifndef MEMO_FOLD_DPP_LEVELS
-#define MEMO_FOLD_DPP_LEVELS 7  // most levels folded in registers (<= 7: 2^(levels - 3) context lanes per wave)
-#endif
 template <typename OutT, int T, int TOP>
 __device__ __forceinline__ void halo_finish(const SweepArgs &A, const Tile &t, uint32_t *lds) {
-    if (MEMO_FOLD_REG && A.nlev <= MEMO_FOLD_DPP_LEVELS)  // (any window: store_four takes the address as it comes)
+    constexpr int kFoldDppLevels = 7;  // most levels folded in registers (<= 7: 2^(levels - 3) context lanes per wave)
+    if (A.nlev <= kFoldDppLevels)  // (any window: store_four takes the address as it comes)
         halo_fold_store_dpp<OutT, T, TOP>(A, t, lds);
     else
         halo_fold_store<OutT, T, TOP>(A, t, lds);
@@ -236,10 +220,7 @@ __device__ __forceinline__ void halo_finish(const SweepArgs &A, const Tile &t, u
 // same test -- v_cmp, s_and_saveexec, s_cbranch_execz, ..., s_or -- costs three scalar instructions and a branch
 // per row, and the CU's one scalar unit was as busy as its vector pipes (1.3e8 SALU against 1.5e8 VALU
 // wave-instructions per launch): dense rows, sustained, k = 21 / 31 / 64: 0.3218 -> 0.3133, 0.3249 -> 0.318,
-// 0.383 -> 0.374 ms (profiles/r02_dense_rows_ab.txt).  MEMO_ROW_CMPX=0 builds the branchy form for A/B.
-#ifndef MEMO_ROW_CMPX
-#define MEMO_ROW_CMPX 1
-#endif
+// 0.383 -> 0.374 ms (profiles/r02_dense_rows_ab.txt).
 
 // 4- and 6-byte rows.  The 4-byte rows carry their order in the top byte of the word, and the cells
 // take the WORD (ds_min_u32 of the row as it was loaded: the min of the words has the min order on
@@ -247,7 +228,7 @@ __device__ __forceinline__ void halo_finish(const SweepArgs &A, const Tile &t, u
 // the store keeps the top bits (TOP = 24 / 20; needs num_docs to fit the field for the sentinel).  Otherwise the cells
 // hold the order itself: the word's top byte shifted down, or the 16-bit order column.
 template <typename Rows, int U, int T, typename OutT, int TOP>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MEMO_HALO_WAVES, 8)))
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void sweep_conservation_halo_kernel(const SweepArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     static_assert(TOP == 0 || (!Rows::kAnnot16 && TOP == Rows::kTopShift), "the order rides in the word only in the 4-byte formats");
@@ -272,76 +253,44 @@ void sweep_conservation_halo_kernel(const SweepArgs A) {
     const uint32_t bias4 = pin_vgpr((int)(lds_base + 4u * (uint32_t)HL - (uint32_t)(32 - A.nlev) * ls4));
     const uint32_t top_bit = pin_vgpr((int)0x80000000u);
     const uint32_t key = pin_vgpr((int)Rows::tile_key(t.a));
-    auto scatter = [&](uint32_t w, uint32_t col) {
-        if (MEMO_ABLATE & 16) {  // keep the loads alive, nothing else
-            asm volatile("" ::"v"(w), "v"(col));
-            return;
-        }
-        if (MEMO_ROW_CMPX && !(MEMO_ABLATE & 3)) {  // n, the test, start - a, the two cells, both ds_min: one block
-            uint32_t r0, r1, r2, nn;
-            MEMO_EXEC_ALL_ONES(A.status);
-            if constexpr (!Rows::kW12)
-                asm volatile(
-                    "v_sub_u32_sdwa %3, %5, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                    "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                    "v_sub_u16 %1, %4, %6\n\t"
-                    "v_ffbh_u32 %0, %3\n\t"
-                    "v_mad_u32_u24 %2, %0, %7, %8\n\t"
-                    "v_lshl_add_u32 %2, %1, 2, %2\n\t"
-                    "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                    "v_ashrrev_i32 %0, %0, %9\n\t"
-                    "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                    "ds_min_u32 %1, %10\n\t"
-                    "ds_min_u32 %2, %10\n\t"
-                    "s_mov_b64 exec, -1"
-                    : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(nn)
-                    : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                    : "memory", "vcc");
-            else
-                asm volatile(
-                    "v_sub_u32_sdwa %3, %5, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-                    "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                    "v_sub_u32 %1, %4, %6\n\t"
-                    "v_bfe_u32 %1, %1, 8, 12\n\t"
-                    "v_ffbh_u32 %0, %3\n\t"
-                    "v_mad_u32_u24 %2, %0, %7, %8\n\t"
-                    "v_lshl_add_u32 %2, %1, 2, %2\n\t"
-                    "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                    "v_ashrrev_i32 %0, %0, %9\n\t"
-                    "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                    "ds_min_u32 %1, %10\n\t"
-                    "ds_min_u32 %2, %10\n\t"
-                    "s_mov_b64 exec, -1"
-                    : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(nn)
-                    : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                    : "memory", "vcc");
-            return;
-        }
-        const int n = km1 - Rows::len(w);  // length of [end - (k-1), start)
-        if (n > 0) {
-            // f = clz(n); 2^j = 2^31 >> f; x4 = address of cell `start` on level f;
-            // ds_min into the cells of blocks [start - n, .. + 2^j) and [start - 2^j, start).
-            // The compiler's own rendering of this needs 13 VALU instructions, one of them a
-            // quarter-rate multiply.
-            const uint32_t d = Rows::rel_start(w, key);  // start - a: v_sub_u16, or subtract + bit-field extract (12-bit form)
-            uint32_t r0, r1, r2;
+    auto scatter = [&](uint32_t w, uint32_t col) {  // n, the test, start - a, the two cells, both ds_min: one block
+        uint32_t r0, r1, r2, nn;
+        MEMO_EXEC_ALL_ONES(A.status);
+        if constexpr (!Rows::kW12)
             asm volatile(
+                "v_sub_u32_sdwa %3, %5, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
+                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
+                "v_sub_u16 %1, %4, %6\n\t"
                 "v_ffbh_u32 %0, %3\n\t"
-                "v_mad_u32_u24 %2, %0, %5, %6\n\t"
-                "v_lshl_add_u32 %2, %4, 2, %2\n\t"
+                "v_mad_u32_u24 %2, %0, %7, %8\n\t"
+                "v_lshl_add_u32 %2, %1, 2, %2\n\t"
                 "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                "v_ashrrev_i32 %0, %0, %7\n\t"
+                "v_ashrrev_i32 %0, %0, %9\n\t"
                 "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-#if !(MEMO_ABLATE & 1)
-                "ds_min_u32 %1, %8\n\t"
-#endif
-#if !(MEMO_ABLATE & 2)
-                "ds_min_u32 %2, %8"
-#endif
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2)
-                : "v"(n), "v"(d), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                : "memory");
-        }
+                "ds_min_u32 %1, %10\n\t"
+                "ds_min_u32 %2, %10\n\t"
+                "s_mov_b64 exec, -1"
+                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(nn)
+                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
+                : "memory", "vcc");
+        else
+            asm volatile(
+                "v_sub_u32_sdwa %3, %5, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
+                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
+                "v_sub_u32 %1, %4, %6\n\t"
+                "v_bfe_u32 %1, %1, 8, 12\n\t"
+                "v_ffbh_u32 %0, %3\n\t"
+                "v_mad_u32_u24 %2, %0, %7, %8\n\t"
+                "v_lshl_add_u32 %2, %1, 2, %2\n\t"
+                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
+                "v_ashrrev_i32 %0, %0, %9\n\t"
+                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
+                "ds_min_u32 %1, %10\n\t"
+                "ds_min_u32 %2, %10\n\t"
+                "s_mov_b64 exec, -1"
+                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(nn)
+                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
+                : "memory", "vcc");
     };
     Rows::template consume<T, U>(A, t, 0, V, N, scatter);
     for (uint32_t b = 1, nb = Rows::template batches<T, U>(t); b < nb; ++b) {  // a dense tile: the rest
@@ -369,7 +318,7 @@ void sweep_conservation_halo_kernel(const SweepArgs A) {
 // indexed by the length (64 entries of two LDS offsets: 4 VALU per row fewer, one ds_read_b64 more) made it slower
 // (0.46 ms: every row then waits for an LDS round trip).
 template <int U, int T, typename OutT, bool A9 = false>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MEMO_HALO_WAVES, 8)))
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void sweep_conservation_halo3_kernel(const SweepArgs A) {
     static_assert(!A9 || sizeof(OutT) == 2, "more than 255 genomes: uint16 results");
     constexpr int TOP = A9 ? 23 : 24;  // a cell = order << TOP | tie-breaking bits
@@ -380,22 +329,6 @@ void sweep_conservation_halo3_kernel(const SweepArgs A) {
     if (!locate_tile_w(A, t, W)) return;
     uint4 V[U];
     Rows::template issue<T, U>(A, t, 0, V);
-    // diagnostic builds only (tools/build_variant.sh): what is the sweep short of?  N more scalar / vector instructions
-    // per wave that do nothing -- if the time follows the scalar ones, the CU's one scalar unit is the bound
-#if defined(MEMO_EXTRA_SALU) || defined(MEMO_EXTRA_VALU)
-    {
-        uint32_t sx = (uint32_t)A.km1, vx = threadIdx.x;
-#ifdef MEMO_EXTRA_SALU
-#pragma unroll
-        for (int i = 0; i < MEMO_EXTRA_SALU; ++i) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sx)::"scc");
-#endif
-#ifdef MEMO_EXTRA_VALU
-#pragma unroll
-        for (int i = 0; i < MEMO_EXTRA_VALU; ++i) asm volatile("v_add_u32 %0, %0, 1" : "+v"(vx));
-#endif
-        if (sx + vx == 0xFFFFFFF0u) atomicOr(A.status, 64);  // (keeps them alive)
-    }
-#endif
     halo_clear<T>(A, lds, ((uint32_t)(A.ncols - 1) << TOP) | ((1u << TOP) - 1u));
 
     const int km1 = A.km1;
@@ -404,59 +337,31 @@ void sweep_conservation_halo3_kernel(const SweepArgs A) {
     const uint32_t bias4 = pin_vgpr((int)(lds_base + 4u * (uint32_t)HL - (uint32_t)(32 - A.nlev) * ls4));
     const uint32_t top_bit = pin_vgpr((int)0x80000000u);
     const uint32_t a10s = pin_vgpr((int)(((uint32_t)t.a & 1023u) << 6));
-    // r = (start - a) mod 2^10 << 6 | length;  data = a word with the row's order in its top byte
-    auto scatter = [&](uint32_t r, uint32_t data) {
-        if (MEMO_ABLATE & 16) {  // keep the loads alive, nothing else
-            asm volatile("" ::"v"(r), "v"(data));
-            return;
-        }
-        const int n = km1 - (int)(r & 63u);
-        if (n > 0) {
-            uint32_t r0, r1, r2;
-            asm volatile(
-                "v_ffbh_u32 %0, %3\n\t"
-                "v_bfe_u32 %1, %4, 6, 10\n\t"
-                "v_mad_u32_u24 %2, %0, %5, %6\n\t"
-                "v_lshl_add_u32 %2, %1, 2, %2\n\t"
-                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                "v_ashrrev_i32 %0, %0, %7\n\t"
-                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                "ds_min_u32 %1, %8\n\t"
-                "ds_min_u32 %2, %8"
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2)
-                : "v"(n), "v"(r), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(data)
-                : "memory");
-        }
-    };
-    auto g = [&](uint32_t b, uint32_t data) {  // 16-bit subtract on the low half; the result's high half is zero
-        if (MEMO_ROW_CMPX) {
-            // the whole row in one block, no branch: v_cmpx puts "this row writes" into EXEC itself, everything after it
-            // runs on those lanes only, s_mov restores EXEC (every lane of the wave is active in the row loop)
-            uint32_t r0, r1, r2, r3;
-            MEMO_EXEC_ALL_ONES(A.status);
-            asm volatile(
-                "v_sub_u16 %3, %4, %5\n\t"
-                "v_and_b32 %0, 63, %3\n\t"
-                "v_sub_u32 %0, %6, %0\n\t"
-                "v_cmpx_lt_i32 vcc, 0, %0\n\t"
-                "v_ffbh_u32 %1, %0\n\t"
-                "v_bfe_u32 %3, %3, 6, 10\n\t"
-                "v_mad_u32_u24 %2, %1, %7, %8\n\t"
-                "v_lshl_add_u32 %2, %3, 2, %2\n\t"
-                "v_mad_i32_i24 %3, %0, -4, %2\n\t"
-                "v_ashrrev_i32 %1, %1, %9\n\t"
-                "v_lshl_add_u32 %2, %1, 2, %2\n\t"
-                "ds_min_u32 %3, %10\n\t"
-                "ds_min_u32 %2, %10\n\t"
-                "s_mov_b64 exec, -1"
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
-                : "v"(b), "v"(a10s), "s"(km1), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(data)
-                : "memory", "vcc");
-            return;
-        }
-        uint32_t r;
-        asm("v_sub_u16 %0, %1, %2" : "=v"(r) : "v"(b), "v"(a10s));
-        scatter(r, data);
+    // b: the row's B field in its low half, data: a word with the row's order in its top byte.  The 16-bit subtract leaves
+    // r = (start - a) mod 2^10 << 6 | length, high half zero.
+    auto g = [&](uint32_t b, uint32_t data) {
+        // the whole row in one block, no branch: v_cmpx puts "this row writes" into EXEC itself, everything after it
+        // runs on those lanes only, s_mov restores EXEC (every lane of the wave is active in the row loop)
+        uint32_t r0, r1, r2, r3;
+        MEMO_EXEC_ALL_ONES(A.status);
+        asm volatile(
+            "v_sub_u16 %3, %4, %5\n\t"
+            "v_and_b32 %0, 63, %3\n\t"
+            "v_sub_u32 %0, %6, %0\n\t"
+            "v_cmpx_lt_i32 vcc, 0, %0\n\t"
+            "v_ffbh_u32 %1, %0\n\t"
+            "v_bfe_u32 %3, %3, 6, 10\n\t"
+            "v_mad_u32_u24 %2, %1, %7, %8\n\t"
+            "v_lshl_add_u32 %2, %3, 2, %2\n\t"
+            "v_mad_i32_i24 %3, %0, -4, %2\n\t"
+            "v_ashrrev_i32 %1, %1, %9\n\t"
+            "v_lshl_add_u32 %2, %1, 2, %2\n\t"
+            "ds_min_u32 %3, %10\n\t"
+            "ds_min_u32 %2, %10\n\t"
+            "s_mov_b64 exec, -1"
+            : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
+            : "v"(b), "v"(a10s), "s"(km1), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(data)
+            : "memory", "vcc");
     };
     Rows::template consume<T, U, decltype(g), A9>(A, t, 0, V, g);
     for (uint32_t b = 1, nb = Rows::template batches<T, U>(t); b < nb; ++b) {  // a dense tile: the rest
@@ -570,7 +475,7 @@ __device__ __forceinline__ void r4_fold_store(const SweepArgs &A, const Tile &t,
 }
 
 template <typename Rows, int U, int T, typename OutT, int TOP>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MEMO_HALO_WAVES, 8)))
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void sweep_conservation_r4_kernel(const SweepArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     static_assert(TOP == 0 || (!Rows::kAnnot16 && TOP == Rows::kTopShift), "the order rides in the word only in the 4-byte formats");
@@ -592,111 +497,56 @@ void sweep_conservation_r4_kernel(const SweepArgs A) {
     const uint32_t top_bit = pin_vgpr((int)0x80000000u);
     const uint32_t key = pin_vgpr((int)Rows::tile_key(t.a));
     auto scatter = [&](uint32_t w, uint32_t col) {
-        if (MEMO_ROW_CMPX) {
-            // the first two blocks of a row as one branch-free block (EXEC narrowed to "n > 0" by v_cmpx, restored at the end);
-            // the third and fourth stay behind the compiler's branches: where no row of a wave needs them (k = 128 on config 3)
-            // skipping them beats issuing them with no lane -- 0.395 against 0.415 ms (profiles/r02_mixed_levels.txt)
-            uint32_t tmp, a1, a2, s4, q, dd;
-            MEMO_EXEC_ALL_ONES(A.status);
-            // diagnostic builds (tools/build_variant.sh): what do the lanes of one instruction on ONE cell cost -- rows of a start
-            // and a level share their second block's cell?  32: the second ds_min goes to the first block's cell (as many instructions,
-            // no two lanes on one address but for equal rows); 64: no second ds_min.  Wrong results either way.
-#if MEMO_ABLATE & 32
-#define MEMO_R4_SECOND "ds_min_u32 %1, %11\n\t"
-#elif MEMO_ABLATE & 64
-#define MEMO_R4_SECOND
-#else
-#define MEMO_R4_SECOND "ds_min_u32 %2, %11\n\t"
-#endif
-#define MEMO_R4_BLOCK(LEN_SEL, REL_START)                                                                         \
-            asm volatile(                                                                                          \
-                "v_mov_b32 %4, 0\n\t"                 /* q = 0 where the row does not write */                     \
-                "v_sub_u32_sdwa %0, %7, %6 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" LEN_SEL "\n\t" \
-                "v_cmpx_lt_i32 vcc, 0, %0\n\t"                                                                    \
-                REL_START                                                                                          \
-                "v_ffbh_u32 %4, %0\n\t"                                                                           \
-                "v_lshrrev_b32 %4, 1, %4\n\t"        /* i' = 15 - i */                                            \
-                "v_mad_u32_u24 %1, %4, %9, %10\n\t"  /* level i */                                                \
-                "v_lshl_add_u32 %2, %5, 2, %1\n\t"   /* cell `start` on level i (%5 = start - a) */               \
-                "v_mad_i32_i24 %1, %0, -4, %2\n\t"   /* a1: cell start - n */                                     \
-                "v_lshl_add_u32 %4, %4, 1, -1\n\t"   /* 2 i' - 1 = 29 - 2 i */                                    \
-                "v_lshrrev_b32 %3, %4, %12\n\t"      /* 4 S (bytes) */                                            \
-                "v_sub_u32 %2, %2, %3\n\t"           /* a2: cell start - S */                                     \
-                "ds_min_u32 %1, %11\n\t"                                                                          \
-                MEMO_R4_SECOND                                                                                     \
-                "v_sub_u32 %4, 29, %4\n\t"           /* 2 i */                                                    \
-                "v_lshrrev_b32 %4, %4, %0\n\t"       /* q */                                                      \
-                "s_mov_b64 exec, -1"                                                                               \
-                : "=&v"(tmp), "=&v"(a1), "=&v"(a2), "=&v"(s4), "=&v"(q), "=&v"(dd)                                 \
-                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(levelK), "v"(TOP ? w : col), "v"(top_bit)              \
-                : "memory", "vcc")
-            if constexpr (!Rows::kW12)
-                MEMO_R4_BLOCK("BYTE_2", "v_sub_u16 %5, %6, %8\n\t");
-            else
-                MEMO_R4_BLOCK("BYTE_0", "v_sub_u32 %5, %6, %8\n\tv_bfe_u32 %5, %5, 8, 12\n\t");
+        // the first two blocks of a row as one branch-free block (EXEC narrowed to "n > 0" by v_cmpx, restored at the end);
+        // the third and fourth stay behind the compiler's branches: where no row of a wave needs them (k = 128 on config 3)
+        // skipping them beats issuing them with no lane -- 0.395 against 0.415 ms (profiles/r02_mixed_levels.txt).
+        // i = floor(log4 n), S = 4^i, q = n >> 2i (the leading base-4 digit): blocks [start - n, +S) and [start - S, start);
+        // q >= 2: one more at start - n + S; q = 3: and one at start - n + 2S
+        uint32_t tmp, a1, a2, s4, q, dd;
+        MEMO_EXEC_ALL_ONES(A.status);
+#define MEMO_R4_BLOCK(LEN_SEL, REL_START)                                                                           \
+        asm volatile(                                                                                               \
+            "v_mov_b32 %4, 0\n\t"                 /* q = 0 where the row does not write */                          \
+            "v_sub_u32_sdwa %0, %7, %6 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" LEN_SEL "\n\t" \
+            "v_cmpx_lt_i32 vcc, 0, %0\n\t"                                                                          \
+            REL_START                                                                                               \
+            "v_ffbh_u32 %4, %0\n\t"                                                                                 \
+            "v_lshrrev_b32 %4, 1, %4\n\t"        /* i' = 15 - i */                                                  \
+            "v_mad_u32_u24 %1, %4, %9, %10\n\t"  /* level i */                                                      \
+            "v_lshl_add_u32 %2, %5, 2, %1\n\t"   /* cell `start` on level i (%5 = start - a) */                     \
+            "v_mad_i32_i24 %1, %0, -4, %2\n\t"   /* a1: cell start - n */                                           \
+            "v_lshl_add_u32 %4, %4, 1, -1\n\t"   /* 2 i' - 1 = 29 - 2 i */                                          \
+            "v_lshrrev_b32 %3, %4, %12\n\t"      /* 4 S (bytes) */                                                  \
+            "v_sub_u32 %2, %2, %3\n\t"           /* a2: cell start - S */                                           \
+            "ds_min_u32 %1, %11\n\t"                                                                                \
+            "ds_min_u32 %2, %11\n\t"                                                                                \
+            "v_sub_u32 %4, 29, %4\n\t"           /* 2 i */                                                          \
+            "v_lshrrev_b32 %4, %4, %0\n\t"       /* q */                                                            \
+            "s_mov_b64 exec, -1"                                                                                    \
+            : "=&v"(tmp), "=&v"(a1), "=&v"(a2), "=&v"(s4), "=&v"(q), "=&v"(dd)                                      \
+            : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(levelK), "v"(TOP ? w : col), "v"(top_bit)                   \
+            : "memory", "vcc")
+        if constexpr (!Rows::kW12)
+            MEMO_R4_BLOCK("BYTE_2", "v_sub_u16 %5, %6, %8\n\t");
+        else
+            MEMO_R4_BLOCK("BYTE_0", "v_sub_u32 %5, %6, %8\n\tv_bfe_u32 %5, %5, 8, 12\n\t");
 #undef MEMO_R4_BLOCK
-#undef MEMO_R4_SECOND
-            if (q >= 2) {
-                const uint32_t data = TOP ? w : col;
-                uint32_t a3, a4;
-                asm volatile(
-                    "v_add_u32 %0, %1, %2\n\t"        // a3 = a1 + 4 S
-                    "ds_min_u32 %0, %3"
-                    : "=&v"(a3)
-                    : "v"(a1), "v"(s4), "v"(data)
-                    : "memory");
-                if (q == 3) {
-                    asm volatile(
-                        "v_add_u32 %0, %1, %2\n\t"    // a4 = a3 + 4 S
-                        "ds_min_u32 %0, %3"
-                        : "=&v"(a4)
-                        : "v"(a3), "v"(s4), "v"(data)
-                        : "memory");
-                }
-            }
-            return;
-        }
-        const int n = km1 - Rows::len(w);  // length of [end - (k-1), start)
-        if (n > 0) {
-            // i = floor(log4 n), S = 4^i, q = n >> 2i (the leading base-4 digit).  Blocks [start - n, +S) and
-            // [start - S, start); q >= 2: one more at start - n + S; q = 3: and one at start - n + 2S.  By hand: 14 - 16
-            // VALU instructions per row after the length / validity / start triple (the compiler's rendering took 24,
-            // one of them a quarter-rate 32-bit multiply; the first hand-written one 16 - 19).
+        if (q >= 2) {
             const uint32_t data = TOP ? w : col;
-            const uint32_t d = Rows::rel_start(w, key);  // start - a
-            uint32_t tmp, a1, a2, s4, q;
+            uint32_t a3, a4;
             asm volatile(
-                "v_ffbh_u32 %0, %5\n\t"
-                "v_lshrrev_b32 %0, 1, %0\n\t"        // i' = 15 - i
-                "v_mad_u32_u24 %1, %0, %7, %8\n\t"   // level i
-                "v_lshl_add_u32 %2, %6, 2, %1\n\t"   // cell `start` on level i
-                "v_mad_i32_i24 %1, %5, -4, %2\n\t"   // a1: cell start - n
-                "v_lshl_add_u32 %0, %0, 1, -1\n\t"   // 2 i' - 1 = 29 - 2 i
-                "v_lshrrev_b32 %3, %0, %10\n\t"      // 4 S (bytes) = 2^31 >> (29 - 2 i)
-                "v_sub_u32 %2, %2, %3\n\t"           // a2: cell start - S
-                "ds_min_u32 %1, %9\n\t"
-                "ds_min_u32 %2, %9\n\t"
-                "v_sub_u32 %0, 29, %0\n\t"           // 2 i
-                "v_lshrrev_b32 %4, %0, %5"             // q
-                : "=&v"(tmp), "=&v"(a1), "=&v"(a2), "=&v"(s4), "=&v"(q)
-                : "v"(n), "v"(d), "s"(ls4), "v"(levelK), "v"(data), "v"(top_bit)
+                "v_add_u32 %0, %1, %2\n\t"        // a3 = a1 + 4 S
+                "ds_min_u32 %0, %3"
+                : "=&v"(a3)
+                : "v"(a1), "v"(s4), "v"(data)
                 : "memory");
-            if (q >= 2) {
-                uint32_t a3, a4;
+            if (q == 3) {
                 asm volatile(
-                    "v_add_u32 %0, %1, %2\n\t"        // a3 = a1 + 4 S
+                    "v_add_u32 %0, %1, %2\n\t"    // a4 = a3 + 4 S
                     "ds_min_u32 %0, %3"
-                    : "=&v"(a3)
-                    : "v"(a1), "v"(s4), "v"(data)
+                    : "=&v"(a4)
+                    : "v"(a3), "v"(s4), "v"(data)
                     : "memory");
-                if (q == 3) {
-                    asm volatile(
-                        "v_add_u32 %0, %1, %2\n\t"    // a4 = a3 + 4 S
-                        "ds_min_u32 %0, %3"
-                        : "=&v"(a4)
-                        : "v"(a3), "v"(s4), "v"(data)
-                        : "memory");
-                }
             }
         }
     };
@@ -886,7 +736,7 @@ __device__ __forceinline__ void plan_fold_store(const SweepArgs &A, const Tile &
 // doubling levels into the blocks of 16 in one LDS pass, 16 -> 4 -> 1 in registers.
 // ------------------------------------------------------------------------------------------
 template <typename Rows, int U, int T, typename OutT, int TOP>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(MEMO_HALO_WAVES, 8)))
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void sweep_conservation_mixed_kernel(const SweepArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     static_assert(TOP == 0 || (!Rows::kAnnot16 && TOP == Rows::kTopShift), "the order rides in the word only in the 4-byte formats");
@@ -911,89 +761,58 @@ void sweep_conservation_mixed_kernel(const SweepArgs A) {
     // (rows of fewer than 16 positions exist only where the plan has arrays for them)
     uint32_t *const cells4 = lds + P.s4() * LS + HL, *const cells1 = lds + P.s1() * LS + HL;
     auto scatter = [&](uint32_t w, uint32_t col) {
-        if (MEMO_ROW_CMPX) {
-            // The long intervals (n >= 16) as one branch-free block: v_cmpx narrows EXEC to "n > 0", then to "clz(n) < 28";
-            // the doubling arithmetic and both ds_min run on those lanes; EXEC restored.  What is left for the
-            // compiler's branch is the rare short interval (0 < n < 16).
-            int n;
-            uint32_t r0, r1, r2, d;
-            MEMO_EXEC_ALL_ONES(A.status);
-            if constexpr (!Rows::kW12)
-                asm volatile(
-                    "v_sub_u32_sdwa %3, %6, %5 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                    "v_sub_u16 %4, %5, %7\n\t"
-                    "v_ffbh_u32 %0, %3\n\t"
-                    "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                    "v_cmpx_gt_u32 vcc, 28, %0\n\t"
-                    "v_mad_u32_u24 %2, %0, %8, %9\n\t"
-                    "v_lshl_add_u32 %2, %4, 2, %2\n\t"
-                    "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                    "v_ashrrev_i32 %0, %0, %10\n\t"
-                    "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                    "ds_min_u32 %1, %11\n\t"
-                    "ds_min_u32 %2, %11\n\t"
-                    "s_mov_b64 exec, -1"
-                    : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(n), "=&v"(d)
-                    : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                    : "memory", "vcc");
-            else
-                asm volatile(
-                    "v_sub_u32_sdwa %3, %6, %5 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-                    "v_sub_u32 %4, %5, %7\n\t"
-                    "v_bfe_u32 %4, %4, 8, 12\n\t"
-                    "v_ffbh_u32 %0, %3\n\t"
-                    "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                    "v_cmpx_gt_u32 vcc, 28, %0\n\t"
-                    "v_mad_u32_u24 %2, %0, %8, %9\n\t"
-                    "v_lshl_add_u32 %2, %4, 2, %2\n\t"
-                    "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                    "v_ashrrev_i32 %0, %0, %10\n\t"
-                    "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                    "ds_min_u32 %1, %11\n\t"
-                    "ds_min_u32 %2, %11\n\t"
-                    "s_mov_b64 exec, -1"
-                    : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(n), "=&v"(d)
-                    : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                    : "memory", "vcc");
-            if ((uint32_t)(n - 1) < 15u) {  // 0 < n < 16: blocks of S = 4 (n >= 4) or 1 at start - n and start - S; two more while n >= 2S, 3S
-                const uint32_t data = TOP ? w : col;
-                const bool four = n >= 4;
-                uint32_t *lv = (four ? cells4 : cells1) + d;
-                const int S = four ? 4 : 1, q = four ? n >> 2 : n;
-                atomicMin(lv - n, data);
-                atomicMin(lv - S, data);
-                if (q >= 2) atomicMin(lv - n + S, data);
-                if (q == 3) atomicMin(lv - n + 2 * S, data);
-            }
-            return;
-        }
-        const int n = km1 - Rows::len(w);  // length of [end - (k-1), start)
-        if (n > 0) {
+        // The long intervals (n >= 16) as one branch-free block: v_cmpx narrows EXEC to "n > 0", then to "clz(n) < 28";
+        // the doubling arithmetic and both ds_min run on those lanes; EXEC restored.  What is left for the
+        // compiler's branch is the rare short interval (0 < n < 16).
+        int n;
+        uint32_t r0, r1, r2, d;
+        MEMO_EXEC_ALL_ONES(A.status);
+        if constexpr (!Rows::kW12)
+            asm volatile(
+                "v_sub_u32_sdwa %3, %6, %5 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
+                "v_sub_u16 %4, %5, %7\n\t"
+                "v_ffbh_u32 %0, %3\n\t"
+                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
+                "v_cmpx_gt_u32 vcc, 28, %0\n\t"
+                "v_mad_u32_u24 %2, %0, %8, %9\n\t"
+                "v_lshl_add_u32 %2, %4, 2, %2\n\t"
+                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
+                "v_ashrrev_i32 %0, %0, %10\n\t"
+                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
+                "ds_min_u32 %1, %11\n\t"
+                "ds_min_u32 %2, %11\n\t"
+                "s_mov_b64 exec, -1"
+                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(n), "=&v"(d)
+                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
+                : "memory", "vcc");
+        else
+            asm volatile(
+                "v_sub_u32_sdwa %3, %6, %5 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
+                "v_sub_u32 %4, %5, %7\n\t"
+                "v_bfe_u32 %4, %4, 8, 12\n\t"
+                "v_ffbh_u32 %0, %3\n\t"
+                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
+                "v_cmpx_gt_u32 vcc, 28, %0\n\t"
+                "v_mad_u32_u24 %2, %0, %8, %9\n\t"
+                "v_lshl_add_u32 %2, %4, 2, %2\n\t"
+                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
+                "v_ashrrev_i32 %0, %0, %10\n\t"
+                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
+                "ds_min_u32 %1, %11\n\t"
+                "ds_min_u32 %2, %11\n\t"
+                "s_mov_b64 exec, -1"
+                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(n), "=&v"(d)
+                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
+                : "memory", "vcc");
+        if ((uint32_t)(n - 1) < 15u) {  // 0 < n < 16: blocks of S = 4 (n >= 4) or 1 at start - n and start - S; two more while n >= 2S, 3S
             const uint32_t data = TOP ? w : col;
-            const uint32_t d = Rows::rel_start(w, key);  // start - a
-            const int f = __builtin_clz((unsigned)n);
-            if (f <= 27) {  // n >= 16: blocks [start - n, .. + 2^j) and [start - 2^j, start), j = floor(log2 n)
-                uint32_t r0, r1, r2;
-                asm volatile(
-                    "v_mad_u32_u24 %2, %5, %6, %7\n\t"
-                    "v_lshl_add_u32 %2, %4, 2, %2\n\t"
-                    "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                    "v_ashrrev_i32 %0, %5, %8\n\t"
-                    "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                    "ds_min_u32 %1, %9\n\t"
-                    "ds_min_u32 %2, %9"
-                    : "=&v"(r0), "=&v"(r1), "=&v"(r2)
-                    : "v"(n), "v"(d), "v"(f), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(data)
-                    : "memory");
-            } else {  // n < 16: blocks of S = 4 (n >= 4) or 1 at start - n and start - S; two more while n >= 2S, 3S
-                const bool four = n >= 4;
-                uint32_t *lv = (four ? cells4 : cells1) + d;
-                const int S = four ? 4 : 1, q = four ? n >> 2 : n;
-                atomicMin(lv - n, data);
-                atomicMin(lv - S, data);
-                if (q >= 2) atomicMin(lv - n + S, data);
-                if (q == 3) atomicMin(lv - n + 2 * S, data);
-            }
+            const bool four = n >= 4;
+            uint32_t *lv = (four ? cells4 : cells1) + d;
+            const int S = four ? 4 : 1, q = four ? n >> 2 : n;
+            atomicMin(lv - n, data);
+            atomicMin(lv - S, data);
+            if (q >= 2) atomicMin(lv - n + S, data);
+            if (q == 3) atomicMin(lv - n + 2 * S, data);
         }
     };
     Rows::template consume<T, U>(A, t, 0, V, N, scatter);
@@ -1112,10 +931,7 @@ SweepKernel cons_kernel(int w, int waves) {
 
 }  // namespace
 
-#ifndef MEMO_HALO_LOADS
-#define MEMO_HALO_LOADS 6
-#endif
-constexpr int kHaloLoads = MEMO_HALO_LOADS;  // 16-byte loads in flight per lane
+constexpr int kHaloLoads = 6;  // 16-byte loads in flight per lane
 
 template <typename Rows, typename OutT, int TOP>
 static SweepKernel halo_kernel(int waves) {
@@ -1237,10 +1053,6 @@ static int pick_levels(const memo_index *ix, int k, bool moderate) {
     if (few_small) return ix->len_seen_exact || blocks4 > (km1 >= 128 && moderate ? 2.9 : 2.15) * rows ? 4 : 3;
     return fallback;
 }
-
-#ifndef MEMO_TABLE_DEFAULT
-#define MEMO_TABLE_DEFAULT 1  // the dense rows are swept by the table-driven kernel wherever the query fits it (0: A/B builds)
-#endif
 
 template <typename OutT>
 static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t k, int32_t num_docs,
@@ -1422,8 +1234,9 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
             ix->last_variant = 0;
             // the dense rows of this k's class (a view that leaves out the rows that cannot write at this k), or all of them.  Views of
             // six rows per group are for the table-driven kernel alone: a query it cannot take (a negative window start, no room for
-            // the tile table) asks again for five-row groups.
-            const bool table = three && (tune.persistent == 5 || (tune.persistent == 0 && MEMO_TABLE_DEFAULT));
+            // the tile table) asks again for five-row groups.  The table-driven kernel sweeps the dense rows wherever the query fits
+            // it; only the debug row sources 5 and 10 (tune.persistent == 1) keep them on sweep_conservation_halo3_kernel.
+            const bool table = three && (tune.persistent == 5 || tune.persistent == 0);
             for (int attempt = 0; three && attempt < 2; ++attempt) {
                 const bool can_six = attempt == 0 && table && top8 && A.nlev <= 5 && qs >= 0;
                 uint32_t *vp3 = nullptr;
@@ -1479,10 +1292,10 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     }
     if (!halo) {
         if (fmt == 12 && w > 2048) w = 2048;  // a 12-bit start field: the slice of a tile spans less than 2^12 positions
-        while ((size_t)A.nlev * (w + kLevelSkew) * 4 > 160 * 1024 && w > 256) w >>= 1;
+        while ((size_t)A.nlev * w * 4 > 160 * 1024 && w > 256) w >>= 1;
         A.hl = 0;
         A.w = w;
-        A.ls = w + kLevelSkew;
+        A.ls = w;
         SweepKernel kern = fmt == 4   ? (checked ? cons_kernel<PackedRows<false, true>, OutT>(w, waves)
                                                  : cons_kernel<PackedRows<false, false>, OutT>(w, waves))
                            : fmt == 12 ? (checked ? cons_kernel<PackedRows<false, true, true>, OutT>(w, waves)

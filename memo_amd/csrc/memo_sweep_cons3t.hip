@@ -49,13 +49,6 @@ __global__ void tile_table_kernel(const int64_t *boff, int64_t nb, int64_t bbase
     out[t] = d;
 }
 
-// Diagnostic builds only (tools/build_variant.sh NAME -DMEMO_T_ABLATE=bits; results are wrong, they size a phase:
-// profiles/r03_phase_ablation.txt): 1 = rows loaded and dropped, 2 = no clear of the level arrays, 4 = no fold (the finest
-// level is stored as it is), 8 = no store, 16 = no row loads
-#ifndef MEMO_T_ABLATE
-#define MEMO_T_ABLATE 0
-#endif
-
 // T = 256: four waves per tile (eight tiles = 32 waves per CU), the only form instantiated (T = 128 lost: see the launcher)
 // A9: an index of 256 .. 511 genomes -- the order in the top NINE bits of a level cell (memo_sweep_dense.h: MEMO_ROW9_AT), uint16 results
 // AW: the row source is a k-class view whose cap is this k - 1 -- every row of it writes, the row blocks carry no test (memo_sweep_dense.h)
@@ -105,30 +98,23 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
             const uint32_t pg = batch * kStageGroups + (uint32_t)(j * T + wave * 64);
-            if (MEMO_T_ABLATE & 16) {
-                V[j] = make_uint4(0x0000003Fu, 0x0000003Fu, 0x0000003Fu, 0x0000003Fu);  // (rows that cannot write)
-                continue;
-            }
             // (a piece that straddles the slice's end reads up to 63 groups BEHIND the slice -- half a KiB per tile on average: TCP_TCC_READ_REQ
             // is 24 % above a k = 17 view's bytes, profiles/r05_six_rows.txt.  Those are the next tile's first lines, which that tile --
             // same XCD, running beside this one -- fetches anyway: clamping the lanes to the slice's last group measured 0.5-1.5 % SLOWER,
-            // same box, alternating builds; -DMEMO_SLICE_CLAMP keeps the experiment.)
+            // same box, alternating builds.)
+            uint4 &v = V[j];  // (named before `lane`: the lambda's capture order shapes the compiler's code for the SP kernels)
             const uint32_t at = pg + (uint32_t)lane;
-#ifdef MEMO_SLICE_CLAMP
-            V[j] = src0[pg < g.ng ? (at < g.ng ? at : g.ng - 1u) : 0u];
-#else
             if constexpr (SP) {
-                if (pg < g.ng) V[j] = src0[at];
+                if (pg < g.ng) v = src0[at];
             } else {
-                V[j] = src0[pg < g.ng ? at : 0u];
+                v = src0[pg < g.ng ? at : 0u];
             }
-#endif
         }
     };
     issue(0);
     const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)lds;
     const int HL = A.hl, W = A.w;
-    if (!(MEMO_T_ABLATE & 2)) clear_levels<NLEV, T>(lds_base, ((uint32_t)(A.ncols - 1) << SH) | ((1u << SH) - 1u));
+    clear_levels<NLEV, T>(lds_base, ((uint32_t)(A.ncols - 1) << SH) | ((1u << SH) - 1u));
     RowConst C;
     C.km1 = A.km1;
     C.status = A.status;
@@ -149,11 +135,6 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     const uint32_t nbatch = (g.ng + kStageGroups - 1) / kStageGroups;
     for (uint32_t batch = 0; batch == 0 || batch < nbatch; ++batch) {
         if (batch) issue(batch);  // (a tile with more than 5120 rows: the rest)
-        if (MEMO_T_ABLATE & 1) {
-#pragma unroll
-            for (int j = 0; j < NL; ++j) asm volatile("" ::"v"(V[j].x), "v"(V[j].y), "v"(V[j].z), "v"(V[j].w));
-            continue;
-        }
         const uint32_t gbase = batch * kStageGroups;
         const uint32_t gleft = g.ng > gbase ? g.ng - gbase : 0;
         if constexpr (SIX && LIVE) {
@@ -190,19 +171,11 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
         read_levels<NLEV>(lds_base + 4u * (uint32_t)xr, L);
         auto lv = [&](int i) { return make_uint4(L[i].x, L[i].y, L[i].z, L[i].w); };
         uint4 M = lv(0);
-        if constexpr (MEMO_T_ABLATE & 4) {
-            M = lv(NLEV - 1);
-        } else {
         if constexpr (NLEV >= 6) fold_step_dpp<4>(M, lv(NLEV - 5), lane);
         if constexpr (NLEV >= 5) fold_step_dpp<3>(M, lv(NLEV - 4), lane);
         if constexpr (NLEV >= 4) fold_step_dpp<2>(M, lv(NLEV - 3), lane);
         if constexpr (NLEV >= 3) fold_step_dpp<1>(M, lv(NLEV - 2), lane);
         if constexpr (NLEV >= 2) fold_step_dpp<0>(M, lv(NLEV - 1), lane);
-        }
-        if (MEMO_T_ABLATE & 8) {
-            asm volatile("" ::"v"(M.x), "v"(M.y), "v"(M.z), "v"(M.w));
-            continue;
-        }
         if (lane < ctx || x0 >= cells) continue;
         const int64_t o = ob + x0;
         if (o >= o_lo && o + 4 <= o_hi) {
@@ -320,16 +293,10 @@ static int tile_table(memo_index *ix, const void *rows_of, const int64_t *boff, 
 // sweep_conservation_halo3_kernel).  A: filled for the unclipped sweep (hl, w, ls, nlev, ncols); tw = tile width.
 // live: a six-row view whose groups carry the dead-group flag (one built with places)
 int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStream_t st, bool annot9, bool all_write, bool six, bool live) {
-#ifdef MEMO_LIVE_NEVER  // (A/B builds: every group of the view scattered, as before the flags)
-    live = false;
-#endif
     if (annot9 && elem_bytes != 2) return 1;
     if (six && (annot9 || A.nlev > 5 || ix->bshift != 5)) return 1;
     if (!A.p3 || A.ls > kLS || A.nlev < 1 || A.nlev > 6 || A.km1 > 63 || A.qs < 0) return 1;
     const int64_t q = A.qs / tw, tile0 = q * tw;
-#ifdef MEMO_TABLE_RASTER_ONLY  // (A/B builds: rounds 3-4 took only windows whose start is a multiple of four -- aligned result stores)
-    if ((tile0 - A.qs) & 3) return 1;
-#endif
     const int64_t ntiles = ((A.qe - tile0) + tw - 1) / tw;
     if (ntiles + 8 >= ((int64_t)1 << 31) || q + ntiles >= ((int64_t)1 << 31)) return 1;
     const void *tab = nullptr;
@@ -351,13 +318,7 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     // few rows per tile?  (the rows the sweep reads, spread over the index's span: groups per tile against the 1024 of a batch)
     const double span = (double)(ix->max_s - ix->min_s) + 1.0;
     const double groups_per_tile = (double)ix->last_rows_read / (six ? 6.0 : 5.0) * (double)tw / (span > 1.0 ? span : 1.0);
-#ifdef MEMO_SPARSE_NEVER   // (A/B builds: rounds 3-5's loads everywhere / the skipped loads everywhere)
-    const bool sp = false;
-#elif defined(MEMO_SPARSE_ALWAYS)
-    const bool sp = true;
-#else
     const bool sp = groups_per_tile < 768.0;
-#endif
     SweepKernel kern = sp ? (all_write ? kernel_of<true, true>(A.nlev, elem_bytes, annot9) : kernel_of<false, true>(A.nlev, elem_bytes, annot9))
                           : (all_write ? kernel_of<true, false>(A.nlev, elem_bytes, annot9) : kernel_of<false, false>(A.nlev, elem_bytes, annot9));
     if (six) {
