@@ -212,12 +212,18 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info);  /*
  *   MEMO_OPT_VIEW_PLACES      1 (default): a dense view is built a second time, the places of its rows inside their 16-byte groups chosen
  *                             against LDS bank conflicts (2-4 % of a sweep; the pass costs twice the plain one), once the class's
  *                             queries have lost to the plain view what that costs (MEMO_OPT_BUILD_COST_PCT applies) -- or at once by
- *                             memo_index_prepare; 0: never (views keep their rows in the order they come in). */
+ *                             memo_index_prepare; 0: never (views keep their rows in the order they come in).
+ *   MEMO_OPT_VIEW_LIVE        1 (default): a placed six-row view flags the groups that hold no row that can decide a minimum (a row of
+ *                             lower order contains each of their rows at every k); once the class's queries have lost to loading
+ *                             those groups what a pass over the view costs (MEMO_OPT_BUILD_COST_PCT applies), a query copies the view
+ *                             without them -- the sweep then reads only the live groups.  Never by memo_index_prepare (it hands out
+ *                             the flagged view); 0: never (the flagged view stays and is swept with its dead groups masked: the A/B). */
 #define MEMO_OPT_VIEWS 1
 #define MEMO_OPT_VIEW_BUDGET_PCT 2
 #define MEMO_OPT_BUILD_COST_PCT 3
 #define MEMO_OPT_VIEW_ROWS 4
 #define MEMO_OPT_VIEW_PLACES 5
+#define MEMO_OPT_VIEW_LIVE 6
 /* Returns the option's PREVIOUS value (>= 0) -- what a caller that changes an option for one pass puts back -- or a negative code. */
 int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value);
 /* Build NOW what queries of one kind would otherwise build on the way: the k-class view of the rows such a query reads (else

@@ -52,6 +52,9 @@ int memo_debug_view_colouring(int32_t on);
  * 0 = five always, -1 (the default) = the library's choice (MEMO_OPT_VIEW_ROWS of the index, else six where the view holds enough rows
  * per bucket for the padding of every bucket to whole groups not to matter). */
 int memo_debug_six_views(int32_t on);
+/* placed six-row views of this index copied without their dead groups so far (MEMO_OPT_VIEW_LIVE; memo_view.hip: live_view_copy), and
+ * whether the six-row view of k's class is such a copy: 1, or 0 (not a copy, or no six-row view of that class is resident) */
+int memo_debug_view_live(const memo_index_t *ix, int32_t k, uint64_t *copies);
 /* this THREAD's later calls: every device allocation for a view or a tile table fails (the test of the no-memory path) */
 int memo_debug_fail_side_allocations(int32_t on);
 /* this thread's later memo_index_pack_dense / dense builders keep the rows that can never write at k <= 64 in the dense rows */

@@ -140,6 +140,9 @@ struct memo_index {
         int64_t *boff = nullptr;
         uint64_t rows = 0, padded = 0;
         uint64_t dead_groups = 0;  // six-row views with places: groups flagged as holding no live row (memo_view.hip: kDeadGroup)
+        int live = 0;            // ... 1: the copy of such a view without them (memo_view.hip: live_view_copy; dead_groups 0, padded = 6 x its
+                                 //   groups, rows still the class's rows: a dead row is answered by a live one that contains it) --
+        double dead_lost_ns = 0; //   a third pass, decided like the others: what the queries on the flagged view have lost to its dead groups
         uint64_t bytes = 0;      // of the rows' allocation (set where a view is installed: a six-row view is (groups + 64) x 16 B, not
                                  //   what its padded row count makes of five-row groups -- ADVICE r05: the budget charged it a fifth too much)
         float build_ms = 0.f;
@@ -151,7 +154,10 @@ struct memo_index {
     int view_rows = 0;            // memo_index_set_option(MEMO_OPT_VIEW_ROWS): 0 the library's choice, 5 / 6 rows per group of a dense view
     int view_places = 1;          // memo_index_set_option(MEMO_OPT_VIEW_PLACES): 0 the rows of a dense view keep the order they come in
     uint64_t view_placings = 0;   // dense views rebuilt with their rows placed (memo_index_info_t.view_placings)
-    double view_ns_per_row[3] = {0, 0, 0};  // measured by the last view build ([0] dense rows, [1] 4-byte words, [2] dense rows with places; 0: the calibrated constant)
+    int view_live = 1;            // memo_index_set_option(MEMO_OPT_VIEW_LIVE): 0 placed six-row views keep their dead groups (flagged, swept with LIVE)
+    uint64_t view_live_copies = 0;  // placed six-row views copied without their dead groups (memo_debug_view_live_copies of the AB library)
+    double view_ns_per_row[4] = {0, 0, 0, 0};  // measured by the last view build ([0] dense rows, [1] 4-byte words, [2] dense rows with places,
+                                               //   [3] the copy without dead groups, per group of the flagged view; 0: the calibrated constant)
     uint64_t view_clock = 0;
     uint64_t view_builds = 0;     // views built over the index's lifetime (memo_index_info_t.view_builds)
     DenseView views[16];          // classes of two: overlaps below 2, 4, 6 ... 32

@@ -82,6 +82,14 @@ int memo_debug_six_views(int32_t on) {
     return MEMO_OK;
 }
 
+int memo_debug_view_live(const memo_index_t *ix, int32_t k, uint64_t *copies) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (copies) *copies = ix->view_live_copies;
+    if (k < 2 || k > 32) return 0;  // (no class)
+    const memo_index::DenseView &v = ix->views6[k / 2 - 1];  // (the class of k - 1: memo_view.hip, dense_rows_for)
+    return v.p3 && v.live ? 1 : 0;
+}
+
 int memo_debug_fail_side_allocations(int32_t on) {
     g_side_alloc_fails = on != 0;
     return MEMO_OK;

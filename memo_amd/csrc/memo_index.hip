@@ -947,6 +947,12 @@ int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value) {
         ix->view_places = (int)value;
         return before;
     }
+    if (option == MEMO_OPT_VIEW_LIVE) {  // (a copy already made stays: it answers exactly what the flagged view does)
+        if (value != 0 && value != 1) return fail(MEMO_EINVAL, "MEMO_OPT_VIEW_LIVE takes 0 or 1");
+        const int before = ix->view_live;
+        ix->view_live = (int)value;
+        return before;
+    }
     if (option == MEMO_OPT_VIEW_ROWS) {
         if (value != 0 && value != 5 && value != 6) return fail(MEMO_EINVAL, "MEMO_OPT_VIEW_ROWS takes 0 (the library's choice), 5 or 6");
         const int before = ix->view_rows;

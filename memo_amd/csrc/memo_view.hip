@@ -525,6 +525,54 @@ __global__ __launch_bounds__(64) void view_live_kernel(const uint4 *__restrict__
     }
 }
 
+// The copy of a placed six-row view without its dead groups (live_view_copy): every group whose kDeadGroup bit is clear, unchanged and
+// in the order it comes (a group carries its bucket mod 32 and ends at a bucket boundary, so nothing is re-encoded), with a bucket table
+// of its own.  count -> the scan of dense_view_build -> table + scatter.  mask: a bit per group, a word per 64 groups; count: live
+// groups per 64.
+__global__ __launch_bounds__(256) void live_count_kernel(const uint4 *__restrict__ groups, uint64_t ng, unsigned long long *__restrict__ mask,
+                                                         uint32_t *__restrict__ count) {
+    const uint64_t chunks = (ng + 63) >> 6;
+    const int lane = threadIdx.x & 63;
+    for (uint64_t chunk = blockIdx.x * 4ull + (threadIdx.x >> 6); chunk < chunks; chunk += gridDim.x * 4ull) {
+        const uint64_t g = (chunk << 6) + (uint64_t)lane;
+        const unsigned long long m = __ballot(g < ng && !(groups[g].x & kDeadGroup));
+        if (lane == 0) {
+            mask[chunk] = m;
+            count[chunk] = (uint32_t)__popcll(m);
+        }
+    }
+}
+
+// live groups before group g (local / blockpre: the scan of count)
+__device__ __forceinline__ uint64_t live_before(uint64_t g, const unsigned long long *mask, const uint32_t *local, const uint64_t *blockpre) {
+    const uint64_t chunk = g >> 6;
+    return blockpre[chunk >> 10] + local[chunk] + (uint64_t)__popcll(mask[chunk] & ((1ull << (g & 63)) - 1ull));
+}
+
+// the copy's bucket table in slots: 6 x the live groups before every bucket's first group (nb entries; the last is 6 x all of them)
+__global__ void live_table_kernel(const int64_t *__restrict__ boff6, uint64_t nb, uint64_t ng, const unsigned long long *__restrict__ mask,
+                                  const uint32_t *__restrict__ local, const uint64_t *__restrict__ blockpre, uint64_t nblk,
+                                  int64_t *__restrict__ out) {
+    const uint64_t b = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    const uint64_t g = (uint64_t)boff6[b] / 6;
+    out[b] = (int64_t)(6 * (g >= ng ? blockpre[nblk] : live_before(g, mask, local, blockpre)));
+}
+
+// the live groups to their places in the copy (nout: groups the copy holds -- a place past it is never written)
+__global__ __launch_bounds__(256) void live_scatter_kernel(const uint4 *__restrict__ groups, uint64_t ng, const unsigned long long *__restrict__ mask,
+                                                           const uint32_t *__restrict__ local, const uint64_t *__restrict__ blockpre,
+                                                           uint4 *__restrict__ out, uint64_t nout) {
+    const uint64_t chunks = (ng + 63) >> 6;
+    const int lane = threadIdx.x & 63;
+    for (uint64_t chunk = blockIdx.x * 4ull + (threadIdx.x >> 6); chunk < chunks; chunk += gridDim.x * 4ull) {
+        const unsigned long long m = mask[chunk];
+        if (!((m >> lane) & 1ull)) continue;
+        const uint64_t at = blockpre[chunk >> 10] + local[chunk] + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (at < nout) out[at] = groups[(chunk << 6) + (uint64_t)lane];
+    }
+}
+
 template <int P>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void view_build_kernel(const ViewArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t view_lds[];
@@ -823,6 +871,63 @@ static int dense_view_build(int device, const uint32_t *src_p3, const int64_t *s
     return rc;
 }
 
+// A placed six-row view (groups of ng = padded / 6, bucket table boff6 of nb entries, dead_groups of them flagged kDeadGroup) without
+// its flagged groups: a new allocation of ng - dead_groups groups (+ 64 zeroed, a wave-load of slack like every view) and a new
+// bucket table.  Exact: a dead row's containers are in the view, a live one among them (containment is transitive and a row's
+// containers start in its bucket or the next), and the dead slots left in live groups only repeat a minimum.  Queued on `st`,
+// waited for once.
+static int live_view_copy(int device, const uint32_t *src_p3, const int64_t *boff6, uint64_t nb, uint64_t padded, uint64_t dead_groups,
+                          hipStream_t st, uint32_t **out_p3, int64_t **out_boff, uint64_t *out_padded) {
+    *out_p3 = nullptr;
+    *out_boff = nullptr;
+    const uint64_t ng = padded / 6;
+    if (!ng || dead_groups == 0 || dead_groups > ng || nb < 2) return MEMO_OK;
+    DeviceGuard guard(device);
+    const uint64_t chunks = (ng + 63) >> 6, nblk = (chunks + 1023) >> 10, nlive = ng - dead_groups;
+    auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
+    const uint64_t o_mask = 0, o_count = o_mask + up(chunks * 8), o_bpre = o_count + up(chunks * 4), tmp_bytes = o_bpre + up((nblk + 1) * 8);
+    char *tmp = nullptr;
+    uint4 *outg = nullptr;
+    int64_t *boff = nullptr;
+    int rc = MEMO_OK;
+    do {
+        hipError_t err = side_alloc((void **)&tmp, tmp_bytes);
+        if (err == hipSuccess) err = side_alloc((void **)&outg, (nlive + 64) * 16);
+        if (err == hipSuccess) err = side_alloc((void **)&boff, nb * 8);
+        if (err == hipErrorOutOfMemory) { rc = kNoRoom; break; }
+        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "live view: %s", hipGetErrorString(err)); break; }
+        unsigned long long *mask = reinterpret_cast<unsigned long long *>(tmp + o_mask);
+        uint32_t *count = reinterpret_cast<uint32_t *>(tmp + o_count);
+        uint64_t *blockpre = reinterpret_cast<uint64_t *>(tmp + o_bpre);
+        const uint4 *src = reinterpret_cast<const uint4 *>(src_p3);
+        const unsigned grid = (unsigned)((chunks + 3) / 4 < 256 * 32 ? (chunks + 3) / 4 : 256 * 32);
+        err = hipMemsetAsync(outg + nlive, 0, 64 * 16, st);
+        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "live view: %s", hipGetErrorString(err)); break; }
+        hipLaunchKernelGGL(live_count_kernel, dim3(grid), dim3(256), 0, st, src, ng, mask, count);
+        hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk), dim3(256), 0, st, count, chunks, count, blockpre);
+        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockpre, nblk);
+        hipLaunchKernelGGL(live_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, boff6, nb, ng, mask, count, blockpre, nblk,
+                           boff);
+        hipLaunchKernelGGL(live_scatter_kernel, dim3(grid), dim3(256), 0, st, src, ng, mask, count, blockpre, outg, nlive);
+        uint64_t total = 0;
+        err = hipGetLastError();
+        if (err == hipSuccess) err = hipMemcpyAsync(&total, blockpre + nblk, 8, hipMemcpyDeviceToHost, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "live view: %s", hipGetErrorString(err)); break; }
+        if (total != nlive) { rc = fail(MEMO_EHIP, "live view: %llu live groups, the placing pass counted %llu", (unsigned long long)total,
+                                        (unsigned long long)nlive); break; }
+        *out_p3 = reinterpret_cast<uint32_t *>(outg);
+        *out_boff = boff;
+        *out_padded = 6 * nlive;
+        outg = nullptr;
+        boff = nullptr;
+    } while (0);
+    (void)hipFree(tmp);
+    (void)hipFree(outg);
+    (void)hipFree(boff);
+    return rc;
+}
+
 // The same for the 4-byte WORDS (formats 4 / 12: the overlap byte sits at bit len_shift): the words whose overlap is below cap, in
 // the order they come, with the kept-rows table -- keep bits, scan, scatter (the order inside the view's buckets is the caller's).
 static int packed_filter(int device, const uint32_t *src, const int64_t *src_boff, uint64_t rows, uint64_t nb, int cap, int min_tenths,
@@ -1009,7 +1114,9 @@ constexpr double kPlacedViewNsPerRow = 0.0078;  // ... with the places of the ro
 constexpr double kPlacedGainPerKm1 = 0.0013;    // what places buy a sweep on the view: 4.4 % at k = 31, 2 % at k = 21 (profiles/r04_view_levels.txt)
 constexpr double kPackedViewNsPerRow = 0.03;    // keep, scan, scatter, and the order inside the view's buckets
 constexpr double kOrderNsPerRow = 0.014;        // copy + the order inside the buckets (more on indexes of many rows per start)
+constexpr double kLiveCopyNsPerGroup = 0.008;   // live_view_copy, per group of the flagged view: two reads of it, a write of its live groups
 constexpr double kPassFixedNs = 200e3;
+constexpr double kPassNs[4] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow, kLiveCopyNsPerGroup};  // (view_ns_per_row)
 
 static double rows_in_window(const memo_index *ix, double src_rows, int64_t window, int km1) {
     const double span = (double)ix->max_s - (double)ix->min_s + 1.0;
@@ -1031,18 +1138,17 @@ static bool view_due(memo_index *ix, memo_index::DenseView &v, int kind, double 
     if (g_prepare_only) return true;
     if (spared > 0) v.lost_ns += rows_in_window(ix, src_rows, window, km1) * spared * kSweepNsPerRow;
     if (++v.seen <= v.ask_after) return false;
-    constexpr double kConst[3] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow};
-    const double per_row = ix->view_ns_per_row[kind] > 0 ? ix->view_ns_per_row[kind] : kConst[kind];
+    const double per_row = ix->view_ns_per_row[kind] > 0 ? ix->view_ns_per_row[kind] : kPassNs[kind];
     const double cost = (src_rows * per_row + kPassFixedNs) * (double)v.backoff * (double)ix->build_cost_pct / 100.0;
     return v.lost_ns >= cost;
 }
 
+// kind 3: the copy without dead groups, src_rows = the flagged view's groups
 static void view_built(memo_index *ix, float build_ms, int kind, double src_rows) {  // what the pass cost, for the next estimate
-    constexpr double kConst[3] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow};
     const double ns = (double)build_ms * 1e6 - kPassFixedNs;
     // within a factor of four of the calibrated constant: the pass is timed with its allocations, and a hipMalloc that stalls (350 ms
     // for 0.85 GB seen on one box: gpurun r5valid) must not make every later view of the index look two hundred times as dear
-    const double floor = 0.25 * kConst[kind], ceil = 4.0 * kConst[kind];
+    const double floor = 0.25 * kPassNs[kind], ceil = 4.0 * kPassNs[kind];
     if (src_rows > 0) ix->view_ns_per_row[kind] = ns / src_rows > floor ? (ns / src_rows < ceil ? ns / src_rows : ceil) : floor;
 }
 
@@ -1055,6 +1161,18 @@ static bool places_due(memo_index *ix, memo_index::DenseView &v, double src_rows
     v.unplaced_ns += read * 1.5 * kSweepNsPerRow * kPlacedGainPerKm1 * (double)km1;  // (a sweep on a view: 0.72 ps per row it reads)
     const double per_row = ix->view_ns_per_row[2] > 0 ? ix->view_ns_per_row[2] : kPlacedViewNsPerRow;
     return v.unplaced_ns >= (src_rows * per_row + kPassFixedNs) * (double)v.backoff * (double)ix->build_cost_pct / 100.0;
+}
+
+// A placed six-row view whose dead groups are flagged: is it time for the copy without them (live_view_copy)?  The sweep on the
+// flagged view loads every group, so a query loses the slots of its window in dead groups x what a sweep pays per row it reads;
+// the copy costs a read of the view.  The same rule again -- and never inside memo_index_prepare, which hands out the flagged view
+// (a whole-window query on config 3 loses ~0.09 ms against a pass of ~0.5 ms: a few such queries build it).
+static bool live_due(memo_index *ix, memo_index::DenseView &v, int64_t window, int km1) {
+    if (g_prepare_only || v.padded < 6) return false;
+    const double groups = (double)(v.padded / 6), share = (double)v.dead_groups / groups;
+    v.dead_lost_ns += rows_in_window(ix, (double)v.padded, window, km1) * share * kSweepNsPerRow;
+    const double per_group = ix->view_ns_per_row[3] > 0 ? ix->view_ns_per_row[3] : kLiveCopyNsPerGroup;
+    return v.dead_lost_ns >= (groups * per_group + kPassFixedNs) * (double)v.backoff * (double)ix->build_cost_pct / 100.0;
 }
 
 // The 4-byte rows brought into a query order (memo_interleave.hip: 2 = the conservation order, 3 = the membership order, 0 =
@@ -1346,6 +1464,38 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint
             ++ix->view_placings;
             ix->last_view_ms = v.build_ms;
             view_built(ix, v.build_ms, 2, src_rows);
+            keep_views_in_budget(ix, &v, base_bytes, true);
+        }
+    } else if (account && v.state == 1 && v.placed && six && !v.live && v.dead_groups > 0 && ix->view_live && live_due(ix, v, window, km1)) {
+        // the placed view without its dead groups: built beside the one in use like the places, then the class switches over.  Not a
+        // view of its own: view_builds, view_placings and views_resident stay; the tile tables of the flagged view go with it, the
+        // sweep below makes the copy's
+        DeviceGuard guard(ix->device);
+        memo_index::DenseView nv;
+        const uint64_t groups = v.padded / 6;
+        const int rc = build_timed(ix, nv, st, [&]() {
+            return live_view_copy(ix->device, v.p3, v.boff, ix->nb, v.padded, v.dead_groups, st, &nv.p3, &nv.boff, &nv.padded);
+        });
+        if (rc && rc != kNoRoom) return rc;
+        if (rc == kNoRoom || !nv.p3) {  // (no room for the copy: the flagged view stays; look again much later)
+            v.dead_lost_ns = 0;
+            if (v.backoff < (1 << 16)) v.backoff *= 4;
+        } else {
+            const int backoff = v.backoff, ask = v.ask_after;
+            const uint64_t rows = v.rows;
+            retire_view(ix, v, true);
+            v = nv;
+            v.cap = cap;
+            v.rows = rows;
+            v.bytes = dense_view_bytes(v.padded, 6);
+            v.state = 1;
+            v.placed = 1;
+            v.live = 1;
+            v.backoff = backoff;
+            v.ask_after = ask;
+            ++ix->view_live_copies;
+            ix->last_view_ms = v.build_ms;
+            view_built(ix, v.build_ms, 3, (double)groups);
             keep_views_in_budget(ix, &v, base_bytes, true);
         }
     }
