@@ -3,6 +3,8 @@
 #ifndef MEMO_SWEEP_H
 #define MEMO_SWEEP_H
 
+#include <type_traits>
+
 #include "memo_common.h"
 
 namespace memo {
@@ -544,6 +546,62 @@ extern unsigned long long *g_stamp_buffer;  // diagnostic builds: 8 words per wo
 
 using SweepKernel = void (*)(const SweepArgs);
 
+// ------------------------------------------------------------------------------------------
+// kernel picker: runtime choices -> template arguments.  A launcher hands a generic lambda that names one kernel family's
+// instance from the arguments it receives (std::integral_constant values, or a Type<> tag for a row type); each picker calls it
+// only with the values listed, so a family instantiates exactly the kernels its launcher can pick.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+struct Type { using type = T; };
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <bool B>
+using Bool = std::integral_constant<bool, B>;
+
+// f(Int<V>) for the V of Vs that equals v; nullptr when none does
+template <int... Vs, typename F>
+SweepKernel pick_int(int v, F &&f) {
+    SweepKernel k = nullptr;
+    (void)((v == Vs ? (k = f(Int<Vs>{}), true) : false) || ...);
+    return k;
+}
+
+template <typename F>
+SweepKernel pick_bool(bool b, F &&f) {
+    return b ? f(Bool<true>{}) : f(Bool<false>{});
+}
+
+// threads per workgroup of the unclipped families: 8, 4 or otherwise 1 wave; of the clipped ones: 4 or otherwise 1
+inline int threads_of(int waves) { return waves == 8 ? 512 : waves == 4 ? 256 : 64; }
+inline int clipped_threads_of(int waves) { return waves == 4 ? 256 : 64; }
+
+// the 4- / 6-byte rows of fmt: 4 = 4-byte words, 12 = words with 12-bit start fields, otherwise (6) words + 16-bit order column.
+// CHECKED: some annot could lie outside the result matrix.
+template <bool CHECKED, typename F>
+SweepKernel pick_packed(int fmt, F &&f) {
+    return fmt == 4    ? f(Type<PackedRows<false, CHECKED>>{})
+           : fmt == 12 ? f(Type<PackedRows<false, CHECKED, true>>{})
+                       : f(Type<PackedRows<true, CHECKED>>{});
+}
+
+// the clipped families read any row source: the packed rows, checked or not, or (fmt 0) the int64 columns
+template <typename F>
+SweepKernel pick_rows_clipped(int fmt, bool checked, F &&f) {
+    if (!fmt) return f(Type<WideRows>{});
+    return checked ? pick_packed<true>(fmt, f) : pick_packed<false>(fmt, f);
+}
+
+// the order rides in the row word (from bit Rows::kTopShift: 8 / 12 bits) when the sentinel num_docs fits that field;
+// f(Int<TOP>), TOP = 0 where it does not or the order has a column of its own
+template <typename Rows, typename F>
+SweepKernel pick_top(int num_docs, F &&f) {
+    if constexpr (Rows::kAnnot16) {
+        return f(Int<0>{});
+    } else {
+        return num_docs < (1 << (32 - Rows::kTopShift)) ? f(Int<Rows::kTopShift>{}) : f(Int<0>{});
+    }
+}
+
 inline int floor_log2(uint32_t v) { return 31 - __builtin_clz(v); }
 int launch_tiles(SweepKernel kernel, SweepArgs &A, int w, int threads, size_t lds, hipStream_t st);
 // memo_sweep_cons3t.hip: the table-driven dense-row sweep; 1 = this query does not fit it
@@ -556,6 +614,20 @@ int pick_rows(const memo_index *ix, int32_t k, int &fmt);
 int check_query_args(const memo_index *ix, int64_t qs, int64_t qe, int32_t k, int32_t num_docs,
                      const void *d_out);
 void fill_args(const memo_index *ix, SweepArgs &A, int64_t qs, int64_t qe, int32_t k, void *d_out);
+
+// the 4-byte words a sweep reads: the k-class view of them where one exists or is due (packed_rows_for, memo_view.hip)
+static inline int use_words(memo_index *ix, SweepArgs &A, int fmt, bool membership, hipStream_t st) {
+    ix->last_rows_read = ix->rows;  // (6-byte rows and the int64 columns have no views)
+    if (fmt != 4 && fmt != 12) return MEMO_OK;
+    uint32_t *vpk = nullptr;
+    int64_t *vboff = nullptr;
+    uint64_t vrows = 0;
+    if (int rc = packed_rows_for(ix, A.km1, A.qe - A.qs, membership, st, &vpk, &vboff, &vrows)) return rc;
+    A.pk = vpk;
+    A.boff = vboff;
+    ix->last_rows_read = vrows;
+    return MEMO_OK;
+}
 
 }  // namespace memo
 

@@ -912,60 +912,9 @@ __global__ __launch_bounds__(256) void long_rows_tail_kernel(const int64_t *ls, 
         out[whole + threadIdx.x] = (OutT)best[threadIdx.x];
 }
 
-template <typename Rows, typename OutT>
-SweepKernel cons_kernel(int w, int waves) {
-#define MEMO_CASE(WW)                                                                         \
-    case WW:                                                                                  \
-        return waves == 4 ? (SweepKernel)sweep_conservation_kernel<Rows, WW, Rows::kLoads, 256, OutT>   \
-                          : (SweepKernel)sweep_conservation_kernel<Rows, WW, Rows::kLoads, 64, OutT>;
-    switch (w) {
-        MEMO_CASE(256)
-        MEMO_CASE(512)
-        MEMO_CASE(1024)
-        MEMO_CASE(2048)
-        MEMO_CASE(4096)
-    }
-#undef MEMO_CASE
-    return nullptr;
-}
-
 }  // namespace
 
 constexpr int kHaloLoads = 6;  // 16-byte loads in flight per lane
-
-template <typename Rows, typename OutT, int TOP>
-static SweepKernel halo_kernel(int waves) {
-    return waves == 8   ? (SweepKernel)sweep_conservation_halo_kernel<Rows, kHaloLoads, 512, OutT, TOP>
-           : waves == 4 ? (SweepKernel)sweep_conservation_halo_kernel<Rows, kHaloLoads, 256, OutT, TOP>
-                        : (SweepKernel)sweep_conservation_halo_kernel<Rows, kHaloLoads, 64, OutT, TOP>;
-}
-
-template <typename Rows, typename OutT, int TOP>
-static SweepKernel r4_kernel(int waves) {
-    return waves == 8   ? (SweepKernel)sweep_conservation_r4_kernel<Rows, kHaloLoads, 512, OutT, TOP>
-           : waves == 4 ? (SweepKernel)sweep_conservation_r4_kernel<Rows, kHaloLoads, 256, OutT, TOP>
-                        : (SweepKernel)sweep_conservation_r4_kernel<Rows, kHaloLoads, 64, OutT, TOP>;
-}
-
-template <typename Rows, typename OutT, int TOP>
-static SweepKernel mixed_kernel(int waves) {
-    return waves == 8   ? (SweepKernel)sweep_conservation_mixed_kernel<Rows, kHaloLoads, 512, OutT, TOP>
-           : waves == 4 ? (SweepKernel)sweep_conservation_mixed_kernel<Rows, kHaloLoads, 256, OutT, TOP>
-                        : (SweepKernel)sweep_conservation_mixed_kernel<Rows, kHaloLoads, 64, OutT, TOP>;
-}
-
-template <typename OutT>
-static SweepKernel halo3_kernel(int waves, bool annot9) {
-    if constexpr (sizeof(OutT) == 2) {
-        if (annot9)  // (256 .. 511 genomes)
-            return waves == 8   ? (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, 512, OutT, true>
-                   : waves == 4 ? (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, 256, OutT, true>
-                                : (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, 64, OutT, true>;
-    }
-    return waves == 8   ? (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, 512, OutT>
-           : waves == 4 ? (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, 256, OutT>
-                        : (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, 64, OutT>;
-}
 
 template <typename OutT>
 static int long_rows_conservation(const memo_index *ix, int64_t qs, int64_t qe, int32_t k, int ncols,
@@ -1054,6 +1003,79 @@ static int pick_levels(const memo_index *ix, int k, bool moderate) {
     return fallback;
 }
 
+// Tile of the clipped sweep: the debug tile width as a power of two up to 4096, else the widest tile whose doubling arrays fit
+// the budget, narrowed on short windows.
+static int clipped_width(int tile_w, int nlev, size_t budget, int64_t len) {
+    int w = tile_w;
+    while (w & (w - 1)) w &= w - 1;  // (the clipped kernels and the doubling arrays come in powers of two)
+    if (w > 4096) w = 4096;
+    if (!w) {
+        w = 4096;
+        while ((size_t)nlev * w * 4 > budget && w > 256) w >>= 1;
+        while (w > 1024 && len / w < 8192) w >>= 1;                // big 4-wave tiles: a few thousand suffice
+        while (w > 256 && w <= 1024 && len / w < 32768) w >>= 1;  // short windows: many small tiles
+    }
+    return w;
+}
+
+// Tile of the radix-4 and mixed level arrays: m arrays of ls cells (the debug tile width, else ls0), halo hl left and hr right
+// of a tile of tw positions (whole buckets).  fits: the tile holds a bucket, the halo is at most two thirds, the arrays fit in LDS.
+struct LevelTile {
+    int hl, hr, ls, tw;
+    bool fits;
+};
+static LevelTile level_tile(int bw, int km1, int fmt, int64_t len, int tile_w, int ls0, int m) {
+    LevelTile t;
+    t.hl = (km1 + 3) & ~3;
+    t.hr = (km1 + bw - 1 + 3) & ~3;
+    int ls = tile_w ? tile_w : ls0;
+    if (ls > 8192) ls = 8192;
+    if (fmt == 12 && ls > 4096) ls = 4096;  // (12-bit start field: start - a < array size <= 2^12)
+    // short windows: enough tiles to fill the chip (a few thousand of them)
+    while (!tile_w && ls > 640 && len / (ls - t.hl - t.hr > bw ? ls - t.hl - t.hr : bw) < 4096) ls = (ls / 2) & ~3;
+    t.ls = ls;
+    t.tw = (ls - t.hl - t.hr) / bw * bw;
+    t.fits = t.tw >= bw && 2 * t.tw >= t.hl + t.hr && (size_t)m * (t.hl + t.tw + t.hr) * 4 <= 160 * 1024;
+    return t;
+}
+
+// The dense rows of this k's class (a view that leaves out the rows that cannot write at this k), or all of them, for the
+// unclipped doubling tile in A.  Views of six rows per group are for the table-driven kernel alone: a query it cannot take (a
+// negative window start, no room for the tile table) asks again for five-row groups.  The table-driven kernel sweeps the dense
+// rows wherever the query fits it; only the debug row sources 5 and 10 (tune.persistent == 1) keep them on
+// sweep_conservation_halo3_kernel.  *variant: 2 / 3 when the table-driven kernel answered on five- / six-row groups; 0: A holds
+// five-row groups for sweep_conservation_halo3_kernel.
+static int sweep_dense_rows(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, bool top8, bool top9, hipStream_t st,
+                            int *variant) {
+    const memo_tuning &tune = ix->tune;
+    const bool table = tune.persistent == 5 || tune.persistent == 0;
+    int view_cap = 0;  // (a view whose cap is k - 1 holds exactly the rows that write at this k: the table-driven kernel's row blocks drop their test)
+    int rpg = 5;       // rows per 16-byte group of the source handed out: 5, or 6 (a view whose groups carry their bucket: memo_view.hip)
+    *variant = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const bool can_six = attempt == 0 && table && top8 && A.nlev <= 5 && A.qs >= 0;
+        uint32_t *vp3 = nullptr;
+        int64_t *vboff = nullptr;
+        uint64_t vrows = 0;
+        if (int rc = dense_rows_for(ix, A.km1, A.qe - A.qs, st, &vp3, &vboff, &vrows, &view_cap, can_six, &rpg, attempt == 0)) return rc;
+        A.p3 = vp3;
+        A.boff = vboff;
+        ix->last_rows_read = vrows;
+        if (table) {
+            // the tile's row slice from a table built once per (index, k): memo_sweep_cons3t.hip; 1 = does not fit
+            const int trc = launch_halo3t(ix, A, tw, elem_bytes, st, top9, view_cap == A.km1 && !tune.no_all_write, rpg == 6,
+                                          rpg == 6 && ix->last_view_placed && ix->last_view_dead_share >= kLiveMinShare);
+            if (trc < 0) return trc;
+            if (trc == MEMO_OK) {
+                *variant = rpg == 6 ? 3 : 2;
+                return MEMO_OK;
+            }
+        }
+        if (rpg != 6) return MEMO_OK;  // (five-row groups: the kernel without a table takes them)
+    }
+    return fail(MEMO_EHIP, "a six-row view reached a sweep that cannot read it");
+}
+
 template <typename OutT>
 static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t k, int32_t num_docs,
                               OutT *d_out, void *stream) {
@@ -1079,21 +1101,12 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     A.nwords = 0;
     int fmt;
     if ((rc = pick_rows(ix, k, fmt))) return rc;
-    hipStream_t st_early = static_cast<hipStream_t>(stream);
-    // the 4-byte words a sweep reads: the k-class view of them where one exists or is due (packed_rows_for, memo_view.hip)
-    auto use_words = [&]() -> int {
-        ix->last_rows_read = ix->rows;  // (6-byte rows and the int64 columns have no views)
-        if (fmt != 4 && fmt != 12) return MEMO_OK;
-        uint32_t *vpk = nullptr;
-        int64_t *vboff = nullptr;
-        uint64_t vrows = 0;
-        const int vrc = packed_rows_for(ix, k - 1, qe - qs, false, st_early, &vpk, &vboff, &vrows);
-        if (vrc) return vrc;
-        A.pk = vpk;
-        A.boff = vboff;
-        ix->last_rows_read = vrows;
-        return MEMO_OK;
-    };
+
+    // -- the plan: the kernel family (numbered as memo_index_info_t.last_sweep: 1 clipped, 2 doubling, 3 radix-4, 4 mixed,
+    //    5 the dense rows), its kernel and its tile
+    const memo_tuning &tune = ix->tune;
+    const int km1 = k - 1, bw = 1 << ix->bshift;
+    const int64_t len = qe - qs;
     // Tile shape, from interleaved A/B on one device (profiles/r01_ab_*.txt).
     //  int64 rows (HBM-bound): four waves share a 4096-position tile -- fewest k-1 row halos per
     //    position; 1-3 % over one wave per 1024 positions at k <= 32, 10 % at k = 101.
@@ -1101,22 +1114,14 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     //    the k-1 halo: 1024 positions x 4 waves wins at k = 31 (20 KiB, 8 workgroups per CU) and at
     //    k = 101 (28 KiB) over 512 or 2048 positions.
     // Short windows want many small tiles either way.
-    const memo_tuning &tune = ix->tune;
-    int w = tune.tile_w, waves = tune.waves == 1 || tune.waves == 4 ? tune.waves : 0;
-    while (w & (w - 1)) w &= w - 1;  // (the clipped kernels and the doubling arrays come in powers of two)
-    if (w > 4096) w = 4096;
     // int64 rows on a sparse index (< 2 rows per position: profiles/r01_sparse_index_tiles.txt) are
     // no longer HBM-bound per tile; they want the packed rows' shape (more workgroups per CU)
     const double span = (double)(ix->max_s - ix->min_s) + 1.0;
     const bool sparse = (double)ix->rows < 2.0 * span;
-    if (!w) {
-        const size_t budget = (fmt || sparse) ? 32 * 1024 : 80 * 1024;
-        w = 4096;
-        while ((size_t)A.nlev * w * 4 > budget && w > 256) w >>= 1;
-        while (w > 1024 && (qe - qs) / w < 8192) w >>= 1;                 // big 4-wave tiles: a few thousand suffice
-        while (w > 256 && w <= 1024 && (qe - qs) / w < 32768) w >>= 1;   // short windows: many small tiles
-    }
-    if (!waves) waves = w >= 1024 ? 4 : 1;  // short windows end up with small tiles: one wave each
+    auto clipped_budget = [&] { return (fmt || sparse) ? (size_t)32 * 1024 : (size_t)80 * 1024; };
+    auto clipped_waves = [&](int ww) { return tune.waves == 1 || tune.waves == 4 ? tune.waves : (ww >= 1024 ? 4 : 1); };
+    int w = clipped_width(tune.tile_w, A.nlev, clipped_budget(), len);
+    int waves = clipped_waves(w);  // short windows end up with small tiles: one wave each
     const bool checked = ix->max_annot >= (uint64_t)A.ncols;  // some row could be outside the matrix
     // unclipped scatter (PackedRows, every annot inside the matrix): w is the size of a level array,
     // HL + tile + HR cells (start - a <= tile + k + 30 inside a slice); the tile is what is left
@@ -1132,76 +1137,51 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     // atomics than the fold steps save.
     const bool moderate = (double)ix->rows < 12.0 * span;
     // (debug switch scatter = 5: the mixed arrays with the library's level plan, whatever pick_levels would say)
-    const int levels = !halo || fmt == 3 ? 0 : tune.scatter == 5 ? 4 : tune.scatter >= 2 ? tune.scatter : (k - 1 >= 64 ? pick_levels(ix, k, moderate) : 2);
-    if (levels == 3) {
-        const int bw = 1 << ix->bshift;
-        const int hl = (k - 1 + 3) & ~3, hr = (k - 1 + bw - 1 + 3) & ~3;
-        const int m = (floor_log2((uint32_t)(k - 1)) >> 1) + 1;
-        int ls = tune.tile_w ? tune.tile_w : 2560;
-        if (ls > 8192) ls = 8192;
-        if (fmt == 12 && ls > 4096) ls = 4096;  // (12-bit start field: start - a < array size <= 2^12)
-        // short windows: enough tiles to fill the chip (a few thousand of them)
-        while (!tune.tile_w && ls > 640 && (qe - qs) / (ls - hl - hr > bw ? ls - hl - hr : bw) < 4096) ls = (ls / 2) & ~3;
-        const int tw = (ls - hl - hr) / bw * bw;
-        if (tw >= bw && 2 * tw >= hl + hr && (size_t)m * (hl + tw + hr) * 4 <= 160 * 1024) {
-            A.nlev = m;
-            A.hl = hl;
-            A.w = tw;
-            A.ls = hl + tw + hr;
-            waves = tune.waves == 1 || tune.waves == 4 || tune.waves == 8 ? tune.waves : (ls >= 2048 ? 8 : 4);
-            // the order rides in the row word when the sentinel num_docs fits its field (8 / 12 bits)
-            SweepKernel kern = fmt == 4    ? (num_docs <= 255 ? r4_kernel<PackedRows<false, false>, OutT, 24>(waves)
-                                                              : r4_kernel<PackedRows<false, false>, OutT, 0>(waves))
-                               : fmt == 12 ? (num_docs <= 4095 ? r4_kernel<PackedRows<false, false, true>, OutT, 20>(waves)
-                                                               : r4_kernel<PackedRows<false, false, true>, OutT, 0>(waves))
-                                           : r4_kernel<PackedRows<true, false>, OutT, 0>(waves);
-            if ((rc = use_words())) return rc;
-            if ((rc = launch_tiles(kern, A, tw, 64 * waves, (size_t)m * A.ls * 4, st))) return rc;
-            ix->last_sweep = 3;
-            return long_rows_conservation<OutT>(ix, qs, qe, k, A.ncols, d_out, st);
-        }
-    }
+    const int levels = !halo || fmt == 3 ? 0 : tune.scatter == 5 ? 4 : tune.scatter >= 2 ? tune.scatter : (km1 >= 64 ? pick_levels(ix, k, moderate) : 2);
+    SweepKernel kern = nullptr;
+    int sweep = 0, tw = 0, arrays = 0;
+    size_t lds = 0;
+    bool three = false, top9 = false, top8 = false, doubling_tile = false;
     // Mixed levels (sweep_conservation_mixed_kernel): 1, 4, 16, then doubling -- of which only the arrays some row of the index
     // can write to exist (level_plan; the debug switch scatter = 4 asks for all of them, the layout of rounds 2-3).  k - 1 >= 16.
-    if (levels == 4 && k - 1 >= 16) {
-        const int bw = 1 << ix->bshift;
-        const int hl = (k - 1 + 3) & ~3, hr = (k - 1 + bw - 1 + 3) & ~3;
-        int ftop = 0;
+    if (levels == 3 || (levels == 4 && km1 >= 16)) {
+        int ftop = 0, m = 0, D = 0;
         uint32_t mask = 0;
-        const int D = level_plan(ix, k - 1, tune.scatter == 4, &ftop, &mask);
-        const int m = plan_of(D, mask).arrays();
-        int ls = tune.tile_w ? tune.tile_w : (40 * 1024 / (4 * m)) & ~63;
-        if (ls > 8192) ls = 8192;
-        if (fmt == 12 && ls > 4096) ls = 4096;  // (12-bit start field: start - a < array size <= 2^12)
-        while (!tune.tile_w && ls > 640 && (qe - qs) / (ls - hl - hr > bw ? ls - hl - hr : bw) < 4096) ls = (ls / 2) & ~3;
-        const int tw = (ls - hl - hr) / bw * bw;
-        if (tw >= bw && 2 * tw >= hl + hr && (size_t)m * (hl + tw + hr) * 4 <= 160 * 1024) {
+        if (levels == 3) {
+            D = m = (floor_log2((uint32_t)km1) >> 1) + 1;
+        } else {
+            D = level_plan(ix, km1, tune.scatter == 4, &ftop, &mask);
+            m = plan_of(D, mask).arrays();
+        }
+        const LevelTile t = level_tile(bw, km1, fmt, len, tune.tile_w, levels == 3 ? 2560 : (40 * 1024 / (4 * m)) & ~63, m);
+        if (t.fits) {
             A.nlev = D;
             A.lvmask = mask;
             A.ftop = ftop;
-            A.hl = hl;
-            A.w = tw;
-            A.ls = hl + tw + hr;
-            waves = tune.waves == 1 || tune.waves == 4 || tune.waves == 8 ? tune.waves : (ls >= 1536 ? 8 : 4);
-            SweepKernel kern = fmt == 4    ? (num_docs <= 255 ? mixed_kernel<PackedRows<false, false>, OutT, 24>(waves)
-                                                              : mixed_kernel<PackedRows<false, false>, OutT, 0>(waves))
-                               : fmt == 12 ? (num_docs <= 4095 ? mixed_kernel<PackedRows<false, false, true>, OutT, 20>(waves)
-                                                               : mixed_kernel<PackedRows<false, false, true>, OutT, 0>(waves))
-                                           : mixed_kernel<PackedRows<true, false>, OutT, 0>(waves);
-            if ((rc = use_words())) return rc;
-            if ((rc = launch_tiles(kern, A, tw, 64 * waves, (size_t)m * A.ls * 4, st))) return rc;
-            ix->last_sweep = 4;
-            ix->last_arrays = m;
-            return long_rows_conservation<OutT>(ix, qs, qe, k, A.ncols, d_out, st);
+            A.hl = t.hl;
+            A.w = tw = t.tw;
+            A.ls = t.hl + t.tw + t.hr;
+            waves = tune.waves == 1 || tune.waves == 4 || tune.waves == 8 ? tune.waves : (t.ls >= (levels == 3 ? 2048 : 1536) ? 8 : 4);
+            sweep = levels;
+            arrays = m;
+            lds = (size_t)m * A.ls * 4;
+            kern = pick_packed<false>(fmt, [&](auto R) {
+                using Rows = typename decltype(R)::type;
+                return pick_top<Rows>(num_docs, [&](auto TOP) {
+                    return pick_int<512, 256, 64>(threads_of(waves), [&](auto T) {
+                        return levels == 3 ? (SweepKernel)sweep_conservation_r4_kernel<Rows, kHaloLoads, T, OutT, TOP>
+                                           : (SweepKernel)sweep_conservation_mixed_kernel<Rows, kHaloLoads, T, OutT, TOP>;
+                    });
+                });
+            });
         }
     }
-    if (halo) {
+    if (!kern && halo) {
         // A/B (profiles/r01_unclipped_scatter.txt): arrays of 1024 cells x 4 waves win at every window
         // length from 10^6 positions up and at k = 21 .. 101
-        const int bw = 1 << ix->bshift;  // a slice ends at a bucket boundary: start - a <= tile + k - 1 + bw - 2
-        const int hl = (k - 1 + 3) & ~3, hr = (k - 1 + bw - 1 + 3) & ~3;
-        if (!tune.tile_w) w = k - 1 >= 128 ? 2048 : 1024;  // (k = 256 on config 5: 1.40 ms with 1024 cells x 4 waves, 1.14 with 2048 x 8)
-        int tw = 0;
+        // (a slice ends at a bucket boundary: start - a <= tile + k - 1 + bw - 2)
+        const int hl = (km1 + 3) & ~3, hr = (km1 + bw - 1 + 3) & ~3;
+        if (!tune.tile_w) w = km1 >= 128 ? 2048 : 1024;  // (k = 256 on config 5: 1.40 ms with 1024 cells x 4 waves, 1.14 with 2048 x 8)
         for (;; w <<= 1) {
             tw = (w - hl - hr) / bw * bw;
             if ((tw >= bw && 2 * tw >= hl + hr) || w >= 4096) break;  // keep the halo under two thirds of the array
@@ -1209,6 +1189,7 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
         while ((size_t)A.nlev * (hl + tw + hr) * 4 > 160 * 1024 && tw > bw) tw = (tw / 2 + bw - 1) / bw * bw;
         if (tw < bw) halo = false;
         else {
+            doubling_tile = true;
             A.hl = hl;
             A.w = tw;
             A.ls = hl + tw + hr;
@@ -1221,94 +1202,75 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
             // profiles/r02_dense_rows_ab.txt).  Short interleaved timings had shown them level: a switch of kernels
             // sets off a swing of the clocks that lasts some thirty launches, and the dense kernel, which draws more
             // power per unit of time, sits on the cap at a lower clock (2.2 against 2.36 GHz).
-            const bool top8 = num_docs <= 255;
+            top8 = num_docs <= 255;
             // (the dense rows may leave out the rows that can never write at k <= 64 -- memo_common.h: boff3 -- and then have
             // their own row numbers and bucket table; they answer only while they still hold a row per position)
             const uint64_t drows = ix->boff3 ? ix->rows3 : ix->rows;
             // 256 .. 511 genomes: the table-driven kernel's nine-bit form (memo_sweep_cons3t.hip: A9), uint16 results, or not the dense rows
-            const bool top9 = !top8 && num_docs <= 511 && ix->max_annot <= 511 && sizeof(OutT) == 2;
-            const bool three = ix->p3 && (!ix->pk || !tune.force_packed) && k - 1 <= 63 && A.ls <= 1024 && (top8 || top9) &&
-                         ((double)drows >= span || !ix->pk);
-            int view_cap = 0;  // (a view whose cap is k - 1 holds exactly the rows that write at this k: the table-driven kernel's row blocks drop their test)
-            int rpg = 5;       // rows per 16-byte group of the source handed out: 5, or 6 (a view whose groups carry their bucket: memo_view.hip)
-            ix->last_variant = 0;
-            // the dense rows of this k's class (a view that leaves out the rows that cannot write at this k), or all of them.  Views of
-            // six rows per group are for the table-driven kernel alone: a query it cannot take (a negative window start, no room for
-            // the tile table) asks again for five-row groups.  The table-driven kernel sweeps the dense rows wherever the query fits
-            // it; only the debug row sources 5 and 10 (tune.persistent == 1) keep them on sweep_conservation_halo3_kernel.
-            const bool table = three && (tune.persistent == 5 || tune.persistent == 0);
-            for (int attempt = 0; three && attempt < 2; ++attempt) {
-                const bool can_six = attempt == 0 && table && top8 && A.nlev <= 5 && qs >= 0;
-                uint32_t *vp3 = nullptr;
-                int64_t *vboff = nullptr;
-                uint64_t vrows = 0;
-                if ((rc = dense_rows_for(ix, k - 1, qe - qs, st, &vp3, &vboff, &vrows, &view_cap, can_six, &rpg, attempt == 0))) return rc;
-                A.p3 = vp3;
-                A.boff = vboff;
-                ix->last_rows_read = vrows;
-                if (table) {
-                    // the tile's row slice from a table built once per (index, k): memo_sweep_cons3t.hip; 1 = does not fit
-                    const int trc = launch_halo3t(ix, A, tw, (int)sizeof(OutT), st, top9, view_cap == k - 1 && !tune.no_all_write, rpg == 6,
-                                                  rpg == 6 && ix->last_view_placed && ix->last_view_dead_share >= kLiveMinShare);
-                    if (trc < 0) return trc;
-                    if (trc == MEMO_OK) {
-                        ix->last_sweep = 5;
-                        ix->last_variant = rpg == 6 ? 3 : 2;
-                        return long_rows_conservation<OutT>(ix, qs, qe, k, A.ncols, d_out, st);
+            top9 = !top8 && num_docs <= 511 && ix->max_annot <= 511 && sizeof(OutT) == 2;
+            three = ix->p3 && (!ix->pk || !tune.force_packed) && km1 <= 63 && A.ls <= 1024 && (top8 || top9) &&
+                    ((double)drows >= span || !ix->pk);
+            if (three || fmt != 3) {  // (else the int64 columns below, or an error when they are gone too)
+                sweep = three ? 5 : 2;
+                lds = (size_t)A.nlev * A.ls * 4;
+                kern = pick_int<512, 256, 64>(threads_of(waves), [&](auto T) -> SweepKernel {
+                    if (three) {  // (no tile table: no room, a negative window start)
+                        if constexpr (sizeof(OutT) == 2) {
+                            if (top9)  // (256 .. 511 genomes)
+                                return (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, T, OutT, true>;
+                        }
+                        return (SweepKernel)sweep_conservation_halo3_kernel<PackedRows3::kLoads, T, OutT>;
                     }
-                }
-                if (rpg != 6) break;  // (five-row groups: the kernel without a table takes them)
-            }
-            if (three && rpg == 6) return fail(MEMO_EHIP, "a six-row view reached a sweep that cannot read it");
-            if (!three && fmt == 3) {
-                halo = false;  // (below: the int64 columns, or an error when they are gone too)
+                    return pick_packed<false>(fmt, [&](auto R) {
+                        using Rows = typename decltype(R)::type;
+                        return pick_top<Rows>(num_docs, [&](auto TOP) {
+                            return (SweepKernel)sweep_conservation_halo_kernel<Rows, kHaloLoads, T, OutT, TOP>;
+                        });
+                    });
+                });
             } else {
-            SweepKernel kern = three      ? halo3_kernel<OutT>(waves, top9)  // (no tile table: no room, a negative window start)
-                               : fmt == 4 ? (top8 ? halo_kernel<PackedRows<false, false>, OutT, 24>(waves)
-                                                  : halo_kernel<PackedRows<false, false>, OutT, 0>(waves))
-                               : fmt == 12 ? (num_docs <= 4095 ? halo_kernel<PackedRows<false, false, true>, OutT, 20>(waves)
-                                                               : halo_kernel<PackedRows<false, false, true>, OutT, 0>(waves))
-                                          : halo_kernel<PackedRows<true, false>, OutT, 0>(waves);
-            if (!three && (rc = use_words())) return rc;
-            if ((rc = launch_tiles(kern, A, tw, 64 * waves, (size_t)A.nlev * A.ls * 4, st))) return rc;
-            ix->last_sweep = three ? 5 : 2;
+                halo = false;
             }
         }
     }
-    if (!halo && fmt == 3) {  // the dense rows cannot answer this one (tile shape, num_docs > 255, sparse index)
-        if (!ix->has_wide)
-            return fail(MEMO_EINVAL, "this query needs the 4-byte rows or the int64 columns, which this index dropped");
-        fmt = 0;
-        w = tune.tile_w;  // tile shape for int64 rows
-        while (w & (w - 1)) w &= w - 1;
-        if (w > 4096) w = 4096;
-        if (!w) {
-            w = 4096;
-            while ((size_t)A.nlev * w * 4 > (sparse ? 32u : 80u) * 1024 && w > 256) w >>= 1;
-            while (w > 1024 && (qe - qs) / w < 8192) w >>= 1;
-            while (w > 256 && w <= 1024 && (qe - qs) / w < 32768) w >>= 1;
+    if (!halo) {  // the clipped sweep (w: 4096 when no doubling tile fits)
+        if (fmt == 3) {  // the dense rows cannot answer this one (tile shape, num_docs > 255, sparse index)
+            if (!ix->has_wide)
+                return fail(MEMO_EINVAL, "this query needs the 4-byte rows or the int64 columns, which this index dropped");
+            fmt = 0;
+            w = clipped_width(tune.tile_w, A.nlev, clipped_budget(), len);  // tile shape for int64 rows
+            waves = clipped_waves(w);
         }
-        waves = tune.waves == 1 || tune.waves == 4 ? tune.waves : (w >= 1024 ? 4 : 1);
-    }
-    if (!halo) {
         if (fmt == 12 && w > 2048) w = 2048;  // a 12-bit start field: the slice of a tile spans less than 2^12 positions
         while ((size_t)A.nlev * w * 4 > 160 * 1024 && w > 256) w >>= 1;
         A.hl = 0;
-        A.w = w;
+        A.w = tw = w;
         A.ls = w;
-        SweepKernel kern = fmt == 4   ? (checked ? cons_kernel<PackedRows<false, true>, OutT>(w, waves)
-                                                 : cons_kernel<PackedRows<false, false>, OutT>(w, waves))
-                           : fmt == 12 ? (checked ? cons_kernel<PackedRows<false, true, true>, OutT>(w, waves)
-                                                  : cons_kernel<PackedRows<false, false, true>, OutT>(w, waves))
-                           : fmt == 6 ? (checked ? cons_kernel<PackedRows<true, true>, OutT>(w, waves)
-                                                 : cons_kernel<PackedRows<true, false>, OutT>(w, waves))
-                                      : cons_kernel<WideRows, OutT>(w, waves);
+        sweep = 1;
+        lds = (size_t)A.nlev * A.ls * 4;
+        kern = pick_rows_clipped(fmt, checked, [&](auto R) {
+            using Rows = typename decltype(R)::type;
+            return pick_int<256, 512, 1024, 2048, 4096>(w, [&](auto W) {
+                return pick_int<256, 64>(clipped_threads_of(waves), [&](auto T) {
+                    return (SweepKernel)sweep_conservation_kernel<Rows, W, Rows::kLoads, T, OutT>;
+                });
+            });
+        });
         if (!kern) return fail(MEMO_EINVAL, "unsupported tile width %d", w);
-        ix->last_rows_read = ix->rows;
-        if ((rc = use_words())) return rc;
-        if ((rc = launch_tiles(kern, A, w, 64 * waves, (size_t)A.nlev * A.ls * 4, st))) return rc;
-        ix->last_sweep = 1;
     }
+
+    // -- the rows, the launch, the record
+    int variant = 0;
+    if (doubling_tile) ix->last_variant = 0;
+    if (three) {
+        if ((rc = sweep_dense_rows(ix, A, tw, (int)sizeof(OutT), top8, top9, st, &variant))) return rc;
+    } else if ((rc = use_words(ix, A, fmt, false, st))) {
+        return rc;
+    }
+    if (!variant && (rc = launch_tiles(kern, A, tw, 64 * waves, lds, st))) return rc;
+    ix->last_sweep = sweep;
+    if (sweep == 4) ix->last_arrays = arrays;
+    if (variant) ix->last_variant = variant;
     return long_rows_conservation<OutT>(ix, qs, qe, k, A.ncols, d_out, st);
 }
 

@@ -194,42 +194,6 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     }
 }
 
-template <typename OutT, int T, bool A9, bool AW, bool SP>
-SweepKernel kernel_for(int nlev) {
-    switch (nlev) {
-        case 1: return (SweepKernel)sweep_conservation_halo3t_kernel<1, OutT, T, A9, AW, false, SP>;
-        case 2: return (SweepKernel)sweep_conservation_halo3t_kernel<2, OutT, T, A9, AW, false, SP>;
-        case 3: return (SweepKernel)sweep_conservation_halo3t_kernel<3, OutT, T, A9, AW, false, SP>;
-        case 4: return (SweepKernel)sweep_conservation_halo3t_kernel<4, OutT, T, A9, AW, false, SP>;
-        case 5: return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, T, A9, AW, false, SP>;
-        case 6: return (SweepKernel)sweep_conservation_halo3t_kernel<6, OutT, T, A9, AW, false, SP>;
-    }
-    return nullptr;
-}
-
-template <bool AW, bool SP>
-SweepKernel kernel_of(int nlev, int elem_bytes, bool annot9) {  // (256 .. 511 genomes: nine-bit orders, uint16 results)
-    return annot9 ? kernel_for<uint16_t, 256, true, AW, SP>(nlev)
-                  : (elem_bytes == 1 ? kernel_for<uint8_t, 256, false, AW, SP>(nlev) : kernel_for<uint16_t, 256, false, AW, SP>(nlev));
-}
-
-template <typename OutT, bool AW, bool SP, bool LIVE>
-SweepKernel kernel_six_of(int nlev) {
-    switch (nlev) {
-        case 1: return (SweepKernel)sweep_conservation_halo3t_kernel<1, OutT, 256, false, AW, true, SP, LIVE>;
-        case 2: return (SweepKernel)sweep_conservation_halo3t_kernel<2, OutT, 256, false, AW, true, SP, LIVE>;
-        case 3: return (SweepKernel)sweep_conservation_halo3t_kernel<3, OutT, 256, false, AW, true, SP, LIVE>;
-        case 4: return (SweepKernel)sweep_conservation_halo3t_kernel<4, OutT, 256, false, AW, true, SP, LIVE>;
-        case 5: return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, 256, false, AW, true, SP, LIVE>;
-    }
-    return nullptr;
-}
-
-template <typename OutT, bool AW, bool SP>
-SweepKernel kernel_six(int nlev, bool live) {
-    return live ? kernel_six_of<OutT, AW, SP, true>(nlev) : kernel_six_of<OutT, AW, SP, false>(nlev);
-}
-
 }  // namespace
 
 namespace memo {
@@ -319,16 +283,25 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     const double span = (double)(ix->max_s - ix->min_s) + 1.0;
     const double groups_per_tile = (double)ix->last_rows_read / (six ? 6.0 : 5.0) * (double)tw / (span > 1.0 ? span : 1.0);
     const bool sp = groups_per_tile < 768.0;
-    SweepKernel kern = sp ? (all_write ? kernel_of<true, true>(A.nlev, elem_bytes, annot9) : kernel_of<false, true>(A.nlev, elem_bytes, annot9))
-                          : (all_write ? kernel_of<true, false>(A.nlev, elem_bytes, annot9) : kernel_of<false, false>(A.nlev, elem_bytes, annot9));
-    if (six) {
-        if (sp)
-            kern = elem_bytes == 1 ? (all_write ? kernel_six<uint8_t, true, true>(A.nlev, live) : kernel_six<uint8_t, false, true>(A.nlev, live))
-                                   : (all_write ? kernel_six<uint16_t, true, true>(A.nlev, live) : kernel_six<uint16_t, false, true>(A.nlev, live));
-        else
-            kern = elem_bytes == 1 ? (all_write ? kernel_six<uint8_t, true, false>(A.nlev, live) : kernel_six<uint8_t, false, false>(A.nlev, live))
-                                   : (all_write ? kernel_six<uint16_t, true, false>(A.nlev, live) : kernel_six<uint16_t, false, false>(A.nlev, live));
-    }
+    SweepKernel kern = pick_int<1, 2, 3, 4, 5, 6>(A.nlev, [&](auto N) {
+        return pick_bool(all_write, [&](auto AW) {
+            return pick_bool(sp, [&](auto SP) -> SweepKernel {
+                if (annot9)  // (256 .. 511 genomes: nine-bit orders, uint16 results)
+                    return (SweepKernel)sweep_conservation_halo3t_kernel<N, uint16_t, 256, true, AW, false, SP>;
+                auto of = [&](auto O) -> SweepKernel {
+                    using OutT = typename decltype(O)::type;
+                    if constexpr (decltype(N)::value <= 5) {
+                        if (six)
+                            return pick_bool(live, [&](auto LIVE) {
+                                return (SweepKernel)sweep_conservation_halo3t_kernel<N, OutT, 256, false, AW, true, SP, LIVE>;
+                            });
+                    }
+                    return (SweepKernel)sweep_conservation_halo3t_kernel<N, OutT, 256, false, AW, false, SP>;
+                };
+                return elem_bytes == 1 ? of(Type<uint8_t>{}) : of(Type<uint16_t>{});
+            });
+        });
+    });
     if (!kern) return 1;
     if (g_prepare_only) return MEMO_OK;  // memo_index_prepare: the table is built, nothing is launched
     if (int prc = refuse_plan_pointer(A.out)) return prc;

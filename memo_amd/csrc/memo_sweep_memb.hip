@@ -431,25 +431,6 @@ __global__ __launch_bounds__(T) void sweep_membership_planes3_kernel(const Sweep
     planes_transpose_store<T>(A, t, lds);
 }
 
-template <typename Rows, int T, int MW>
-SweepKernel planes_kernel_m(bool skewed) {
-    return skewed ? (SweepKernel)sweep_membership_planes_kernel<Rows, 6, T, MW, true> : (SweepKernel)sweep_membership_planes_kernel<Rows, 6, T, MW, false>;
-}
-
-template <typename Rows, int T>
-SweepKernel planes_kernel_t(int mw, bool skewed) {
-    return mw == 0   ? planes_kernel_m<Rows, T, 0>(skewed)
-           : mw == 2 ? planes_kernel_m<Rows, T, 2>(skewed)
-           : mw == 3 ? planes_kernel_m<Rows, T, 3>(skewed)
-           : mw == 4 ? planes_kernel_m<Rows, T, 4>(skewed)
-                     : planes_kernel_m<Rows, T, 8>(skewed);
-}
-
-template <typename Rows>
-SweepKernel planes_kernel(int T, int mw, bool skewed) {
-    return T == 64 ? planes_kernel_t<Rows, 64>(mw, skewed) : planes_kernel_t<Rows, 256>(mw, skewed);
-}
-
 __global__ void fill_membership_kernel(uint32_t *out, int64_t n, int nw, int ncols) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
@@ -478,39 +459,6 @@ __global__ void long_rows_membership_kernel(const int64_t *ls, const int64_t *le
 }
 
 
-template <typename Rows>
-SweepKernel memb_kernel(int w, int waves) {
-#define MEMO_CASE(WW)                                                                              \
-    case WW:                                                                                       \
-        return waves == 4 ? (SweepKernel)sweep_membership_kernel<Rows, WW, Rows::kLoads, 256>      \
-                          : (SweepKernel)sweep_membership_kernel<Rows, WW, Rows::kLoads, 64>;
-    switch (w) {
-        MEMO_CASE(256)
-        MEMO_CASE(512)
-        MEMO_CASE(1024)
-        MEMO_CASE(2048)
-        MEMO_CASE(4096)
-    }
-#undef MEMO_CASE
-    return nullptr;
-}
-
-template <typename Rows>
-SweepKernel memb_runs_kernel(int w, int waves) {
-#define MEMO_CASE(WW)                                                                                \
-    case WW:                                                                                         \
-        return waves == 4 ? (SweepKernel)sweep_membership_runs_kernel<Rows, WW, Rows::kLoads, 256>   \
-                          : (SweepKernel)sweep_membership_runs_kernel<Rows, WW, Rows::kLoads, 64>;
-    switch (w) {
-        MEMO_CASE(256)
-        MEMO_CASE(512)
-        MEMO_CASE(1024)
-        MEMO_CASE(2048)
-        MEMO_CASE(4096)
-    }
-#undef MEMO_CASE
-    return nullptr;
-}
 }  // namespace
 
 static int long_rows_membership(const memo_index *ix, int64_t qs, int64_t qe, int32_t k, int ncols, int nw,
@@ -522,6 +470,25 @@ static int long_rows_membership(const memo_index *ix, int64_t qs, int64_t qe, in
                        ix->whole_set ? ix->whole_qs : qs, ix->whole_set ? ix->whole_qe : qe);
     HIP_TRY(hipGetLastError());
     return MEMO_OK;
+}
+
+// Bit planes of one tile of the planes kernels: tw positions (whole words), A.nlev words of halo left of the tile, plane rows
+// of A.ls words (odd), A.hl words of skew per 32-genome group.  Returns the LDS bytes: the planes or the staged result, whichever
+// is larger.
+static size_t planes_tile(SweepArgs &A, int tw, int km1, int bw, int nw) {
+    const int pw = tw / 32, hlw = (km1 + 31) / 32;
+    int skew = 0;
+    for (int pow2 = 4; pow2 <= 64; pow2 <<= 1)
+        if (nw == pow2) skew = (64 / nw + 32) & 63;  // G * (32 * PITCH + skew) = G * 64 / nw (mod 64), PITCH odd
+    A.w = tw;
+    A.nlev = hlw;  // words of halo left of the tile
+    // last bit of a run: 32 hlw + tile + k - 1 + bw - 3; one more word for the short path's second ds_or
+    A.ls = (hlw + pw + ((km1 + bw - 3) >> 5) + 1) | 1;
+    A.hl = skew;
+    A.magic = (uint32_t)((((uint64_t)1 << 32) + 32 * nw - 1) / (32 * nw));
+    const size_t planes = ((size_t)32 * nw * A.ls + (size_t)nw * skew + 8) * 4;
+    const size_t staged = ((size_t)pw * (32 * nw + nw) + 4) * 4;
+    return planes > staged ? planes : staged;
 }
 
 extern "C" {
@@ -547,185 +514,153 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     A.ncols = num_docs;
     A.nlev = floor_log2((uint32_t)(k - 1)) + 1;
     A.nwords = nw;
+    A.word_base = 0;
+    A.out_words = nw;
     int fmt;
     if ((rc = pick_rows(ix, k, fmt))) return rc;
-    // the 4-byte words a sweep reads: the k-class view of them where one exists or is due (packed_rows_for, memo_view.hip)
-    auto use_words = [&]() -> int {
-        ix->last_rows_read = ix->rows;
-        if (fmt != 4 && fmt != 12) return MEMO_OK;
-        uint32_t *vpk = nullptr;
-        int64_t *vboff = nullptr;
-        uint64_t vrows = 0;
-        const int vrc = packed_rows_for(ix, k - 1, qe - qs, true, st, &vpk, &vboff, &vrows);
-        if (vrc) return vrc;
-        A.pk = vpk;
-        A.boff = vboff;
-        ix->last_rows_read = vrows;
-        return MEMO_OK;
-    };
-    ix->last_sweep = 7;  // a membership kernel on the 4- / 6-byte rows or the int64 columns (6: on the dense rows)
-    const memo_tuning &tune0 = ix->tune;
+    ix->last_sweep = 7;  // a membership kernel on the 4- / 6-byte rows or the int64 columns (6: on the dense rows, once launched)
+
+    // -- the plan: the kernel and its tile; the slices of genome words it sweeps (runs: 64 words at most per launch)
+    const memo_tuning &tune = ix->tune;
+    const int km1 = k - 1, bw = 1 << ix->bshift;
+    const int64_t len = qe - qs;
+    SweepKernel kern = nullptr;
+    int tw = 0, threads = 256, slice = nw;
+    size_t lds = 0;
     // The dense rows where an index holds no 4- / 6-byte rows and they can answer: the planes kernel on them (k - 1 <= 63,
     // at most 255 genomes, every annot inside the matrix, an index of >= 1 row per position like the other unclipped
     // kernels; a tile whose plane rows stay within the 10-bit start field).  What this buys is a 3.2-byte-per-row index
     // that answers both queries; it is not faster than the 4-byte rows here (config 4, back to back: 0.658 against 0.634 ms
     // at k = 31, 0.81 against 0.76 at k = 48 -- a membership sweep writes 1.6 GB, the 0.4 GB of rows it saves are paid
     // for by the longer decode and the shorter tiles; profiles/r02_dense_rows_ab.txt), so resident 4-byte rows are preferred.
-    {
-        const int bw = 1 << ix->bshift, hlw = (k - 1 + 31) / 32;
-        const double span = (double)(ix->max_s - ix->min_s) + 1.0;
-        int tw = (1024 - (k - 1) - bw - 32 * hlw) / bw * bw;
-        tw = tw / 32 * 32;
-        if (tune0.tile_w && tune0.tile_w < tw) tw = tune0.tile_w / bw * bw / 32 * 32;
-        if (nw * (tw / 32) > 256) tw = 32 * (256 / nw);
-        const bool dense_ok = ix->p3 && !ix->pk && !(tune0.force_wide && ix->has_wide) && k - 1 <= 63 &&
-                              num_docs <= 255 && ix->max_annot < (uint64_t)num_docs && (double)ix->rows >= span &&
-                              (tune0.memb_algo == 0 || tune0.memb_algo == 4) && tw >= bw && tw >= 32 && tw % bw == 0;
-        if (dense_ok) {
-            {   // the dense rows of this k's class (a view that leaves out the rows that cannot write at this k), or all of them
-                uint32_t *vp3 = nullptr;
-                int64_t *vboff = nullptr;
-                uint64_t vrows = 0;
-                if ((rc = dense_rows_for(ix, k - 1, qe - qs, st, &vp3, &vboff, &vrows))) return rc;
-                A.p3 = vp3;
-                A.boff = vboff;
-                ix->last_rows_read = vrows;
+    const double span = (double)(ix->max_s - ix->min_s) + 1.0;
+    tw = (1024 - km1 - bw - 32 * ((km1 + 31) / 32)) / bw * bw;
+    tw = tw / 32 * 32;
+    if (tune.tile_w && tune.tile_w < tw) tw = tune.tile_w / bw * bw / 32 * 32;
+    if (nw * (tw / 32) > 256) tw = 32 * (256 / nw);
+    const bool dense = ix->p3 && !ix->pk && !(tune.force_wide && ix->has_wide) && km1 <= 63 &&
+                       num_docs <= 255 && ix->max_annot < (uint64_t)num_docs && (double)ix->rows >= span &&
+                       (tune.memb_algo == 0 || tune.memb_algo == 4) && tw >= bw && tw >= 32 && tw % bw == 0;
+    if (dense) {
+        lds = planes_tile(A, tw, km1, bw, nw);
+        // (k - 1 <= 63 here: a run reaches at most two words past its first)
+        kern = pick_int<0, 2>(km1 <= 31 ? 0 : 2, [&](auto MW) {
+            return pick_bool(A.hl != 0, [&](auto SK) {
+                return (SweepKernel)sweep_membership_planes3_kernel<PackedRows3::kLoads, 256, MW, SK>;
+            });
+        });
+    } else {
+        if (fmt == 3) {  // only the dense rows are left, and they cannot answer this one
+            if (!ix->has_wide)
+                return fail(MEMO_EINVAL, "this membership query needs the 4-byte rows or the int64 columns, which this index dropped");
+            fmt = 0;
+        }
+        // algorithm: 4 = planes (unclipped bit planes per genome, result staged), 3 = runs (clipped bit planes
+        // + register transpose), 2 = doubling
+        const size_t per_pos_doubling = (size_t)A.nlev * nw * 4;
+        int algo = tune.memb_algo;
+        // A/B on config 4 (profiles/r01_membership_algorithms.txt): packed rows 0.87 ms runs vs 1.13 ms
+        // doubling; int64 rows (HBM-bound either way) 2.52 ms doubling vs 2.64 ms runs
+        if (!algo) algo = (fmt || per_pos_doubling * 256 > 40 * 1024) ? 3 : 2;
+        // whatever was asked for: a tile of 256 positions has to fit in LDS, else runs (which can slice)
+        if (algo == 2 && (per_pos_doubling * 256 > 128 * 1024 || nw > 64)) algo = 3;
+        const bool checked = ix->max_annot >= (uint64_t)A.ncols;
+        int w = tune.tile_w, waves = tune.waves == 1 || tune.waves == 4 ? tune.waves : 0;
+        while (w & (w - 1)) w &= w - 1;  // (tile widths are powers of two here; the debug switch also takes other array sizes)
+        if (w > 4096) w = 4096;
+        // 4 = unclipped bit planes + staged result: packed rows with every annot inside the matrix, at most
+        // 16 result words; otherwise whatever else was chosen
+        if ((algo == 4 || (tune.memb_algo == 0 && algo == 3)) && fmt && !checked && nw <= 16) {
+            const int T = waves == 1 ? 64 : 256;
+            // ~16 KiB of planes per tile whatever the number of result words (128 of the 256 lanes transpose a block each): 1024
+            // positions at four words (config 4), 2048 at two, 4096 at one, 512 at eight -- on the sequence-built index (50 genomes: two
+            // words) 2048 against 1024 positions: 0.267 against 0.297 ms at k = 31; 4096 is slower again, as 2048 and 512 are at four
+            // words; 250 genomes: 512 against 1024: 1.39 against 1.59 ms (profiles/r05_large_k.txt)
+            tw = w ? w : (4096 / nw < 256 ? 256 : 4096 / nw / 32 * 32);  // (whole 32-position words)
+            if (fmt == 12 && tw > 2048) tw = 2048;       // (12-bit start field)
+            if (tw > 32 * (T / nw)) tw = 32 * (T / nw);  // one 32 x 32 block per lane
+            tw = tw / bw * bw;
+            if (tw >= bw && tw >= 32) {
+                lds = planes_tile(A, tw, km1, bw, nw);
+                threads = T;
+                // the row block by the most words a run can reach past its first: 0 = the two-word block (k - 1 <= 31), else 2, 3, 4 or 8
+                const int reach = (km1 + 30) / 32, mw = km1 <= 31 ? 0 : (reach <= 2 ? 2 : reach <= 3 ? 3 : reach <= 4 ? 4 : 8);
+                kern = pick_packed<false>(fmt, [&](auto R) {
+                    return pick_int<64, 256>(T, [&](auto TT) {
+                        return pick_int<0, 2, 3, 4, 8>(mw, [&](auto MW) {
+                            return pick_bool(A.hl != 0, [&](auto SK) {
+                                return (SweepKernel)sweep_membership_planes_kernel<typename decltype(R)::type, 6, TT, MW, SK>;
+                            });
+                        });
+                    });
+                });
             }
-            const int pw = tw / 32;
-            int skew = 0;
-            for (int pow2 = 4; pow2 <= 64; pow2 <<= 1)
-                if (nw == pow2) skew = (64 / nw + 32) & 63;
-            A.w = tw;
-            A.nlev = hlw;
-            A.ls = (hlw + pw + ((k - 1 + bw - 3) >> 5) + 1) | 1;
-            A.hl = skew;
-            A.magic = (uint32_t)((((uint64_t)1 << 32) + 32 * nw - 1) / (32 * nw));
-            A.word_base = 0;
-            A.out_words = nw;
-            const size_t planes = ((size_t)32 * nw * A.ls + (size_t)nw * skew + 8) * 4;
-            const size_t staged = ((size_t)pw * (32 * nw + nw) + 4) * 4;
-            // (k - 1 <= 63 here: a run reaches at most two words past its first)
-            SweepKernel kern = k - 1 <= 31 ? (skew ? (SweepKernel)sweep_membership_planes3_kernel<PackedRows3::kLoads, 256, 0, true>
-                                                   : (SweepKernel)sweep_membership_planes3_kernel<PackedRows3::kLoads, 256, 0, false>)
-                                           : (skew ? (SweepKernel)sweep_membership_planes3_kernel<PackedRows3::kLoads, 256, 2, true>
-                                                   : (SweepKernel)sweep_membership_planes3_kernel<PackedRows3::kLoads, 256, 2, false>);
-            if ((rc = launch_tiles(kern, A, tw, 256, planes > staged ? planes : staged, st))) return rc;
-            ix->last_sweep = 6;
-            return long_rows_membership(ix, qs, qe, k, A.ncols, nw, d_out, st);
+        }
+        if (!kern) {
+            if (!waves) waves = 4;
+            threads = 64 * waves;
+            const bool runs = algo == 3 || algo == 4;
+            if (runs) {
+                // 4 * nw bytes of LDS per position: beyond 2048 genomes even a 256-position tile is too big,
+                // so the genome words are swept in slices of 64 (the rows are read once per slice; every
+                // slice writes its own words of the result)
+                slice = nw <= 64 ? nw : 64;
+                if (!w) {  // a lane transposes one 32 x 32 block: keep nw * W / 32 >= threads
+                    w = 4096;
+                    while ((size_t)slice * 4 * w > 32 * 1024 && w > 256) w >>= 1;
+                    while (w > 256 && len / w < 16384) w >>= 1;
+                }
+                int skew = 1;
+                while (skew * 2 * slice <= 32) skew *= 2;  // largest power of two <= 32 / nw (1 when nw > 16)
+                A.nlev = skew;
+                auto lds_bytes = [&](int ww) { return ((size_t)32 * slice * (ww / 32 + 1) + (size_t)slice * skew) * 4; };
+                if (fmt == 12 && w > 2048) w = 2048;  // (12-bit start field)
+                while (lds_bytes(w) > 160 * 1024 && w > 256) w >>= 1;
+                lds = lds_bytes(w);
+            } else {
+                const size_t per_pos = per_pos_doubling;
+                if (!w) {  // config 4 A/B: int64 rows 512 positions x 4 waves (40 KiB); packed rows 256 x 4 (20 KiB)
+                    const size_t budget = (waves == 4 ? (fmt ? 20u : 40u) : 20u) * 1024;
+                    w = 4096;
+                    while (per_pos * w > budget && w > 256) w >>= 1;
+                    while (w > 256 && len / w < 16384) w >>= 1;
+                }
+                while (per_pos * w > 160 * 1024 && w > 256) w >>= 1;
+                if (fmt == 12 && w > 2048) w = 2048;  // (12-bit start field)
+                lds = per_pos * w;
+            }
+            tw = w;
+            kern = pick_rows_clipped(fmt, checked, [&](auto R) {
+                using Rows = typename decltype(R)::type;
+                return pick_int<256, 512, 1024, 2048, 4096>(w, [&](auto W) {
+                    return pick_int<256, 64>(clipped_threads_of(waves), [&](auto T) {
+                        return runs ? (SweepKernel)sweep_membership_runs_kernel<Rows, W, Rows::kLoads, T>
+                                    : (SweepKernel)sweep_membership_kernel<Rows, W, Rows::kLoads, T>;
+                    });
+                });
+            });
+            if (!kern) return fail(MEMO_EINVAL, "unsupported tile width %d", w);
         }
     }
-    if (fmt == 3) {  // only the dense rows are left, and they cannot answer this one
-        if (!ix->has_wide)
-            return fail(MEMO_EINVAL, "this membership query needs the 4-byte rows or the int64 columns, which this index dropped");
-        fmt = 0;
+
+    // -- the rows (once per query: every slice of genome words reads the same rows), the launches, the record
+    if (dense) {  // the dense rows of this k's class (a view that leaves out the rows that cannot write at this k), or all of them
+        uint32_t *vp3 = nullptr;
+        int64_t *vboff = nullptr;
+        uint64_t vrows = 0;
+        if ((rc = dense_rows_for(ix, km1, len, st, &vp3, &vboff, &vrows))) return rc;
+        A.p3 = vp3;
+        A.boff = vboff;
+        ix->last_rows_read = vrows;
+    } else if ((rc = use_words(ix, A, fmt, true, st))) {
+        return rc;
     }
-    // algorithm: 4 = planes (unclipped bit planes per genome, result staged), 3 = runs (clipped bit planes
-    // + register transpose), 2 = doubling
-    const memo_tuning &tune = ix->tune;
-    const size_t per_pos_doubling = (size_t)A.nlev * nw * 4;
-    int algo = tune.memb_algo;
-    // A/B on config 4 (profiles/r01_membership_algorithms.txt): packed rows 0.87 ms runs vs 1.13 ms
-    // doubling; int64 rows (HBM-bound either way) 2.52 ms doubling vs 2.64 ms runs
-    if (!algo) algo = (fmt || per_pos_doubling * 256 > 40 * 1024) ? 3 : 2;
-    // whatever was asked for: a tile of 256 positions has to fit in LDS, else runs (which can slice)
-    if (algo == 2 && (per_pos_doubling * 256 > 128 * 1024 || nw > 64)) algo = 3;
-    const bool checked = ix->max_annot >= (uint64_t)A.ncols;
-    int w = tune.tile_w, waves = tune.waves == 1 || tune.waves == 4 ? tune.waves : 0;
-    while (w & (w - 1)) w &= w - 1;  // (tile widths are powers of two here; the debug switch also takes other array sizes)
-    if (w > 4096) w = 4096;
-    A.word_base = 0;
-    A.out_words = nw;
-    // 4 = unclipped bit planes + staged result: packed rows with every annot inside the matrix, at most
-    // 16 result words; otherwise whatever else was chosen
-    if ((algo == 4 || (tune.memb_algo == 0 && algo == 3)) && fmt && !checked && nw <= 16) {
-        const int bw = 1 << ix->bshift, T = waves == 1 ? 64 : 256;
-        // ~16 KiB of planes per tile whatever the number of result words (128 of the 256 lanes transpose a block each): 1024
-        // positions at four words (config 4), 2048 at two, 4096 at one, 512 at eight -- on the sequence-built index (50 genomes: two
-        // words) 2048 against 1024 positions: 0.267 against 0.297 ms at k = 31; 4096 is slower again, as 2048 and 512 are at four
-        // words; 250 genomes: 512 against 1024: 1.39 against 1.59 ms (profiles/r05_large_k.txt)
-        int tw = w ? w : (4096 / nw < 256 ? 256 : 4096 / nw / 32 * 32);  // (whole 32-position words)
-        if (fmt == 12 && tw > 2048) tw = 2048;       // (12-bit start field)
-        if (tw > 32 * (T / nw)) tw = 32 * (T / nw);  // one 32 x 32 block per lane
-        tw = tw / bw * bw;
-        if (tw >= bw && tw >= 32) {
-            const int pw = tw / 32;
-            int skew = 0;
-            for (int pow2 = 4; pow2 <= 64; pow2 <<= 1)
-                if (nw == pow2) skew = (64 / nw + 32) & 63;  // G * (32 * PITCH + skew) = G * 64 / nw (mod 64), PITCH odd
-            A.w = tw;
-            const int hlw = (k - 1 + 31) / 32;
-            A.nlev = hlw;  // words of halo left of the tile
-            // last bit of a run: 32 hlw + tile + k - 1 + bw - 3; one more word for the short path's second ds_or
-            A.ls = (hlw + pw + ((k - 1 + bw - 3) >> 5) + 1) | 1;
-            A.hl = skew;
-            A.magic = (uint32_t)((((uint64_t)1 << 32) + 32 * nw - 1) / (32 * nw));
-            const size_t planes = ((size_t)32 * nw * A.ls + (size_t)nw * skew + 8) * 4;
-            const size_t staged = ((size_t)pw * (32 * nw + nw) + 4) * 4;
-            // the row block by the most words a run can reach past its first: 0 = the two-word block (k - 1 <= 31), else 2, 3, 4 or 8
-            const int reach = (k - 1 + 30) / 32, mw = k - 1 <= 31 ? 0 : (reach <= 2 ? 2 : reach <= 3 ? 3 : reach <= 4 ? 4 : 8);
-            SweepKernel kern = fmt == 4    ? planes_kernel<PackedRows<false, false>>(T, mw, skew != 0)
-                               : fmt == 12 ? planes_kernel<PackedRows<false, false, true>>(T, mw, skew != 0)
-                                           : planes_kernel<PackedRows<true, false>>(T, mw, skew != 0);
-            if ((rc = use_words())) return rc;
-            if ((rc = launch_tiles(kern, A, tw, T, planes > staged ? planes : staged, st))) return rc;
-            return long_rows_membership(ix, qs, qe, k, A.ncols, nw, d_out, st);
-        }
+    for (int base = 0; base < nw; base += slice) {
+        A.word_base = base;
+        A.nwords = nw - base < slice ? nw - base : slice;
+        if ((rc = launch_tiles(kern, A, tw, threads, lds, st))) return rc;
     }
-    if (algo == 4) algo = 3;
-    if (algo == 3) {
-        if (!waves) waves = 4;
-        // 4 * nw bytes of LDS per position: beyond 2048 genomes even a 256-position tile is too big,
-        // so the genome words are swept in slices of 64 (the rows are read once per slice; every
-        // slice writes its own words of the result)
-        const int slice = nw <= 64 ? nw : 64;
-        if (!w) {  // a lane transposes one 32 x 32 block: keep nw * W / 32 >= threads
-            w = 4096;
-            while ((size_t)slice * 4 * w > 32 * 1024 && w > 256) w >>= 1;
-            while (w > 256 && (qe - qs) / w < 16384) w >>= 1;
-        }
-        int skew = 1;
-        while (skew * 2 * slice <= 32) skew *= 2;  // largest power of two <= 32 / nw (1 when nw > 16)
-        A.nlev = skew;
-        auto lds_bytes = [&](int ww) { return ((size_t)32 * slice * (ww / 32 + 1) + (size_t)slice * skew) * 4; };
-        if (fmt == 12 && w > 2048) w = 2048;  // (12-bit start field)
-        while (lds_bytes(w) > 160 * 1024 && w > 256) w >>= 1;
-        const size_t lds = lds_bytes(w);
-        SweepKernel kern = fmt == 4   ? (checked ? memb_runs_kernel<PackedRows<false, true>>(w, waves)
-                                                 : memb_runs_kernel<PackedRows<false, false>>(w, waves))
-                           : fmt == 12 ? (checked ? memb_runs_kernel<PackedRows<false, true, true>>(w, waves)
-                                                  : memb_runs_kernel<PackedRows<false, false, true>>(w, waves))
-                           : fmt == 6 ? (checked ? memb_runs_kernel<PackedRows<true, true>>(w, waves)
-                                                 : memb_runs_kernel<PackedRows<true, false>>(w, waves))
-                                      : memb_runs_kernel<WideRows>(w, waves);
-        if (!kern) return fail(MEMO_EINVAL, "unsupported tile width %d", w);
-        if ((rc = use_words())) return rc;  // (once per query: every slice of genome words reads the same rows)
-        for (int base = 0; base < nw; base += slice) {
-            A.word_base = base;
-            A.nwords = nw - base < slice ? nw - base : slice;
-            if ((rc = launch_tiles(kern, A, w, 64 * waves, lds, st))) return rc;
-        }
-        return long_rows_membership(ix, qs, qe, k, A.ncols, nw, d_out, st);
-    }
-    const size_t per_pos = per_pos_doubling;
-    if (!waves) waves = 4;
-    if (!w) {  // config 4 A/B: int64 rows 512 positions x 4 waves (40 KiB); packed rows 256 x 4 (20 KiB)
-        const size_t budget = (waves == 4 ? (fmt ? 20u : 40u) : 20u) * 1024;
-        w = 4096;
-        while (per_pos * w > budget && w > 256) w >>= 1;
-        while (w > 256 && (qe - qs) / w < 16384) w >>= 1;
-    }
-    while (per_pos * w > 160 * 1024 && w > 256) w >>= 1;
-    if (fmt == 12 && w > 2048) w = 2048;  // (12-bit start field)
-    SweepKernel kern = fmt == 4   ? (checked ? memb_kernel<PackedRows<false, true>>(w, waves)
-                                             : memb_kernel<PackedRows<false, false>>(w, waves))
-                       : fmt == 12 ? (checked ? memb_kernel<PackedRows<false, true, true>>(w, waves)
-                                              : memb_kernel<PackedRows<false, false, true>>(w, waves))
-                       : fmt == 6 ? (checked ? memb_kernel<PackedRows<true, true>>(w, waves)
-                                             : memb_kernel<PackedRows<true, false>>(w, waves))
-                                  : memb_kernel<WideRows>(w, waves);
-    if (!kern) return fail(MEMO_EINVAL, "unsupported tile width %d", w);
-    if ((rc = use_words())) return rc;
-    if ((rc = launch_tiles(kern, A, w, 64 * waves, per_pos * w, st))) return rc;
+    if (dense) ix->last_sweep = 6;
     return long_rows_membership(ix, qs, qe, k, A.ncols, nw, d_out, st);
 }
 
