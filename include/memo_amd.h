@@ -128,7 +128,8 @@ typedef struct memo_index_info {
     uint64_t view_placings;   /* dense views (re)built with their rows placed, over the index's lifetime */
     int32_t last_view_rows_per_group; /* rows per 16-byte group of the dense rows the last sweep read: 5, or 6 (a view whose groups carry
                                their bucket: 2.67 B per row; last_rows_read then counts the places a bucket leaves empty too) */
-    int32_t reserved;
+    int32_t last_tile_width;  /* positions per tile of the last table-driven sweep (last_variant 2 / 3; 0 otherwise): 1568 at k = 31 on
+                               the radix-4 arrays of a six-row view (MEMO_OPT_WIDE_TILES), 928 on the doubling arrays */
 } memo_index_info_t;
 
 const char *memo_last_error(void);
@@ -217,13 +218,17 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info);  /*
  *                             lower order contains each of their rows at every k); once the class's queries have lost to loading
  *                             those groups what a pass over the view costs (MEMO_OPT_BUILD_COST_PCT applies), a query copies the view
  *                             without them -- the sweep then reads only the live groups.  Never by memo_index_prepare (it hands out
- *                             the flagged view); 0: never (the flagged view stays and is swept with its dead groups masked: the A/B). */
+ *                             the flagged view); 0: never (the flagged view stays and is swept with its dead groups masked: the A/B).
+ *   MEMO_OPT_WIDE_TILES       1 (default): a six-row view with few rows per tile (a live copy) is swept at k - 1 = 16 .. 31 on radix-4
+ *                             level arrays -- three of 1664 cells, tiles of 1568 positions at k = 31 -- (memo_index_info_t.last_tile_width);
+ *                             0: on today's five doubling arrays of 1024 cells (928 positions at k = 31), for A/B runs and tests. */
 #define MEMO_OPT_VIEWS 1
 #define MEMO_OPT_VIEW_BUDGET_PCT 2
 #define MEMO_OPT_BUILD_COST_PCT 3
 #define MEMO_OPT_VIEW_ROWS 4
 #define MEMO_OPT_VIEW_PLACES 5
 #define MEMO_OPT_VIEW_LIVE 6
+#define MEMO_OPT_WIDE_TILES 7
 /* Returns the option's PREVIOUS value (>= 0) -- what a caller that changes an option for one pass puts back -- or a negative code. */
 int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value);
 /* Build NOW what queries of one kind would otherwise build on the way: the k-class view of the rows such a query reads (else

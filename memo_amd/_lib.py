@@ -48,7 +48,7 @@ class IndexInfo(C.Structure):
                 ("last_view_ms", C.c_float), ("row_order", C.c_int32), ("side_bytes", C.c_uint64),
                 ("views_resident", C.c_int32), ("tile_tables_resident", C.c_int32), ("view_builds", C.c_uint64),
                 ("last_level_arrays", C.c_int32), ("last_view_placed", C.c_int32), ("view_placings", C.c_uint64),
-                ("last_view_rows_per_group", C.c_int32), ("reserved", C.c_int32)]
+                ("last_view_rows_per_group", C.c_int32), ("last_tile_width", C.c_int32)]
 
 
 # every symbol the product headers declare: name -> (restype, argtypes)

@@ -155,6 +155,7 @@ struct memo_index {
     int view_places = 1;          // memo_index_set_option(MEMO_OPT_VIEW_PLACES): 0 the rows of a dense view keep the order they come in
     uint64_t view_placings = 0;   // dense views rebuilt with their rows placed (memo_index_info_t.view_placings)
     int view_live = 1;            // memo_index_set_option(MEMO_OPT_VIEW_LIVE): 0 placed six-row views keep their dead groups (flagged, swept with LIVE)
+    int wide_tiles = 1;           // memo_index_set_option(MEMO_OPT_WIDE_TILES): 0 six-row views keep the doubling tiles where R4 would apply (A/B)
     uint64_t view_live_copies = 0;  // placed six-row views copied without their dead groups (memo_debug_view_live_copies of the AB library)
     double view_ns_per_row[4] = {0, 0, 0, 0};  // measured by the last view build ([0] dense rows, [1] 4-byte words, [2] dense rows with places,
                                                //   [3] the copy without dead groups, per group of the flagged view; 0: the calibrated constant)
@@ -203,6 +204,7 @@ struct memo_index {
     int last_sweep = 0;          // level arrays of the last conservation sweep (memo_index_info_t.last_sweep)
     int last_arrays = 0;         // mixed level arrays (last_sweep 4): how many of them the sweep's level plan allocated
     int last_variant = 0;        // ... 2 table-driven on five-row groups (memo_sweep_cons3t.hip), 3 on a view of six rows per group; 0 no table
+    int last_tile_w = 0;         // ... and its tile width (info.last_tile_width: 1568 at k = 31 on the radix-4 arrays, 928 on the doubling ones)
     int has_wide = 1;          // the three int64 columns are still resident
     // rows with end < start (never written by the reference's index builder, but legal input to
     // memo_query.py): copied aside at finalize and applied by long_rows_kernel after each sweep

@@ -874,6 +874,7 @@ static void fill_info(const memo_index *ix, memo_index_info_t *info) {
     info->view_placings = ix->view_placings;
     info->last_view_placed = ix->last_view_placed;
     info->last_view_rows_per_group = ix->last_view_rpg;
+    info->last_tile_width = ix->last_tile_w;
 }
 
 int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info) {
@@ -893,7 +894,7 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info) {
         MEMO_INFO_FIELD(dense_row_count), MEMO_INFO_FIELD(last_rows_read), MEMO_INFO_FIELD(last_view_ms), MEMO_INFO_FIELD(row_order),
         MEMO_INFO_FIELD(side_bytes), MEMO_INFO_FIELD(views_resident), MEMO_INFO_FIELD(tile_tables_resident), MEMO_INFO_FIELD(view_builds),
         MEMO_INFO_FIELD(last_level_arrays), MEMO_INFO_FIELD(last_view_placed), MEMO_INFO_FIELD(view_placings),
-        MEMO_INFO_FIELD(last_view_rows_per_group), MEMO_INFO_FIELD(reserved), (uint32_t)sizeof(memo_index_info_t)};
+        MEMO_INFO_FIELD(last_view_rows_per_group), MEMO_INFO_FIELD(last_tile_width), (uint32_t)sizeof(memo_index_info_t)};
 #undef MEMO_INFO_FIELD
     uint32_t n = 0;
     for (uint32_t s : starts)
@@ -951,6 +952,12 @@ int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value) {
         if (value != 0 && value != 1) return fail(MEMO_EINVAL, "MEMO_OPT_VIEW_LIVE takes 0 or 1");
         const int before = ix->view_live;
         ix->view_live = (int)value;
+        return before;
+    }
+    if (option == MEMO_OPT_WIDE_TILES) {
+        if (value != 0 && value != 1) return fail(MEMO_EINVAL, "MEMO_OPT_WIDE_TILES takes 0 or 1");
+        const int before = ix->wide_tiles;
+        ix->wide_tiles = (int)value;
         return before;
     }
     if (option == MEMO_OPT_VIEW_ROWS) {

@@ -608,6 +608,11 @@ int launch_tiles(SweepKernel kernel, SweepArgs &A, int w, int threads, size_t ld
 // live: the row source is a six-row view with dead-group flags, at least kLiveMinShare of its groups flagged (below that a wave's
 // ballots and packing have little to save; profiles/r07_live_rows.txt has the shares measured)
 constexpr double kLiveMinShare = 0.25;
+// A six-row view without flags at k - 1 in [16, 31] is swept on radix-4 arrays in wide tiles (R4) while a wide tile holds fewer than
+// kR4MaxGroups of its groups (MEMO_OPT_WIDE_TILES 0 keeps the doubling tiles); A's tile fields are rewritten for it.  Config 3 at
+// k = 31 (profiles/r09_wide_tiles.txt): the live copy, ~180 groups per wide tile, 0.095 against 0.122 ms; the placed view without
+// flags or copy, ~670, 0.200 against 0.188 -- its extra blocks per row cost more LDS cycles than the wider tile saves
+constexpr double kR4MaxGroups = 384.0;
 int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStream_t st, bool annot9 = false, bool all_write = false,
                   bool six = false, bool live = false);
 int pick_rows(const memo_index *ix, int32_t k, int &fmt);

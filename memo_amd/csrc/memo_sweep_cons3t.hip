@@ -22,7 +22,9 @@ struct TileDesc {  // 32 bytes
     uint32_t g0_lo, g0_hi;  // first group of the slice (five-row groups: a multiple of 8)
     uint32_t ng;            // groups; 0xFFFFFFFF: more than 2^32 rows reach this tile (unsupported)
     uint32_t first, end;    // rows [first, end) of the slice, counted from row 5 * g0
-    uint32_t pad[3];
+    uint32_t g_wrap;        // six-row groups: the first group of the slice (counted from g0) whose bucket lies 1024 or more positions past
+                            // the tile's first one (a group carries its bucket mod 32; the R4 kernel's wide tiles reach past 1024 cells)
+    uint32_t pad[2];
 };
 
 // tile T covers pivot positions [T * w, (T + 1) * w); its rows: T * w <= start < roundup((T + 1) * w + k - 1, bucket)
@@ -45,7 +47,13 @@ __global__ void tile_table_kernel(const int64_t *boff, int64_t nb, int64_t bbase
     d.ng = r1 - (uint64_t)rpg * g0 >= 0xFFFF0000ull ? 0xFFFFFFFFu : (uint32_t)(g1 - g0);
     d.first = (uint32_t)(r0 - (uint64_t)rpg * g0);
     d.end = (uint32_t)(r1 - (uint64_t)rpg * g0);
-    d.pad[0] = d.pad[1] = d.pad[2] = 0;
+    d.g_wrap = 0;
+    if (rpg == 6) {  // (bshift 5: buckets of 32 positions)
+        const int64_t bw = ((a + 1024) >> bshift) - bbase;
+        const uint64_t gw = bw <= 0 ? 0 : (uint64_t)boff[bw > last ? last : bw] / 6;
+        d.g_wrap = gw <= g0 ? 0u : (gw - g0 >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(gw - g0));
+    }
+    d.pad[0] = d.pad[1] = 0;
     out[t] = d;
 }
 
@@ -64,12 +72,18 @@ __global__ void tile_table_kernel(const int64_t *boff, int64_t nb, int64_t bbase
 // launcher sets from the rows per tile (profiles/r06_headline.txt; masking the dead loads off with EXEC = 0 instead gained nothing).
 // LIVE (SIX only): the view's groups say which of them hold no live row (memo_view.hip: view_live_kernel) -- a dead group's lane
 // sits out its rows' atomics, a piece without a live group is skipped (memo_sweep_dense.h: live_pieces)
-template <int NLEV, typename OutT, int T, bool A9 = false, bool AW = false, bool SIX = false, bool SP = false, bool LIVE = false>
+// R4 (SIX, not LIVE, k - 1 in [16, 31]): radix-4 level arrays -- blocks of 16, 4 and 1 -- of kLS4 = 1664 cells in place of the five
+// doubling arrays of 1024: the same 20 KiB per tile (eight tiles per CU), 1.69x the positions per tile at k = 31 (memo_sweep_dense.h:
+// group_rows4; the launcher takes it for six-row views with few rows per tile, launch_halo3t)
+template <int NLEV, typename OutT, int T, bool A9 = false, bool AW = false, bool SIX = false, bool SP = false, bool LIVE = false,
+          bool R4 = false>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(T == 256 ? 8 : 4, 8)))
 void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     static_assert(!A9 || sizeof(OutT) == 2, "more than 255 genomes: uint16 results");
     static_assert(!(A9 && SIX), "six-row groups hold eight-bit annots");
     static_assert(!LIVE || SIX, "dead-group flags: six-row views");
+    static_assert(!R4 || (SIX && !LIVE && NLEV == 5 && T == 256), "radix-4 arrays: six-row views without flags, k - 1 in [16, 31]");
+    constexpr int LSZ = R4 ? kLS4 : kLS;  // cells per level array
     constexpr int SH = A9 ? 23 : 24;  // a cell = order << SH | tie-breaking bits
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     constexpr int NW = T / 64, NL = kStageGroups / T;  // waves; 16-byte groups per lane and batch
@@ -80,7 +94,7 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     const uint32_t tabs = (uint32_t)A.tile_abs0 + tile;  // the tile's number in pivot coordinates
     const TileDesc *dp = static_cast<const TileDesc *>(A.ttab) + (tabs < (uint32_t)A.ntab ? tabs : (uint32_t)A.ntab - 1u);
     const uint4 d0 = *reinterpret_cast<const uint4 *>(dp);
-    const uint32_t d_end = dp->end;
+    const uint32_t d_end = dp->end, d_wrap = dp->g_wrap;
     Geo g;
     g.g0 = 0;
     g.ng = d0.z;
@@ -114,7 +128,7 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     issue(0);
     const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)lds;
     const int HL = A.hl, W = A.w;
-    clear_levels<NLEV, T>(lds_base, ((uint32_t)(A.ncols - 1) << SH) | ((1u << SH) - 1u));
+    clear_levels<NLEV, T>(lds_base, ((uint32_t)(A.ncols - 1) << SH) | ((1u << SH) - 1u));  // (R4: 3 x 6656 B inside the 20 KiB of five)
     RowConst C;
     C.km1 = A.km1;
     C.status = A.status;
@@ -125,8 +139,8 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     SixConst C6;
     C6.km1 = A.km1;
     C6.status = A.status;
-    C6.ls4 = C.ls4;
-    C6.bias4 = C.bias4;
+    C6.ls4 = R4 ? (uint32_t)(-2 * LSZ) : C.ls4;
+    C6.bias4 = R4 ? (uint32_t)pin_vgpr((int)(lds_base + 4u * (uint32_t)HL + 8u * (uint32_t)LSZ)) : C.bias4;
     C6.top_bit = C.top_bit;
     C6.nega = (uint32_t)pin_vgpr((int)((0u - tabs * (uint32_t)W) & 1023u));
     const uint32_t span = g.end - g.first;
@@ -137,7 +151,10 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
         if (batch) issue(batch);  // (a tile with more than 5120 rows: the rest)
         const uint32_t gbase = batch * kStageGroups;
         const uint32_t gleft = g.ng > gbase ? g.ng - gbase : 0;
-        if constexpr (SIX && LIVE) {
+        if constexpr (R4) {
+            r4_pieces<T, NL, AW>(V, lane, wave, gleft, d_wrap > gbase ? d_wrap - gbase : 0u, C6);
+            continue;
+        } else if constexpr (SIX && LIVE) {
             live_pieces<T, NL, AW>(V, lane, wave, gleft, C6);
             continue;
         } else if constexpr (SIX) {
@@ -158,7 +175,7 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     // fold in registers + store (halo_fold_store_dpp of memo_sweep_cons.hip, unrolled for NLEV)
     OutT *out = static_cast<OutT *>(A.out);
     const int cells = HL + W;
-    constexpr int ctx = NLEV <= 1 ? 0 : (NLEV <= 3 ? 1 : 1 << (NLEV - 3));
+    constexpr int ctx = R4 ? 4 : (NLEV <= 1 ? 0 : (NLEV <= 3 ? 1 : 1 << (NLEV - 3)));
     constexpr int valid = 64 - ctx;
     const int64_t a_rel = (int64_t)tabs * W - A.qs;  // the tile's first position, as an output index
     const int64_t ob = a_rel - HL;
@@ -166,16 +183,25 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     const int64_t o_hi = a_rel + (tile == (uint32_t)A.ntiles - 1u ? A.x_hi_last : W);
     for (int base = wave * 4 * valid; base + 4 * ctx < cells; base += NW * 4 * valid) {
         const int x0 = base + 4 * lane;
-        const int xr = x0 < kLS - 4 ? x0 : kLS - 4;  // (past the array: lanes whose results are dropped below)
+        const int xr = x0 < LSZ - 4 ? x0 : LSZ - 4;  // (past the array: lanes whose results are dropped below)
         u32x4 L[6];
-        read_levels<NLEV>(lds_base + 4u * (uint32_t)xr, L);
         auto lv = [&](int i) { return make_uint4(L[i].x, L[i].y, L[i].z, L[i].w); };
-        uint4 M = lv(0);
-        if constexpr (NLEV >= 6) fold_step_dpp<4>(M, lv(NLEV - 5), lane);
-        if constexpr (NLEV >= 5) fold_step_dpp<3>(M, lv(NLEV - 4), lane);
-        if constexpr (NLEV >= 4) fold_step_dpp<2>(M, lv(NLEV - 3), lane);
-        if constexpr (NLEV >= 3) fold_step_dpp<1>(M, lv(NLEV - 2), lane);
-        if constexpr (NLEV >= 2) fold_step_dpp<0>(M, lv(NLEV - 1), lane);
+        uint4 M;
+        if constexpr (R4) {  // blocks of 16 -> 4 -> positions (memo_sweep_fold.h)
+            read_levels_r4(lds_base + 4u * (uint32_t)xr, L);
+            M = lv(2);
+            uint4 M4 = lv(1);
+            r4_fold16(M4, lv(0));
+            r4_fold4(M, M4);
+        } else {
+            read_levels<NLEV>(lds_base + 4u * (uint32_t)xr, L);
+            M = lv(0);
+            if constexpr (NLEV >= 6) fold_step_dpp<4>(M, lv(NLEV - 5), lane);
+            if constexpr (NLEV >= 5) fold_step_dpp<3>(M, lv(NLEV - 4), lane);
+            if constexpr (NLEV >= 4) fold_step_dpp<2>(M, lv(NLEV - 3), lane);
+            if constexpr (NLEV >= 3) fold_step_dpp<1>(M, lv(NLEV - 2), lane);
+            if constexpr (NLEV >= 2) fold_step_dpp<0>(M, lv(NLEV - 1), lane);
+        }
         if (lane < ctx || x0 >= cells) continue;
         const int64_t o = ob + x0;
         if (o >= o_lo && o + 4 <= o_hi) {
@@ -260,13 +286,34 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     if (annot9 && elem_bytes != 2) return 1;
     if (six && (annot9 || A.nlev > 5 || ix->bshift != 5)) return 1;
     if (!A.p3 || A.ls > kLS || A.nlev < 1 || A.nlev > 6 || A.km1 > 63 || A.qs < 0) return 1;
+    // few rows per tile?  (the rows the sweep reads, spread over the index's span: groups per tile against the 1024 of a batch)
+    const double span = (double)(ix->max_s - ix->min_s) + 1.0;
+    auto groups_per_tile = [&](int w) { return (double)ix->last_rows_read / (six ? 6.0 : 5.0) * (double)w / (span > 1.0 ? span : 1.0); };
+    // R4: the radix-4 arrays in a tile of kLS4 cells (memo_sweep_dense.h), the same halo left and right as the doubling tile's
+    const int hl0 = A.hl, w0 = A.w, ls0 = A.ls;
+    bool r4 = false;
+    if (six && !live && ix->wide_tiles && A.km1 >= 16 && A.km1 <= 31 && A.nlev == 5) {
+        const int bw = 1 << ix->bshift, hl = (A.km1 + 3) & ~3, hr = (A.km1 + bw - 1 + 3) & ~3, tw4 = (kLS4 - hl - hr) / bw * bw;
+        if (groups_per_tile(tw4) < kR4MaxGroups) {
+            r4 = true;
+            A.hl = hl;
+            A.w = tw = tw4;
+            A.ls = hl + tw4 + hr;
+        }
+    }
+    auto no = [&](int rc) {  // (the caller's tile back: it answers with another kernel)
+        A.hl = hl0;
+        A.w = w0;
+        A.ls = ls0;
+        return rc;
+    };
     const int64_t q = A.qs / tw, tile0 = q * tw;
     const int64_t ntiles = ((A.qe - tile0) + tw - 1) / tw;
-    if (ntiles + 8 >= ((int64_t)1 << 31) || q + ntiles >= ((int64_t)1 << 31)) return 1;
+    if (ntiles + 8 >= ((int64_t)1 << 31) || q + ntiles >= ((int64_t)1 << 31)) return no(1);
     const void *tab = nullptr;
     int64_t ntab = 0;
     const int rc = tile_table(ix, A.p3, A.boff, tw, A.km1, st, &tab, &ntab, six ? 6 : 5);
-    if (rc) return rc;
+    if (rc) return no(rc);
     A.tile0 = tile0;
     A.ntiles = ntiles;
     A.tiles_per_xcd = (ntiles + 7) / 8;
@@ -279,10 +326,7 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     // what a wave does around its rows outweighs the rows: 7-9 % SLOWER on the k-class views of config 3 (0.217 against
     // 0.203 ms at k = 31, 0.168 against 0.154 at k = 17) and 1-4 % slower on all the rows; profiles/r03_views.txt.  Sixteen
     // waves per CU hide the scatter's LDS latency worse than thirty-two, whatever they save in instructions.)
-    // few rows per tile?  (the rows the sweep reads, spread over the index's span: groups per tile against the 1024 of a batch)
-    const double span = (double)(ix->max_s - ix->min_s) + 1.0;
-    const double groups_per_tile = (double)ix->last_rows_read / (six ? 6.0 : 5.0) * (double)tw / (span > 1.0 ? span : 1.0);
-    const bool sp = groups_per_tile < 768.0;
+    const bool sp = groups_per_tile(tw) < 768.0;
     SweepKernel kern = pick_int<1, 2, 3, 4, 5, 6>(A.nlev, [&](auto N) {
         return pick_bool(all_write, [&](auto AW) {
             return pick_bool(sp, [&](auto SP) -> SweepKernel {
@@ -290,6 +334,9 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
                     return (SweepKernel)sweep_conservation_halo3t_kernel<N, uint16_t, 256, true, AW, false, SP>;
                 auto of = [&](auto O) -> SweepKernel {
                     using OutT = typename decltype(O)::type;
+                    if constexpr (decltype(N)::value == 5) {
+                        if (r4) return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, 256, false, AW, true, SP, false, true>;
+                    }
                     if constexpr (decltype(N)::value <= 5) {
                         if (six)
                             return pick_bool(live, [&](auto LIVE) {
@@ -302,7 +349,8 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
             });
         });
     });
-    if (!kern) return 1;
+    if (!kern) return no(1);
+    ix->last_tile_w = tw;
     if (g_prepare_only) return MEMO_OK;  // memo_index_prepare: the table is built, nothing is launched
     if (int prc = refuse_plan_pointer(A.out)) return prc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(A.tiles_per_xcd * 8)), dim3(256), (size_t)A.nlev * 4096, st, A);

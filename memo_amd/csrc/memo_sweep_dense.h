@@ -314,6 +314,86 @@ __device__ __forceinline__ void live_pieces(const uint4 (&V)[NL], int lane, int 
     }
 }
 
+// ---- R4: six-row views on RADIX-4 level arrays in wide tiles (k - 1 in [16, 31]; memo_sweep_cons3t.hip) -------------------------
+// Three arrays of kLS4 cells -- blocks of 16, 4 and 1 -- where the doubling arrays need five of 1024: 19 968 bytes, still eight tiles
+// per CU, and a tile of 1568 positions at k = 31 instead of 928.  A row's interval of n positions (n < 32) takes blocks of
+// S = 16 / 4 / 1 (the largest power of four <= n) at its first cell and at its end - S, plus one at first + S when n > 2S and one
+// at first + 2S when n > 3S (lanes past their row's block count masked off by v_cmpx): 2 to 4 ds_min per row instead of 2.
+constexpr int kLS4 = 1664;
+// operands: %0-%3 temporaries; %4-%9 LO of rows 0 .. 5; %10-%15 their D; %16 BIAS (the bias of the arrays + 4 * the cell of the group's
+// bucket); %17 km1 (SGPR), %18 -2 * kLS4 (SGPR); masked form: %19 the lane's group number, %20 groups left (SGPR).
+// E = 2 * (2 - level) = (~ffbh(n)) & 30 (v_bfi_b32): 4, 2, 0 for blocks of 16, 4, 1; the level's cell = BIAS + E * (-2 kLS4) + 4 start,
+// the block's bytes 4 << E.  EXEC is all ones again after every row (the mask by group number comes again in front of each).
+#define MEMO_ROW4_AT_(LO, D, TEST)                       \
+    "v_bfe_u32 %0, " LO ", 5, 5\n\t"                     \
+    "v_sub_u32 %0, %17, %0\n\t"                          \
+    TEST                                                 \
+    "v_ffbh_u32 %1, %0\n\t"                              \
+    "v_and_b32 %3, 31, " LO "\n\t"                       \
+    "v_bfi_b32 %1, %1, 0, 30\n\t"                        \
+    "v_mad_i32_i24 %2, %1, %18, %16\n\t"                 \
+    "v_lshl_add_u32 %2, %3, 2, %2\n\t"                   \
+    "v_lshlrev_b32_e64 %1, %1, 4\n\t"                    \
+    "v_mad_i32_i24 %3, %0, -4, %2\n\t"                   \
+    "v_sub_u32 %2, %2, %1\n\t"                           \
+    "ds_min_u32 %3, " D "\n\t"                           \
+    "ds_min_u32 %2, " D "\n\t"                           \
+    "v_add_u32 %3, %3, %1\n\t"                           \
+    "v_cmpx_lt_u32 vcc, %3, %2\n\t"                      \
+    "ds_min_u32 %3, " D "\n\t"                           \
+    "v_add_u32 %3, %3, %1\n\t"                           \
+    "v_cmpx_lt_u32 vcc, %3, %2\n\t"                      \
+    "ds_min_u32 %3, " D "\n\t"                           \
+    MEMO_ROW3_DONE
+#define MEMO_ROW4_MASK "v_cmpx_gt_u32 vcc, %20, %19\n\t"
+#define MEMO_SIX_ROWS4(PRE, TEST)                                                                                              \
+    PRE MEMO_ROW4_AT_("%4", "%10", TEST) PRE MEMO_ROW4_AT_("%5", "%11", TEST) PRE MEMO_ROW4_AT_("%6", "%12", TEST)                \
+    PRE MEMO_ROW4_AT_("%7", "%13", TEST) PRE MEMO_ROW4_AT_("%8", "%14", TEST) PRE MEMO_ROW4_AT_("%9", "%15", TEST)
+
+// C.bias4: the arrays' bias for R4 (lds + 4 * hl + 2 * 4 kLS4), C.ls4: -2 * kLS4.  wrap: 1024 for a group whose bucket lies 1024 cells
+// or more past the tile's first cell (a group carries its bucket mod 32, which places it within 1024 cells only; the tile table's g_wrap)
+template <bool MASKED, bool AW>
+__device__ __forceinline__ void group_rows4(const uint4 &V, const SixConst &C, uint32_t wrap, uint32_t lg, uint32_t left) {
+    const uint32_t lo4 = V.x >> 10, d4 = V.y << 14, lo5 = V.w >> 10, d5 = V.z << 14;
+    const uint32_t cell = ((__builtin_amdgcn_ubfe(V.z, 18, 5) * 32u + C.nega) & 1023u) + wrap;
+    const uint32_t bias = C.bias4 + 4u * cell;
+    uint32_t r0, r1, r2, r3;
+    MEMO_EXEC_ALL_ONES(C.status);
+#define MEMO_SIX4_IN "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w), "v"(lo4), "v"(lo5), "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w), "v"(d4), "v"(d5), \
+                     "v"(bias), "s"(C.km1), "s"(C.ls4)
+    if constexpr (MASKED && AW) {
+        asm volatile(MEMO_SIX_ROWS4(MEMO_ROW4_MASK, "") MEMO_G3_OUT : MEMO_SIX4_IN, "v"(lg), "s"(left) : "memory", "vcc");
+    } else if constexpr (MASKED) {
+        asm volatile(MEMO_SIX_ROWS4(MEMO_ROW4_MASK, MEMO_ROW3_TEST) MEMO_G3_OUT : MEMO_SIX4_IN, "v"(lg), "s"(left) : "memory", "vcc");
+    } else if constexpr (AW) {
+        asm volatile(MEMO_SIX_ROWS4("", "") MEMO_G3_OUT : MEMO_SIX4_IN : "memory", "vcc");
+    } else {
+        asm volatile(MEMO_SIX_ROWS4("", MEMO_ROW3_TEST) MEMO_G3_OUT : MEMO_SIX4_IN : "memory", "vcc");
+    }
+#undef MEMO_SIX4_IN
+}
+
+// the NL groups of a lane (as six_pieces) on the radix-4 arrays; wleft: the slice's groups before g_wrap, counted from this batch
+template <int T, int NL, bool AW, int J = 0>
+__device__ __forceinline__ void r4_pieces(const uint4 (&V)[NL], int lane, int wave, uint32_t gleft, uint32_t wleft, const SixConst &C) {
+    if constexpr (J < NL) {
+        const uint32_t pg = (uint32_t)(J * T + wave * 64);
+        if (pg >= gleft) return;
+        const uint32_t lg = pg + (uint32_t)lane;
+        const uint32_t wrap = lg >= wleft ? 1024u : 0u;
+        if (pg + 64u <= gleft) group_rows4<false, AW>(V[J], C, wrap, 0, 0);
+        else group_rows4<true, AW>(V[J], C, wrap, lg, gleft);
+        r4_pieces<T, NL, AW, J + 1>(V, lane, wave, gleft, wleft, C);
+    }
+}
+
+// the three radix-4 arrays at the same cell (kLS4 cells apart), waited for in the same statement
+__device__ __forceinline__ void read_levels_r4(uint32_t addr, u32x4 (&L)[6]) {
+    asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %3 offset:6656\n\tds_read_b128 %2, %3 offset:13312\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(L[0]), "=&v"(L[1]), "=&v"(L[2]) : "v"(addr) : "memory");
+}
+static_assert(kLS4 * 4 == 6656, "read_levels_r4: the arrays' offsets");
+
 // the J-th group of a lane, already in registers (MODE 1 / 2)
 template <int J, int T = 256, bool A9 = false, bool AW = false>
 __device__ __forceinline__ bool reg_piece(const uint4 &V, int tid, int wave, uint32_t gbase, uint32_t gleft, const Geo &g,
