@@ -51,15 +51,29 @@ size_t memo_emit_bed(const int32_t *rec, const int64_t *start, const int64_t *en
  *   chunk: pivot positions per walk thread (<= 0: the default).
  * memo_ms_add_genome: builds the suffix array, LCP and min hierarchy of `text` (n < 2^31 - 1 bytes) on the
  *   device and writes the genome's MS into DAP column `column`.  One genome at a time; buffers are reused.
+ * memo_ms_add_records: the same for the genome whose records S_1 .. S_s lie back to back in seq (rec_begin: nrec + 1
+ *   offsets; no separators), of any total length.  The device assembles its text S_1 $ ... S_s $ rc(S_1) $ ... rc(S_s) $
+ *   (rc as `samtools faidx -i`) in pieces, each a run of whole strings under the int32 suffix-array limit; no match
+ *   crosses a $, so the MS against the text is the elementwise maximum over the pieces, and that is what the column
+ *   receives (the first piece stores, the later ones take the maximum; other columns are never touched).
+ *   piece_bytes <= 0: the cap is min(2^30, what the free device memory allows), raised to fit the longest string where
+ *   memory allows; else a hard cap in [2, 2^31 - 2].  A string longer than the cap (len + 1 bytes with its $) is
+ *   refused before anything is written.  *pieces (may be NULL): how many pieces ran (0 for nrec = 0: a zero column).
+ * memo_ms_plan_pieces: the plan memo_ms_add_records follows (host only, no device): strings S_1 .. S_s, rc(S_1) ..
+ *   rc(S_s) of rec_len[r] + 1 bytes each, greedily into pieces of at most `cap` bytes; piece_of_string (2 nrec
+ *   entries) and *pieces may be NULL.
  * memo_ms_fetch: host copy of DAP rows [first, first + positions).
  * memo_ms_push_dap: memo_dap_push_dev of those rows (same device, same column count).
- * memo_ms_timings: device milliseconds so far of {suffix arrays, LCP + hierarchy, walks}.
+ * memo_ms_timings: device milliseconds so far of {suffix arrays, LCP + hierarchy, walks}, summed over pieces.
  * memo_suffix_array: the suffix array of text[0, n) on `device` into sa_out (n int32); a suffix that is a
  *   prefix of another sorts first. */
 typedef struct memo_ms memo_ms_t;
 int memo_ms_create(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec, int32_t columns, int64_t chunk,
                    int32_t device, memo_ms_t **out);
 int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t column);
+int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int32_t column,
+                        int64_t piece_bytes, int32_t *pieces);
+int memo_ms_plan_pieces(const int64_t *rec_len, int32_t nrec, int64_t cap, int32_t *piece_of_string, int32_t *pieces);
 int memo_ms_fetch(memo_ms_t *h, int64_t first, int64_t positions, int32_t *out);
 int memo_ms_push_dap(memo_ms_t *h, memo_dap_t *dap, int64_t first, int64_t positions, uint64_t *out_rows);
 int memo_ms_timings(memo_ms_t *h, float *out3);

@@ -8,6 +8,7 @@
 #define MEMO_AMD_DEBUG_H
 
 #include "memo_amd.h"
+#include "memo_amd_dap.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -72,6 +73,11 @@ int memo_debug_stream_rows(memo_index_t *ix, void *stream);
 /* -DMEMO_STAMPS builds of the conservation sweep: a device buffer of 8 uint64 per workgroup that
  * receives the cycles wave 0 spent in each phase (NULL = off) */
 int memo_debug_set_stamp_buffer(uint64_t *d_buffer);
+/* piece `piece` of a genome text as memo_ms_add_records assembles it on the device (same arguments, same plan), copied to out:
+ * its *out_n bytes and the 64 zero bytes behind them, when out_cap holds them.  Returns the number of pieces.  The handle's
+ * DAP matrix is not touched. */
+int memo_debug_ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes,
+                             int32_t piece, uint8_t *out, int64_t out_cap, int64_t *out_n);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,8 @@ SYMBOLS = {
     "memo_dap_destroy": (None, [_P]),
     "memo_ms_create": (C.c_int, [_P, _P, _I32, _I32, _I64, _I32, C.POINTER(_P)]),
     "memo_ms_add_genome": (C.c_int, [_P, _P, _I64, _I32]),
+    "memo_ms_add_records": (C.c_int, [_P, _P, _P, _I32, _I32, _I64, C.POINTER(_I32)]),
+    "memo_ms_plan_pieces": (C.c_int, [_P, _I32, _I64, _P, C.POINTER(_I32)]),
     "memo_ms_fetch": (C.c_int, [_P, _I64, _I64, _P]),
     "memo_ms_push_dap": (C.c_int, [_P, _P, _I64, _I64, C.POINTER(_U64)]),
     "memo_ms_timings": (C.c_int, [_P, _P]),
@@ -152,6 +154,7 @@ DEBUG_SYMBOLS = {
     "memo_debug_one_shot_way": (C.c_int, [_I32]),
     "memo_debug_last_one_shot_sweep": (C.c_int, []),
     "memo_debug_set_stamp_buffer": (C.c_int, [_P]),
+    "memo_debug_ms_piece_text": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _I64, C.POINTER(_I64)]),
 }
 
 

@@ -11,9 +11,12 @@ statistics (MS) with MONI, genome by genome on the host.  Here every stage runs 
      names and offsets take the place of the .fai that `samtools faidx` writes (index.sh:55-56).
   2. genome g's text (index.sh:63-65): S_1 $ S_2 $ ... S_s $ rc(S_1) $ ... rc(S_s) $, with $ a NUL byte (no
      pivot byte can be NUL: such input is refused) and rc the reverse complement of `samtools faidx -i`
-     (A-T, C-G, R-Y, K-M, B-V, D-H swap, every other byte stays).
+     (A-T, C-G, R-Y, K-M, B-V, D-H swap, every other byte stays).  The records go to the device once, back to
+     back; the device assembles the text in pieces, each a run of whole strings under the int32 suffix-array
+     limit (the cap: MEMO_INDEX_PIECE_BYTES, else min(2^30, what the free device memory allows)).
   3. MS of every pivot position against every genome text (memo_ms_*, memo_amd/csrc/memo_ms.hip: suffix array,
-     LCP, MS walk), straight into the DAP matrix [positions][genomes - 1] in HBM (index.sh:83).
+     LCP, MS walk per piece), straight into the DAP matrix [positions][genomes - 1] in HBM (index.sh:83).  No
+     match crosses a $, so the elementwise maximum over the pieces is the MS against the whole text, exactly.
   4. DAP -> index rows on the device (memo_dap_push_dev; --mem --overlap, plus --order for the conservation
      index: index.sh:86-103) -> DIR/PREFIX.parquet (f0 utf8, f1 f2 f3 int64, ZSTD: parquet_compress_bed.py).
 
@@ -21,12 +24,15 @@ Not written, by design: MONI's *.w_rc* files, dap.txt, PREFIX.bed and the pivot'
 reads them.
 
 Refused with a message (never a wrong result): gzip input, a NUL byte, a pivot record of length 0, a pivot
-record of 2^30 positions or more, a genome text of 2^31 - 1 bytes or more, more than 4096 genomes besides the
-pivot, a DAP matrix that does not fit in the device's free memory.
+record of 2^30 positions or more, a genome record of 2^31 - 2 bases or more (or longer than the piece cap less
+one byte), more than 4096 genomes besides the pivot, a DAP matrix or a piece's working set that does not fit in
+the device's free memory, a MEMO_INDEX_PIECE_BYTES that is not an integer in [2, 2^31 - 2].  A genome's whole
+text may exceed 2^31 bytes: a human assembly (~6.2 GB of text) runs in a handful of pieces.
 """
 import ctypes as C
 import getopt
 import os
+import re
 import sys
 import time
 
@@ -51,7 +57,8 @@ _WHITESPACE = b" \t\r\n\v\f"
 # samtools faidx -i: the IUPAC complement; every other byte (N, S, W, ...) is its own complement
 _COMPLEMENT = bytes.maketrans(b"ACGTRYKMBVDH", b"TGCAYRMKVBHD")
 MAX_RECORD = (1 << 30) - 1        # memo_dap: positions of one pivot record
-MAX_TEXT = (1 << 31) - 2          # memo_ms: int32 suffix array of one genome text
+MAX_TEXT = (1 << 31) - 2          # memo_ms: int32 suffix array of one genome text (and of one piece)
+PIECE_ENV = "MEMO_INDEX_PIECE_BYTES"   # `memo index`: the piece cap (unset: the library's default)
 MAX_COLUMNS = 4096                # memo_dap: genomes besides the pivot
 
 
@@ -129,6 +136,18 @@ class MatchingStatistics:
             raise MemoError(-1, f"genome text of {len(text)} bytes: the limit is {MAX_TEXT}")
         check(lib().memo_ms_add_genome(self._h, bytes(text), len(text), column))
 
+    def add_records(self, seqs, column, piece_bytes=0):
+        """matching statistics of the pivot against the genome whose records are `seqs` (list of bytes), into DAP
+        column `column`: its text genome_text(seqs) is assembled on the device in pieces of at most `piece_bytes`
+        bytes (<= 0: the library's default cap), of any total length; returns the number of pieces"""
+        seqs = [bytes(s) for s in seqs]
+        rec_begin = np.zeros(len(seqs) + 1, np.int64)
+        rec_begin[1:] = np.cumsum([len(s) for s in seqs])
+        pieces = C.c_int32()
+        check(lib().memo_ms_add_records(self._h, b"".join(seqs), rec_begin.ctypes.data, len(seqs), column,
+                                        int(piece_bytes), C.byref(pieces)))
+        return pieces.value
+
     def fetch(self, first=0, positions=None):
         positions = self.positions - first if positions is None else positions
         out = np.empty((positions, self.columns), np.int32)
@@ -151,6 +170,31 @@ class MatchingStatistics:
 
     def __exit__(self, *a):
         self.close()
+
+
+def plan_pieces(lengths, cap):
+    """(pieces, int32 piece of every string): memo_ms_add_records' plan for records of these lengths -- strings S_1 ..
+    S_s, rc(S_1) .. rc(S_s) of len + 1 bytes each, greedily into pieces of at most `cap` bytes (host only)"""
+    lengths = np.ascontiguousarray(lengths, np.int64)
+    piece = np.zeros(2 * len(lengths), np.int32)
+    pieces = C.c_int32()
+    check(lib().memo_ms_plan_pieces(lengths.ctypes.data, len(lengths), int(cap), piece.ctypes.data, C.byref(pieces)))
+    return pieces.value, piece
+
+
+def piece_bytes_from_env(environ=os.environ):
+    """the piece cap MEMO_INDEX_PIECE_BYTES asks for (0: unset, the library's default); FastaError when it is not an
+    integer in [2, 2^31 - 2]"""
+    raw = environ.get(PIECE_ENV, "")
+    if raw == "":
+        return 0
+    try:
+        cap = int(raw)
+    except ValueError:
+        cap = None
+    if cap is None or not 2 <= cap <= MAX_TEXT:
+        raise FastaError(f"{PIECE_ENV}={raw!r}: need an integer in [2, {MAX_TEXT}]")
+    return cap
 
 
 def matching_statistics(pivot, genomes, device=0, chunk=0):
@@ -178,13 +222,14 @@ def read_genome_list(path):
     return paths
 
 
-def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log=print, keep_ms=False):
-    """index.sh end to end; returns per-stage seconds (and the MS matrix when keep_ms)"""
+def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log=print, keep_ms=False, piece_bytes=0):
+    """index.sh end to end; returns per-stage seconds, the pieces of every genome's text (and the MS matrix when
+    keep_ms).  piece_bytes: the cap of a piece of genome text (<= 0: the library's default)"""
     from .dap_to_bed import DapConverter, write_parquet
     t0 = time.perf_counter()
     paths = read_genome_list(genome_list)
     names, pivot, rec_begin = pivot_layout(read_fasta(paths[0]), paths[0])
-    stats = {"positions": int(rec_begin[-1]), "genomes": len(paths), "read_s": 0.0}
+    stats = {"positions": int(rec_begin[-1]), "genomes": len(paths), "read_s": 0.0, "pieces": [], "per_genome": []}
     stats["read_s"] += time.perf_counter() - t0
     out_path = os.path.join(out_dir, prefix + ".parquet")
     os.makedirs(out_dir or ".", exist_ok=True)
@@ -192,10 +237,23 @@ def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log
         t1 = time.perf_counter()
         for c, path in enumerate(paths[1:]):
             tr = time.perf_counter()
-            text = genome_text([s for _, s in read_fasta(path)])
-            stats["read_s"] += time.perf_counter() - tr
+            records = read_fasta(path)
+            read_s = time.perf_counter() - tr
+            stats["read_s"] += read_s
             log(f"Finding MS between pivot and {os.path.basename(path)}")
-            ms.add(text, c)
+            before = ms.timings()
+            try:
+                stats["pieces"].append(ms.add_records([s for _, s in records], c, piece_bytes))
+            except MemoError as exc:
+                m = re.search(r"genome record (\d+) ", str(exc))
+                if not m:
+                    raise
+                raise FastaError(f"{path}: record '{records[int(m.group(1))][0]}': {exc}") from None
+            after = ms.timings()
+            stats["per_genome"].append({"bases": sum(len(s) for _, s in records), "records": len(records),
+                                        "pieces": stats["pieces"][-1], "read_s": read_s,
+                                        **{k: after[k] - before[k] for k in after}})
+            del records
         stats["ms_s"] = time.perf_counter() - t1
         stats.update(ms.timings())
         if keep_ms:
@@ -239,8 +297,9 @@ def main(argv):
         if not val.get("-p"):
             raise FastaError("no output prefix: give one with -p")
         read_genome_list(val.get("-g", ""))          # refuse before the device is touched
+        piece_bytes = piece_bytes_from_env()
         build_index(val["-g"], val["-o"], val["-p"], "-m" in val, int(os.environ.get("MEMO_DEVICE", "0")),
-                    log=lambda s: print(s, flush=True))
+                    log=lambda s: print(s, flush=True), piece_bytes=piece_bytes)
     except (FastaError, MemoError) as exc:
         sys.stderr.write(f"memo index: {exc}\n")
         sys.exit(1)

@@ -28,6 +28,10 @@ int download_pipelined(int device, void *host, const void *dev, size_t bytes, hi
 int upload_pipelined(int device, void *dev, const void *host, size_t bytes);
 // memo_dap.hip: the device and column count of a DAP handle (memo_ms_push_dap checks them)
 void dap_shape(const memo_dap_t *h, int *device, int *columns);
+// memo_ms.hip: piece `piece` of a genome given as records, as memo_ms_add_records assembles it on the device, copied to out
+// (its n bytes and the kPad zeros behind them, when out_cap holds them); returns the number of pieces (memo_debug_ms_piece_text)
+int ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes, int32_t piece,
+                  uint8_t *out, int64_t out_cap, int64_t *out_n);
 double pinned_alloc_ms_total();  // memo_hostcore.cpp: time this process has spent allocating pinned staging slots (MEMO_TIMING)
 
 struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the current device

@@ -129,4 +129,9 @@ int memo_debug_set_stamp_buffer(uint64_t *d_buffer) {
 #endif
 }
 
+int memo_debug_ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes,
+                              int32_t piece, uint8_t *out, int64_t out_cap, int64_t *out_n) {
+    return ms_piece_text(h, seq, rec_begin, nrec, piece_bytes, piece, out, out_cap, out_n);
+}
+
 }  // extern "C"

@@ -15,6 +15,12 @@
 //                     interval is one suffix), record MS[i] = l, advance through x = ISA[SA[lo] + 1] and the maximal
 //                     range around x with LCP >= l - 1.  Exact from any start, so chunks need no fix-up.
 //
+//   pieces            a genome given as records (memo_ms_add_records) is uploaded once, back to back, and its text is
+//                     assembled on the device piece by piece: each piece a run of whole strings (records, then their
+//                     reverse complements), each with its NUL.  No match crosses a NUL, so the MS against the whole
+//                     text is the elementwise maximum of the MS against the pieces: the first piece's walk stores,
+//                     the later ones store max(M, l).  Every piece stays under the int32 suffix-array limit.
+//
 // MS columns are written straight into a device DAP matrix int32 [positions][columns] that memo_dap_push_dev
 // (memo_dap.hip) consumes in place.  Bad input sets a device error word that the host turns into an error;
 // nothing traps or spins.  rocPRIM lives in this translation unit only (its headers compile slowly).
@@ -256,6 +262,7 @@ struct WalkArgs {
     int64_t nchunks;
     int32_t *M;               // DAP [positions][C]
     int C, col;
+    int merge;                // 0: store l (the first piece); 1: store max(M, l) (later pieces)
     int *err;
 };
 
@@ -308,7 +315,8 @@ __global__ void __launch_bounds__(kBlock) ms_walk_kernel(const WalkArgs A) {
             hi = a2 - 1;
             ++l;
         }
-        A.M[(i) * (int64_t)A.C + A.col] = (int32_t)l;
+        int32_t *m = A.M + i * (int64_t)A.C + A.col;
+        *m = A.merge && *m > (int32_t)l ? *m : (int32_t)l;
         // advance: P[i + 1, i + l) is the suffix after SA[lo], less its first character
         if (l > 1) {
             const int64_t s1 = (int64_t)A.SA[lo] + 1;
@@ -332,6 +340,64 @@ __global__ void __launch_bounds__(kBlock) ms_walk_kernel(const WalkArgs A) {
         }
     }
     if (err) atomicOr(A.err, err);
+}
+
+// ---- piece texts -----------------------------------------------------------------------------------------
+
+// the complement of `samtools faidx -i` (build_index._COMPLEMENT): A-T, C-G, R-Y, K-M, B-V, D-H; every other byte stays
+__device__ __forceinline__ uint8_t complement(uint8_t c) {
+    switch (c) {
+        case 'A': return 'T';
+        case 'T': return 'A';
+        case 'C': return 'G';
+        case 'G': return 'C';
+        case 'R': return 'Y';
+        case 'Y': return 'R';
+        case 'K': return 'M';
+        case 'M': return 'K';
+        case 'B': return 'V';
+        case 'V': return 'B';
+        case 'D': return 'H';
+        case 'H': return 'D';
+        default: return c;
+    }
+}
+
+// One piece of S_1 $ ... S_s $ rc(S_1) $ ... rc(S_s) $: strings [s0, s1) into T[0, n), then zeros up to `bytes` (a multiple
+// of 8 that covers n + kPad).  R: the records back to back; G[j] (j <= 2 nrec): where string j starts in the whole text, so
+// string j is G[j + 1] - G[j] - 1 bytes and record r starts at R[G[r] - r].  Eight output bytes per thread, one 8-byte store.
+__global__ void __launch_bounds__(kBlock) piece_text_kernel(const uint8_t *R, const int64_t *G, int nrec, int s0, int s1, int64_t n,
+                                                            int64_t bytes, uint8_t *T) {
+    const int64_t p0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 8;
+    if (p0 >= bytes) return;
+    uint64_t w = 0;
+    if (p0 < n) {
+        const int64_t base = G[s0];
+        int a = s0, b = s1;  // the last string j with G[j] - base <= p0
+        while (b - a > 1) {
+            const int mid = (a + b) >> 1;
+            if (G[mid] - base <= p0) a = mid; else b = mid;
+        }
+        int j = a;
+        int64_t beg = G[j] - base, end = G[j + 1] - base;  // string j with its NUL: [beg, end)
+        for (int k = 0; k < 8 && p0 + k < n; ++k) {
+            const int64_t p = p0 + k;
+            while (p >= end) {
+                ++j;
+                beg = end;
+                end = G[j + 1] - base;
+            }
+            const int64_t q = p - beg, len = end - beg - 1;
+            uint8_t c = 0;
+            if (q < len) {
+                const int r = j < nrec ? j : j - nrec;
+                const int64_t src = G[r] - r;
+                c = j < nrec ? R[src + q] : complement(R[src + len - 1 - q]);
+            }
+            w |= (uint64_t)c << (8 * k);
+        }
+    }
+    *reinterpret_cast<uint64_t *>(T + p0) = w;
 }
 
 template <typename T>
@@ -448,9 +514,9 @@ struct memo_ms {
     int device = 0, C = 0, nrec = 0;
     int64_t npos = 0;
     int64_t chunk = 0;
-    std::vector<int64_t> h_rec_begin;
-    DevBuf<uint8_t> P, T;
-    DevBuf<int64_t> rec_begin, chunk_begin;
+    std::vector<int64_t> h_rec_begin, h_G;
+    DevBuf<uint8_t> P, T, R;  // R: the records of memo_ms_add_records' genome, back to back
+    DevBuf<int64_t> rec_begin, chunk_begin, G;  // G: where each of its strings starts in the whole text
     DevBuf<int32_t> M, SA, ISA, LCP, levels;
     DevBuf<int> err;
     SaWork W;
@@ -461,7 +527,7 @@ struct memo_ms {
 namespace {
 
 void release(memo_ms *h) {
-    h->P.release(); h->T.release(); h->rec_begin.release(); h->chunk_begin.release();
+    h->P.release(); h->T.release(); h->R.release(); h->rec_begin.release(); h->chunk_begin.release(); h->G.release();
     h->M.release(); h->SA.release(); h->ISA.release(); h->LCP.release(); h->levels.release(); h->err.release();
     h->W.release();
     for (auto &e : h->ev)
@@ -488,7 +554,207 @@ int fits(int64_t need, const char *what) {
     return MEMO_OK;
 }
 
+// device bytes of one genome text's working set (suffix array, ISA, LCP, hierarchy), and what of it the handle holds already
+uint64_t text_bytes(int64_t n) { return sa_bytes(n) + (uint64_t)n * 12 + (uint64_t)n / 8; }
+int64_t resident_bytes(const memo_ms *h) {
+    return (int64_t)(h->T.cap + (h->SA.cap + h->ISA.cap + h->LCP.cap) * 4 + h->W.key.cap * 16 + h->W.suf.cap * 28);
+}
+
+constexpr int64_t kMaxPiece = ((int64_t)1 << 31) - 2;   // int32 suffix array
+constexpr int64_t kDefaultPiece = (int64_t)1 << 30;
+
+// strings S_1 .. S_s, rc(S_1) .. rc(S_s) (len + 1 bytes each, the NUL counted) into pieces of at most `cap` bytes, greedily in
+// that order; piece_of_string: 2 nrec entries (may be NULL)
+int plan_pieces(const int64_t *rec_len, int32_t nrec, int64_t cap, int32_t *piece_of_string, int32_t *pieces) {
+    if (nrec < 0 || nrec >= (1 << 30)) return fail(MEMO_EINVAL, "record count %d outside [0, 2^30)", nrec);
+    if (cap < 2 || cap > kMaxPiece) return fail(MEMO_EINVAL, "piece cap %lld outside [2, 2^31 - 2]", (long long)cap);
+    if (nrec && !rec_len) return fail(MEMO_EINVAL, "rec_len is NULL");
+    for (int r = 0; r < nrec; ++r) {
+        if (rec_len[r] < 0) return fail(MEMO_EINVAL, "genome record %d has length %lld", r, (long long)rec_len[r]);
+        if (rec_len[r] >= cap)  // len + 1 bytes with its NUL
+            return fail(MEMO_EINVAL, "genome record %d of %lld bases needs %lld bytes with its separator, more than the piece cap of %lld",
+                        r, (long long)rec_len[r], (long long)rec_len[r] + 1, (long long)cap);
+    }
+    int32_t p = 0;
+    int64_t used = 0;
+    for (int j = 0; j < 2 * nrec; ++j) {
+        const int64_t c = rec_len[j < nrec ? j : j - nrec] + 1;
+        if (used + c > cap) {
+            ++p;
+            used = 0;
+        }
+        used += c;
+        if (piece_of_string) piece_of_string[j] = p;
+    }
+    if (pieces) *pieces = nrec ? p + 1 : 0;
+    return MEMO_OK;
+}
+
+// A genome given as records, made ready for its pieces: checked, planned (piece_bytes <= 0: the default cap), its records and
+// string offsets G on the device, the buffers of its largest piece allocated.  first[p]: the first string of piece p
+// (first[pieces] = 2 nrec).  Nothing of the DAP matrix is touched.
+int prepare_records(memo_ms *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes,
+                    std::vector<int32_t> &first, hipStream_t st) {
+    if (nrec < 0 || nrec >= (1 << 30)) return fail(MEMO_EINVAL, "record count %d outside [0, 2^30)", nrec);
+    if (piece_bytes > kMaxPiece || (piece_bytes > 0 && piece_bytes < 2))
+        return fail(MEMO_EINVAL, "piece cap %lld outside [2, 2^31 - 2]", (long long)piece_bytes);
+    first.assign(1, 0);
+    if (nrec == 0) return MEMO_OK;
+    if (!rec_begin) return fail(MEMO_EINVAL, "rec_begin is NULL");
+    if (rec_begin[0] != 0) return fail(MEMO_EINVAL, "rec_begin[0] must be 0");
+    std::vector<int64_t> len(nrec);
+    int64_t longest = 0;
+    for (int r = 0; r < nrec; ++r) {
+        len[r] = rec_begin[r + 1] - rec_begin[r];
+        if (len[r] < 0) return fail(MEMO_EINVAL, "rec_begin is not ascending at record %d", r);
+        longest = len[r] > longest ? len[r] : longest;
+    }
+    const int64_t S = rec_begin[nrec];
+    if (S && !seq) return fail(MEMO_EINVAL, "seq is NULL");
+    int rc;
+    if (piece_bytes > 0 && (rc = plan_pieces(len.data(), nrec, piece_bytes, nullptr, nullptr))) return rc;  // before any upload
+    // the records once, back to back; G[j] = where string j starts in the whole text
+    std::vector<int64_t> &G = h->h_G;
+    G.assign(2 * (size_t)nrec + 1, 0);
+    for (int j = 0; j < 2 * nrec; ++j) G[j + 1] = G[j] + len[j < nrec ? j : j - nrec] + 1;
+    if ((rc = h->R.ensure((size_t)S + 8)) || (rc = h->G.ensure(G.size()))) return rc;
+    if (S) HIP_TRY(hipMemcpyAsync(h->R.p, seq, (size_t)S, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->G.p, G.data(), G.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the caller's buffer may go once this returns, on any path
+    int64_t cap = piece_bytes;
+    if (cap <= 0) {  // min(2^30, what the free memory allows), raised to fit the longest string where memory allows
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t avail = (uint64_t)free_b + (uint64_t)resident_bytes(h);
+        int64_t n_mem = avail > (64u << 20) ? (int64_t)((avail - (64u << 20)) * 8 / 547) : 0;  // text_bytes(n) ~ 68.375 n + 64 MiB
+        while (n_mem > 0 && text_bytes(n_mem) > avail) --n_mem;
+        n_mem = n_mem < kMaxPiece ? n_mem : kMaxPiece;
+        cap = kDefaultPiece < n_mem ? kDefaultPiece : n_mem;
+        if (longest + 1 > cap) cap = longest + 1 < n_mem ? longest + 1 : n_mem;
+        cap = cap < 2 ? 2 : cap;
+    }
+    std::vector<int32_t> piece(2 * (size_t)nrec);
+    int32_t pieces = 0;
+    if ((rc = plan_pieces(len.data(), nrec, cap, piece.data(), &pieces))) return rc;
+    int64_t biggest = 0;
+    for (int j = 0; j < 2 * nrec; ++j)
+        if (j + 1 == 2 * nrec || piece[j + 1] != piece[j]) {
+            first.push_back(j + 1);
+            const int64_t n = G[j + 1] - G[first[first.size() - 2]];
+            biggest = n > biggest ? n : biggest;
+        }
+    // the largest piece must fit before the first one writes the column
+    const int64_t need = (int64_t)text_bytes(biggest) - resident_bytes(h);
+    if (need > 0 && (rc = fits(need, "the largest piece's suffix array and LCP"))) return rc;
+    const size_t tbytes = ((size_t)biggest + kPad + 7) & ~(size_t)7;
+    if ((rc = h->T.ensure(tbytes)) || (rc = h->SA.ensure(biggest)) || (rc = h->ISA.ensure(biggest)) || (rc = h->LCP.ensure(biggest)))
+        return rc;
+    return MEMO_OK;
+}
+
+// piece [first[p], first[p + 1]) of the prepared genome into h->T (kPad zeros behind it); returns its length
+int64_t assemble_piece(memo_ms *h, int32_t nrec, const std::vector<int32_t> &first, int p, hipStream_t st) {
+    const int64_t n = h->h_G[first[p + 1]] - h->h_G[first[p]];
+    const int64_t bytes = (n + kPad + 7) & ~(int64_t)7;
+    hipLaunchKernelGGL(piece_text_kernel, dim3(grid_for(bytes / 8)), dim3(kBlock), 0, st, h->R.p, h->G.p, nrec, first[p],
+                       first[p + 1], n, bytes, h->T.p);
+    return n;
+}
+
+// the suffix array, LCP, hierarchy and walk of the text in h->T[0, n) (padded; SA, ISA, LCP allocated), into `column`:
+// stored, or merged by max when `merge`
+int ms_of_text(memo_ms *h, int64_t n, int32_t column, int merge, hipStream_t st) {
+    int rc;
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    if ((rc = build_sa(h->T.p, n, h->SA.p, h->W, st))) return rc;
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    // ISA and PHI (PHI in the rank scratch), PLCP (in grp), LCP
+    int32_t *phi = h->W.rank.p, *plcp = h->W.grp.p;
+    hipLaunchKernelGGL(isa_phi_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, h->SA.p, n, h->ISA.p, phi);
+    hipLaunchKernelGGL(plcp_kernel, dim3(grid_for((n + kLcpChunk - 1) / kLcpChunk)), dim3(kBlock), 0, st, h->T.p, n, phi, plcp);
+    hipLaunchKernelGGL(lcp_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, h->SA.p, plcp, n, h->LCP.p);
+    HIP_TRY(hipGetLastError());
+    // the min hierarchy over LCP
+    Hierarchy H{};
+    int64_t sizes[kMaxLevels], offs[kMaxLevels], total = 0;
+    int levels = 1;
+    sizes[0] = n;
+    while (sizes[levels - 1] > 1 && levels < kMaxLevels) {
+        sizes[levels] = (sizes[levels - 1] + kFanout - 1) / kFanout;
+        offs[levels] = total;
+        total += sizes[levels];
+        ++levels;
+    }
+    if ((rc = h->levels.ensure((size_t)(total ? total : 1)))) return rc;
+    H.levels = levels;
+    H.lv[0] = h->LCP.p;
+    H.size[0] = n;
+    for (int k = 1; k < levels; ++k) {
+        H.lv[k] = h->levels.p + offs[k];
+        H.size[k] = sizes[k];
+        hipLaunchKernelGGL(block_min_kernel, dim3(grid_for(sizes[k])), dim3(kBlock), 0, st, H.lv[k - 1], sizes[k - 1],
+                           h->levels.p + offs[k], sizes[k]);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[2], st));
+    // the walk
+    WalkArgs A{};
+    A.T = h->T.p;
+    A.SA = h->SA.p;
+    A.ISA = h->ISA.p;
+    A.H = H;
+    A.n = n;
+    A.P = h->P.p;
+    A.rec_begin = h->rec_begin.p;
+    A.chunk_begin = h->chunk_begin.p;
+    A.nrec = h->nrec;
+    A.chunk = h->chunk;
+    int64_t nchunks = 0;
+    for (int r = 0; r < h->nrec; ++r) nchunks += (h->h_rec_begin[r + 1] - h->h_rec_begin[r] + h->chunk - 1) / h->chunk;
+    A.nchunks = nchunks;
+    A.M = h->M.p;
+    A.C = h->C;
+    A.col = column;
+    A.merge = merge;
+    A.err = h->err.p;
+    HIP_TRY(hipMemsetAsync(h->err.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(ms_walk_kernel, dim3(grid_for(nchunks)), dim3(kBlock), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], st));
+    int errw = 0;
+    HIP_TRY(hipMemcpyAsync(&errw, h->err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float a = 0, b = 0, c = 0;
+    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
+    h->ms_sa += a;
+    h->ms_lcp += b;
+    h->ms_walk += c;
+    if (errw) return fail(MEMO_EHIP, "matching statistics of column %d: the walk kernel reported error bits 0x%x", column, errw);
+    return MEMO_OK;
+}
+
 }  // namespace
+
+int memo::ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes, int32_t piece,
+                        uint8_t *out, int64_t out_cap, int64_t *out_n) {
+    if (!h || !out_n) return fail(MEMO_EINVAL, "NULL argument");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
+    hipStream_t st = nullptr;
+    std::vector<int32_t> first;
+    int rc = prepare_records(h, seq, rec_begin, nrec, piece_bytes, first, st);
+    if (rc) return rc;
+    const int np = (int)first.size() - 1;
+    if (piece < 0 || piece >= np) return fail(MEMO_EINVAL, "piece %d outside [0, %d)", piece, np);
+    const int64_t n = assemble_piece(h, nrec, first, piece, st);
+    HIP_TRY(hipGetLastError());
+    *out_n = n;
+    if (out && n + kPad <= out_cap) HIP_TRY(hipMemcpyAsync(out, h->T.p, (size_t)(n + kPad), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return np;
+}
 
 extern "C" {
 
@@ -591,79 +857,38 @@ int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t col
     }
     if (!text) return fail(MEMO_EINVAL, "text is NULL");
     // what is not allocated yet must fit (the buffers grow only)
-    const int64_t have = (int64_t)(h->T.cap + (h->SA.cap + h->ISA.cap + h->LCP.cap) * 4 + h->W.key.cap * 16 + h->W.suf.cap * 28);
-    const int64_t need = (int64_t)sa_bytes(n) + n * 12 + n / 8 - have;
+    const int64_t need = (int64_t)text_bytes(n) - resident_bytes(h);
     int rc = need > 0 ? fits(need, "this genome's suffix array and LCP") : MEMO_OK;
     if (rc) return rc;
     if ((rc = upload_padded(h->T, text, n, st)) || (rc = h->SA.ensure(n)) || (rc = h->ISA.ensure(n)) ||
         (rc = h->LCP.ensure(n)))
         return rc;
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    if ((rc = build_sa(h->T.p, n, h->SA.p, h->W, st))) return rc;
-    HIP_TRY(hipEventRecord(h->ev[1], st));
-    // ISA and PHI (PHI in the rank scratch), PLCP (in grp), LCP
-    int32_t *phi = h->W.rank.p, *plcp = h->W.grp.p;
-    hipLaunchKernelGGL(isa_phi_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, h->SA.p, n, h->ISA.p, phi);
-    hipLaunchKernelGGL(plcp_kernel, dim3(grid_for((n + kLcpChunk - 1) / kLcpChunk)), dim3(kBlock), 0, st, h->T.p, n, phi, plcp);
-    hipLaunchKernelGGL(lcp_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, h->SA.p, plcp, n, h->LCP.p);
-    HIP_TRY(hipGetLastError());
-    // the min hierarchy over LCP
-    Hierarchy H{};
-    int64_t sizes[kMaxLevels], offs[kMaxLevels], total = 0;
-    int levels = 1;
-    sizes[0] = n;
-    while (sizes[levels - 1] > 1 && levels < kMaxLevels) {
-        sizes[levels] = (sizes[levels - 1] + kFanout - 1) / kFanout;
-        offs[levels] = total;
-        total += sizes[levels];
-        ++levels;
+    return ms_of_text(h, n, column, 0, st);
+}
+
+int memo_ms_plan_pieces(const int64_t *rec_len, int32_t nrec, int64_t cap, int32_t *piece_of_string, int32_t *pieces) {
+    return plan_pieces(rec_len, nrec, cap, piece_of_string, pieces);
+}
+
+int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int32_t column,
+                        int64_t piece_bytes, int32_t *pieces) {
+    if (!h) return fail(MEMO_EINVAL, "handle is NULL");
+    if (column < 0 || column >= h->C) return fail(MEMO_EINVAL, "column %d outside [0, %d)", column, h->C);
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
+    hipStream_t st = nullptr;
+    std::vector<int32_t> first;
+    int rc = prepare_records(h, seq, rec_begin, nrec, piece_bytes, first, st);
+    if (rc) return rc;
+    const int np = (int)first.size() - 1;
+    if (np == 0)  // no records: the text is empty and matches nothing
+        HIP_TRY(hipMemset2D(h->M.p + column, (size_t)h->C * 4, 0, 4, (size_t)h->npos));
+    for (int p = 0; p < np; ++p) {
+        const int64_t n = assemble_piece(h, nrec, first, p, st);
+        HIP_TRY(hipGetLastError());
+        if ((rc = ms_of_text(h, n, column, p > 0, st))) return rc;
     }
-    if ((rc = h->levels.ensure((size_t)(total ? total : 1)))) return rc;
-    H.levels = levels;
-    H.lv[0] = h->LCP.p;
-    H.size[0] = n;
-    for (int k = 1; k < levels; ++k) {
-        H.lv[k] = h->levels.p + offs[k];
-        H.size[k] = sizes[k];
-        hipLaunchKernelGGL(block_min_kernel, dim3(grid_for(sizes[k])), dim3(kBlock), 0, st, H.lv[k - 1], sizes[k - 1],
-                           h->levels.p + offs[k], sizes[k]);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[2], st));
-    // the walk
-    WalkArgs A{};
-    A.T = h->T.p;
-    A.SA = h->SA.p;
-    A.ISA = h->ISA.p;
-    A.H = H;
-    A.n = n;
-    A.P = h->P.p;
-    A.rec_begin = h->rec_begin.p;
-    A.chunk_begin = h->chunk_begin.p;
-    A.nrec = h->nrec;
-    A.chunk = h->chunk;
-    int64_t nchunks = 0;
-    for (int r = 0; r < h->nrec; ++r) nchunks += (h->h_rec_begin[r + 1] - h->h_rec_begin[r] + h->chunk - 1) / h->chunk;
-    A.nchunks = nchunks;
-    A.M = h->M.p;
-    A.C = h->C;
-    A.col = column;
-    A.err = h->err.p;
-    HIP_TRY(hipMemsetAsync(h->err.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(ms_walk_kernel, dim3(grid_for(nchunks)), dim3(kBlock), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[3], st));
-    int errw = 0;
-    HIP_TRY(hipMemcpyAsync(&errw, h->err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float a = 0, b = 0, c = 0;
-    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
-    h->ms_sa += a;
-    h->ms_lcp += b;
-    h->ms_walk += c;
-    if (errw) return fail(MEMO_EHIP, "matching statistics of column %d: the walk kernel reported error bits 0x%x", column, errw);
+    if (pieces) *pieces = np;
     return MEMO_OK;
 }
 
