@@ -55,6 +55,11 @@ constexpr int kStatusBadAnnot = 1;            // sticky device flag: the referen
 constexpr int kStatusHugeSlice = 2;           // sticky device flag: >= 2^32 rows reach one tile
 constexpr int kStatusExecNarrow = 4;          // -DMEMO_EXEC_CHECK builds: a branch-free row block was entered with lanes disabled
 
+// The one-time passes over an index's rows that one rule decides (memo_view.hip: pass_due): a k-class view of the dense rows, of the
+// 4-byte words, a dense view with the places of its rows chosen, the copy of a placed six-row view without its dead groups, the
+// query order of the 4-byte rows
+enum Pass { kPassDenseView, kPassPackedView, kPassPlaces, kPassLiveCopy, kPassRowOrder, kPasses };
+
 }  // namespace memo
 
 #define HIP_TRY(expr)                                                                          \
@@ -111,12 +116,11 @@ struct memo_index {
     // Rows that came in through memo_builder_* or memo_index_import_packed are in start order (or in whatever order their
     // file holds): an index that answers one query -- the one-shot forms, `memo query` -- should not pay a pass over its rows
     // for an order that spares a fraction of one sweep.  They are ordered once the queries that read them have lost to the
-    // start order what the ordering pass costs (order_due, memo_view.hip: the same ski-rental rule as the views), by
+    // start order what the ordering pass costs (keep_row_order, memo_view.hip: the same ski-rental rule as the views), by
     // memo_index_prepare, or by memo_index_pack on the finished index.
     int order_pending = 0;
     double order_lost_ns = 0;    // what the queries so far would have saved on rows in the query order (estimate)
     int order_backoff = 1;       // (x 4 after an ordering that found no room for its second copy)
-    double order_ns_per_row = 0;  // measured by the last ordering pass (0: the calibrated constant)
     float pack_ms = 0.f;       // device time of the last memo_index_pack (census + packing kernel)
     uint32_t *p3 = nullptr;    // dense rows (memo_index_pack_dense): 16 bytes per 5 rows; annot <= 255 only
     // The dense rows may be FEWER than the index's rows: a row whose 6-bit length field is saturated (overlap >= 63, or
@@ -161,8 +165,8 @@ struct memo_index {
     int view_live = 1;            // memo_index_set_option(MEMO_OPT_VIEW_LIVE): 0 placed six-row views keep their dead groups (flagged, swept with LIVE)
     int wide_tiles = 1;           // memo_index_set_option(MEMO_OPT_WIDE_TILES): 0 six-row views keep the doubling tiles where R4 would apply (A/B)
     uint64_t view_live_copies = 0;  // placed six-row views copied without their dead groups (memo_debug_view_live_copies of the AB library)
-    double view_ns_per_row[4] = {0, 0, 0, 0};  // measured by the last view build ([0] dense rows, [1] 4-byte words, [2] dense rows with places,
-                                               //   [3] the copy without dead groups, per group of the flagged view; 0: the calibrated constant)
+    double pass_ns[memo::kPasses] = {};  // per row of its source, as the index's last pass of each kind measured it (memo::Pass; the copy without
+                                         //   dead groups: per group of the flagged view; 0: the calibrated constant, memo_view.hip: kPassNs)
     uint64_t view_clock = 0;
     uint64_t view_builds = 0;     // views built over the index's lifetime (memo_index_info_t.view_builds)
     DenseView views[16];          // classes of two: overlaps below 2, 4, 6 ... 32

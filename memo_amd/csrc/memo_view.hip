@@ -752,6 +752,51 @@ hipError_t side_alloc(void **p, size_t bytes) {
     return err;
 }
 
+namespace {
+// The scratch and output buffers of one pass: freed when the pass returns, except what it hands to its caller (release).
+struct SideBuffers {
+    const char *what;  // (the pass, for its error messages)
+    static constexpr int kMost = 5;
+    void *owned[kMost] = {};
+    int n = 0;
+    hipError_t err = hipSuccess;
+    explicit SideBuffers(const char *pass) : what(pass) {}
+    SideBuffers(const SideBuffers &) = delete;
+    SideBuffers &operator=(const SideBuffers &) = delete;
+    ~SideBuffers() {
+        for (int i = 0; i < n; ++i) (void)hipFree(owned[i]);
+    }
+    template <typename T>
+    SideBuffers &alloc(T **p, size_t bytes) {  // (after a failed allocation the later ones of the group are not tried)
+        *p = nullptr;
+        if (err == hipSuccess) err = n < kMost ? side_alloc((void **)p, bytes) : hipErrorInvalidValue;
+        if (err == hipSuccess) owned[n++] = *p;
+        return *this;
+    }
+    int status() const {  // of the allocations so far: no room is not an error (the query runs on the rows it has)
+        if (err == hipErrorOutOfMemory) return kNoRoom;
+        return err == hipSuccess ? MEMO_OK : failed(err);
+    }
+    int failed(hipError_t e) const { return fail(MEMO_EHIP, "%s: %s", what, hipGetErrorString(e)); }
+    template <typename T>
+    T *release(T *p) {
+        for (int i = 0; i < n; ++i)
+            if (owned[i] == p) owned[i] = nullptr;
+        return p;
+    }
+};
+
+// the offsets of the arrays a pass carves out of ONE scratch allocation (each at a multiple of 256 bytes)
+struct Carve {
+    uint64_t bytes = 0;
+    uint64_t take(uint64_t size) {
+        const uint64_t at = bytes;
+        bytes += (size + 255) & ~(uint64_t)255;
+        return at;
+    }
+};
+}  // namespace
+
 // The dense rows of `src` (groups, bucket table of nb entries, row count) whose overlap is below `cap`, as a view of their own
 // -- groups of rpg = 5 rows back to back with the kept-rows table, or of rpg = 6 rows that carry their bucket, with a table in
 // units of (padded) rows -- or nothing (*out_p3 stays NULL) when fewer than min_tenths tenths of the rows would go.
@@ -766,109 +811,98 @@ static int dense_view_build(int device, const uint32_t *src_p3, const int64_t *s
     DeviceGuard guard(device);
     const uint64_t groups = (rows + 4) / 5, chunks = (groups + 63) >> 6, nblk = (chunks + 1023) >> 10;
     const uint64_t nbk = nb - 1, nblk6 = (nbk + 1023) >> 10;
-    // one allocation for everything that goes again: keep bytes, the two scans' arrays
-    auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint64_t o_keep = 0, o_count = o_keep + up(chunks * 64), o_bpre = o_count + up(chunks * 4), o_gcount = o_bpre + up((nblk + 1) * 8),
-                   o_gblock = o_gcount + up(rpg == 6 ? nbk * 4 + 4 : 0), o_dead = o_gblock + up(rpg == 6 ? (nblk6 + 1) * 8 : 0);
     const bool live = rpg == 6 && colour_km1 > 0 && cap <= 32;  // (the dead rows: views of six rows with places)
-    const uint64_t o_ndead = o_dead + up(live ? chunks * 64 : 0), tmp_bytes = o_ndead + up(live ? 8 : 0);
+    // one allocation for everything that goes again: keep bytes, the two scans' arrays
+    Carve tmp_at;
+    const uint64_t o_keep = tmp_at.take(chunks * 64), o_count = tmp_at.take(chunks * 4), o_bpre = tmp_at.take((nblk + 1) * 8),
+                   o_gcount = tmp_at.take(rpg == 6 ? nbk * 4 + 4 : 0), o_gblock = tmp_at.take(rpg == 6 ? (nblk6 + 1) * 8 : 0),
+                   o_dead = tmp_at.take(live ? chunks * 64 : 0), o_ndead = tmp_at.take(live ? 8 : 0);
     if (out_dead) *out_dead = 0;
+    SideBuffers side("dense view");
     char *tmp = nullptr;
     uint4 *outg = nullptr;
     int64_t *boffv = nullptr, *boff6 = nullptr;
-    int rc = MEMO_OK;
-    do {
-        hipError_t err = side_alloc((void **)&tmp, tmp_bytes);
-        if (err == hipSuccess) err = side_alloc((void **)&boffv, nb * 8);
-        if (err == hipErrorOutOfMemory) { rc = kNoRoom; break; }
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "dense view: %s", hipGetErrorString(err)); break; }
-        uint8_t *keep8 = reinterpret_cast<uint8_t *>(tmp + o_keep);
-        uint32_t *count = reinterpret_cast<uint32_t *>(tmp + o_count);
-        uint64_t *blockpre = reinterpret_cast<uint64_t *>(tmp + o_bpre);
-        uint32_t *gcount = reinterpret_cast<uint32_t *>(tmp + o_gcount);
-        uint64_t *gblock = reinterpret_cast<uint64_t *>(tmp + o_gblock);
-        const uint4 *p3 = reinterpret_cast<const uint4 *>(src_p3);
-        const unsigned cgrid = (unsigned)((chunks + 3) / 4 < 256 * 32 ? (chunks + 3) / 4 : 256 * 32);
-        hipLaunchKernelGGL(view_count_kernel, dim3(cgrid), dim3(256), 0, st, p3, rows, (uint32_t)cap, keep8, count);
-        hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk), dim3(256), 0, st, count, chunks, count, blockpre);
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockpre, nblk);
-        hipLaunchKernelGGL(view_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src_boff, nb, rows, keep8, count, blockpre,
-                           nblk, boffv);
-        uint64_t total = 0, total6 = 0;
+    if (int rc = side.alloc(&tmp, tmp_at.bytes).alloc(&boffv, nb * 8).status()) return rc;
+    uint8_t *keep8 = reinterpret_cast<uint8_t *>(tmp + o_keep);
+    uint32_t *count = reinterpret_cast<uint32_t *>(tmp + o_count);
+    uint64_t *blockpre = reinterpret_cast<uint64_t *>(tmp + o_bpre);
+    uint32_t *gcount = reinterpret_cast<uint32_t *>(tmp + o_gcount);
+    uint64_t *gblock = reinterpret_cast<uint64_t *>(tmp + o_gblock);
+    const uint4 *p3 = reinterpret_cast<const uint4 *>(src_p3);
+    const unsigned cgrid = (unsigned)((chunks + 3) / 4 < 256 * 32 ? (chunks + 3) / 4 : 256 * 32);
+    hipLaunchKernelGGL(view_count_kernel, dim3(cgrid), dim3(256), 0, st, p3, rows, (uint32_t)cap, keep8, count);
+    hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk), dim3(256), 0, st, count, chunks, count, blockpre);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockpre, nblk);
+    hipLaunchKernelGGL(view_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src_boff, nb, rows, keep8, count, blockpre,
+                       nblk, boffv);
+    uint64_t total = 0, total6 = 0;
+    hipError_t err = hipGetLastError();
+    if (rpg == 6 && err == hipSuccess) {  // groups per bucket -> groups before every bucket
+        hipLaunchKernelGGL(view_group_counts_kernel, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, boffv, (int64_t)nbk, gcount, 6);
+        hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk6), dim3(256), 0, st, gcount, nbk, gcount, gblock);
+        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, gblock, nblk6);
         err = hipGetLastError();
-        if (rpg == 6 && err == hipSuccess) {  // groups per bucket -> groups before every bucket
-            hipLaunchKernelGGL(view_group_counts_kernel, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, boffv, (int64_t)nbk, gcount, 6);
-            hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk6), dim3(256), 0, st, gcount, nbk, gcount, gblock);
-            hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, gblock, nblk6);
-            err = hipGetLastError();
-            if (err == hipSuccess) err = hipMemcpyAsync(&total6, gblock + nblk6, 8, hipMemcpyDeviceToHost, st);
-        }
-        if (err == hipSuccess) err = hipMemcpyAsync(&total, blockpre + nblk, 8, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "dense view: %s", hipGetErrorString(err)); break; }
-        if (total + rows / 10 * (uint64_t)min_tenths > rows) break;  // too few would go
-        const uint64_t padded = rpg == 6 ? 6 * total6 : ((total + 15) & ~(uint64_t)15) + kPadRows;
-        const uint64_t ngroups = rpg == 6 ? total6 + 64 : dense_groups_for(padded), used = rpg == 6 ? total6 : total / 5;
-        err = side_alloc((void **)&outg, ngroups * 16);
-        if (err == hipSuccess && rpg == 6) err = side_alloc((void **)&boff6, nb * 8);
-        if (err == hipErrorOutOfMemory) { rc = kNoRoom; break; }
-        if (err == hipSuccess) err = hipMemsetAsync(outg + used, 0, (ngroups - used) * 16, st);  // (behind the rows; P = 5: the last, partial group too)
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "dense view: %s", hipGetErrorString(err)); break; }
-        ViewArgs a;
-        a.src = p3;
-        a.boff = src_boff;
-        a.boffv = boffv;
-        a.glocal = gcount;
-        a.gblock = gblock;
-        a.nbuckets = (int64_t)nbk;
-        a.rows = rows;
-        a.out = outg;
-        a.boff6 = boff6;
-        a.cap = (uint32_t)cap;
-        a.km1 = colour_km1;
-        a.dead8 = nullptr;
-        a.dead_groups = reinterpret_cast<unsigned long long *>(tmp + o_ndead);
-        uint64_t ndead = 0;
-        if (live) {
-            uint8_t *dead8 = reinterpret_cast<uint8_t *>(tmp + o_dead);
-            err = hipMemsetAsync(dead8, 0, o_ndead + 8 - o_dead, st);  // (the dead bits and their group count)
-            if (err != hipSuccess) { rc = fail(MEMO_EHIP, "dense view: %s", hipGetErrorString(err)); break; }
-            hipLaunchKernelGGL(view_live_kernel, dim3((unsigned)(nbk < 256 * 32 ? nbk : 256 * 32)), dim3(64), 0, st, p3, src_boff, (int64_t)nbk,
-                               (uint32_t)cap, reinterpret_cast<uint32_t *>(dead8));
-            a.dead8 = dead8;
-        }
-        // buckets per run: as many as (nearly always) fit the stage whole, so that a run is one piece and every lane has a bucket
-        const double per_bucket = (double)total / (double)nbk;
-        a.stage_rows = colour_km1 > 0 ? kViewCapPlaced : kViewCapPlain;
-        int rb = per_bucket > 1.0 ? (int)(0.85 * a.stage_rows / per_bucket) : kViewRun;
-        a.run_buckets = rb > kViewRun ? kViewRun : (rb < 4 ? 4 : rb);
-        const size_t lds_bytes = view_lds_bytes(a.stage_rows, colour_km1 > 0);
-        const int64_t nruns = ((int64_t)nbk + a.run_buckets - 1) / a.run_buckets;
-        if (rpg == 5)
-            hipLaunchKernelGGL(view_zero_edges_kernel, dim3((unsigned)((nruns + 1 + 255) / 256)), dim3(256), 0, st, boffv, (int64_t)nbk,
-                               a.run_buckets, outg);
-        const unsigned grid = (unsigned)(nruns < 256 * 16 * 4 ? nruns : 256 * 16 * 4);
-        if (rpg == 6)
-            hipLaunchKernelGGL(view_build_kernel<6>, dim3(grid), dim3(64), lds_bytes, st, a);
-        else
-            hipLaunchKernelGGL(view_build_kernel<5>, dim3(grid), dim3(64), lds_bytes, st, a);
-        err = hipGetLastError();
-        if (err == hipSuccess && live) err = hipMemcpyAsync(&ndead, a.dead_groups, 8, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "dense view: %s", hipGetErrorString(err)); break; }
-        if (out_dead) *out_dead = ndead;
-        *out_p3 = reinterpret_cast<uint32_t *>(outg);
-        *out_boff = rpg == 6 ? boff6 : boffv;
-        *out_rows = total;
-        *out_padded = padded;
-        outg = nullptr;
-        if (rpg == 6) boff6 = nullptr; else boffv = nullptr;
-    } while (0);
-    (void)hipFree(tmp);
-    (void)hipFree(outg);
-    (void)hipFree(boffv);
-    (void)hipFree(boff6);
-    return rc;
+        if (err == hipSuccess) err = hipMemcpyAsync(&total6, gblock + nblk6, 8, hipMemcpyDeviceToHost, st);
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(&total, blockpre + nblk, 8, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return side.failed(err);
+    if (total + rows / 10 * (uint64_t)min_tenths > rows) return MEMO_OK;  // too few would go
+    const uint64_t padded = rpg == 6 ? 6 * total6 : ((total + 15) & ~(uint64_t)15) + kPadRows;
+    const uint64_t ngroups = rpg == 6 ? total6 + 64 : dense_groups_for(padded), used = rpg == 6 ? total6 : total / 5;
+    side.alloc(&outg, ngroups * 16);
+    if (rpg == 6) side.alloc(&boff6, nb * 8);
+    if (int rc = side.status()) return rc;
+    err = hipMemsetAsync(outg + used, 0, (ngroups - used) * 16, st);  // (behind the rows; P = 5: the last, partial group too)
+    if (err != hipSuccess) return side.failed(err);
+    ViewArgs a;
+    a.src = p3;
+    a.boff = src_boff;
+    a.boffv = boffv;
+    a.glocal = gcount;
+    a.gblock = gblock;
+    a.nbuckets = (int64_t)nbk;
+    a.rows = rows;
+    a.out = outg;
+    a.boff6 = boff6;
+    a.cap = (uint32_t)cap;
+    a.km1 = colour_km1;
+    a.dead8 = nullptr;
+    a.dead_groups = reinterpret_cast<unsigned long long *>(tmp + o_ndead);
+    uint64_t ndead = 0;
+    if (live) {
+        uint8_t *dead8 = reinterpret_cast<uint8_t *>(tmp + o_dead);
+        err = hipMemsetAsync(dead8, 0, o_ndead + 8 - o_dead, st);  // (the dead bits and their group count)
+        if (err != hipSuccess) return side.failed(err);
+        hipLaunchKernelGGL(view_live_kernel, dim3((unsigned)(nbk < 256 * 32 ? nbk : 256 * 32)), dim3(64), 0, st, p3, src_boff, (int64_t)nbk,
+                           (uint32_t)cap, reinterpret_cast<uint32_t *>(dead8));
+        a.dead8 = dead8;
+    }
+    // buckets per run: as many as (nearly always) fit the stage whole, so that a run is one piece and every lane has a bucket
+    const double per_bucket = (double)total / (double)nbk;
+    a.stage_rows = colour_km1 > 0 ? kViewCapPlaced : kViewCapPlain;
+    int rb = per_bucket > 1.0 ? (int)(0.85 * a.stage_rows / per_bucket) : kViewRun;
+    a.run_buckets = rb > kViewRun ? kViewRun : (rb < 4 ? 4 : rb);
+    const size_t lds_bytes = view_lds_bytes(a.stage_rows, colour_km1 > 0);
+    const int64_t nruns = ((int64_t)nbk + a.run_buckets - 1) / a.run_buckets;
+    if (rpg == 5)
+        hipLaunchKernelGGL(view_zero_edges_kernel, dim3((unsigned)((nruns + 1 + 255) / 256)), dim3(256), 0, st, boffv, (int64_t)nbk,
+                           a.run_buckets, outg);
+    const unsigned grid = (unsigned)(nruns < 256 * 16 * 4 ? nruns : 256 * 16 * 4);
+    if (rpg == 6)
+        hipLaunchKernelGGL(view_build_kernel<6>, dim3(grid), dim3(64), lds_bytes, st, a);
+    else
+        hipLaunchKernelGGL(view_build_kernel<5>, dim3(grid), dim3(64), lds_bytes, st, a);
+    err = hipGetLastError();
+    if (err == hipSuccess && live) err = hipMemcpyAsync(&ndead, a.dead_groups, 8, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return side.failed(err);
+    if (out_dead) *out_dead = ndead;
+    *out_p3 = reinterpret_cast<uint32_t *>(side.release(outg));
+    *out_boff = side.release(rpg == 6 ? boff6 : boffv);
+    *out_rows = total;
+    *out_padded = padded;
+    return MEMO_OK;
 }
 
 // A placed six-row view (groups of ng = padded / 6, bucket table boff6 of nb entries, dead_groups of them flagged kDeadGroup) without
@@ -884,48 +918,37 @@ static int live_view_copy(int device, const uint32_t *src_p3, const int64_t *bof
     if (!ng || dead_groups == 0 || dead_groups > ng || nb < 2) return MEMO_OK;
     DeviceGuard guard(device);
     const uint64_t chunks = (ng + 63) >> 6, nblk = (chunks + 1023) >> 10, nlive = ng - dead_groups;
-    auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint64_t o_mask = 0, o_count = o_mask + up(chunks * 8), o_bpre = o_count + up(chunks * 4), tmp_bytes = o_bpre + up((nblk + 1) * 8);
+    Carve tmp_at;
+    const uint64_t o_mask = tmp_at.take(chunks * 8), o_count = tmp_at.take(chunks * 4), o_bpre = tmp_at.take((nblk + 1) * 8);
+    SideBuffers side("live view");
     char *tmp = nullptr;
     uint4 *outg = nullptr;
     int64_t *boff = nullptr;
-    int rc = MEMO_OK;
-    do {
-        hipError_t err = side_alloc((void **)&tmp, tmp_bytes);
-        if (err == hipSuccess) err = side_alloc((void **)&outg, (nlive + 64) * 16);
-        if (err == hipSuccess) err = side_alloc((void **)&boff, nb * 8);
-        if (err == hipErrorOutOfMemory) { rc = kNoRoom; break; }
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "live view: %s", hipGetErrorString(err)); break; }
-        unsigned long long *mask = reinterpret_cast<unsigned long long *>(tmp + o_mask);
-        uint32_t *count = reinterpret_cast<uint32_t *>(tmp + o_count);
-        uint64_t *blockpre = reinterpret_cast<uint64_t *>(tmp + o_bpre);
-        const uint4 *src = reinterpret_cast<const uint4 *>(src_p3);
-        const unsigned grid = (unsigned)((chunks + 3) / 4 < 256 * 32 ? (chunks + 3) / 4 : 256 * 32);
-        err = hipMemsetAsync(outg + nlive, 0, 64 * 16, st);
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "live view: %s", hipGetErrorString(err)); break; }
-        hipLaunchKernelGGL(live_count_kernel, dim3(grid), dim3(256), 0, st, src, ng, mask, count);
-        hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk), dim3(256), 0, st, count, chunks, count, blockpre);
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockpre, nblk);
-        hipLaunchKernelGGL(live_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, boff6, nb, ng, mask, count, blockpre, nblk,
-                           boff);
-        hipLaunchKernelGGL(live_scatter_kernel, dim3(grid), dim3(256), 0, st, src, ng, mask, count, blockpre, outg, nlive);
-        uint64_t total = 0;
-        err = hipGetLastError();
-        if (err == hipSuccess) err = hipMemcpyAsync(&total, blockpre + nblk, 8, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "live view: %s", hipGetErrorString(err)); break; }
-        if (total != nlive) { rc = fail(MEMO_EHIP, "live view: %llu live groups, the placing pass counted %llu", (unsigned long long)total,
-                                        (unsigned long long)nlive); break; }
-        *out_p3 = reinterpret_cast<uint32_t *>(outg);
-        *out_boff = boff;
-        *out_padded = 6 * nlive;
-        outg = nullptr;
-        boff = nullptr;
-    } while (0);
-    (void)hipFree(tmp);
-    (void)hipFree(outg);
-    (void)hipFree(boff);
-    return rc;
+    if (int rc = side.alloc(&tmp, tmp_at.bytes).alloc(&outg, (nlive + 64) * 16).alloc(&boff, nb * 8).status()) return rc;
+    unsigned long long *mask = reinterpret_cast<unsigned long long *>(tmp + o_mask);
+    uint32_t *count = reinterpret_cast<uint32_t *>(tmp + o_count);
+    uint64_t *blockpre = reinterpret_cast<uint64_t *>(tmp + o_bpre);
+    const uint4 *src = reinterpret_cast<const uint4 *>(src_p3);
+    const unsigned grid = (unsigned)((chunks + 3) / 4 < 256 * 32 ? (chunks + 3) / 4 : 256 * 32);
+    hipError_t err = hipMemsetAsync(outg + nlive, 0, 64 * 16, st);
+    if (err != hipSuccess) return side.failed(err);
+    hipLaunchKernelGGL(live_count_kernel, dim3(grid), dim3(256), 0, st, src, ng, mask, count);
+    hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk), dim3(256), 0, st, count, chunks, count, blockpre);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockpre, nblk);
+    hipLaunchKernelGGL(live_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, boff6, nb, ng, mask, count, blockpre, nblk,
+                       boff);
+    hipLaunchKernelGGL(live_scatter_kernel, dim3(grid), dim3(256), 0, st, src, ng, mask, count, blockpre, outg, nlive);
+    uint64_t total = 0;
+    err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(&total, blockpre + nblk, 8, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return side.failed(err);
+    if (total != nlive)
+        return fail(MEMO_EHIP, "live view: %llu live groups, the placing pass counted %llu", (unsigned long long)total, (unsigned long long)nlive);
+    *out_p3 = reinterpret_cast<uint32_t *>(side.release(outg));
+    *out_boff = side.release(boff);
+    *out_padded = 6 * nlive;
+    return MEMO_OK;
 }
 
 // The same for the 4-byte WORDS (formats 4 / 12: the overlap byte sits at bit len_shift): the words whose overlap is below cap, in
@@ -938,50 +961,35 @@ static int packed_filter(int device, const uint32_t *src, const int64_t *src_bof
     DeviceGuard guard(device);
     const uint64_t n32 = (rows + 31) >> 5, nblk = (n32 + 1023) >> 10;
     const unsigned row_grid = (unsigned)((rows + 255) / 256 < ((uint64_t)1 << 20) ? (rows + 255) / 256 : (uint64_t)1 << 20);
+    SideBuffers side("packed view");
     uint32_t *keep = nullptr, *local = nullptr, *words = nullptr;
     uint64_t *blockpre = nullptr;
     int64_t *boffv = nullptr;
-    int rc = MEMO_OK;
-    do {
-        hipError_t err = side_alloc((void **)&keep, n32 * 4 + 4);
-        if (err == hipSuccess) err = side_alloc((void **)&local, n32 * 4);
-        if (err == hipSuccess) err = side_alloc((void **)&blockpre, (nblk + 1) * 8);
-        if (err == hipErrorOutOfMemory) { rc = kNoRoom; break; }
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "packed view: %s", hipGetErrorString(err)); break; }
-        hipLaunchKernelGGL(packed_keep_kernel, dim3(row_grid), dim3(256), 0, st, src, rows, len_shift, (uint32_t)cap, keep, local);
-        hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk), dim3(256), 0, st, local, n32, local, blockpre);
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockpre, nblk);
-        uint64_t total = 0;
-        err = hipGetLastError();
-        if (err == hipSuccess) err = hipMemcpyAsync(&total, blockpre + nblk, 8, hipMemcpyDeviceToHost, st);
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "packed view: %s", hipGetErrorString(err)); break; }
-        if (total + rows / 10 * (uint64_t)min_tenths > rows) break;  // too few would go
-        const uint64_t padded = ((total + 15) & ~(uint64_t)15) + kPadRows;
-        err = side_alloc((void **)&words, padded * 4);
-        if (err == hipSuccess) err = side_alloc((void **)&boffv, nb * 8);
-        if (err == hipErrorOutOfMemory) { rc = kNoRoom; break; }
-        if (err == hipSuccess) err = hipMemsetAsync(words + total, 0, (padded - total) * 4, st);
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "packed view: %s", hipGetErrorString(err)); break; }
-        hipLaunchKernelGGL(packed_scatter_kernel, dim3(row_grid), dim3(256), 0, st, src, rows, keep, local, blockpre, words);
-        hipLaunchKernelGGL(dense_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src_boff, nb, rows, total, keep, local,
-                           blockpre, boffv);
-        err = hipGetLastError();
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err != hipSuccess) { rc = fail(MEMO_EHIP, "packed view: %s", hipGetErrorString(err)); break; }
-        *out_pk = words;
-        *out_boff = boffv;
-        *out_rows = total;
-        *out_padded = padded;
-        words = nullptr;
-        boffv = nullptr;
-    } while (0);
-    (void)hipFree(keep);
-    (void)hipFree(local);
-    (void)hipFree(blockpre);
-    (void)hipFree(words);
-    (void)hipFree(boffv);
-    return rc;
+    if (int rc = side.alloc(&keep, n32 * 4 + 4).alloc(&local, n32 * 4).alloc(&blockpre, (nblk + 1) * 8).status()) return rc;
+    hipLaunchKernelGGL(packed_keep_kernel, dim3(row_grid), dim3(256), 0, st, src, rows, len_shift, (uint32_t)cap, keep, local);
+    hipLaunchKernelGGL(scan_local_kernel, dim3((unsigned)nblk), dim3(256), 0, st, local, n32, local, blockpre);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, blockpre, nblk);
+    uint64_t total = 0;
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(&total, blockpre + nblk, 8, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return side.failed(err);
+    if (total + rows / 10 * (uint64_t)min_tenths > rows) return MEMO_OK;  // too few would go
+    const uint64_t padded = ((total + 15) & ~(uint64_t)15) + kPadRows;
+    if (int rc = side.alloc(&words, padded * 4).alloc(&boffv, nb * 8).status()) return rc;
+    err = hipMemsetAsync(words + total, 0, (padded - total) * 4, st);
+    if (err != hipSuccess) return side.failed(err);
+    hipLaunchKernelGGL(packed_scatter_kernel, dim3(row_grid), dim3(256), 0, st, src, rows, keep, local, blockpre, words);
+    hipLaunchKernelGGL(dense_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src_boff, nb, rows, total, keep, local,
+                       blockpre, boffv);
+    err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return side.failed(err);
+    *out_pk = side.release(words);
+    *out_boff = side.release(boffv);
+    *out_rows = total;
+    *out_padded = padded;
+    return MEMO_OK;
 }
 
 // ix->p3 holds every row of the index (rows3 == rows, no boff3).  When more than a tenth of them can never write at
@@ -1022,7 +1030,14 @@ void flush_retired(memo_index *ix) {
     ix->retired_bytes = 0;
 }
 
-static void retire_view(memo_index *ix, memo_index::DenseView &v, bool dense) {
+// The back-off of a pass that found no room or whose view was evicted (DenseView::backoff, memo_index::order_backoff): x 4, up to
+// 2^16; and the queries that must pass before an evicted class is looked at again (DenseView::ask_after): 0, 16, then x 4 alike.
+static int backoff_step(int x) { return x < (1 << 16) ? x * 4 : x; }
+static int ask_after_step(int x) { return x ? backoff_step(x) : 16; }
+
+// evicted: by the budget -- the class starts again, later (back-off: see DenseView); else the view is being replaced by another of
+// the same class (its places, its live copy, a new row order), which is as due as it was
+static void retire_view(memo_index *ix, memo_index::DenseView &v, bool evicted) {
     for (size_t i = 0; i < ix->ttabs.size();) {  // the tile tables made for it go with it (a later allocation may land on its address)
         if (ix->ttabs[i].rows_of == v.p3) {
             retire(ix, ix->ttabs[i].d, (uint64_t)ix->ttabs[i].n * 32);
@@ -1033,10 +1048,9 @@ static void retire_view(memo_index *ix, memo_index::DenseView &v, bool dense) {
     }
     retire(ix, v.p3, v.bytes);
     retire(ix, v.boff, ix->nb * 8);
-    const int again = v.backoff < (1 << 16) ? v.backoff * 4 : v.backoff;  // back-off: see DenseView
-    const int ask = v.ask_after ? (v.ask_after < (1 << 16) ? v.ask_after * 4 : v.ask_after) : 16;
+    const int backoff = evicted ? backoff_step(v.backoff) : v.backoff, ask = evicted ? ask_after_step(v.ask_after) : v.ask_after;
     v = memo_index::DenseView();
-    v.backoff = again;
+    v.backoff = backoff;
     v.ask_after = ask;
 }
 
@@ -1088,7 +1102,7 @@ static void keep_views_in_budget(memo_index *ix, const memo_index::DenseView *fr
             for (int i = 0; i < kPacked; ++i) look(ix->pviews[i]);
         }
         if (total <= budget || !lru) break;
-        retire_view(ix, *lru, dense);
+        retire_view(ix, *lru, true);
     }
     if (ix->retired_bytes > budget + base_bytes) {  // (rare: many evictions and no memo_query_check in between)
         (void)hipDeviceSynchronize();
@@ -1105,7 +1119,7 @@ static void keep_views_in_budget(memo_index *ix, const memo_index::DenseView *fr
 // what a sweep pays per row -- and the view is built by the query that finds the sum has reached the view's estimated cost:
 // the ski-rental rule (never more than twice the cost of having known the future).  memo_index_prepare builds at once;
 // MEMO_OPT_BUILD_COST_PCT scales the threshold (0: the class's first query builds).  The same rule decides when rows that
-// came in start order are brought into the query order (order_due).
+// came in start order are brought into the query order (keep_row_order).
 // Calibration (MI355X, profiles/r05_view_pass.txt): a sweep's time per row it reads; a pass's time per row of its source --
 // replaced by what the index's own last pass measured -- plus what allocations and the two waits cost whatever the size.
 constexpr double kSweepNsPerRow = 0.00048;      // config 3, k = 31: (0.298 - 0.179 ms) / 2.5e8 rows a view spares
@@ -1116,7 +1130,8 @@ constexpr double kPackedViewNsPerRow = 0.03;    // keep, scan, scatter, and the 
 constexpr double kOrderNsPerRow = 0.014;        // copy + the order inside the buckets (more on indexes of many rows per start)
 constexpr double kLiveCopyNsPerGroup = 0.008;   // live_view_copy, per group of the flagged view: two reads of it, a write of its live groups
 constexpr double kPassFixedNs = 200e3;
-constexpr double kPassNs[4] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow, kLiveCopyNsPerGroup};  // (view_ns_per_row)
+// per unit of every pass (Pass, memo_common.h: a row of its source; the live copy: a group of the flagged view), until the index has measured one
+constexpr double kPassNs[kPasses] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow, kLiveCopyNsPerGroup, kOrderNsPerRow};
 
 static double rows_in_window(const memo_index *ix, double src_rows, int64_t window, int km1) {
     const double span = (double)ix->max_s - (double)ix->min_s + 1.0;
@@ -1133,23 +1148,46 @@ static double share_below(const memo_index *ix, int cap) {
     return below / (double)ix->len_hist_rows;
 }
 
-// kind: 0 a view of the dense rows, 1 of the 4-byte words.  spared: the share of src_rows the view leaves out.
-static bool view_due(memo_index *ix, memo_index::DenseView &v, int kind, double src_rows, double spared, int64_t window, int km1) {
+// The rule: a pass over `units` rows (groups) is due when its ledger -- what the queries so far have lost to its absence -- has
+// reached its estimated cost, `backoff` times over.  What a query adds to a ledger is its caller's estimate (below).
+static bool pass_due(const memo_index *ix, double lost_ns, int backoff, Pass pass, double units) {
+    const double per_unit = ix->pass_ns[pass] > 0 ? ix->pass_ns[pass] : kPassNs[pass];
+    return lost_ns >= (units * per_unit + kPassFixedNs) * (double)backoff * (double)ix->build_cost_pct / 100.0;
+}
+
+static void pass_measured(memo_index *ix, Pass pass, float ms, double units) {  // what the pass cost, for the next estimate
+    const double ns = (double)ms * 1e6 - kPassFixedNs;
+    // within a factor of four of the calibrated constant: the pass is timed with its allocations, and a hipMalloc that stalls (350 ms
+    // for 0.85 GB seen on one box: gpurun r5valid) must not make every later view of the index look two hundred times as dear
+    const double floor = 0.25 * kPassNs[pass], ceil = 4.0 * kPassNs[pass];
+    if (units > 0) ix->pass_ns[pass] = ns / units > floor ? (ns / units < ceil ? ns / units : ceil) : floor;
+}
+
+// one pass: run on `st` between two events, the caller's stream waited for (later queries may come on other streams)
+template <typename Build>
+static int build_timed(hipStream_t st, float *ms, Build build) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_TRY(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        return fail(MEMO_EHIP, "hipEventCreate failed");
+    }
+    (void)hipEventRecord(e0, st);
+    const int rc = build();
+    (void)hipEventRecord(e1, st);
+    (void)hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+}
+
+// A class without its view (pass: kPassDenseView or kPassPackedView).  spared: the share of src_rows the view would leave out.
+static bool view_due(memo_index *ix, memo_index::DenseView &v, Pass pass, double src_rows, double spared, int64_t window, int km1) {
     if (g_prepare_only) return true;
     if (spared > 0) v.lost_ns += rows_in_window(ix, src_rows, window, km1) * spared * kSweepNsPerRow;
     if (++v.seen <= v.ask_after) return false;
-    const double per_row = ix->view_ns_per_row[kind] > 0 ? ix->view_ns_per_row[kind] : kPassNs[kind];
-    const double cost = (src_rows * per_row + kPassFixedNs) * (double)v.backoff * (double)ix->build_cost_pct / 100.0;
-    return v.lost_ns >= cost;
-}
-
-// kind 3: the copy without dead groups, src_rows = the flagged view's groups
-static void view_built(memo_index *ix, float build_ms, int kind, double src_rows) {  // what the pass cost, for the next estimate
-    const double ns = (double)build_ms * 1e6 - kPassFixedNs;
-    // within a factor of four of the calibrated constant: the pass is timed with its allocations, and a hipMalloc that stalls (350 ms
-    // for 0.85 GB seen on one box: gpurun r5valid) must not make every later view of the index look two hundred times as dear
-    const double floor = 0.25 * kPassNs[kind], ceil = 4.0 * kPassNs[kind];
-    if (src_rows > 0) ix->view_ns_per_row[kind] = ns / src_rows > floor ? (ns / src_rows < ceil ? ns / src_rows : ceil) : floor;
+    return pass_due(ix, v.lost_ns, v.backoff, pass, src_rows);
 }
 
 // A dense view that exists with its rows in the order they came: is it time to build it again with their places chosen
@@ -1159,8 +1197,7 @@ static bool places_due(memo_index *ix, memo_index::DenseView &v, double src_rows
     if (g_prepare_only) return true;
     const double read = rows_in_window(ix, (double)(six ? v.padded : v.rows), window, km1);
     v.unplaced_ns += read * 1.5 * kSweepNsPerRow * kPlacedGainPerKm1 * (double)km1;  // (a sweep on a view: 0.72 ps per row it reads)
-    const double per_row = ix->view_ns_per_row[2] > 0 ? ix->view_ns_per_row[2] : kPlacedViewNsPerRow;
-    return v.unplaced_ns >= (src_rows * per_row + kPassFixedNs) * (double)v.backoff * (double)ix->build_cost_pct / 100.0;
+    return pass_due(ix, v.unplaced_ns, v.backoff, kPassPlaces, src_rows);
 }
 
 // A placed six-row view whose dead groups are flagged: is it time for the copy without them (live_view_copy)?  The sweep on the
@@ -1171,8 +1208,7 @@ static bool live_due(memo_index *ix, memo_index::DenseView &v, int64_t window, i
     if (g_prepare_only || v.padded < 6) return false;
     const double groups = (double)(v.padded / 6), share = (double)v.dead_groups / groups;
     v.dead_lost_ns += rows_in_window(ix, (double)v.padded, window, km1) * share * kSweepNsPerRow;
-    const double per_group = ix->view_ns_per_row[3] > 0 ? ix->view_ns_per_row[3] : kLiveCopyNsPerGroup;
-    return v.dead_lost_ns >= (groups * per_group + kPassFixedNs) * (double)v.backoff * (double)ix->build_cost_pct / 100.0;
+    return pass_due(ix, v.dead_lost_ns, v.backoff, kPassLiveCopy, groups);
 }
 
 // The 4-byte rows brought into a query order (memo_interleave.hip: 2 = the conservation order, 3 = the membership order, 0 =
@@ -1206,45 +1242,31 @@ static int order_words_on(memo_index *ix, int mode, hipStream_t st) {
     const hipError_t aerr = side_alloc((void **)&copy, bytes);
     if (aerr == hipErrorOutOfMemory) return kNoRoom;
     HIP_TRY(aerr);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
-    if (err == hipSuccess) err = hipEventRecord(e0, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(copy, ix->pk, bytes, hipMemcpyDeviceToDevice, st);
-    int rc = MEMO_OK;
-    if (err == hipSuccess) rc = interleave_words(copy, ix->boff, ix->nb, ix->bshift, ix->packed_fmt, mode, st, ix->d_scratch);
-    if (err == hipSuccess && !rc) err = hipEventRecord(e1, st);
-    if (err == hipSuccess && !rc) err = hipEventSynchronize(e1);
     float ms = 0.f;
-    if (err == hipSuccess && !rc) (void)hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (err != hipSuccess || rc) {
-        (void)hipStreamSynchronize(st);
+    const int rc = build_timed(st, &ms, [&]() {
+        const hipError_t err = hipMemcpyAsync(copy, ix->pk, bytes, hipMemcpyDeviceToDevice, st);
+        if (err != hipSuccess) return fail(MEMO_EHIP, "ordering the rows: %s", hipGetErrorString(err));
+        return interleave_words(copy, ix->boff, ix->nb, ix->bshift, ix->packed_fmt, mode, st, ix->d_scratch);
+    });
+    if (rc) {
+        (void)hipStreamSynchronize(st);  // (what was queued may still be writing the copy)
         (void)hipFree(copy);
-        return rc ? rc : fail(MEMO_EHIP, "ordering the rows: %s", hipGetErrorString(err));
+        return rc;
     }
     for (memo_index::DenseView &v : ix->pviews)  // (views are subsets in the old order)
-        if (v.p3) {
-            const int keep = v.backoff, ask = v.ask_after;  // (not an eviction: the class is as due as it was)
-            retire_view(ix, v, false);
-            v.backoff = keep;
-            v.ask_after = ask;
-        }
+        if (v.p3) retire_view(ix, v, false);
     retire(ix, ix->pk, bytes);
     ix->pk = copy;
     ix->row_order = mode;
     ix->order_pending = 0;
-    const double ns = (double)ms * 1e6 - kPassFixedNs;
-    const double per = ns / (double)ix->rows;  // (within a factor of four of the constant, like view_built)
-    ix->order_ns_per_row = per > 0.25 * kOrderNsPerRow ? (per < 4.0 * kOrderNsPerRow ? per : 4.0 * kOrderNsPerRow) : 0.25 * kOrderNsPerRow;
+    pass_measured(ix, kPassRowOrder, ms, (double)ix->rows);
     return MEMO_OK;
 }
 
 // Is it time to bring the 4-byte rows into the query order?  Rows that came in through the builder or an import are in start
 // order; what that costs a sweep depends on how many rows share a start (a half-wave's atomics on one cell: profiles/
 // r04_row_order.txt -- 1.5 % of a sweep at 5 rows per start, 7 % at 25, 20 % at 25 and k = 101), and the ordering pass costs
-// a dozen sweeps or more: the queries so far must have lost that much (order_due), or memo_index_prepare asks for it.
+// a dozen sweeps or more: the queries so far must have lost that much (pass_due), or memo_index_prepare asks for it.
 // WHICH order follows from the kind of query that has paid for the pass: conservation deals a bucket's rows over its starts
 // (interleave mode 2), membership over annot mod 32 (mode 3: the lanes of a half-wave on different genomes' plane rows).  Round 4
 // had measured the two level on config 4 -- under a planes kernel whose every row waited for the LDS (memo_sweep_memb.hip:
@@ -1265,21 +1287,14 @@ static int keep_row_order(memo_index *ix, int64_t window, int km1, bool membersh
         gain = gain > 0.2 ? 0.2 : gain;
         if (!pending && membership) gain = kMembershipOrderGain;
         ix->order_lost_ns += rows_in_window(ix, (double)ix->rows, window, km1) * 1.3 * kSweepNsPerRow * gain;
-        const double per_row = ix->order_ns_per_row > 0 ? ix->order_ns_per_row : kOrderNsPerRow;
-        const double cost = ((double)ix->rows * per_row + kPassFixedNs) * (double)ix->order_backoff * (double)ix->build_cost_pct / 100.0;
-        if (ix->order_lost_ns < cost) return MEMO_OK;
+        if (!pass_due(ix, ix->order_lost_ns, ix->order_backoff, kPassRowOrder, (double)ix->rows)) return MEMO_OK;
     }
     const int rc = order_words_on(ix, want, st);
-    if (rc == kNoRoom) {  // (the pressure may pass: look again, later)
-        ix->order_lost_ns = 0;
-        if (ix->order_backoff < (1 << 16)) ix->order_backoff *= 4;
-        return MEMO_OK;
-    }
-    if (!rc) {
-        ix->order_lost_ns = 0;
-        if (!pending && ix->order_backoff < (1 << 16)) ix->order_backoff *= 4;  // (a change of kinds: the next one has to be worth more)
-    }
-    return rc;
+    if (rc && rc != kNoRoom) return rc;
+    ix->order_lost_ns = 0;
+    // no room: the pressure may pass -- look again, later; a change of kinds: the next one has to be worth more
+    if (rc == kNoRoom || !pending) ix->order_backoff = backoff_step(ix->order_backoff);
+    return MEMO_OK;
 }
 
 // the class of k - 1 = km1 for the 4-byte words: caps in steps of 2 up to 32 (an odd k -- 21, 31 -- gets exactly the rows that
@@ -1300,23 +1315,70 @@ static int view_slot(int km1, int *cap) {
     return -1;
 }
 
-// one view: built on `st` between two events, the caller's stream waited for (later queries may come on other streams)
+// The first view of a class: `build` fills v's rows (timed, on st), then the view is installed -- or the class is marked as not
+// worth a view (state 2: too few rows would go), or, with no room on the device, starts again, later (the sweep reads all the rows).
+// pass: what was built (kPassPlaces: a dense view with its rows placed at once); rpg: 5 / 6 rows per group, 0 the 4-byte words.
 template <typename Build>
-static int build_timed(memo_index *ix, memo_index::DenseView &v, hipStream_t st, Build build) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        return fail(MEMO_EHIP, "hipEventCreate failed");
+static int install_view(memo_index *ix, memo_index::DenseView &v, hipStream_t st, int cap, Pass pass, double units, int rpg, uint64_t base_bytes,
+                        Build build) {
+    DeviceGuard guard(ix->device);
+    const int rc = build_timed(st, &v.build_ms, build);
+    if (rc && rc != kNoRoom) return rc;
+    v.cap = cap;
+    v.bytes = rpg ? dense_view_bytes(v.padded, rpg) : v.padded * 4;
+    v.state = v.p3 ? 1 : (rc == kNoRoom ? 0 : 2);
+    if (rc == kNoRoom) {  // (the pressure may pass: look again, but not with every query)
+        v.lost_ns = 0;
+        v.seen = 0;
+        v.backoff = backoff_step(v.backoff);
+        v.ask_after = ask_after_step(v.ask_after);
     }
-    (void)hipEventRecord(e0, st);
-    const int rc = build();
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    (void)hipEventElapsedTime(&v.build_ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    if (v.state == 1) {
+        ++ix->view_builds;
+        v.placed = pass == kPassPlaces ? 1 : 0;
+        if (v.placed) ++ix->view_placings;
+        ix->last_view_ms = v.build_ms;
+        pass_measured(ix, pass, v.build_ms, units);
+        keep_views_in_budget(ix, &v, base_bytes, rpg != 0);
+    }
+    return MEMO_OK;
+}
+
+// A resident dense view replaced by another of its class (pass: kPassPlaces -- the same rows, placed; kPassLiveCopy -- the placed
+// six-row view without its dead groups): `build` fills a second view beside the one in use (sweeps queued on the caller's other
+// streams may still read that one), then the class switches over and the old copy waits on the retire list with its tile tables.
+// No room for the second copy: the view stays as it is and `ledger`, the pass's sum, starts again towards four times the cost.
+template <typename Build>
+static int replace_view(memo_index *ix, memo_index::DenseView &v, hipStream_t st, Pass pass, double units, int rpg, uint64_t base_bytes,
+                        double &ledger, Build build) {
+    DeviceGuard guard(ix->device);
+    memo_index::DenseView nv;
+    const int rc = build_timed(st, &nv.build_ms, [&]() { return build(nv); });
+    if (rc && rc != kNoRoom) return rc;
+    if (rc == kNoRoom || !nv.p3) {
+        ledger = 0;
+        v.backoff = backoff_step(v.backoff);
+        return MEMO_OK;
+    }
+    nv.cap = v.cap;
+    nv.bytes = dense_view_bytes(nv.padded, rpg);
+    nv.state = 1;
+    nv.placed = 1;
+    nv.backoff = v.backoff;  // (not an eviction: the class is as due as it was)
+    nv.ask_after = v.ask_after;
+    if (pass == kPassLiveCopy) {  // not a view of its own: view_builds, view_placings and views_resident stay
+        nv.rows = v.rows;         // (the class's rows: a dead row is answered by a live one that contains it)
+        nv.live = 1;
+        ++ix->view_live_copies;
+    } else {
+        ++ix->view_placings;
+    }
+    retire_view(ix, v, false);
+    v = nv;
+    ix->last_view_ms = v.build_ms;
+    pass_measured(ix, pass, v.build_ms, units);
+    keep_views_in_budget(ix, &v, base_bytes, true);
+    return MEMO_OK;
 }
 
 // The same k-class views for the 4-byte words (formats 4 and 12; what membership queries, k > 64 and indexes of more than 511
@@ -1333,32 +1395,16 @@ int packed_rows_for(memo_index *ix, int km1, int64_t window, bool membership, hi
     const int slot = view_slot(km1, &cap);
     if (slot < 0) return MEMO_OK;
     memo_index::DenseView &v = ix->pviews[slot];
-    if (v.state == 0 && !view_due(ix, v, 1, (double)ix->rows, 1.0 - share_below(ix, cap), window, km1)) return MEMO_OK;
+    if (v.state == 0 && !view_due(ix, v, kPassPackedView, (double)ix->rows, 1.0 - share_below(ix, cap), window, km1)) return MEMO_OK;
     if (v.state == 0) {
-        DeviceGuard guard(ix->device);
-        const int rc = build_timed(ix, v, st, [&]() {
+        const int rc = install_view(ix, v, st, cap, kPassPackedView, (double)ix->rows, 0, ix->rows * 4, [&]() {
             int r = packed_filter(ix->device, ix->pk, ix->boff, ix->rows, ix->nb, cap, 2, st, ix->packed_fmt == 12 ? 0 : 16, &v.p3, &v.boff,
                                   &v.rows, &v.padded);
             // (what the filter leaves of an interleaved bucket is no longer dealt evenly: the view's buckets are ordered again)
             if (!r && v.p3 && ix->row_order) r = interleave_words(v.p3, v.boff, ix->nb, ix->bshift, ix->packed_fmt, ix->row_order, st, ix->d_scratch);
             return r;
         });
-        if (rc && rc != kNoRoom) return rc;  // (no room on the device for a view: the sweep reads all the rows)
-        v.cap = cap;
-        v.bytes = v.padded * 4;
-        v.state = v.p3 ? 1 : (rc == kNoRoom ? 0 : 2);
-        if (rc == kNoRoom) {  // (the pressure may pass: look again, but not with every query)
-            v.lost_ns = 0;
-            v.seen = 0;
-            if (v.backoff < (1 << 16)) v.backoff *= 4;
-            v.ask_after = v.ask_after ? (v.ask_after < (1 << 16) ? v.ask_after * 4 : v.ask_after) : 16;
-        }
-        if (v.state == 1) {
-            ++ix->view_builds;
-            ix->last_view_ms = v.build_ms;
-            view_built(ix, v.build_ms, 1, (double)ix->rows);
-            keep_views_in_budget(ix, &v, ix->rows * 4, false);
-        }
+        if (rc) return rc;
     }
     if (v.state == 1) {
         v.stamp = ++ix->view_clock;
@@ -1404,7 +1450,7 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint
     memo_index::DenseView &v = *vp;
     if (!account) {  // (the same query asking again: what is there, no ledger, no build)
         if (v.state != 1) return MEMO_OK;
-    } else if (v.state == 0 && !view_due(ix, v, 0, src_rows, spared, window, km1)) {
+    } else if (v.state == 0 && !view_due(ix, v, kPassDenseView, src_rows, spared, window, km1)) {
         return MEMO_OK;
     }
     const bool can_place = ix->view_places && g_view_colouring != 0;
@@ -1413,92 +1459,25 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint
     const uint64_t nsrc = *rows;
     const uint64_t base_bytes = dense_groups_for(ix->boff3 ? ix->padded3 : ix->padded) * 16;
     const int rpg_arg = six ? 6 : 5;
+    int rc = MEMO_OK;  // at most one pass a query
     if (v.state == 0) {
-        DeviceGuard guard(ix->device);
         const bool place = can_place && g_prepare_only;  // (asked for: everything at once; a query: first the view)
-        const int rc = build_timed(ix, v, st, [&]() {
+        rc = install_view(ix, v, st, cap, place ? kPassPlaces : kPassDenseView, src_rows, rpg_arg, base_bytes, [&]() {
             return dense_view_build(ix->device, src_p3, src_boff, nsrc, ix->nb, cap, 2, st, rpg_arg, place ? cap : 0, &v.p3, &v.boff, &v.rows,
                                     &v.padded, &v.dead_groups);
         });
-        if (rc && rc != kNoRoom) return rc;  // (no room on the device for a view: the sweep reads all the rows)
-        v.cap = cap;
-        v.bytes = dense_view_bytes(v.padded, rpg_arg);
-        v.state = v.p3 ? 1 : (rc == kNoRoom ? 0 : 2);
-        if (rc == kNoRoom) {
-            v.lost_ns = 0;
-            v.seen = 0;
-            if (v.backoff < (1 << 16)) v.backoff *= 4;
-            v.ask_after = v.ask_after ? (v.ask_after < (1 << 16) ? v.ask_after * 4 : v.ask_after) : 16;
-        }
-        if (v.state == 1) {
-            ++ix->view_builds;
-            v.placed = place ? 1 : 0;
-            if (place) ++ix->view_placings;
-            ix->last_view_ms = v.build_ms;
-            view_built(ix, v.build_ms, place ? 2 : 0, src_rows);
-            keep_views_in_budget(ix, &v, base_bytes, true);
-        }
     } else if (account && v.state == 1 && !v.placed && can_place && places_due(ix, v, src_rows, window, km1, six)) {
-        // the same view again, its rows placed: built beside the one in use (sweeps queued on the caller's other streams may still
-        // read that one), then the class switches over and the old copy waits on the retire list with its tile tables
-        DeviceGuard guard(ix->device);
-        memo_index::DenseView nv;
-        const int rc = build_timed(ix, nv, st, [&]() {
+        rc = replace_view(ix, v, st, kPassPlaces, src_rows, rpg_arg, base_bytes, v.unplaced_ns, [&](memo_index::DenseView &nv) {
             return dense_view_build(ix->device, src_p3, src_boff, nsrc, ix->nb, cap, 0, st, rpg_arg, cap, &nv.p3, &nv.boff, &nv.rows, &nv.padded,
                                     &nv.dead_groups);
         });
-        if (rc && rc != kNoRoom) return rc;
-        if (rc == kNoRoom || !nv.p3) {  // (no room for the second copy: the view stays as it is; look again much later)
-            v.unplaced_ns = 0;
-            if (v.backoff < (1 << 16)) v.backoff *= 4;
-        } else {
-            const int backoff = v.backoff, ask = v.ask_after;
-            retire_view(ix, v, true);
-            v = nv;
-            v.cap = cap;
-            v.bytes = dense_view_bytes(v.padded, rpg_arg);
-            v.state = 1;
-            v.placed = 1;
-            v.backoff = backoff;
-            v.ask_after = ask;
-            ++ix->view_placings;
-            ix->last_view_ms = v.build_ms;
-            view_built(ix, v.build_ms, 2, src_rows);
-            keep_views_in_budget(ix, &v, base_bytes, true);
-        }
     } else if (account && v.state == 1 && v.placed && six && !v.live && v.dead_groups > 0 && ix->view_live && live_due(ix, v, window, km1)) {
-        // the placed view without its dead groups: built beside the one in use like the places, then the class switches over.  Not a
-        // view of its own: view_builds, view_placings and views_resident stay; the tile tables of the flagged view go with it, the
-        // sweep below makes the copy's
-        DeviceGuard guard(ix->device);
-        memo_index::DenseView nv;
-        const uint64_t groups = v.padded / 6;
-        const int rc = build_timed(ix, nv, st, [&]() {
+        // (measured per group of the flagged view; its tile tables go with it, the sweep below makes the copy's)
+        rc = replace_view(ix, v, st, kPassLiveCopy, (double)(v.padded / 6), 6, base_bytes, v.dead_lost_ns, [&](memo_index::DenseView &nv) {
             return live_view_copy(ix->device, v.p3, v.boff, ix->nb, v.padded, v.dead_groups, st, &nv.p3, &nv.boff, &nv.padded);
         });
-        if (rc && rc != kNoRoom) return rc;
-        if (rc == kNoRoom || !nv.p3) {  // (no room for the copy: the flagged view stays; look again much later)
-            v.dead_lost_ns = 0;
-            if (v.backoff < (1 << 16)) v.backoff *= 4;
-        } else {
-            const int backoff = v.backoff, ask = v.ask_after;
-            const uint64_t rows = v.rows;
-            retire_view(ix, v, true);
-            v = nv;
-            v.cap = cap;
-            v.rows = rows;
-            v.bytes = dense_view_bytes(v.padded, 6);
-            v.state = 1;
-            v.placed = 1;
-            v.live = 1;
-            v.backoff = backoff;
-            v.ask_after = ask;
-            ++ix->view_live_copies;
-            ix->last_view_ms = v.build_ms;
-            view_built(ix, v.build_ms, 3, (double)groups);
-            keep_views_in_budget(ix, &v, base_bytes, true);
-        }
     }
+    if (rc) return rc;
     if (v.state == 1) {
         v.stamp = ++ix->view_clock;
         *p3 = v.p3;
