@@ -45,7 +45,7 @@ int memo_debug_row_order(memo_index_t *ix, int32_t order);
  * memo_index_set_option(MEMO_OPT_VIEWS), which also drops the views.) */
 int memo_debug_no_views(memo_index_t *ix, int32_t on);
 /* this THREAD's later builds of a dense k-class view: 0 = the rows keep the order they come in, whoever asks; 1 (the default) = the place
- * of a row inside its 16-byte group may be chosen against LDS bank conflicts (memo_view.hip: view_place_bucket; MEMO_OPT_VIEW_PLACES of
+ * of a row inside its 16-byte group may be chosen against LDS bank conflicts (memo_view_build.hip: view_place_bucket; MEMO_OPT_VIEW_PLACES of
  * the index decides).  Results never depend on it. */
 int memo_debug_view_colouring(int32_t on);
 /* this THREAD's later conservation queries on dense rows: which kind of k-class view they build and read where views of SIX rows per
@@ -53,7 +53,7 @@ int memo_debug_view_colouring(int32_t on);
  * 0 = five always, -1 (the default) = the library's choice (MEMO_OPT_VIEW_ROWS of the index, else six where the view holds enough rows
  * per bucket for the padding of every bucket to whole groups not to matter). */
 int memo_debug_six_views(int32_t on);
-/* placed six-row views of this index copied without their dead groups so far (MEMO_OPT_VIEW_LIVE; memo_view.hip: live_view_copy), and
+/* placed six-row views of this index copied without their dead groups so far (MEMO_OPT_VIEW_LIVE; memo_view_build.hip: live_view_copy), and
  * whether the six-row view of k's class is such a copy: 1, or 0 (not a copy, or no six-row view of that class is resident) */
 int memo_debug_view_live(const memo_index_t *ix, int32_t k, uint64_t *copies);
 /* this THREAD's later calls: every device allocation for a view or a tile table fails (the test of the no-memory path) */

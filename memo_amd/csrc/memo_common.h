@@ -60,6 +60,16 @@ constexpr int kStatusExecNarrow = 4;          // -DMEMO_EXEC_CHECK builds: a bra
 // query order of the 4-byte rows
 enum Pass { kPassDenseView, kPassPackedView, kPassPlaces, kPassLiveCopy, kPassRowOrder, kPasses };
 
+// What a view pass (memo_view_build.hip) hands back, and the part of a DenseView it fills: the view's rows (dense groups, or 4-byte
+// words), its bucket table (nb entries), the rows of the source it holds, the rows its table counts (slots of six-row groups; five-row
+// groups and words: rows rounded up + kPadRows) and, of a six-row view with places, the groups flagged as holding no live row
+// (memo_view_build.hip: kDeadGroup).  p3 == nullptr: nothing built (too few rows would go).
+struct BuiltView {
+    uint32_t *p3 = nullptr;
+    int64_t *boff = nullptr;
+    uint64_t rows = 0, padded = 0, dead_groups = 0;
+};
+
 }  // namespace memo
 
 #define HIP_TRY(expr)                                                                          \
@@ -125,7 +135,7 @@ struct memo_index {
     uint32_t *p3 = nullptr;    // dense rows (memo_index_pack_dense): 16 bytes per 5 rows; annot <= 255 only
     // The dense rows may be FEWER than the index's rows: a row whose 6-bit length field is saturated (overlap >= 63, or
     // end < start) can never write at k <= 64 -- all the dense rows answer -- so when more than a tenth of the rows are
-    // such rows they are left out (dense_compact, memo_index.hip: 40 % of the rows of an index built from sequences,
+    // such rows they are left out (dense_compact, memo_view.hip: 40 % of the rows of an index built from sequences,
     // profiles/r03_realistic_index*.json; none of the synthetic one).  The dense stream then has its own row numbers and
     // its own bucket table; boff3 == nullptr: the dense rows are the index's rows, numbered alike (rows3 == rows).
     int64_t *boff3 = nullptr;
@@ -134,7 +144,7 @@ struct memo_index {
     // query with k - 1 <= 2 / 4 / ... / 32 can be touched by -- with their own bucket table; built by memo_index_prepare, or by the
     // query that finds that its class's queries have by now paid more for the rows a view would have spared them than the view costs
     // (view_due: ski rental), kept within the views' budget (memo_index_set_option: MEMO_OPT_VIEW_BUDGET_PCT)
-    struct DenseView {
+    struct DenseView : memo::BuiltView {
         int cap = 0, state = 0;  // state: 0 not looked at yet, 1 built, 2 not worth it (it would spare less than a fifth)
         double lost_ns = 0;      // what this class's queries since it was last looked at would have saved with the view (estimate)
         int backoff = 1;         // the view is due when lost_ns reaches backoff x its estimated cost: x 4 after every eviction or failed
@@ -142,13 +152,9 @@ struct memo_index {
         int seen = 0;            // queries of the class since it was last looked at ...
         int ask_after = 0;       // ... of which this many must pass before it is looked at again: 0, then 16, 64 ... after evictions (what
                                  //   keeps the back-off alive when MEMO_OPT_BUILD_COST_PCT is 0 and every cost is nothing)
-        int placed = 0;          // dense views: the rows' places inside their groups were chosen against LDS bank conflicts (memo_view.hip):
+        int placed = 0;          // dense views: the rows' places inside their groups were chosen against LDS bank conflicts (memo_view_build.hip):
         double unplaced_ns = 0;  //   a second pass, decided like the first -- what the class's queries on the view as it is have lost to that
-        uint32_t *p3 = nullptr;
-        int64_t *boff = nullptr;
-        uint64_t rows = 0, padded = 0;
-        uint64_t dead_groups = 0;  // six-row views with places: groups flagged as holding no live row (memo_view.hip: kDeadGroup)
-        int live = 0;            // ... 1: the copy of such a view without them (memo_view.hip: live_view_copy; dead_groups 0, padded = 6 x its
+        int live = 0;            // 1: the copy of a placed six-row view without its dead groups (memo_view_build.hip: live_view_copy; dead_groups 0, padded = 6 x its
                                  //   groups, rows still the class's rows: a dead row is answered by a live one that contains it) --
         double dead_lost_ns = 0; //   a third pass, decided like the others: what the queries on the flagged view have lost to its dead groups
         uint64_t bytes = 0;      // of the rows' allocation (set where a view is installed: a six-row view is (groups + 64) x 16 B, not
@@ -170,12 +176,11 @@ struct memo_index {
     uint64_t view_clock = 0;
     uint64_t view_builds = 0;     // views built over the index's lifetime (memo_index_info_t.view_builds)
     DenseView views[16];          // classes of two: overlaps below 2, 4, 6 ... 32
-    DenseView views6[16];         // the same classes as groups of SIX rows that carry their bucket (memo_view.hip; what the table-driven sweep reads where it can)
+    DenseView views6[16];         // the same classes as groups of SIX rows that carry their bucket (memo_view_build.hip; what the table-driven sweep reads where it can)
     DenseView pviews[24];         // the same for the 4-byte words (caps 2 .. 32 by 2, .. 64 by 8, .. 128 by 16; `p3` holds words there): packed_rows_for
     uint64_t last_rows_read = 0;  // rows of the row source the last sweep read (info.last_rows_read)
     float last_view_ms = 0.f;     // device time of the view build, when the last sweep's view was built by it (else 0)
     int last_view_placed = 0, last_view_rpg = 5;  // (memo_index_info_t: of the dense rows the last sweep read)
-    double last_view_dead_share = 0;              // ... the share of its groups flagged dead (the sweep skips them where it pays)
     uint64_t max_annot = 0;    // largest annot of the packed rows
     // Sampled histogram of the packed rows' overlap field (min(end - start, 255)): with it the length n = k - 1 -
     // overlap of a row's interval is known in distribution for any k, which is what the choice between the level
@@ -228,45 +233,24 @@ struct memo_index {
 };
 
 namespace memo {
+// (the k-class views' own declarations: memo_view.h)
 void drop_dense(memo_index *ix);       // frees the dense rows, their bucket table and the tile tables
-int dense_compact(memo_index *ix);     // memo_index.hip: leave the rows that can never write out of the dense rows (see boff3)
-// ... or a k-class view of them (memo_view.hip); window: the query's length (what a view would save this query decides when it is built);
-// allow_six: the caller reads views of six rows per group too (*rpg says which kind it got: 5 or 6); account = false: a query's
-// SECOND call (its six-row view found no tile table): hands back a five-row view that exists, adds nothing to the class's ledgers
-// and builds nothing -- the query has been counted once already
-int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, uint32_t **p3, int64_t **boff, uint64_t *rows,
-                   int *view_cap = nullptr, bool allow_six = false, int *rpg = nullptr, bool account = true);
-extern thread_local int g_six_views;  // (AB library, memo_debug_six_views: -1 the library's choice, 0 five rows per group always, 1 six wherever they apply)
-constexpr int kNoRoom = 1;  // (internal) the device has no memory for a view / tile table: run without it
 constexpr size_t kMaxTileTables = 64;
-void retire(memo_index *ix, void *p, uint64_t bytes);  // memo_index.hip: out of service now, freed once the device has drained
-void flush_retired(memo_index *ix);                    // ... which the caller guarantees (it synchronised the device)
 int builder_why(const memo_builder_t *b);  // memo_hostpack.hip: which rows a builder refused with MEMO_EUNPACKABLE (BlockResult::bad bits)
-extern thread_local bool g_dense_keep_all;  // (AB library, memo_debug_dense_keep_all: dense_compact keeps every row)
-extern thread_local int g_one_shot_way;     // (AB library, memo_debug_one_shot_way: 1 = int64 columns, 2 = 4-byte words)
-extern thread_local bool g_prepare_only;  // memo_index_prepare: the query path builds what it would build and launches nothing
+extern thread_local int g_one_shot_way;     // memo_index.hip (AB library, memo_debug_one_shot_way: 1 = int64 columns, 2 = 4-byte words)
+extern thread_local bool g_prepare_only;  // memo_sweep.hip; memo_index_prepare: the query path builds what it would build and launches nothing
 // ... and hands this as the result pointer: a launch site that missed g_prepare_only refuses it instead of writing to it (launch_tiles,
 // launch_halo3t, the fill and long-row launches: memo_sweep.hip: refuse_plan_pointer)
 static void *const kNeverWritten = reinterpret_cast<void *>(uintptr_t(4096));
 int refuse_plan_pointer(const void *d_out);
-extern thread_local bool g_side_alloc_fails;  // (AB library, memo_debug_fail_side_allocations: every side_alloc fails -- the test of kNoRoom)
-hipError_t side_alloc(void **p, size_t bytes);
-void drop_dense_views(memo_index *ix);
-int packed_rows_for(memo_index *ix, int km1, int64_t window, bool membership, hipStream_t st, uint32_t **pk, int64_t **boff, uint64_t *rows);  // k-class view of the words (+ their order)
-void drop_packed_views(memo_index *ix);
-inline uint64_t dense_view_bytes(uint64_t padded, int rows_per_group) {  // what dense_view_build allocates for a view's rows
-    return (rows_per_group == 6 ? padded / 6 + 64 : (padded + 4) / 5 + 64) * 16;
-}
 inline uint64_t dense_groups_for(uint64_t padded) { return (padded + 4) / 5 + 64; }  // (+ one wave-load of slack: a wave reads its 64 groups whole)
 void drop_tile_tables(memo_index *ix);  // memo_sweep_cons3t.hip: the tables derive from the dense rows and the bucket table
 // memo_interleave.hip: reorder the 4-byte rows inside every bucket (mode 0: start order, 1: chunks of four dealt round-robin
 // over the bucket's starts, 2: the same with the rows of a start ordered by overlap mod 32), in place, queued on st
 int interleave_words(uint32_t *words, const int64_t *boff, uint64_t nb, int bshift, int fmt, int mode, hipStream_t st, uint64_t *scratch);  // scratch: ix->d_scratch
-extern thread_local int g_view_colouring;  // 1: the dense rows' k-class views may get their rows' places inside a group chosen against bank conflicts (memo_debug_view_colouring of the AB library turns it off)
 constexpr int kRowOrderDefault = 2;  // interleave_words mode the product applies wherever 4-byte rows come into being
-int order_words_now(memo_index *ix, int mode);  // memo_index.hip: waits for the device, orders ix->pk in place, waits again
 inline int row_order_mode(const memo_index *ix) { return ix->tune.row_order ? ix->tune.row_order - 1 : kRowOrderDefault; }
-extern thread_local int g_last_one_shot_sweep;  // which kernel family answered this thread's last one-shot call
+extern thread_local int g_last_one_shot_sweep;  // memo_index.hip: which kernel family answered this thread's last one-shot call
 }
 
 // fills ix->len_hist from the resident 4- / 6-byte rows (a few thousand 1024-row blocks, evenly spread); NULL stream, synchronous

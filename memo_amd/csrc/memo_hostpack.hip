@@ -5,7 +5,7 @@
 // knows nothing of HIP and therefore also runs under the CPU sanitizers (tests/test_host_sanitizers.py).
 #include <new>
 
-#include "memo_common.h"
+#include "memo_view.h"
 #include "memo_cpus.h"
 #include "memo_hostcore.h"
 

@@ -9,7 +9,7 @@
 #include <cstddef>
 #include <new>
 
-#include "memo_common.h"
+#include "memo_view.h"
 #include "memo_hostcore.h"
 
 using namespace memo;
@@ -28,6 +28,7 @@ void drop_dense(memo_index *ix) {
 
 namespace memo {
 thread_local int g_last_one_shot_sweep = 0;  // memo_index_info_t.last_sweep of this thread's last one-shot call (memo_debug.hip)
+thread_local int g_one_shot_way = 0;         // which way in one_shot() takes (AB library, memo_debug_one_shot_way: 1 = int64 columns, 2 = 4-byte words)
 }
 
 extern "C" __attribute__((visibility("hidden"))) int memo_sort_rows_by_start(int64_t *s, int64_t *e, int64_t *o, uint64_t rows,

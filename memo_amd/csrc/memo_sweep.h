@@ -5,7 +5,7 @@
 
 #include <type_traits>
 
-#include "memo_common.h"
+#include "memo_view.h"
 
 namespace memo {
 
@@ -624,13 +624,12 @@ void fill_args(const memo_index *ix, SweepArgs &A, int64_t qs, int64_t qe, int32
 static inline int use_words(memo_index *ix, SweepArgs &A, int fmt, bool membership, hipStream_t st) {
     ix->last_rows_read = ix->rows;  // (6-byte rows and the int64 columns have no views)
     if (fmt != 4 && fmt != 12) return MEMO_OK;
-    uint32_t *vpk = nullptr;
-    int64_t *vboff = nullptr;
-    uint64_t vrows = 0;
-    if (int rc = packed_rows_for(ix, A.km1, A.qe - A.qs, membership, st, &vpk, &vboff, &vrows)) return rc;
-    A.pk = vpk;
-    A.boff = vboff;
-    ix->last_rows_read = vrows;
+    RowSource src;
+    if (int rc = packed_rows_for(ix, A.km1, A.qe - A.qs, membership, st, src)) return rc;
+    A.pk = src.p3;
+    A.boff = src.boff;
+    ix->last_rows_read = src.rows;  // (last_view_placed / last_view_rpg speak of dense rows: they stay)
+    ix->last_view_ms = src.build_ms;
     return MEMO_OK;
 }
 

@@ -65,17 +65,15 @@ int launch_tiles(SweepKernel kernel, SweepArgs &A, int w, int threads, size_t ld
     return MEMO_OK;
 }
 
-// which row source a query reads: packed when the index has it and k - 1 <= 255, else the int64 columns.
-// fmt: 0 = int64 columns, 4 / 6 = packed words (+ 16-bit order column), 3 = only the dense rows are left
-// (memo_index_pack_dense dropped the words): k - 1 <= 63, and only kernels that read PackedRows3
+// memo_index_prepare: the query path builds what it would build and launches nothing (memo_common.h) ...
 thread_local bool g_prepare_only = false;
 int refuse_plan_pointer(const void *d_out) {  // (a launch must never see memo_index_prepare's stand-in for a result)
     return d_out == kNeverWritten ? fail(MEMO_EHIP, "internal: a sweep was about to be launched into memo_index_prepare's placeholder result") : MEMO_OK;
 }
-thread_local bool g_side_alloc_fails = false;
-thread_local int g_view_colouring = 1;
-thread_local int g_six_views = -1;
 
+// which row source a query reads: packed when the index has it and k - 1 <= 255, else the int64 columns.
+// fmt: 0 = int64 columns, 4 / 6 = packed words (+ 16-bit order column), 3 = only the dense rows are left
+// (memo_index_pack_dense dropped the words): k - 1 <= 63, and only kernels that read PackedRows3
 int pick_rows(const memo_index *ix, int32_t k, int &fmt) {
     fmt = 0;
     if (ix->packed_fmt && k - 1 <= 255 && !(ix->tune.force_wide && ix->has_wide)) fmt = ix->pk ? ix->packed_fmt : 0;

@@ -1049,29 +1049,26 @@ static int sweep_dense_rows(memo_index *ix, SweepArgs &A, int tw, int elem_bytes
                             int *variant) {
     const memo_tuning &tune = ix->tune;
     const bool table = tune.persistent == 5 || tune.persistent == 0;
-    int view_cap = 0;  // (a view whose cap is k - 1 holds exactly the rows that write at this k: the table-driven kernel's row blocks drop their test)
-    int rpg = 5;       // rows per 16-byte group of the source handed out: 5, or 6 (a view whose groups carry their bucket: memo_view.hip)
     *variant = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool can_six = attempt == 0 && table && top8 && A.nlev <= 5 && A.qs >= 0;
-        uint32_t *vp3 = nullptr;
-        int64_t *vboff = nullptr;
-        uint64_t vrows = 0;
-        if (int rc = dense_rows_for(ix, A.km1, A.qe - A.qs, st, &vp3, &vboff, &vrows, &view_cap, can_six, &rpg, attempt == 0)) return rc;
-        A.p3 = vp3;
-        A.boff = vboff;
-        ix->last_rows_read = vrows;
+        RowSource src;  // (memo_view.h; rpg 6: a view whose groups carry their bucket)
+        if (int rc = dense_rows_for(ix, A.km1, A.qe - A.qs, st, src, can_six, attempt == 0)) return rc;
+        A.p3 = src.p3;
+        A.boff = src.boff;
+        note_dense_rows_read(ix, src);
         if (table) {
             // the tile's row slice from a table built once per (index, k): memo_sweep_cons3t.hip; 1 = does not fit
-            const int trc = launch_halo3t(ix, A, tw, elem_bytes, st, top9, view_cap == A.km1 && !tune.no_all_write, rpg == 6,
-                                          rpg == 6 && ix->last_view_placed && ix->last_view_dead_share >= kLiveMinShare);
+            // (a view whose cap is k - 1 holds exactly the rows that write at this k: the table-driven kernel's row blocks drop their test)
+            const int trc = launch_halo3t(ix, A, tw, elem_bytes, st, top9, src.cap == A.km1 && !tune.no_all_write, src.rpg == 6,
+                                          src.rpg == 6 && src.placed && src.dead_share >= kLiveMinShare);
             if (trc < 0) return trc;
             if (trc == MEMO_OK) {
-                *variant = rpg == 6 ? 3 : 2;
+                *variant = src.rpg == 6 ? 3 : 2;
                 return MEMO_OK;
             }
         }
-        if (rpg != 6) return MEMO_OK;  // (five-row groups: the kernel without a table takes them)
+        if (src.rpg != 6) return MEMO_OK;  // (five-row groups: the kernel without a table takes them)
     }
     return fail(MEMO_EHIP, "a six-row view reached a sweep that cannot read it");
 }

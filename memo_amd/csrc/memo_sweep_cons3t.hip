@@ -60,7 +60,7 @@ __global__ void tile_table_kernel(const int64_t *boff, int64_t nb, int64_t bbase
 // T = 256: four waves per tile (eight tiles = 32 waves per CU), the only form instantiated (T = 128 lost: see the launcher)
 // A9: an index of 256 .. 511 genomes -- the order in the top NINE bits of a level cell (memo_sweep_dense.h: MEMO_ROW9_AT), uint16 results
 // AW: the row source is a k-class view whose cap is this k - 1 -- every row of it writes, the row blocks carry no test (memo_sweep_dense.h)
-// SIX: the row source is a k-class view in groups of six rows that carry their bucket (memo_view.hip: view_build_kernel<6>; the
+// SIX: the row source is a k-class view in groups of six rows that carry their bucket (memo_view_build.hip: view_build_kernel<6>; the
 // library's choice of view where it applies: -2.3 % at k = 31 against five-row views, profiles/r05_view_pass.txt)
 // SP: a row source of few rows per tile (under ~3/4 of the 1024 groups a batch of loads covers: the k-class views of config 3, every
 // sequence-built index) -- a piece past the tile's slice issues NO load (a wave-uniform branch).  Rounds 3-5 issued all four loads of a
@@ -70,7 +70,7 @@ __global__ void tile_table_kernel(const int64_t *boff, int64_t nb, int64_t bbase
 // k = 21 -3.4 %, k = 17 -4.5 %, k = 9 -6 % on config 3's views.  Not for tiles of several full batches (config 5: +2 ... +6 %:
 // behind the branches the compiler waits for ALL of a batch's loads before its first piece), hence a template flag the
 // launcher sets from the rows per tile (profiles/r06_headline.txt; masking the dead loads off with EXEC = 0 instead gained nothing).
-// LIVE (SIX only): the view's groups say which of them hold no live row (memo_view.hip: view_live_kernel) -- a dead group's lane
+// LIVE (SIX only): the view's groups say which of them hold no live row (memo_view_build.hip: view_live_kernel) -- a dead group's lane
 // sits out its rows' atomics, a piece without a live group is skipped (memo_sweep_dense.h: live_pieces)
 // R4 (SIX, not LIVE, k - 1 in [16, 31]): radix-4 level arrays -- blocks of 16, 4 and 1 -- of kLS4 = 1664 cells in place of the five
 // doubling arrays of 1024: the same 20 KiB per tile (eight tiles per CU), 1.69x the positions per tile at k = 31 (memo_sweep_dense.h:

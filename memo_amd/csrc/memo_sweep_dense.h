@@ -223,7 +223,7 @@ __device__ __forceinline__ void group_rows(const uint4 &V, const RowConst &C, ui
     }
 }
 
-// ---- groups of SIX rows that carry their bucket (memo_view.hip: view_build_kernel<6>, pack_six) ---------------------------------
+// ---- groups of SIX rows that carry their bucket (memo_view_build.hip: view_build_kernel<6>, pack_six) ---------------------------------
 // A row's ten bits (start mod 32 | overlap << 5) are the low bits of LO, its ds_min operand D has its annot on top; BIAS = the level
 // arrays' bias + 4 * the cell of the group's bucket.  operands: %0-%3 temporaries; %4-%9 LO of rows 0 .. 5; %10-%15 their D;
 // %16 BIAS; %17 km1 (SGPR), %18 ls4 (SGPR), %19 top_bit; masked form: %20 the lane's group number, %21 groups left (SGPR)
@@ -292,7 +292,7 @@ __device__ __forceinline__ void six_pieces(const uint4 (&V)[NL], int lane, int w
     }
 }
 
-// ---- LIVE: views whose groups say which of them hold no live row (memo_view.hip: view_live_kernel, kDeadGroup) -----------------
+// ---- LIVE: views whose groups say which of them hold no live row (memo_view_build.hip: view_live_kernel, kDeadGroup) -----------------
 // A view row that a row of lower order contains at every k never decides a minimum; the view builder puts a bucket's live rows
 // in its first groups and sets kDeadGroup in the first dword of every group without one (most of config 3's at k = 31).
 // The loads stay as they are (the bytes a sweep reads do not change); a dead group's lane sits out its rows' two atomics each, which

@@ -645,13 +645,11 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
 
     // -- the rows (once per query: every slice of genome words reads the same rows), the launches, the record
     if (dense) {  // the dense rows of this k's class (a view that leaves out the rows that cannot write at this k), or all of them
-        uint32_t *vp3 = nullptr;
-        int64_t *vboff = nullptr;
-        uint64_t vrows = 0;
-        if ((rc = dense_rows_for(ix, km1, len, st, &vp3, &vboff, &vrows))) return rc;
-        A.p3 = vp3;
-        A.boff = vboff;
-        ix->last_rows_read = vrows;
+        RowSource src;
+        if ((rc = dense_rows_for(ix, km1, len, st, src))) return rc;
+        A.p3 = src.p3;
+        A.boff = src.boff;
+        note_dense_rows_read(ix, src);
     } else if ((rc = use_words(ix, A, fmt, true, st))) {
         return rc;
     }

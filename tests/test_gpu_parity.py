@@ -2140,7 +2140,7 @@ def test_row_order_inside_buckets_never_changes_a_result(memo, oracle, ab):
 
 
 def test_places_inside_a_dense_group_never_change_a_result(memo, oracle, ab):
-    """memo_view.hip, view_place_bucket: the rows of a dense k-class view get their place inside their 16-byte group (and
+    """memo_view_build.hip, view_place_bucket: the rows of a dense k-class view get their place inside their 16-byte group (and
     their group inside the bucket) chosen against LDS bank conflicts.  Views built with and without it, on a ragged index
     with empty stretches, a few buckets above the kernel's 128-row limit and windows that begin inside a bucket: the same rows
     read, results equal to the oracle and to each other, every k of every class of two."""
@@ -2259,7 +2259,7 @@ def _lds_cycles(rows_w, km1, rpg):
 
 
 def test_dense_views_as_the_fused_pass_builds_them(memo, oracle, ab):
-    """memo_view.hip (round 5): a dense k-class view is built by count -> scan -> ONE fused pass (compaction, the places of the rows
+    """memo_view_build.hip (round 5): a dense k-class view is built by count -> scan -> ONE fused pass (compaction, the places of the rows
     inside their groups, packing) instead of round 4's five kernels.  (1) Rows in the order they come: the exported bytes equal a NumPy
     twin's -- views of five rows per group and of six, the dense rows with the never-writing rows left out (dense_compact: the same pass),
     eight- and nine-bit annots, on a ragged index with empty stretches, buckets above the placing limits (96 / 128 rows) and one bucket
@@ -2453,7 +2453,7 @@ def test_dense_rows_of_256_to_511_genomes(memo, oracle, ab):
 
 
 def test_six_row_views_equal_five_row_views(memo, oracle, ab):
-    """The dense k-class views as groups of SIX rows that carry their bucket (memo_view.hip: view_build_kernel<6>; 2.67 B per row;
+    """The dense k-class views as groups of SIX rows that carry their bucket (memo_view_build.hip: view_build_kernel<6>; 2.67 B per row;
     the library's own choice where they apply since round 5) on the table-driven kernel's form for them (info.last_variant 3),
     forced on and off through memo_debug_six_views of the A/B library so that BOTH kinds answer every case.  Ragged index with an empty stretch and a bucket above the builder's 96-row limit, every k class it takes
     (k - 1 <= 31), windows that begin inside a bucket, both result types: equal to the oracle and to the five-row views."""

@@ -1,4 +1,4 @@
-"""Dead rows of placed six-row views (memo_view.hip: view_live_kernel) and the sweep that skips the groups holding none that live
+"""Dead rows of placed six-row views (memo_view_build.hip: view_live_kernel) and the sweep that skips the groups holding none that live
 (memo_sweep_cons3t.hip: LIVE).  A view row (s, ov, order) covers [s + ov - (k - 1), s) at every k; a row of strictly lower order
 with s_a >= s_b and s_a + ov_a <= s_b + ov_b contains it at every k, so it never decides a minimum.  The view keeps every row (the
 bytes a sweep reads do not change); a group of six slots without a live row carries kDeadGroup (bit 20 of its first dword)."""

@@ -1,4 +1,4 @@
-"""Placed six-row views without their dead groups (memo_view.hip: live_view_copy).  The placing pass flags every group of a placed
+"""Placed six-row views without their dead groups (memo_view_build.hip: live_view_copy).  The placing pass flags every group of a placed
 six-row view that holds no live row (kDeadGroup, bit 20 of its first dword; tests/test_live_rows.py); once a class's queries have lost
 to loading those groups what a pass over the view costs, a query copies the view without them -- the unflagged groups unchanged, in
 the order they come, with a bucket table of their own -- and the class switches over (MEMO_OPT_VIEW_LIVE, option 6)."""

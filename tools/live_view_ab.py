@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the sweep on config 3's placed six-row k-class view: the copy without dead groups (MEMO_OPT_VIEW_LIVE 1, memo_view.hip:
+"""A/B of the sweep on config 3's placed six-row k-class view: the copy without dead groups (MEMO_OPT_VIEW_LIVE 1, memo_view_build.hip:
 live_view_copy) against the flagged view swept with LIVE (MEMO_OPT_VIEW_LIVE 0).  Per round, variant and k: the views are dropped,
 memo_index_prepare builds the placed view, and the live variant's copy is built by the queries that pay for it under the default
 ledger (counted: `queries_to_copy`; the pass's device time: `copy_ms`).  Then `--launches` launches back to back, each between a HIP

@@ -5,7 +5,7 @@ profiles/r04_lds_atomics.txt (a half-wave's 32 ds_min take max(2, lanes on the f
 
   current      the 4-byte rows' interleaved order (memo_interleave.hip, mode 2), filtered
   coloured     round 4's colour_view_kernel (rows taken by A mod 32, one of five places chosen greedily, laid down in that order);
-               round 5 (memo_view.hip: view_place_bucket) takes the rows in the order they come: 5.76 against 5.53 by this model
+               round 5 (memo_view_build.hip: view_place_bucket) takes the rows in the order they come: 5.76 against 5.53 by this model
 
 Anywhere (numpy only).  Prints cycles per row instruction and half-wave: first block, second block; at four alignments of the tile's
 first group.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Round 5: what building a dense k-class view costs (memo_index_prepare -> info.last_view_ms: HIP events around the whole pass on its
-stream, allocations and the two host waits included), round 4's five kernels against the fused pass of memo_view.hip, views of five
+stream, allocations and the two host waits included), round 4's five kernels against the fused pass of memo_view_build.hip, views of five
 and of six rows per group.  BASELINE config 3 (or --workload c5: 500 genomes, nine-bit annots).  GPU box; A/B library."""
 import argparse
 import json

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Round 5: the conservation sweep on a dense k-class view as memo_view.hip builds it: five and six rows per group, rows placed and
+"""Round 5: the conservation sweep on a dense k-class view as memo_view_build.hip builds it: five and six rows per group, rows placed and
 not.  (With round 4's builder still in the tree -- places chosen after a sort by the first block's bank -- its views measured 0.6 %
 faster at k = 31 than the fused pass's placed ones, level at k = 21: profiles/r05_view_pass.txt.)  One index per variant,
 `--launches` launches back to back, median of the last two thirds; variants alternate `--reps` times.  GPU box; A/B library."""
