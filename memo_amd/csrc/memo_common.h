@@ -47,6 +47,29 @@ struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the cur
     }
 };
 
+// The one owner of one hipMalloc allocation: freed when it is reset or goes (the caller has the index's device selected), and read
+// as the T * it holds, so that launch sites pass it as they passed the pointer.  Not an allocator and not a base class.
+template <typename T>
+struct DevPtr {
+    T *p = nullptr;
+    DevPtr() = default;
+    DevPtr(DevPtr &&b) noexcept : p(b.release()) {}
+    DevPtr &operator=(DevPtr &&b) noexcept { return adopt(b.release()), *this; }
+    ~DevPtr() { reset(); }
+    operator T *() const { return p; }
+    hipError_t alloc(size_t n) { return reset(), hipMalloc(&p, n * sizeof(T)); }
+    void reset() { adopt(nullptr); }
+    void adopt(T *q) {  // q: from hipMalloc, owned by nobody else
+        if (p) (void)hipFree(p);
+        p = q;
+    }
+    T *release() {  // the caller owns it now (the retire list: memo_view.hip)
+        T *q = p;
+        p = nullptr;
+        return q;
+    }
+};
+
 constexpr uint64_t kPadRows = 4096;           // sentinel rows behind the last real row
 constexpr int64_t kSentinel = INT64_MAX / 4;  // start/end of a padding row: clips to "empty"
 constexpr int kDefaultBucketShift = 5;        // 32 pivot positions per bucket
@@ -108,8 +131,8 @@ struct memo_index {
     memo_tuning tune;
     uint64_t rows = 0;
     uint64_t padded = 0;
-    int64_t *s = nullptr, *e = nullptr, *o = nullptr;
-    int64_t *boff = nullptr;  // boff[b] = first row with start >= (b << bshift); boff[nb-1] == rows
+    memo::DevPtr<int64_t> s, e, o;
+    memo::DevPtr<int64_t> boff;  // boff[b] = first row with start >= (b << bshift); boff[nb-1] == rows
     uint64_t nb = 0;
     int bshift = 0;
     int64_t bbase = 0;        // boff[0] belongs to bucket `bbase` (a region slice imported from the CLI's cache; else 0)
@@ -117,8 +140,8 @@ struct memo_index {
     int finalized = 0;
     int was_sorted = 0;
     // packed rows (memo_index_pack): one word per row, layout by the largest annot (PackedRows, memo_sweep.h)
-    uint32_t *pk = nullptr;
-    uint16_t *pa = nullptr;    // format 6 only: 16-bit annot per row (the word's top byte is 0)
+    memo::DevPtr<uint32_t> pk;
+    memo::DevPtr<uint16_t> pa;  // format 6 only: 16-bit annot per row (the word's top byte is 0)
     int packed_fmt = 0;        // 0 = none, 4 = word with 8-bit annot, 12 = word with 12-bit annot and 12-bit start,
                                //   6 = word + 16-bit annot column
     uint64_t packed_rows = 0;  // rows the pk (pa) allocation holds (reused by the next memo_index_pack)
@@ -132,13 +155,13 @@ struct memo_index {
     double order_lost_ns = 0;    // what the queries so far would have saved on rows in the query order (estimate)
     int order_backoff = 1;       // (x 4 after an ordering that found no room for its second copy)
     float pack_ms = 0.f;       // device time of the last memo_index_pack (census + packing kernel)
-    uint32_t *p3 = nullptr;    // dense rows (memo_index_pack_dense): 16 bytes per 5 rows; annot <= 255 only
+    memo::DevPtr<uint32_t> p3;  // dense rows (memo_index_pack_dense): 16 bytes per 5 rows; annot <= 255 only
     // The dense rows may be FEWER than the index's rows: a row whose 6-bit length field is saturated (overlap >= 63, or
     // end < start) can never write at k <= 64 -- all the dense rows answer -- so when more than a tenth of the rows are
     // such rows they are left out (dense_compact, memo_view.hip: 40 % of the rows of an index built from sequences,
     // profiles/r03_realistic_index*.json; none of the synthetic one).  The dense stream then has its own row numbers and
     // its own bucket table; boff3 == nullptr: the dense rows are the index's rows, numbered alike (rows3 == rows).
-    int64_t *boff3 = nullptr;
+    memo::DevPtr<int64_t> boff3;
     uint64_t rows3 = 0, padded3 = 0;
     // k-class views of the dense rows (dense_rows_for, memo_view.hip): the rows whose overlap is below 2 / 4 / ... / 32 -- all a
     // query with k - 1 <= 2 / 4 / ... / 32 can be touched by -- with their own bucket table; built by memo_index_prepare, or by the
@@ -221,23 +244,46 @@ struct memo_index {
     int has_wide = 1;          // the three int64 columns are still resident
     // rows with end < start (never written by the reference's index builder, but legal input to
     // memo_query.py): copied aside at finalize and applied by long_rows_kernel after each sweep
-    int64_t *ls = nullptr, *le = nullptr, *lo = nullptr;
-    uint64_t n_long = 0;
+    struct LongRows {
+        memo::DevPtr<int64_t> cols;  // one allocation of [3 n]: the starts, the ends, the annots
+        uint64_t n = 0;
+        const int64_t *s() const { return cols; }
+        const int64_t *e() const { return cols + n; }
+        const int64_t *o() const { return cols + 2 * n; }
+        hipError_t set(const int64_t *host, uint64_t rows, hipStream_t st);  // from host columns [3 rows] (read until st has been waited for)
+        int collect(const memo_index *ix, uint64_t found, hipStream_t st);  // the `found` such rows of ix's int64 columns (memo_index_finalize); waits for st
+        int download(int device, int64_t *host) const;                      // to the [3 n] layout of the exports
+    } long_rows;
     // memo_multi.hip (resident form) sweeps a SUB-window of the caller's window on this index.  A row with end < start
     // can reach any distance left of its start, so it has to pass the reference's filter (memo_query.py:25-27) on the
     // WHOLE window, not on the sub-window: while whole_set, the long-row kernels filter by [whole_qs, whole_qe).
     int64_t whole_qs = 0, whole_qe = 0;
     int whole_set = 0;
-    int *d_status = nullptr;   // sticky flags set by the sweep kernels
-    uint64_t *d_scratch = nullptr;  // finalize(): [0] unsorted pairs, [1] rows with end < start
+    memo::DevPtr<int> d_status;  // sticky flags set by the sweep kernels
+    memo::DevPtr<uint64_t> d_scratch;  // finalize(): [0] unsorted pairs, [1] rows with end < start
 };
 
 namespace memo {
 // (the k-class views' own declarations: memo_view.h)
-void drop_dense(memo_index *ix);       // frees the dense rows, their bucket table and the tile tables
+// What derives from what in an index, in this order: the 4-byte words (+ annot column) are made from the int64 columns and the
+// bucket table, the dense rows (+ their own table) from the words, and of each of the two a query makes k-class views, of the dense
+// rows and their views tile tables.  rows_changed (memo_index.hip) is the one place that says what a change at a level makes stale:
+// everything BELOW it goes, and the state words that describe it are reset -- kLevelColumns: the rows themselves (finalized = 0; the
+// words, packed_fmt = 0, packed_rows = 0; and on); kLevelWords: the words are about to be rewritten (the dense rows, rows3 = padded3
+// = 0, every view and tile table; packed_fmt = 0); kLevelDense: the dense rows are replaced (their views, every tile table; the
+// words and their views stay); kLevelDerived: every view, with the tile tables made for it.  keep_word_buffers: the pk / pa
+// allocations and packed_rows stay for the next memo_index_pack.  The caller has the index's device selected.
+enum Level { kLevelColumns, kLevelWords, kLevelDense, kLevelDerived };
+void rows_changed(memo_index *ix, Level at, bool keep_word_buffers = false);
+int need_wide(const memo_index *ix);  // MEMO_OK, or the refusal of an index whose int64 columns memo_index_pack dropped
+int device_ok(int device);            // MEMO_OK, or the refusal of a device number that is not among the visible ones
+inline uint64_t padded_for(uint64_t rows) { return ((rows + 15) & ~(uint64_t)15) + kPadRows; }
+// The one birth of an index (memo_index.hip): an empty one of `rows` rows on a checked device, with its status and scratch words; the
+// status word's clear is queued on st (the builder's ring stream, which it waits for with its copies), st == nullptr: done on return
+int new_index(uint64_t rows, int device, hipStream_t st, memo_index **out);
 constexpr size_t kMaxTileTables = 64;
 int builder_why(const memo_builder_t *b);  // memo_hostpack.hip: which rows a builder refused with MEMO_EUNPACKABLE (BlockResult::bad bits)
-extern thread_local int g_one_shot_way;     // memo_index.hip (AB library, memo_debug_one_shot_way: 1 = int64 columns, 2 = 4-byte words)
+extern thread_local int g_one_shot_way;     // memo_oneshot.hip (AB library, memo_debug_one_shot_way: 1 = int64 columns, 2 = 4-byte words)
 extern thread_local bool g_prepare_only;  // memo_sweep.hip; memo_index_prepare: the query path builds what it would build and launches nothing
 // ... and hands this as the result pointer: a launch site that missed g_prepare_only refuses it instead of writing to it (launch_tiles,
 // launch_halo3t, the fill and long-row launches: memo_sweep.hip: refuse_plan_pointer)
@@ -250,7 +296,7 @@ void drop_tile_tables(memo_index *ix);  // memo_sweep_cons3t.hip: the tables der
 int interleave_words(uint32_t *words, const int64_t *boff, uint64_t nb, int bshift, int fmt, int mode, hipStream_t st, uint64_t *scratch);  // scratch: ix->d_scratch
 constexpr int kRowOrderDefault = 2;  // interleave_words mode the product applies wherever 4-byte rows come into being
 inline int row_order_mode(const memo_index *ix) { return ix->tune.row_order ? ix->tune.row_order - 1 : kRowOrderDefault; }
-extern thread_local int g_last_one_shot_sweep;  // memo_index.hip: which kernel family answered this thread's last one-shot call
+extern thread_local int g_last_one_shot_sweep;  // memo_oneshot.hip: which kernel family answered this thread's last one-shot call
 }
 
 // fills ix->len_hist from the resident 4- / 6-byte rows (a few thousand 1024-row blocks, evenly spread); NULL stream, synchronous

@@ -108,11 +108,11 @@ int memo_debug_one_shot_way(int32_t way) {
 
 int memo_debug_stream_rows(memo_index_t *ix, void *stream) {
     if (!ix) return fail(MEMO_EINVAL, "index is NULL");
-    if (!ix->has_wide) return fail(MEMO_EINVAL, "the int64 columns were dropped");
+    if (int rc = need_wide(ix)) return rc;
     DeviceGuard guard(ix->device);
     hipLaunchKernelGGL(stream_rows_kernel, dim3(256 * 8), dim3(256), 0, static_cast<hipStream_t>(stream),
                        ix->s, ix->e, ix->o, ix->rows & ~(uint64_t)1,
-                       reinterpret_cast<unsigned long long *>(ix->d_scratch));
+                       reinterpret_cast<unsigned long long *>(ix->d_scratch.p));
     HIP_TRY(hipGetLastError());
     return MEMO_OK;
 }

@@ -1,6 +1,6 @@
 // memo_hostpack.hip -- the fast way in for HOST rows, device side: the HIP implementation of the seam the host core
 // is written against (memo_hostcore.h: pinned memory, copy stream, events), the builder's create / finish (device
-// allocations, the index it hands over) and the export / import of packed and dense rows (the CLI's sidecar cache).
+// allocations, the index it hands over -- born in memo_index.hip: new_index) and the export / import of packed and dense rows (the CLI's sidecar cache).
 // The threaded host code -- worker pool, pinned ring, the row packers, the push loop -- is memo_hostcore.cpp, which
 // knows nothing of HIP and therefore also runs under the CPU sanitizers (tests/test_host_sanitizers.py).
 #include <new>
@@ -115,9 +115,7 @@ int memo_builder_create_rows(uint64_t max_rows, int32_t device, int32_t bucket_s
         return fail(MEMO_EINVAL, "row_format must be MEMO_ROWS_PACKED (0) or MEMO_ROWS_DENSE (1)");
     if (bucket_shift <= 0) bucket_shift = kDefaultBucketShift;
     if (bucket_shift > 8) return fail(MEMO_EINVAL, "bucket_shift must be <= 8 (tile width 256)");
-    const int ndev = memo_device_count();
-    if (device < 0 || device >= ndev)
-        return fail(MEMO_EHIP, "HIP device %d not available (%d visible)", device, ndev);
+    if (int rc = device_ok(device)) return rc;
     DeviceGuard guard(device);
     if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
     memo_builder *b = new (std::nothrow) memo_builder();
@@ -126,7 +124,7 @@ int memo_builder_create_rows(uint64_t max_rows, int32_t device, int32_t bucket_s
     b->bshift = bucket_shift;
     b->cap = max_rows;
     b->dense = row_format == MEMO_ROWS_DENSE;
-    b->padded = ((max_rows + 15) & ~(uint64_t)15) + kPadRows;
+    b->padded = padded_for(max_rows);
     b->d_groups = b->dense ? dense_groups_for(b->padded) : 0;
     const size_t bytes = b->dense ? (size_t)b->d_groups * 16 : (size_t)b->padded * sizeof(uint32_t);
     hipError_t err = hipMalloc(&b->d_pk, bytes);
@@ -187,11 +185,10 @@ int memo_builder_finish(memo_builder_t *b, memo_index_t **out) {
     if (b->failed) return fail(b->failed, "the builder already failed");
     DeviceGuard guard(b->device);
     if (int rc = builder_flush_core(b)) return rc;
-    memo_index *ix = new (std::nothrow) memo_index();
-    if (!ix) return fail(MEMO_EHIP, "out of host memory");
-    ix->device = b->device;
-    ix->rows = b->rows;
-    ix->padded = b->padded;
+    hipStream_t st = static_cast<hipStream_t>(b->ring->stream);  // (everything below is queued on the ring stream and waited for once)
+    memo_index *ix = nullptr;
+    if (int rc = new_index(b->rows, b->device, st, &ix)) return rc;
+    ix->padded = b->padded;  // (of the builder's capacity: the allocation it hands over)
     ix->packed_rows = b->dense ? 0 : b->padded;
     ix->has_wide = 0;
     ix->was_sorted = 1;
@@ -204,57 +201,32 @@ int memo_builder_finish(memo_builder_t *b, memo_index_t **out) {
     const uint64_t nb = (uint64_t)((top >> b->bshift) + 3);
     if (b->boff.size() < nb) b->boff.resize(nb);
     for (int64_t q = b->last_bucket + 1; q < (int64_t)nb; ++q) b->boff[(size_t)q] = (int64_t)b->rows;
-    int rc = MEMO_OK;
-    hipStream_t st = static_cast<hipStream_t>(b->ring->stream);
-    do {
-        hipError_t err = hipMalloc(&ix->boff, nb * sizeof(int64_t));
-        if (err == hipSuccess) err = hipMalloc(&ix->d_status, 64);
-        if (err == hipSuccess) err = hipMalloc(&ix->d_scratch, 64);
-        if (err == hipSuccess) err = hipMemsetAsync(ix->d_status, 0, 64, st);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(ix->boff, b->boff.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice, st);
-        // the rows behind the last one are read (never used) by whole-wave loads: keep them defined
-        if (err == hipSuccess) {
-            if (b->dense)
-                err = hipMemsetAsync(b->d_pk + 4 * b->groups_sent, 0, (size_t)(b->d_groups - b->groups_sent) * 16, st);
-            else
-                err = hipMemsetAsync(b->d_pk + b->rows, 0, (b->padded - b->rows) * 4, st);
-        }
-
-        const uint64_t n_long = b->long_rows.size() / 3;
-        std::vector<int64_t> cols;
-        if (err == hipSuccess && n_long) {
-            cols.resize(3 * n_long);
-            for (uint64_t i = 0; i < n_long; ++i) {
-                cols[i] = b->long_rows[3 * i];
-                cols[n_long + i] = b->long_rows[3 * i + 1];
-                cols[2 * n_long + i] = b->long_rows[3 * i + 2];
-            }
-            err = hipMalloc(&ix->ls, n_long * 8);
-            if (err == hipSuccess) err = hipMalloc(&ix->le, n_long * 8);
-            if (err == hipSuccess) err = hipMalloc(&ix->lo, n_long * 8);
-            if (err == hipSuccess) err = hipMemcpyAsync(ix->ls, cols.data(), n_long * 8, hipMemcpyHostToDevice, st);
-            if (err == hipSuccess) err = hipMemcpyAsync(ix->le, cols.data() + n_long, n_long * 8, hipMemcpyHostToDevice, st);
-            if (err == hipSuccess) err = hipMemcpyAsync(ix->lo, cols.data() + 2 * n_long, n_long * 8, hipMemcpyHostToDevice, st);
-            ix->n_long = n_long;
-        }
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err != hipSuccess) {
-            rc = fail(MEMO_EHIP, "finishing the packed index: %s", hipGetErrorString(err));
-            break;
-        }
-    } while (0);
-    if (rc) {
+    const uint64_t n_long = b->long_rows.size() / 3;
+    std::vector<int64_t> cols(3 * n_long);  // the builder's [n, 3] triples as columns
+    for (uint64_t i = 0; i < n_long; ++i) {
+        cols[i] = b->long_rows[3 * i];
+        cols[n_long + i] = b->long_rows[3 * i + 1];
+        cols[2 * n_long + i] = b->long_rows[3 * i + 2];
+    }
+    hipError_t err = ix->boff.alloc(nb);
+    if (err == hipSuccess) err = hipMemcpyAsync(ix->boff, b->boff.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    // the rows behind the last one are read (never used) by whole-wave loads: keep them defined
+    if (err == hipSuccess) {
+        if (b->dense)
+            err = hipMemsetAsync(b->d_pk + 4 * b->groups_sent, 0, (size_t)(b->d_groups - b->groups_sent) * 16, st);
+        else
+            err = hipMemsetAsync(b->d_pk + b->rows, 0, (b->padded - b->rows) * 4, st);
+    }
+    if (err == hipSuccess) err = ix->long_rows.set(cols.data(), n_long, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) {
         memo_index_destroy(ix);
-        return rc;
+        return fail(MEMO_EHIP, "finishing the packed index: %s", hipGetErrorString(err));
     }
     for (int s = 0; s < PinnedRing::kSlots; ++s) b->ring->in_flight[s] = false;
     ix->nb = nb;
-    if (b->dense)
-        ix->p3 = b->d_pk;
-    else
-        ix->pk = b->d_pk;
-    b->d_pk = nullptr;  // the index owns them now
+    (b->dense ? ix->p3 : ix->pk).adopt(b->d_pk);  // the index owns them now
+    b->d_pk = nullptr;
     ix->packed_fmt = b->dense ? 4 : b->fmt;  // (dense rows: what an index looks like after memo_index_pack_dense(ix, 0))
     ix->order_pending = b->dense ? 0 : 1;    // (start order now; the query order once the queries have lost to it what the pass costs: memo_view.hip, keep_row_order)
     ix->finalized = 1;
@@ -279,19 +251,13 @@ int memo_builder_finish(memo_builder_t *b, memo_index_t **out) {
 int memo_index_export_packed(memo_index_t *ix, uint32_t *pk, uint16_t *pa, int64_t *boff, int64_t *long_rows) {
     if (!ix) return fail(MEMO_EINVAL, "index is NULL");
     if (!ix->finalized || !ix->packed_fmt || !ix->pk) return fail(MEMO_ENOTREADY, "the index has no packed rows (memo_index_pack)");
-    if ((ix->rows && !pk) || (ix->packed_fmt == 6 && ix->rows && !pa) || !boff || (ix->n_long && !long_rows))
+    if ((ix->rows && !pk) || (ix->packed_fmt == 6 && ix->rows && !pa) || !boff || (ix->long_rows.n && !long_rows))
         return fail(MEMO_EINVAL, "output pointer is NULL");
     int rc;
     if ((rc = download_pipelined(ix->device, pk, ix->pk, ix->rows * 4, nullptr))) return rc;
     if (ix->packed_fmt == 6 && (rc = download_pipelined(ix->device, pa, ix->pa, ix->rows * 2, nullptr))) return rc;
     if ((rc = download_pipelined(ix->device, boff, ix->boff, ix->nb * 8, nullptr))) return rc;
-    if (ix->n_long) {
-        DeviceGuard guard(ix->device);
-        HIP_TRY(hipMemcpy(long_rows, ix->ls, ix->n_long * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(long_rows + ix->n_long, ix->le, ix->n_long * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(long_rows + 2 * ix->n_long, ix->lo, ix->n_long * 8, hipMemcpyDeviceToHost));
-    }
-    return MEMO_OK;
+    return ix->long_rows.download(ix->device, long_rows);
 }
 
 // export of the dense rows of an index that holds them: ceil(rows / 5) groups of 16 bytes, the bucket table
@@ -299,18 +265,12 @@ int memo_index_export_packed(memo_index_t *ix, uint32_t *pk, uint16_t *pa, int64
 int memo_index_export_dense(memo_index_t *ix, void *groups, int64_t *boff, int64_t *long_rows) {
     if (!ix) return fail(MEMO_EINVAL, "index is NULL");
     if (!ix->finalized || !ix->p3) return fail(MEMO_ENOTREADY, "the index has no dense rows (memo_index_pack_dense)");
-    if ((ix->rows && !groups) || !boff || (ix->n_long && !long_rows)) return fail(MEMO_EINVAL, "output pointer is NULL");
+    if ((ix->rows && !groups) || !boff || (ix->long_rows.n && !long_rows)) return fail(MEMO_EINVAL, "output pointer is NULL");
     int rc;
     const uint64_t drows = ix->boff3 ? ix->rows3 : ix->rows;  // (info.dense_row_count)
     if ((rc = download_pipelined(ix->device, groups, ix->p3, (size_t)((drows + 4) / 5) * 16, nullptr))) return rc;
     if ((rc = download_pipelined(ix->device, boff, ix->boff3 ? ix->boff3 : ix->boff, ix->nb * 8, nullptr))) return rc;
-    if (ix->n_long) {
-        DeviceGuard guard(ix->device);
-        HIP_TRY(hipMemcpy(long_rows, ix->ls, ix->n_long * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(long_rows + ix->n_long, ix->le, ix->n_long * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(long_rows + 2 * ix->n_long, ix->lo, ix->n_long * 8, hipMemcpyDeviceToHost));
-    }
-    return MEMO_OK;
+    return ix->long_rows.download(ix->device, long_rows);
 }
 
 }  // extern "C"
@@ -334,15 +294,9 @@ static int import_rows(uint64_t rows, int32_t device, int32_t bucket_shift, int6
     if (lead < 0 || lead > (dense ? 4 : 0) || boff[buckets - 2] - row_base > (int64_t)rows || boff[buckets - 2] < row_base)
         return fail(MEMO_EINVAL, "bucket table does not match the rows (first %lld, last %lld, row base %lld, rows %llu)",
                     (long long)boff[0], (long long)boff[buckets - 2], (long long)row_base, (unsigned long long)rows);
-    const int ndev = memo_device_count();
-    if (device < 0 || device >= ndev) return fail(MEMO_EHIP, "HIP device %d not available (%d visible)", device, ndev);
+    memo_index *ix = nullptr;
+    if (int rc = new_index(rows, device, nullptr, &ix)) return rc;
     DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
-    memo_index *ix = new (std::nothrow) memo_index();
-    if (!ix) return fail(MEMO_EHIP, "out of host memory");
-    ix->device = device;
-    ix->rows = rows;
-    ix->padded = ((rows + 15) & ~(uint64_t)15) + kPadRows;
     ix->packed_rows = dense ? 0 : ix->padded;
     ix->has_wide = 0;
     ix->was_sorted = 1;
@@ -357,43 +311,23 @@ static int import_rows(uint64_t rows, int32_t device, int32_t bucket_shift, int6
         ix->rows3 = rows;
         ix->padded3 = ix->padded;
     }
-    int rc = MEMO_OK;
-    do {
-        hipError_t err = dense ? hipMalloc(&ix->p3, groups * 16) : hipMalloc(&ix->pk, ix->padded * 4);
-        if (err == hipSuccess && pa) err = hipMalloc(&ix->pa, ix->padded * 2);
-        if (err == hipSuccess) err = hipMalloc(&ix->boff, buckets * 8);
-        if (err == hipSuccess) err = hipMalloc(&ix->d_status, 64);
-        if (err == hipSuccess) err = hipMalloc(&ix->d_scratch, 64);
-        if (err == hipSuccess) err = hipMemset(ix->d_status, 0, 64);
-        if (err == hipSuccess)
-            err = dense ? hipMemset(ix->p3 + 4 * used, 0, (groups - used) * 16) : hipMemset(ix->pk + rows, 0, (ix->padded - rows) * 4);
-        if (err == hipSuccess && pa) err = hipMemset(ix->pa + rows, 0, (ix->padded - rows) * 2);
-        if (err == hipSuccess && n_long) {
-            err = hipMalloc(&ix->ls, n_long * 8);
-            if (err == hipSuccess) err = hipMalloc(&ix->le, n_long * 8);
-            if (err == hipSuccess) err = hipMalloc(&ix->lo, n_long * 8);
-            if (err == hipSuccess) err = hipMemcpy(ix->ls, long_rows, n_long * 8, hipMemcpyHostToDevice);
-            if (err == hipSuccess) err = hipMemcpy(ix->le, long_rows + n_long, n_long * 8, hipMemcpyHostToDevice);
-            if (err == hipSuccess) err = hipMemcpy(ix->lo, long_rows + 2 * n_long, n_long * 8, hipMemcpyHostToDevice);
-            ix->n_long = n_long;
-        }
-        if (err != hipSuccess) {
-            rc = fail(MEMO_EHIP, "importing a packed index: %s", hipGetErrorString(err));
-            break;
-        }
-        if (dense) {
-            if ((rc = upload_pipelined(device, ix->p3, dense, used * 16))) break;
-        } else {
-            if ((rc = upload_pipelined(device, ix->pk, pk, rows * 4))) break;
-            if (pa && (rc = upload_pipelined(device, ix->pa, pa, rows * 2))) break;
-        }
-        if ((rc = upload_pipelined(device, ix->boff, boff, (buckets - 1) * 8))) break;
+    hipError_t err = dense ? ix->p3.alloc(groups * 4) : ix->pk.alloc(ix->padded);
+    if (err == hipSuccess && pa) err = ix->pa.alloc(ix->padded);
+    if (err == hipSuccess) err = ix->boff.alloc(buckets);
+    if (err == hipSuccess)
+        err = dense ? hipMemset(ix->p3 + 4 * used, 0, (groups - used) * 16) : hipMemset(ix->pk + rows, 0, (ix->padded - rows) * 4);
+    if (err == hipSuccess && pa) err = hipMemset(ix->pa + rows, 0, (ix->padded - rows) * 2);
+    if (err == hipSuccess) err = ix->long_rows.set(long_rows, n_long, nullptr);  // (waited for with the table, below)
+    int rc = hip_rc(err, "importing a packed index");
+    if (!rc) rc = dense ? upload_pipelined(device, ix->p3, dense, used * 16) : upload_pipelined(device, ix->pk, pk, rows * 4);
+    if (!rc && pa) rc = upload_pipelined(device, ix->pa, pa, rows * 2);
+    if (!rc) rc = upload_pipelined(device, ix->boff, boff, (buckets - 1) * 8);
+    if (!rc) {
         hipLaunchKernelGGL(rebase_table_kernel, dim3((unsigned)((buckets + 255) / 256)), dim3(256), 0, nullptr, ix->boff,
                            buckets, row_base, (int64_t)rows);
         err = hipGetLastError();
-        if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-        if (err != hipSuccess) rc = fail(MEMO_EHIP, "importing a packed index: %s", hipGetErrorString(err));
-    } while (0);
+        rc = hip_rc(err == hipSuccess ? hipStreamSynchronize(nullptr) : err, "importing a packed index");
+    }
     if (rc) {
         memo_index_destroy(ix);
         return rc;

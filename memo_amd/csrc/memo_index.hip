@@ -1,58 +1,28 @@
-// memo_index.hip -- the resident index: upload, validation, bucket table, packed rows; the
-// one-shot host entry points; `memo view` binning; synthetic rows; small device-buffer helpers.
+// memo_index.hip -- the resident index and its life: error plumbing; birth (new_index), the row-change rule (rows_changed) and the
+// rows with end < start; create / upload / truncate / columns / finalize / pack / pack_dense and the overlap census; info and
+// options; prepare; synthetic rows.  Two small index-free jobs live here too: `memo view` binning and the four memo_dev_* helpers.
+// (The one-shot host forms are memo_oneshot.hip, the builder and export / import memo_hostpack.hip, the views memo_view.hip.)
 //
 // Counterpart of the arrays /root/reference/src/memo_query.py hands from filter_pq to memo_init
 // (:28-36, :45): three int64 columns, kept in HBM so that many windows reuse one upload.
-#include <chrono>
 #include <cstdarg>
 #include <exception>
 #include <cstddef>
 #include <new>
 
 #include "memo_view.h"
-#include "memo_hostcore.h"
 
 using namespace memo;
-
-namespace memo {
-void drop_dense(memo_index *ix) {
-    drop_tile_tables(ix);
-    drop_dense_views(ix);
-    (void)hipFree(ix->p3);
-    (void)hipFree(ix->boff3);
-    ix->p3 = nullptr;
-    ix->boff3 = nullptr;
-    ix->rows3 = ix->padded3 = 0;
-}
-}  // namespace memo
-
-namespace memo {
-thread_local int g_last_one_shot_sweep = 0;  // memo_index_info_t.last_sweep of this thread's last one-shot call (memo_debug.hip)
-thread_local int g_one_shot_way = 0;         // which way in one_shot() takes (AB library, memo_debug_one_shot_way: 1 = int64 columns, 2 = 4-byte words)
-}
 
 extern "C" __attribute__((visibility("hidden"))) int memo_sort_rows_by_start(int64_t *s, int64_t *e, int64_t *o, uint64_t rows,
                                        uint64_t padded_rows, hipStream_t stream, char *err,
                                        size_t errcap);
 
-namespace memo {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-}  // namespace memo
-
 namespace {
 
 // ------------------------------------------------------------------------------------------
-// index build: validation, padding, bucket table, synthetic rows
+// kernels: validation, padding and the bucket table (finalize); the 4-byte words and the dense rows (pack, pack_dense); the
+// overlap census; `memo view` binning; synthetic rows
 // ------------------------------------------------------------------------------------------
 __global__ void check_rows_kernel(const int64_t *s, const int64_t *e, uint64_t rows,
                                   uint64_t *scratch) {
@@ -196,7 +166,6 @@ __global__ void pack3_rows_kernel(const uint32_t *pk, uint64_t padded, uint64_t 
     }
 }
 
-
 // boff[b] = lower_bound(start, b << shift); the last bucket is pinned to `rows`
 __global__ void bucket_table_kernel(const int64_t *s, uint64_t rows, int64_t *boff, uint64_t nb,
                                     int shift) {
@@ -215,362 +184,6 @@ __global__ void bucket_table_kernel(const int64_t *s, uint64_t rows, int64_t *bo
     boff[b] = (int64_t)lo;
 }
 
-// `memo view` binning (plot_conservation.py:52-56): counts[b][v] = #{p in [edge[b], edge[b+1]) : vec[p] == v}
-// for v in 0..num_docs.  One workgroup per (bin, slice of the bin); LDS histogram when it fits.
-template <bool LDS_HIST>
-__global__ __launch_bounds__(256) void bin_conservation_kernel(const uint16_t *vec, const int64_t *edges,
-                                                               int ncols, int slices,
-                                                               unsigned long long *counts) {
-    extern __shared__ uint32_t hist[];
-    const int b = blockIdx.x / slices, sl = blockIdx.x % slices;
-    const int64_t lo = edges[b], hi = edges[b + 1];
-    const int64_t per = (hi - lo + slices - 1) / slices;
-    const int64_t p0 = lo + sl * per, p1 = p0 + per < hi ? p0 + per : hi;
-    if (LDS_HIST) {
-        for (int i = threadIdx.x; i < ncols; i += 256) hist[i] = 0;
-        __syncthreads();
-    }
-    for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
-        const int v = vec[p];
-        if (v < ncols) {
-            if (LDS_HIST) atomicAdd(&hist[v], 1u);
-            else atomicAdd(&counts[(int64_t)b * ncols + v], 1ull);
-        }
-    }
-    if (LDS_HIST) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < ncols; i += 256)
-            if (hist[i]) atomicAdd(&counts[(int64_t)b * ncols + i], (unsigned long long)hist[i]);
-    }
-}
-
-// Transport coding of uint8 conservation results for the multi-GPU gather: one nibble per position
-// (values >= 15 become 15 and go to an exception list as position << 8 | value).  Lossless; halves
-// what a slice puts on its xGMI link when few values reach 15.
-__global__ __launch_bounds__(256) void nibble_pack_kernel(const uint8_t *in, int64_t n, uint32_t *nib,
-                                                          unsigned long long *exc, unsigned int *count,
-                                                          unsigned int cap) {
-    // A workgroup codes 32768 consecutive positions (16 rounds of 256 threads x 8 positions).  Exceptions
-    // are collected in LDS -- no barrier between the rounds, LDS atomics order themselves -- and appended
-    // with ONE global atomic per workgroup: a quarter of a million same-address atomics would cost
-    // milliseconds, and round 1's version, which met at three barriers per round, ran at a fifth of its
-    // memory bound.  More than 4096 exceptions in 32768 positions (an eighth of them >= 15) is not data this
-    // coding is for: the count is saturated so that the receiver sees an incomplete slice.
-    constexpr int kRounds = 16, kHeld = 4096;
-    __shared__ unsigned long long held[kHeld];
-    __shared__ unsigned int n_held, base;
-    if (threadIdx.x == 0) n_held = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) count[1] = cap;  // header word 1
-    __syncthreads();
-    const int64_t groups = (n + 7) / 8;
-#pragma unroll 4
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t g = ((int64_t)blockIdx.x * kRounds + r) * 256 + threadIdx.x;
-        if (g >= groups) break;
-        unsigned long long eight = 0;  // 8 results in one load (the tail group byte by byte)
-        if (g * 8 + 8 <= n) {
-            eight = *reinterpret_cast<const unsigned long long *>(in + g * 8);
-        } else {
-            for (int i = 0; g * 8 + i < n; ++i) eight |= (unsigned long long)in[g * 8 + i] << (8 * i);
-        }
-        uint32_t word = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const uint32_t v = (uint32_t)(eight >> (8 * i)) & 0xFFu;
-            if (v >= 15u) {
-                const unsigned int slot = atomicAdd(&n_held, 1u);
-                if (slot < (unsigned)kHeld) held[slot] = ((unsigned long long)(g * 8 + i) << 8) | v;
-            }
-            word |= (v < 15u ? v : 15u) << (4 * i);
-        }
-        nib[g] = word;
-    }
-    __syncthreads();
-    const unsigned int mine = n_held;
-    if (!mine) return;
-    if (mine > (unsigned)kHeld) {
-        if (threadIdx.x == 0) count[2] = 1;  // header word 2: overflow -- the slice is incomplete, whatever the capacity
-        return;
-    }
-    if (threadIdx.x == 0) base = atomicAdd(count, mine);
-    __syncthreads();
-    for (unsigned int i = threadIdx.x; i < mine; i += 256)
-        if (base + i < cap) exc[base + i] = held[i];
-}
-
-__global__ void nibble_unpack_kernel(const uint32_t *nib, int64_t n, uint8_t *out) {
-    for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g * 8 < n;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t word = nib[g];
-        unsigned long long eight = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) eight |= (unsigned long long)((word >> (4 * i)) & 15u) << (8 * i);
-        if (g * 8 + 8 <= n) {
-            *reinterpret_cast<unsigned long long *>(out + g * 8) = eight;
-        } else {
-            for (int i = 0; g * 8 + i < n; ++i) out[g * 8 + i] = (uint8_t)(eight >> (8 * i));
-        }
-    }
-}
-
-__global__ void nibble_exceptions_kernel(const unsigned long long *exc, const unsigned int *head, int64_t n,
-                                         uint8_t *out) {
-    const unsigned int count = head[0] < head[1] ? head[0] : head[1];  // found, capacity
-    for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-        const unsigned long long e = exc[i];
-        const int64_t p = (int64_t)(e >> 8);
-        if (p < n) out[p] = (uint8_t)(e & 0xFF);
-    }
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t seed, uint64_t x) {
-    uint64_t z = seed + (x + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__global__ void synth_rows_kernel(int64_t *s, int64_t *e, int64_t *o, uint64_t rows,
-                                  uint64_t row_begin, uint64_t num, uint64_t den, uint64_t nm1,
-                                  uint64_t seed) {
-    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < rows;
-         j += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t i = row_begin + j;
-        const int64_t st = 1 + (int64_t)((i * den) / num);
-        s[j] = st;
-        e[j] = st + (int64_t)(mix64(seed, 2 * i) % 60);
-        o[j] = 1 + (int64_t)(mix64(seed, 2 * i + 1) % nm1);
-    }
-}
-
-}  // namespace
-
-extern "C" {
-
-const char *memo_last_error(void) { return g_err; }
-
-const char *memo_version(void) { return "memo_amd 0.1 (gfx950)"; }
-
-int memo_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-static void drop_packed(memo_index *ix) {  // the rows are about to change
-    drop_dense(ix);
-    drop_packed_views(ix);
-    (void)hipFree(ix->pk);
-    (void)hipFree(ix->pa);
-    ix->pk = nullptr;
-    ix->pa = nullptr;
-    ix->packed_fmt = 0;
-    ix->packed_rows = 0;
-}
-
-// the rows are about to change but the index keeps its size: the packed copy is stale, its buffers
-// can serve the next memo_index_pack
-static void stale_packed(memo_index *ix) {
-    drop_dense(ix);
-    drop_packed_views(ix);
-    ix->packed_fmt = 0;
-}
-
-int memo_index_create(uint64_t rows, int32_t device, memo_index_t **out) {
-    if (!out) return fail(MEMO_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (rows > ((uint64_t)1 << 40)) return fail(MEMO_EINVAL, "too many rows");
-    int ndev = memo_device_count();
-    if (device < 0 || device >= ndev)
-        return fail(MEMO_EHIP, "HIP device %d not available (%d visible)", device, ndev);
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
-    memo_index *ix = new (std::nothrow) memo_index();
-    if (!ix) return fail(MEMO_EHIP, "out of host memory");
-    ix->device = device;
-    ix->rows = rows;
-    ix->padded = ((rows + 15) & ~(uint64_t)15) + kPadRows;
-    const size_t bytes = ix->padded * sizeof(int64_t);
-    hipError_t err = hipMalloc(&ix->s, bytes);
-    if (err == hipSuccess) err = hipMalloc(&ix->e, bytes);
-    if (err == hipSuccess) err = hipMalloc(&ix->o, bytes);
-    if (err == hipSuccess) err = hipMalloc(&ix->d_status, 64);
-    if (err == hipSuccess) err = hipMalloc(&ix->d_scratch, 64);
-    if (err == hipSuccess) err = hipMemset(ix->d_status, 0, 64);
-    if (err != hipSuccess) {
-        memo_index_destroy(ix);
-        return fail(MEMO_EHIP, "hipMalloc of %zu bytes x3 failed: %s", bytes, hipGetErrorString(err));
-    }
-    *out = ix;
-    return MEMO_OK;
-}
-
-void memo_index_destroy(memo_index_t *ix) {
-    if (!ix) return;
-    DeviceGuard guard(ix->device);
-    (void)hipFree(ix->s);
-    (void)hipFree(ix->e);
-    (void)hipFree(ix->o);
-    drop_dense(ix);
-    drop_packed_views(ix);
-    (void)hipFree(ix->boff);
-    (void)hipFree(ix->pk);
-    (void)hipFree(ix->pa);
-    (void)hipFree(ix->ls);
-    (void)hipFree(ix->le);
-    (void)hipFree(ix->lo);
-    (void)hipFree(ix->d_status);
-    (void)hipFree(ix->d_scratch);
-    flush_retired(ix);  // (hipFree waits for the device)
-    delete ix;
-}
-
-int memo_index_upload(memo_index_t *ix, const int64_t *start, const int64_t *end,
-                      const int64_t *annot, uint64_t rows) {
-    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
-    if (rows != ix->rows) return fail(MEMO_EINVAL, "upload of %llu rows into an index of %llu",
-                                      (unsigned long long)rows, (unsigned long long)ix->rows);
-    if (rows && (!start || !end || !annot)) return fail(MEMO_EINVAL, "column pointer is NULL");
-    if (!ix->has_wide) return fail(MEMO_EINVAL, "the int64 columns of this index were dropped by memo_index_pack");
-    DeviceGuard guard(ix->device);
-    drop_packed(ix);
-    if (rows) {
-        HIP_TRY(hipMemcpy(ix->s, start, rows * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->e, end, rows * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->o, annot, rows * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    ix->finalized = 0;
-    return MEMO_OK;
-}
-
-int memo_index_upload_rows(memo_index_t *ix, uint64_t row_offset, const int64_t *start,
-                           const int64_t *end, const int64_t *annot, uint64_t rows) {
-    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
-    if (row_offset > ix->rows || rows > ix->rows - row_offset)
-        return fail(MEMO_EINVAL, "rows [%llu, +%llu) do not fit an index of %llu rows",
-                    (unsigned long long)row_offset, (unsigned long long)rows, (unsigned long long)ix->rows);
-    if (rows && (!start || !end || !annot)) return fail(MEMO_EINVAL, "column pointer is NULL");
-    if (!ix->has_wide) return fail(MEMO_EINVAL, "the int64 columns of this index were dropped by memo_index_pack");
-    DeviceGuard guard(ix->device);
-    drop_packed(ix);
-    if (rows) {
-        HIP_TRY(hipMemcpy(ix->s + row_offset, start, rows * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->e + row_offset, end, rows * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->o + row_offset, annot, rows * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    ix->finalized = 0;
-    return MEMO_OK;
-}
-
-int memo_index_truncate(memo_index_t *ix, uint64_t rows) {
-    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
-    if (rows > ix->rows) return fail(MEMO_EINVAL, "cannot grow an index (%llu > %llu rows)",
-                                     (unsigned long long)rows, (unsigned long long)ix->rows);
-    if (!ix->has_wide) return fail(MEMO_EINVAL, "the int64 columns of this index were dropped by memo_index_pack");
-    {
-        DeviceGuard guard(ix->device);
-        drop_packed(ix);
-    }
-    ix->rows = rows;  // `padded` keeps the allocated size; finalize() rewrites the sentinel rows behind `rows`
-    ix->finalized = 0;
-    return MEMO_OK;
-}
-
-int memo_index_columns(memo_index_t *ix, int64_t **d_start, int64_t **d_end, int64_t **d_annot) {
-    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
-    if (!ix->has_wide) return fail(MEMO_EINVAL, "the int64 columns of this index were dropped by memo_index_pack");
-    {
-        DeviceGuard guard(ix->device);
-        drop_packed(ix);
-    }
-    if (d_start) *d_start = ix->s;
-    if (d_end) *d_end = ix->e;
-    if (d_annot) *d_annot = ix->o;
-    ix->finalized = 0;  // the caller may be about to rewrite the rows
-    return MEMO_OK;
-}
-
-int memo_index_finalize(memo_index_t *ix, int32_t bucket_shift, int32_t allow_sort) {
-    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
-    if (!ix->has_wide) return fail(MEMO_EINVAL, "the int64 columns of this index were dropped by memo_index_pack");
-    if (bucket_shift <= 0) bucket_shift = kDefaultBucketShift;
-    if (bucket_shift > 8) return fail(MEMO_EINVAL, "bucket_shift must be <= 8 (tile width 256)");
-    DeviceGuard guard(ix->device);
-    hipStream_t st = nullptr;
-    const uint64_t rows = ix->rows;
-    stale_packed(ix);  // a device sort below would leave packed rows stale; pack again after finalize
-    ix->finalized = 0;
-    {
-        const uint64_t npad = ix->padded - rows;
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, st,
-                           ix->s, ix->e, ix->o, rows, ix->padded);
-        HIP_TRY(hipGetLastError());
-    }
-    uint64_t h[8] = {0};
-    ix->was_sorted = 1;
-    if (rows) {
-        HIP_TRY(hipMemsetAsync(ix->d_scratch, 0, 64, st));
-        const unsigned grid = (unsigned)(rows / 256 + 1 < 4096 ? rows / 256 + 1 : 4096);
-        hipLaunchKernelGGL(check_rows_kernel, dim3(grid), dim3(256), 0, st, ix->s, ix->e, rows,
-                           ix->d_scratch);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(h, ix->d_scratch, 24, hipMemcpyDeviceToHost));
-        if (h[2]) return fail(MEMO_EINVAL, "%llu rows have coordinates beyond +-2^61", (unsigned long long)h[2]);
-        (void)hipFree(ix->ls);
-        (void)hipFree(ix->le);
-        (void)hipFree(ix->lo);
-        ix->ls = ix->le = ix->lo = nullptr;
-        ix->n_long = 0;
-        if (h[1]) {  // rows with end < start: set aside for long_rows_kernel
-            if (h[1] > ((uint64_t)1 << 22))
-                return fail(MEMO_ELONGROW, "%llu rows have end < start: not a MEMO overlap index",
-                            (unsigned long long)h[1]);
-            HIP_TRY(hipMalloc(&ix->ls, h[1] * sizeof(int64_t)));
-            HIP_TRY(hipMalloc(&ix->le, h[1] * sizeof(int64_t)));
-            HIP_TRY(hipMalloc(&ix->lo, h[1] * sizeof(int64_t)));
-            HIP_TRY(hipMemsetAsync(ix->d_scratch + 6, 0, 8, st));
-            hipLaunchKernelGGL(collect_long_rows_kernel, dim3(grid), dim3(256), 0, st, ix->s, ix->e, ix->o, rows,
-                               ix->ls, ix->le, ix->lo, (unsigned long long *)(ix->d_scratch + 6));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(st));
-            ix->n_long = h[1];
-        }
-        if (h[0]) {
-            ix->was_sorted = 0;
-            if (!allow_sort)
-                return fail(MEMO_EUNSORTED, "rows are not sorted by start (%llu descents)",
-                            (unsigned long long)h[0]);
-            char msg[256] = "";
-            if (memo_sort_rows_by_start(ix->s, ix->e, ix->o, rows, ix->padded, st, msg, sizeof msg) != 0)
-                return fail(MEMO_EHIP, "device sort failed: %s", msg);
-        }
-        HIP_TRY(hipMemcpy(&ix->min_s, ix->s, sizeof(int64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&ix->max_s, ix->s + (rows - 1), sizeof(int64_t), hipMemcpyDeviceToHost));
-    } else {
-        ix->min_s = 0;
-        ix->max_s = -1;
-    }
-    // buckets 0 .. ceil((max_s + 1) / width), plus one pinned to `rows`
-    const int64_t top = ix->max_s < 0 ? 0 : ix->max_s;
-    const uint64_t nb = (uint64_t)((top >> bucket_shift) + 3);
-    if (ix->boff) {
-        (void)hipFree(ix->boff);
-        ix->boff = nullptr;
-    }
-    HIP_TRY(hipMalloc(&ix->boff, nb * sizeof(int64_t)));
-    hipLaunchKernelGGL(bucket_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st,
-                       ix->s, rows, ix->boff, nb, bucket_shift);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    ix->nb = nb;
-    ix->bshift = bucket_shift;
-    ix->finalized = 1;
-    return MEMO_OK;
-}
-
-}  // extern "C"
-
-namespace {
 // one workgroup per sampled block of 1024 rows: LDS histogram of the overlap byte, then its non-empty bins to HBM
 __global__ __launch_bounds__(256) void len_census_kernel(const uint32_t *__restrict__ pk, uint64_t rows, int shift,
                                                          uint64_t step, unsigned int *__restrict__ hist) {
@@ -587,10 +200,7 @@ __global__ __launch_bounds__(256) void len_census_kernel(const uint32_t *__restr
     __syncthreads();
     if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
 }
-}  // namespace
 
-
-namespace {
 // the same for dense rows: one workgroup per sampled block of 256 groups (1280 rows)
 __global__ __launch_bounds__(256) void dense_census_kernel(const uint4 *__restrict__ p3, uint64_t rows, uint64_t step,
                                                            unsigned int *__restrict__ hist) {
@@ -632,71 +242,368 @@ __global__ __launch_bounds__(256) void len_seen_kernel(const uint32_t *__restric
         if (hi) atomicOr(&seen[w + 1], hi);
     }
 }
+
+// `memo view` binning (plot_conservation.py:52-56): counts[b][v] = #{p in [edge[b], edge[b+1]) : vec[p] == v}
+// for v in 0..num_docs.  One workgroup per (bin, slice of the bin); LDS histogram when it fits.
+template <bool LDS_HIST>
+__global__ __launch_bounds__(256) void bin_conservation_kernel(const uint16_t *vec, const int64_t *edges,
+                                                               int ncols, int slices,
+                                                               unsigned long long *counts) {
+    extern __shared__ uint32_t hist[];
+    const int b = blockIdx.x / slices, sl = blockIdx.x % slices;
+    const int64_t lo = edges[b], hi = edges[b + 1];
+    const int64_t per = (hi - lo + slices - 1) / slices;
+    const int64_t p0 = lo + sl * per, p1 = p0 + per < hi ? p0 + per : hi;
+    if (LDS_HIST) {
+        for (int i = threadIdx.x; i < ncols; i += 256) hist[i] = 0;
+        __syncthreads();
+    }
+    for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
+        const int v = vec[p];
+        if (v < ncols) {
+            if (LDS_HIST) atomicAdd(&hist[v], 1u);
+            else atomicAdd(&counts[(int64_t)b * ncols + v], 1ull);
+        }
+    }
+    if (LDS_HIST) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < ncols; i += 256)
+            if (hist[i]) atomicAdd(&counts[(int64_t)b * ncols + i], (unsigned long long)hist[i]);
+    }
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t seed, uint64_t x) {
+    uint64_t z = seed + (x + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__global__ void synth_rows_kernel(int64_t *s, int64_t *e, int64_t *o, uint64_t rows,
+                                  uint64_t row_begin, uint64_t num, uint64_t den, uint64_t nm1,
+                                  uint64_t seed) {
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < rows;
+         j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = row_begin + j;
+        const int64_t st = 1 + (int64_t)((i * den) / num);
+        s[j] = st;
+        e[j] = st + (int64_t)(mix64(seed, 2 * i) % 60);
+        o[j] = 1 + (int64_t)(mix64(seed, 2 * i + 1) % nm1);
+    }
+}
+
 }  // namespace
 
+namespace memo {
+
+// ------------------------------------------------------------------------------------------
+// error plumbing
+// ------------------------------------------------------------------------------------------
+thread_local char g_err[512] = "";
+
+int fail(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+int device_ok(int device) {
+    const int ndev = memo_device_count();
+    return device >= 0 && device < ndev ? MEMO_OK : fail(MEMO_EHIP, "HIP device %d not available (%d visible)", device, ndev);
+}
+
+int need_wide(const memo_index *ix) {
+    return ix->has_wide ? MEMO_OK : fail(MEMO_EINVAL, "the int64 columns of this index were dropped by memo_index_pack");
+}
+
+// ------------------------------------------------------------------------------------------
+// the life of an index: its one birth, and what a change of its rows makes stale
+// ------------------------------------------------------------------------------------------
+int new_index(uint64_t rows, int device, hipStream_t st, memo_index **out) {
+    if (int rc = device_ok(device)) return rc;
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    memo_index *ix = new (std::nothrow) memo_index();
+    if (!ix) return fail(MEMO_EHIP, "out of host memory");
+    ix->device = device;
+    ix->rows = rows;
+    ix->padded = padded_for(rows);
+    hipError_t err = ix->d_status.alloc(16);
+    if (err == hipSuccess) err = ix->d_scratch.alloc(8);
+    if (err == hipSuccess) err = st ? hipMemsetAsync(ix->d_status, 0, 64, st) : hipMemset(ix->d_status, 0, 64);
+    if (err != hipSuccess) {
+        memo_index_destroy(ix);
+        return fail(MEMO_EHIP, "the status words of a new index: %s", hipGetErrorString(err));
+    }
+    *out = ix;
+    return MEMO_OK;
+}
+
+void rows_changed(memo_index *ix, Level at, bool keep_word_buffers) {
+    if (at <= kLevelDense) {
+        drop_tile_tables(ix);  // (all of them, before the views: drop_dense_views then finds none to retire)
+        ix->p3.reset();
+        ix->boff3.reset();
+        ix->rows3 = ix->padded3 = 0;
+    }
+    drop_dense_views(ix);
+    if (at != kLevelDense) drop_packed_views(ix);  // (new dense rows are made of the same words)
+    if (at <= kLevelWords) {
+        ix->packed_fmt = 0;
+        if (!keep_word_buffers) {
+            ix->pk.reset();
+            ix->pa.reset();
+            ix->packed_rows = 0;
+        }
+    }
+    if (at == kLevelColumns) ix->finalized = 0;
+}
+
+}  // namespace memo
+
+// ------------------------------------------------------------------------------------------
+// the rows with end < start
+// ------------------------------------------------------------------------------------------
+hipError_t memo_index::LongRows::set(const int64_t *host, uint64_t rows, hipStream_t st) {
+    n = 0;
+    cols.reset();
+    if (!rows) return hipSuccess;
+    hipError_t err = cols.alloc(3 * rows);
+    if (err == hipSuccess) err = hipMemcpyAsync(cols.p, host, 3 * rows * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) n = rows;
+    return err;
+}
+
+int memo_index::LongRows::collect(const memo_index *ix, uint64_t found, hipStream_t st) {
+    n = 0;
+    cols.reset();
+    if (!found) return MEMO_OK;
+    if (found > ((uint64_t)1 << 22))
+        return fail(MEMO_ELONGROW, "%llu rows have end < start: not a MEMO overlap index", (unsigned long long)found);
+    HIP_TRY(cols.alloc(3 * found));
+    HIP_TRY(hipMemsetAsync(ix->d_scratch + 6, 0, 8, st));
+    const unsigned grid = (unsigned)(ix->rows / 256 + 1 < 4096 ? ix->rows / 256 + 1 : 4096);
+    hipLaunchKernelGGL(collect_long_rows_kernel, dim3(grid), dim3(256), 0, st, ix->s, ix->e, ix->o, ix->rows, cols.p, cols.p + found,
+                       cols.p + 2 * found, (unsigned long long *)(ix->d_scratch + 6));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    n = found;
+    return MEMO_OK;
+}
+
+int memo_index::LongRows::download(int device, int64_t *host) const {
+    if (!n) return MEMO_OK;
+    DeviceGuard guard(device);
+    HIP_TRY(hipMemcpy(host, cols, 3 * n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return MEMO_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the overlap census
+// ------------------------------------------------------------------------------------------
 int memo_len_census(memo_index *ix) {
     ix->len_hist_rows = 0;
     ix->len_seen_exact = 0;
     for (unsigned int &c : ix->len_seen) c = 0;
     for (unsigned int &c : ix->len_hist) c = 0;
     if (!ix->rows) return MEMO_OK;
+    // an index that holds the dense rows only (the builder's dense way in, memo_index_import_dense): the same sampled
+    // histogram from their 6-bit overlap fields (63 = "63 or more") -- what the rule that decides when a k-class view is
+    // worth its pass (memo_view.hip: view_due) estimates the view's size from
+    const bool dense_only = !ix->pk && ix->p3;
+    const uint64_t drows = ix->boff3 ? ix->rows3 : ix->rows, groups = (drows + 4) / 5;
+    if (dense_only ? !groups : (!ix->pk || (ix->packed_fmt != 4 && ix->packed_fmt != 6 && ix->packed_fmt != 12))) return MEMO_OK;
     DeviceGuard guard(ix->device);
-    unsigned int *d_hist = nullptr;
-    if (!ix->pk && ix->p3) {
-        // an index that holds the dense rows only (the builder's dense way in, memo_index_import_dense): the same sampled
-        // histogram from their 6-bit overlap fields (63 = "63 or more") -- what the rule that decides when a k-class view is
-        // worth its pass (memo_view.hip: view_due) estimates the view's size from
-        const uint64_t drows = ix->boff3 ? ix->rows3 : ix->rows, groups = (drows + 4) / 5;
-        if (!groups) return MEMO_OK;
-        HIP_TRY(hipMalloc(&d_hist, sizeof(ix->len_hist)));
-        const uint64_t blocks = (groups + 255) / 256, step = blocks / 4096 + 1, grid = (blocks + step - 1) / step;
-        hipError_t err = hipMemsetAsync(d_hist, 0, sizeof(ix->len_hist), nullptr);
+    DevPtr<unsigned int> d_hist;  // (one allocation for both passes over the words)
+    HIP_TRY(d_hist.alloc(256));
+    // one pass: the device histogram cleared, `launch` on the NULL stream, `bytes` of it copied back (which waits for it)
+    auto pass = [&](void *host, size_t bytes, auto launch) {
+        hipError_t err = hipMemsetAsync(d_hist, 0, bytes, nullptr);
         if (err == hipSuccess) {
-            hipLaunchKernelGGL(dense_census_kernel, dim3((unsigned)grid), dim3(256), 0, nullptr, reinterpret_cast<const uint4 *>(ix->p3),
-                               drows, step, d_hist);
+            launch();
             err = hipGetLastError();
         }
-        if (err == hipSuccess) err = hipMemcpy(ix->len_hist, d_hist, sizeof(ix->len_hist), hipMemcpyDeviceToHost);
-        (void)hipFree(d_hist);
-        if (err != hipSuccess) return fail(MEMO_EHIP, "overlap census: %s", hipGetErrorString(err));
-        for (unsigned int c : ix->len_hist) ix->len_hist_rows += c;
-        // (the histogram is of the dense rows: when rows that never write were left out of them, scale it to the index's rows so
-        // that shares are shares of ix->rows, as they are for an index with 4-byte rows)
-        if (ix->boff3 && ix->len_hist_rows) {
-            const double gone = (double)(ix->rows - ix->rows3) / (double)ix->rows3;
-            ix->len_hist[255] += (unsigned int)(gone * (double)ix->len_hist_rows);
-            ix->len_hist_rows += (unsigned int)(gone * (double)ix->len_hist_rows);
-        }
-        return MEMO_OK;
+        return err == hipSuccess ? hipMemcpy(host, d_hist, bytes, hipMemcpyDeviceToHost) : err;
+    };
+    const int shift = ix->packed_fmt == 12 ? 0 : 16;
+    hipError_t err;
+    if (dense_only) {
+        const uint64_t blocks = (groups + 255) / 256, step = blocks / 4096 + 1, grid = (blocks + step - 1) / step;
+        err = pass(ix->len_hist, sizeof(ix->len_hist), [&] {
+            hipLaunchKernelGGL(dense_census_kernel, dim3((unsigned)grid), dim3(256), 0, nullptr, reinterpret_cast<const uint4 *>(ix->p3.p),
+                               drows, step, d_hist);
+        });
+    } else {
+        const uint64_t blocks = (ix->rows + 1023) / 1024, step = blocks / 4096 + 1, grid = (blocks + step - 1) / step;
+        err = pass(ix->len_hist, sizeof(ix->len_hist), [&] {
+            hipLaunchKernelGGL(len_census_kernel, dim3((unsigned)grid), dim3(256), 0, nullptr, ix->pk, ix->rows, shift, step, d_hist);
+        });
+        // ... and, exactly, WHICH overlaps occur (every row, not a sample): the sweeps for k - 1 >= 64 allocate, clear and fold
+        // only the level arrays some row of the index can write to (memo_sweep_cons.hip: level_plan)
+        if (err == hipSuccess)
+            err = pass(ix->len_seen, sizeof(ix->len_seen), [&] {
+                hipLaunchKernelGGL(len_seen_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, nullptr, ix->pk, ix->rows,
+                                   shift, d_hist);
+            });
     }
-    if (!ix->pk || (ix->packed_fmt != 4 && ix->packed_fmt != 6 && ix->packed_fmt != 12)) return MEMO_OK;
-    HIP_TRY(hipMalloc(&d_hist, sizeof(ix->len_hist)));
-    const uint64_t blocks = (ix->rows + 1023) / 1024, step = blocks / 4096 + 1, grid = (blocks + step - 1) / step;
-    hipError_t err = hipMemsetAsync(d_hist, 0, sizeof(ix->len_hist), nullptr);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(len_census_kernel, dim3((unsigned)grid), dim3(256), 0, nullptr, ix->pk, ix->rows,
-                           ix->packed_fmt == 12 ? 0 : 16, step, d_hist);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipMemcpy(ix->len_hist, d_hist, sizeof(ix->len_hist), hipMemcpyDeviceToHost);
-    // ... and, exactly, WHICH overlaps occur (every row, not a sample): the sweeps for k - 1 >= 64 allocate, clear and fold
-    // only the level arrays some row of the index can write to (memo_sweep_cons.hip: level_plan)
-    if (err == hipSuccess) err = hipMemsetAsync(d_hist, 0, 32, nullptr);
-    if (err == hipSuccess) {
-        const uint64_t wg = (ix->rows + 1023) / 1024;
-        hipLaunchKernelGGL(len_seen_kernel, dim3((unsigned)(wg < 4096 ? wg : 4096)), dim3(256), 0, nullptr, ix->pk, ix->rows,
-                           ix->packed_fmt == 12 ? 0 : 16, d_hist);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipMemcpy(ix->len_seen, d_hist, 32, hipMemcpyDeviceToHost);
-    (void)hipFree(d_hist);
     if (err != hipSuccess) return fail(MEMO_EHIP, "overlap census: %s", hipGetErrorString(err));
     for (unsigned int c : ix->len_hist) ix->len_hist_rows += c;
-    ix->len_seen_exact = 1;
+    // (the dense rows' histogram: when rows that never write were left out of them, scale it to the index's rows so
+    // that shares are shares of ix->rows, as they are for an index with 4-byte rows)
+    if (dense_only && ix->boff3 && ix->len_hist_rows) {
+        const double gone = (double)(ix->rows - ix->rows3) / (double)ix->rows3;
+        ix->len_hist[255] += (unsigned int)(gone * (double)ix->len_hist_rows);
+        ix->len_hist_rows += (unsigned int)(gone * (double)ix->len_hist_rows);
+    }
+    ix->len_seen_exact = dense_only ? 0 : 1;
     return MEMO_OK;
 }
 
 extern "C" {
+
+const char *memo_last_error(void) { return g_err; }
+
+const char *memo_version(void) { return "memo_amd 0.1 (gfx950)"; }
+
+int memo_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+int memo_index_create(uint64_t rows, int32_t device, memo_index_t **out) {
+    if (!out) return fail(MEMO_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (rows > ((uint64_t)1 << 40)) return fail(MEMO_EINVAL, "too many rows");
+    memo_index *ix = nullptr;
+    if (int rc = new_index(rows, device, nullptr, &ix)) return rc;
+    DeviceGuard guard(device);
+    const uint64_t padded = ix->padded;
+    hipError_t err = ix->s.alloc(padded);
+    if (err == hipSuccess) err = ix->e.alloc(padded);
+    if (err == hipSuccess) err = ix->o.alloc(padded);
+    if (err != hipSuccess) {
+        memo_index_destroy(ix);
+        return fail(MEMO_EHIP, "hipMalloc of %zu bytes x3 failed: %s", (size_t)padded * sizeof(int64_t), hipGetErrorString(err));
+    }
+    *out = ix;
+    return MEMO_OK;
+}
+
+void memo_index_destroy(memo_index_t *ix) {
+    if (!ix) return;
+    DeviceGuard guard(ix->device);
+    rows_changed(ix, kLevelColumns);  // (views and tile tables have no owner of their own)
+    ix->d_status.reset();             // (every index has one: this hipFree is what waits for the device before the retire list goes)
+    flush_retired(ix);
+    delete ix;
+}
+
+int memo_index_upload(memo_index_t *ix, const int64_t *start, const int64_t *end,
+                      const int64_t *annot, uint64_t rows) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (rows != ix->rows) return fail(MEMO_EINVAL, "upload of %llu rows into an index of %llu",
+                                      (unsigned long long)rows, (unsigned long long)ix->rows);
+    return memo_index_upload_rows(ix, 0, start, end, annot, rows);
+}
+
+int memo_index_upload_rows(memo_index_t *ix, uint64_t row_offset, const int64_t *start,
+                           const int64_t *end, const int64_t *annot, uint64_t rows) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (row_offset > ix->rows || rows > ix->rows - row_offset)
+        return fail(MEMO_EINVAL, "rows [%llu, +%llu) do not fit an index of %llu rows",
+                    (unsigned long long)row_offset, (unsigned long long)rows, (unsigned long long)ix->rows);
+    if (rows && (!start || !end || !annot)) return fail(MEMO_EINVAL, "column pointer is NULL");
+    if (int rc = need_wide(ix)) return rc;
+    DeviceGuard guard(ix->device);
+    rows_changed(ix, kLevelColumns);
+    if (rows) {
+        HIP_TRY(hipMemcpy(ix->s + row_offset, start, rows * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->e + row_offset, end, rows * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->o + row_offset, annot, rows * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    return MEMO_OK;
+}
+
+int memo_index_truncate(memo_index_t *ix, uint64_t rows) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (rows > ix->rows) return fail(MEMO_EINVAL, "cannot grow an index (%llu > %llu rows)",
+                                     (unsigned long long)rows, (unsigned long long)ix->rows);
+    if (int rc = need_wide(ix)) return rc;
+    DeviceGuard guard(ix->device);
+    rows_changed(ix, kLevelColumns);
+    ix->rows = rows;  // `padded` keeps the allocated size; finalize() rewrites the sentinel rows behind `rows`
+    return MEMO_OK;
+}
+
+int memo_index_columns(memo_index_t *ix, int64_t **d_start, int64_t **d_end, int64_t **d_annot) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (int rc = need_wide(ix)) return rc;
+    DeviceGuard guard(ix->device);
+    rows_changed(ix, kLevelColumns);  // (it only hands out pointers, but the caller may be about to rewrite the rows through them)
+    if (d_start) *d_start = ix->s;
+    if (d_end) *d_end = ix->e;
+    if (d_annot) *d_annot = ix->o;
+    return MEMO_OK;
+}
+
+int memo_index_finalize(memo_index_t *ix, int32_t bucket_shift, int32_t allow_sort) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (int rc = need_wide(ix)) return rc;
+    if (bucket_shift <= 0) bucket_shift = kDefaultBucketShift;
+    if (bucket_shift > 8) return fail(MEMO_EINVAL, "bucket_shift must be <= 8 (tile width 256)");
+    DeviceGuard guard(ix->device);
+    hipStream_t st = nullptr;
+    const uint64_t rows = ix->rows;
+    // (the pk / pa allocations stay: a device sort below leaves the words stale, and the pack that follows reuses them)
+    rows_changed(ix, kLevelColumns, true);
+    {
+        const uint64_t npad = ix->padded - rows;
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, st,
+                           ix->s, ix->e, ix->o, rows, ix->padded);
+        HIP_TRY(hipGetLastError());
+    }
+    uint64_t h[8] = {0};
+    ix->was_sorted = 1;
+    if (rows) {
+        HIP_TRY(hipMemsetAsync(ix->d_scratch, 0, 64, st));
+        const unsigned grid = (unsigned)(rows / 256 + 1 < 4096 ? rows / 256 + 1 : 4096);
+        hipLaunchKernelGGL(check_rows_kernel, dim3(grid), dim3(256), 0, st, ix->s, ix->e, rows,
+                           ix->d_scratch);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(h, ix->d_scratch, 24, hipMemcpyDeviceToHost));
+        if (h[2]) return fail(MEMO_EINVAL, "%llu rows have coordinates beyond +-2^61", (unsigned long long)h[2]);
+        if (int rc = ix->long_rows.collect(ix, h[1], st)) return rc;  // rows with end < start: set aside for long_rows_kernel
+        if (h[0]) {
+            ix->was_sorted = 0;
+            if (!allow_sort)
+                return fail(MEMO_EUNSORTED, "rows are not sorted by start (%llu descents)",
+                            (unsigned long long)h[0]);
+            char msg[256] = "";
+            if (memo_sort_rows_by_start(ix->s, ix->e, ix->o, rows, ix->padded, st, msg, sizeof msg) != 0)
+                return fail(MEMO_EHIP, "device sort failed: %s", msg);
+        }
+        HIP_TRY(hipMemcpy(&ix->min_s, ix->s, sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&ix->max_s, ix->s + (rows - 1), sizeof(int64_t), hipMemcpyDeviceToHost));
+    } else {
+        ix->min_s = 0;
+        ix->max_s = -1;
+    }
+    // buckets 0 .. ceil((max_s + 1) / width), plus one pinned to `rows`
+    const int64_t top = ix->max_s < 0 ? 0 : ix->max_s;
+    const uint64_t nb = (uint64_t)((top >> bucket_shift) + 3);
+    HIP_TRY(ix->boff.alloc(nb));
+    hipLaunchKernelGGL(bucket_table_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st,
+                       ix->s, rows, ix->boff, nb, bucket_shift);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    ix->nb = nb;
+    ix->bshift = bucket_shift;
+    ix->finalized = 1;
+    return MEMO_OK;
+}
 
 int memo_index_pack(memo_index_t *ix, int32_t keep_wide) {
     if (!ix) return fail(MEMO_EINVAL, "index is NULL");
@@ -708,84 +615,67 @@ int memo_index_pack(memo_index_t *ix, int32_t keep_wide) {
     if (ix->rows && ix->min_s < 0) return fail(MEMO_EINVAL, "rows with a negative start cannot be packed");
     DeviceGuard guard(ix->device);
     hipStream_t st = nullptr;
-    // the pass is timed on the device (info.pack_ms): SURVEY.md 8(d) wants the narrowing pass reported
-    // apart from the query.  Event pair around the census and the packing kernel; allocation is outside.
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIP_TRY(hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) {
-        (void)hipEventDestroy(ev0);
-        return fail(MEMO_EHIP, "hipEventCreate failed");
-    }
-    struct Events {
-        hipEvent_t a, b;
-        ~Events() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    } events{ev0, ev1};
-    // a packed copy of the same size is reused (packing again after a re-finalize, or to time the pass)
-    drop_dense(ix);  // derived from the words that are about to be rewritten
-    drop_packed_views(ix);
-    const bool had = ix->pk && ix->packed_rows == ix->padded;
-    if (!had) drop_packed(ix);
-    ix->packed_fmt = 0;
-    if (!ix->pk) HIP_TRY(hipMalloc(&ix->pk, ix->padded * sizeof(uint32_t)));
+    // (words of the same size are reused -- packing again after a re-finalize, or to time the pass; pa stays with them until the
+    // layout is known)
+    rows_changed(ix, kLevelWords, ix->pk && ix->packed_rows == ix->padded);
+    if (!ix->pk) HIP_TRY(ix->pk.alloc(ix->padded));
     ix->packed_rows = ix->padded;
     uint64_t h[8] = {0};
-    HIP_TRY(hipEventRecord(ev0, st));
-    // The layout follows from the largest annot: guessed from a sample of the annot column (every 256th row), packed at once with
-    // the exact census taken on the way, packed again only when a row the sample missed needs a wider layout.
-    auto layout_of = [](uint64_t top) { return top <= 255 ? 4 : (top <= 4095 ? 12 : 6); };
     int fmt = 4;
-    if (ix->rows) {
-        HIP_TRY(hipMemsetAsync(ix->d_scratch, 0, 64, st));
-        // (~2.6 * 10^5 samples: each is a cache line of its own from a step of 16 on, and every 256th row took 0.21 ms on 5 * 10^8 rows)
-        const uint64_t step = ix->rows > (1u << 20) ? (ix->rows >> 18 > 256 ? ix->rows >> 18 : 256) : 1, samples = ix->rows / step + 1;
-        const unsigned grid = (unsigned)(samples / 256 + 1 < 4096 ? samples / 256 + 1 : 4096);
-        hipLaunchKernelGGL(annot_census_kernel, dim3(grid), dim3(256), 0, st, ix->o, ix->rows, ix->d_scratch, step);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(h, ix->d_scratch, 64, hipMemcpyDeviceToHost));
-        if (h[3])
-            return fail(MEMO_EINVAL, "rows have an annot outside [0, 65535]: cannot be packed");
-        fmt = layout_of(h[5]);
-        for (int pass = 0; pass < 2; ++pass) {
-            if (fmt == 6 && !ix->pa) HIP_TRY(hipMalloc(&ix->pa, ix->padded * sizeof(uint16_t)));
-            HIP_TRY(hipMemsetAsync(ix->d_scratch, 0, 64, st));
-            hipLaunchKernelGGL(pack_rows_kernel, dim3(4096), dim3(256), 0, st, ix->s, ix->e, ix->o, ix->rows, ix->padded, ix->pk,
-                               fmt == 6 ? ix->pa : nullptr, fmt, pass == 0 ? ix->d_scratch : nullptr);
-            HIP_TRY(hipGetLastError());
-            if (pass) break;
-            HIP_TRY(hipMemcpyAsync(h, ix->d_scratch, 64, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (h[3])
-                return fail(MEMO_EINVAL, "%llu rows have an annot outside [0, 65535]: cannot be packed", (unsigned long long)h[3]);
-            if (layout_of(h[5]) == fmt) break;
-            fmt = layout_of(h[5]);  // (a row the sample missed: once more, in the layout it needs)
-        }
-    } else {
-        hipLaunchKernelGGL(pack_rows_kernel, dim3(64), dim3(256), 0, st, ix->s, ix->e, ix->o, ix->rows, ix->padded, ix->pk, nullptr, fmt,
-                           nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    ix->max_annot = h[5];
-    if (fmt != 6 && ix->pa) {
-        (void)hipFree(ix->pa);
-        ix->pa = nullptr;
-    }
-    ix->row_order = 0;
-    if (const int mode = row_order_mode(ix); mode && (fmt == 4 || fmt == 12) && ix->rows) {  // the order inside a bucket (memo_interleave.hip)
-        if (int rc = interleave_words(ix->pk, ix->boff, ix->nb, ix->bshift, fmt, mode, st, ix->d_scratch)) return rc;
-        ix->row_order = mode;
-    }
-    HIP_TRY(hipEventRecord(ev1, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    // The pass is timed on the device (info.pack_ms): SURVEY.md 8(d) wants the narrowing pass reported apart from the query.
+    // Between the events: the census, the packing kernel and the order inside the buckets; the words' allocation is outside.
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    const int rc = build_timed(st, &ms, [&]() -> int {
+        // The layout follows from the largest annot: guessed from a sample of the annot column (every 256th row), packed at once with
+        // the exact census taken on the way, packed again only when a row the sample missed needs a wider layout.
+        auto layout_of = [](uint64_t top) { return top <= 255 ? 4 : (top <= 4095 ? 12 : 6); };
+        if (ix->rows) {
+            HIP_TRY(hipMemsetAsync(ix->d_scratch, 0, 64, st));
+            // (~2.6 * 10^5 samples: each is a cache line of its own from a step of 16 on, and every 256th row took 0.21 ms on 5 * 10^8 rows)
+            const uint64_t step = ix->rows > (1u << 20) ? (ix->rows >> 18 > 256 ? ix->rows >> 18 : 256) : 1, samples = ix->rows / step + 1;
+            const unsigned grid = (unsigned)(samples / 256 + 1 < 4096 ? samples / 256 + 1 : 4096);
+            hipLaunchKernelGGL(annot_census_kernel, dim3(grid), dim3(256), 0, st, ix->o, ix->rows, ix->d_scratch, step);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(h, ix->d_scratch, 64, hipMemcpyDeviceToHost));
+            if (h[3])  // (the index is left with packed_fmt == 0 and its buffers)
+                return fail(MEMO_EINVAL, "rows have an annot outside [0, 65535]: cannot be packed");
+            fmt = layout_of(h[5]);
+            for (int pass = 0; pass < 2; ++pass) {
+                if (fmt == 6 && !ix->pa) HIP_TRY(ix->pa.alloc(ix->padded));
+                HIP_TRY(hipMemsetAsync(ix->d_scratch, 0, 64, st));
+                hipLaunchKernelGGL(pack_rows_kernel, dim3(4096), dim3(256), 0, st, ix->s, ix->e, ix->o, ix->rows, ix->padded, ix->pk,
+                                   fmt == 6 ? ix->pa.p : nullptr, fmt, pass == 0 ? ix->d_scratch.p : nullptr);
+                HIP_TRY(hipGetLastError());
+                if (pass) break;
+                HIP_TRY(hipMemcpyAsync(h, ix->d_scratch, 64, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                if (h[3])
+                    return fail(MEMO_EINVAL, "%llu rows have an annot outside [0, 65535]: cannot be packed", (unsigned long long)h[3]);
+                if (layout_of(h[5]) == fmt) break;
+                fmt = layout_of(h[5]);  // (a row the sample missed: once more, in the layout it needs)
+            }
+        } else {
+            hipLaunchKernelGGL(pack_rows_kernel, dim3(64), dim3(256), 0, st, ix->s, ix->e, ix->o, ix->rows, ix->padded, ix->pk, nullptr, fmt,
+                               nullptr);
+            HIP_TRY(hipGetLastError());
+        }
+        ix->max_annot = h[5];
+        if (fmt != 6) ix->pa.reset();  // (only format 6 has the annot column)
+        ix->row_order = 0;
+        if (const int mode = row_order_mode(ix); mode && (fmt == 4 || fmt == 12) && ix->rows) {  // the order inside a bucket (memo_interleave.hip)
+            if (int r = interleave_words(ix->pk, ix->boff, ix->nb, ix->bshift, fmt, mode, st, ix->d_scratch)) return r;
+            ix->row_order = mode;
+        }
+        return MEMO_OK;
+    });
+    if (rc) return rc;
     ix->pack_ms = ms;
     ix->packed_fmt = fmt;
-    if (int rc = memo_len_census(ix)) return rc;
+    if (int rc2 = memo_len_census(ix)) return rc2;
     if (!keep_wide) {
-        (void)hipFree(ix->s);
-        (void)hipFree(ix->e);
-        (void)hipFree(ix->o);
-        ix->s = ix->e = ix->o = nullptr;
+        ix->s.reset();
+        ix->e.reset();
+        ix->o.reset();
         ix->has_wide = 0;
     }
     return MEMO_OK;
@@ -794,33 +684,26 @@ int memo_index_pack(memo_index_t *ix, int32_t keep_wide) {
 int memo_index_pack_dense(memo_index_t *ix, int32_t keep_packed) {
     if (!ix) return fail(MEMO_EINVAL, "index is NULL");
     if (!ix->finalized) return fail(MEMO_ENOTREADY, "index not finalized");
-    if (ix->p3) {
-        if (!keep_packed && ix->pk) {
-            DeviceGuard guard(ix->device);
-            drop_packed_views(ix);
-            (void)hipFree(ix->pk);
-            ix->pk = nullptr;
-            ix->packed_rows = 0;
-        }
-        return MEMO_OK;
-    }
-    if (!ix->pk || (ix->packed_fmt != 4 && !(ix->packed_fmt == 12 && ix->max_annot <= 511)))
-        return fail(MEMO_EINVAL, "dense rows are built from the 4-byte rows: memo_index_pack first, and every annot <= 511");
     DeviceGuard guard(ix->device);
-    hipStream_t st = nullptr;
-    const uint64_t groups = dense_groups_for(ix->padded);
-    HIP_TRY(hipMalloc(&ix->p3, groups * 16));
-    hipLaunchKernelGGL(pack3_rows_kernel, dim3(4096), dim3(256), 0, st, ix->pk, ix->padded, groups,
-                       reinterpret_cast<uint4 *>(ix->p3), ix->packed_fmt == 12 ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    ix->rows3 = ix->rows;
-    ix->padded3 = ix->padded;
-    if (int rc = dense_compact(ix)) return rc;
-    if (!keep_packed) {
+    if (!ix->p3) {
+        if (!ix->pk || (ix->packed_fmt != 4 && !(ix->packed_fmt == 12 && ix->max_annot <= 511)))
+            return fail(MEMO_EINVAL, "dense rows are built from the 4-byte rows: memo_index_pack first, and every annot <= 511");
+        hipStream_t st = nullptr;
+        const uint64_t groups = dense_groups_for(ix->padded);
+        HIP_TRY(ix->p3.alloc(groups * 4));
+        hipLaunchKernelGGL(pack3_rows_kernel, dim3(4096), dim3(256), 0, st, ix->pk, ix->padded, groups,
+                           reinterpret_cast<uint4 *>(ix->p3.p), ix->packed_fmt == 12 ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        ix->rows3 = ix->rows;
+        ix->padded3 = ix->padded;
+        if (int rc = dense_compact(ix)) return rc;
+    }
+    // Not a change of the rows: they stay what they are, and one copy of them leaves with its views.  packed_fmt stays as it is -- the
+    // state a dense builder produces; on an index that had its dense rows already this is all the call does.
+    if (!keep_packed && ix->pk) {
         drop_packed_views(ix);
-        (void)hipFree(ix->pk);
-        ix->pk = nullptr;
+        ix->pk.reset();
         ix->packed_rows = 0;
     }
     return MEMO_OK;
@@ -843,7 +726,7 @@ static void fill_info(const memo_index *ix, memo_index_info_t *info) {
     info->last_sweep = ix->last_sweep;
     info->last_variant = ix->last_variant;
     info->dense_rows = ix->p3 ? 1 : 0;
-    info->long_rows = ix->n_long;
+    info->long_rows = ix->long_rows.n;
     info->max_annot = ix->max_annot;
     info->bucket_base = ix->bbase;
     info->device_bytes = (ix->has_wide ? ix->padded * 3 * sizeof(int64_t) : 0) + ix->nb * sizeof(int64_t) + 128 +
@@ -854,18 +737,11 @@ static void fill_info(const memo_index *ix, memo_index_info_t *info) {
     info->last_view_ms = ix->last_view_ms;
     info->row_order = ix->row_order;
     uint64_t side = ix->retired_bytes;
-    for (const memo_index::DenseView &v : ix->views) {
-        side += v.p3 ? v.bytes + ix->nb * 8 : 0;
-        info->views_resident += v.p3 ? 1 : 0;
-    }
-    for (const memo_index::DenseView &v : ix->views6) {
-        side += v.p3 ? v.bytes + ix->nb * 8 : 0;
-        info->views_resident += v.p3 ? 1 : 0;
-    }
-    for (const memo_index::DenseView &v : ix->pviews) {
-        side += v.p3 ? v.bytes + ix->nb * 8 : 0;
-        info->views_resident += v.p3 ? 1 : 0;
-    }
+    for (bool dense : {true, false})
+        each_view(ix, dense, [&](const memo_index::DenseView &v) {
+            side += v.p3 ? v.bytes + ix->nb * 8 : 0;
+            info->views_resident += v.p3 ? 1 : 0;
+        });
     for (const memo_index::TileTable &t : ix->ttabs) side += (uint64_t)t.n * 32;
     info->tile_tables_resident = (int32_t)ix->ttabs.size();
     info->side_bytes = side;
@@ -905,66 +781,38 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info) {
     return MEMO_OK;
 }
 
+
+// {option, the field it sets, the values it takes: `lo`, and `first` .. `hi`, the refusal of any other}
+static const struct {
+    int32_t option;
+    int memo_index::*field;
+    int64_t lo, first, hi;
+    const char *takes;
+} kOptions[] = {
+    {MEMO_OPT_VIEWS, &memo_index::views_on, 0, 1, 1, "MEMO_OPT_VIEWS takes 0 or 1"},
+    {MEMO_OPT_VIEW_BUDGET_PCT, &memo_index::view_budget_pct, 0, 1, 1600, "MEMO_OPT_VIEW_BUDGET_PCT takes 0 .. 1600"},
+    {MEMO_OPT_BUILD_COST_PCT, &memo_index::build_cost_pct, 0, 1, 100000, "MEMO_OPT_BUILD_COST_PCT takes 0 .. 100000"},
+    {MEMO_OPT_VIEW_PLACES, &memo_index::view_places, 0, 1, 1, "MEMO_OPT_VIEW_PLACES takes 0 or 1"},
+    {MEMO_OPT_VIEW_LIVE, &memo_index::view_live, 0, 1, 1, "MEMO_OPT_VIEW_LIVE takes 0 or 1"},  // (a copy already made stays: it answers exactly what the flagged view does)
+    {MEMO_OPT_WIDE_TILES, &memo_index::wide_tiles, 0, 1, 1, "MEMO_OPT_WIDE_TILES takes 0 or 1"},
+    {MEMO_OPT_VIEW_ROWS, &memo_index::view_rows, 0, 5, 6, "MEMO_OPT_VIEW_ROWS takes 0 (the library's choice), 5 or 6"},
+};
+
 int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value) {
     if (!ix) return fail(MEMO_EINVAL, "index is NULL");
-    if (option == MEMO_OPT_VIEWS) {
-        if (value != 0 && value != 1) return fail(MEMO_EINVAL, "MEMO_OPT_VIEWS takes 0 or 1");
-        const int before = ix->views_on;
-        ix->views_on = (int)value;
-        if (!value) {
+    for (const auto &o : kOptions) {
+        if (o.option != option) continue;
+        if (value != o.lo && (value < o.first || value > o.hi)) return fail(MEMO_EINVAL, "%s", o.takes);
+        const int before = ix->*o.field;
+        ix->*o.field = (int)value;
+        if (option == MEMO_OPT_VIEWS && !value) {
             DeviceGuard guard(ix->device);
             HIP_TRY(hipDeviceSynchronize());
-            for (int kind = 0; kind < 2; ++kind)
-            for (memo_index::DenseView &v : (kind ? ix->views6 : ix->views))
-                if (v.p3) {  // (their tile tables go with them)
-                    for (size_t i = 0; i < ix->ttabs.size();)
-                        if (ix->ttabs[i].rows_of == v.p3) {
-                            (void)hipFree(ix->ttabs[i].d);
-                            ix->ttabs.erase(ix->ttabs.begin() + (long)i);
-                        } else {
-                            ++i;
-                        }
-                }
-            drop_dense_views(ix);
-            drop_packed_views(ix);
+            // (the device is drained: the views are freed, not retired, and what drop_dense_views retires -- the tile tables made for
+            // them -- is freed at once; the tables of the dense rows themselves stay)
+            rows_changed(ix, kLevelDerived);
             flush_retired(ix);
         }
-        return before;
-    }
-    if (option == MEMO_OPT_VIEW_BUDGET_PCT) {
-        if (value < 0 || value > 1600) return fail(MEMO_EINVAL, "MEMO_OPT_VIEW_BUDGET_PCT takes 0 .. 1600");
-        const int before = ix->view_budget_pct;
-        ix->view_budget_pct = (int)value;
-        return before;
-    }
-    if (option == MEMO_OPT_BUILD_COST_PCT) {
-        if (value < 0 || value > 100000) return fail(MEMO_EINVAL, "MEMO_OPT_BUILD_COST_PCT takes 0 .. 100000");
-        const int before = ix->build_cost_pct;
-        ix->build_cost_pct = (int)value;
-        return before;
-    }
-    if (option == MEMO_OPT_VIEW_PLACES) {
-        if (value != 0 && value != 1) return fail(MEMO_EINVAL, "MEMO_OPT_VIEW_PLACES takes 0 or 1");
-        const int before = ix->view_places;
-        ix->view_places = (int)value;
-        return before;
-    }
-    if (option == MEMO_OPT_VIEW_LIVE) {  // (a copy already made stays: it answers exactly what the flagged view does)
-        if (value != 0 && value != 1) return fail(MEMO_EINVAL, "MEMO_OPT_VIEW_LIVE takes 0 or 1");
-        const int before = ix->view_live;
-        ix->view_live = (int)value;
-        return before;
-    }
-    if (option == MEMO_OPT_WIDE_TILES) {
-        if (value != 0 && value != 1) return fail(MEMO_EINVAL, "MEMO_OPT_WIDE_TILES takes 0 or 1");
-        const int before = ix->wide_tiles;
-        ix->wide_tiles = (int)value;
-        return before;
-    }
-    if (option == MEMO_OPT_VIEW_ROWS) {
-        if (value != 0 && value != 5 && value != 6) return fail(MEMO_EINVAL, "MEMO_OPT_VIEW_ROWS takes 0 (the library's choice), 5 or 6");
-        const int before = ix->view_rows;
-        ix->view_rows = (int)value;
         return before;
     }
     return fail(MEMO_EINVAL, "unknown index option %d", option);
@@ -1006,160 +854,19 @@ int memo_index_prepare(memo_index_t *ix, int32_t k, int32_t num_docs, int32_t me
     return MEMO_OK;
 }
 
-// The drop-in for memo_query.py:103-104 + :70: host columns in, host result out.  Rows that can be packed
-// (start-sorted, start >= 0, annot in [0, 65535]: every index dap_to_bed.py writes) and k <= 256 take the
-// fast way in -- narrowed on the host into pinned memory, 4-6 B/row over PCIe, PackedRows kernels
-// (memo_hostpack.hip); anything else is uploaded as int64 columns and finalized on the device.
-// stride 1: three columns; 3: ROWS -- filter_pq's own [M, 3] array, row-major (start = the array, end = start + 1, annot = start + 2)
-static int one_shot(const int64_t *start, const int64_t *end, const int64_t *annot, uint64_t rows,
-                    int64_t qs, int64_t qe, int32_t k, int32_t num_docs, void *out, int32_t device,
-                    bool membership, int stride = 1) {
-    if (rows && (!start || !end || !annot)) return fail(MEMO_EINVAL, "column pointer is NULL");
-    const uint64_t st = (uint64_t)stride;
-    memo_index_t *ix = nullptr;
-    int rc = MEMO_OK;
-    // MEMO_TIMING=1: phase times of the call on stderr (host clock; every phase ends synchronised)
-    const bool timing = getenv("MEMO_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    const auto t0 = now();
-    const double pinned0 = pinned_alloc_ms_total();
-    double in_ms[3] = {0, 0, 0};  // the last builder's device allocation / packing + copies / finish (table, census, destroy)
-    if (rows && k > 1 && k - 1 <= 255 && g_one_shot_way != 1) {
-        // the dense rows first (3.2 B per row over PCIe and in HBM, sweep_conservation_halo3_kernel) when they can
-        // answer THIS query -- judged from the first and last start before the rows are touched, and again from the
-        // largest annot once they have been packed; else (or when a row does not fit them) the 4-byte words
-        const bool try_dense = g_one_shot_way != 2 &&
-                               memo_dense_rows_can_answer(rows, start[0], start[(rows - 1) * st], 0, k, num_docs, membership);
-        for (int dense = try_dense ? 1 : 0; dense >= 0 && !ix; --dense) {
-            memo_builder_t *b = nullptr;
-            const auto ta = now();
-            if ((rc = memo_builder_create_rows(rows, device, 0, dense ? MEMO_ROWS_DENSE : MEMO_ROWS_PACKED, &b))) return rc;
-            const auto tb = now();
-            rc = stride == 1 ? memo_builder_push(b, start, end, annot, rows) : memo_builder_push_rows(b, start, rows);
-            const auto tc = now();
-            if (!rc) rc = memo_builder_finish(b, &ix);
-            const int why = builder_why(b);
-            memo_builder_destroy(b);
-            in_ms[0] = ms(ta, tb), in_ms[1] = ms(tb, tc), in_ms[2] = ms(tc, now());
-            if (rc == MEMO_EUNPACKABLE) {
-                rc = MEMO_OK;
-                ix = nullptr;
-                if (dense && (why & ~16)) break;  // (unsorted, negative start, wild annot: the 4-byte words would refuse them too)
-            } else if (rc) {
-                return rc;
-            } else if (dense && !memo_dense_rows_can_answer(ix->rows, ix->min_s, ix->max_s, ix->max_annot, k, num_docs, membership)) {
-                // (the rule query_conservation applies: ALL the index's rows against its span -- rows that can never write
-                // may have left the dense rows, memo_common.h: boff3 -- and the largest annot against the result matrix)
-                memo_index_destroy(ix);  // (an annot outside the result matrix: the 4-byte kernels flag the reference's IndexError)
-                ix = nullptr;
-            }
-        }
-    }
-    if (!ix) {
-        // (rows that could not be packed on the host -- unsorted, wild annots, k > 256: the int64 columns go up and the device validates
-        // and sorts.  From ROWS the three columns are made here first: the rare way, one more pass over the host's memory)
-        std::vector<int64_t> cols;
-        if (stride != 1 && rows) {
-            try {
-                cols.resize(3 * rows);
-            } catch (const std::exception &) {
-                return fail(MEMO_EHIP, "out of host memory for the columns of %llu rows", (unsigned long long)rows);
-            }
-            int64_t *cs = cols.data(), *ce = cs + rows, *ca = ce + rows;
-            HostPool::get().run((int)((rows + 65535) / 65536), [&](int t) {
-                const uint64_t i0 = (uint64_t)t * 65536, i1 = i0 + 65536 < rows ? i0 + 65536 : rows;
-                for (uint64_t i = i0; i < i1; ++i) cs[i] = start[3 * i], ce[i] = start[3 * i + 1], ca[i] = start[3 * i + 2];
-            });
-            start = cs, end = ce, annot = ca;
-        }
-        if ((rc = memo_index_create(rows, device, &ix))) return rc;
-        rc = memo_index_upload(ix, start, end, annot, rows);
-        if (!rc) rc = memo_index_finalize(ix, 0, 1);
-        if (rc) {
-            memo_index_destroy(ix);
-            return rc;
-        }
-    }
-    const auto t1 = now();
-    auto t2 = t1;
-    void *d_out = nullptr;
-    size_t bytes = 0;
-    do {
-        if (qe < qs) { rc = fail(MEMO_EINVAL, "ValueError: negative dimensions are not allowed (window end < start)"); break; }
-        const int64_t L = qe - qs;
-        if (L > 0 && !out) { rc = fail(MEMO_EINVAL, "output pointer is NULL"); break; }
-        bytes = membership ? (size_t)L * ((num_docs + 31) / 32) * 4 : (size_t)L * 2;
-        DeviceGuard guard(device);
-        if (bytes) {
-            hipError_t err = hipMalloc(&d_out, bytes);
-            if (err != hipSuccess) { rc = fail(MEMO_EHIP, "hipMalloc(%zu): %s", bytes, hipGetErrorString(err)); break; }
-        }
-        rc = membership ? memo_query_membership_dev(ix, qs, qe, k, num_docs, (uint32_t *)d_out, nullptr)
-                        : memo_query_conservation_dev(ix, qs, qe, k, num_docs, (uint16_t *)d_out, nullptr);
-        if (rc) break;
-        if ((rc = memo_query_check(ix, nullptr))) break;
-        g_last_one_shot_sweep = ix->last_sweep;
-        t2 = now();
-        if (bytes) rc = download_pipelined(device, out, d_out, bytes, nullptr);
-    } while (0);
-    if (timing && !rc) {
-        const auto t3 = now();
-        fprintf(stderr,
-                "memo one-shot: %llu rows %s: rows in %.1f ms (%.1f GB/s of int64 columns; allocation %.1f, packing + copies %.1f "
-                "with %d host threads, finish %.1f; pinned slots allocated in this call %.1f), result alloc + sweep + check %.1f ms, result out %.1f ms (%.1f GB/s), total %.1f ms\n",
-                (unsigned long long)rows, ix->has_wide ? "as int64 columns" : (ix->packed_fmt == 6 ? "packed to 6 B" : ix->pk ? "packed to 4 B" : "packed to 3.2 B (dense rows)"),
-                ms(t0, t1), rows * 24.0 / 1e6 / (ms(t0, t1) + 1e-9), in_ms[0], in_ms[1], memo_host_threads(nullptr, nullptr), in_ms[2], pinned_alloc_ms_total() - pinned0, ms(t1, t2), ms(t2, t3),
-                bytes / 1e6 / (ms(t2, t3) + 1e-9), ms(t0, t3));
-    }
-    if (d_out) {
-        DeviceGuard guard(device);
-        (void)hipFree(d_out);
-    }
-    memo_index_destroy(ix);
-    return rc;
-}
-
-int memo_conservation(const int64_t *start, const int64_t *end, const int64_t *annot, uint64_t rows,
-                      int64_t qs, int64_t qe, int32_t k, int32_t num_docs, uint16_t *out,
-                      int32_t device) {
-    return one_shot(start, end, annot, rows, qs, qe, k, num_docs, out, device, false);
-}
-
-int memo_membership(const int64_t *start, const int64_t *end, const int64_t *annot, uint64_t rows,
-                    int64_t qs, int64_t qe, int32_t k, int32_t num_docs, uint32_t *out_bits,
-                    int32_t device) {
-    return one_shot(start, end, annot, rows, qs, qe, k, num_docs, out_bits, device, true);
-}
-
-int memo_conservation_rows(const int64_t *rows3, uint64_t rows, int64_t qs, int64_t qe, int32_t k, int32_t num_docs, uint16_t *out,
-                           int32_t device) {
-    if (rows && !rows3) return fail(MEMO_EINVAL, "rows pointer is NULL");
-    return one_shot(rows3, rows3 + 1, rows3 + 2, rows, qs, qe, k, num_docs, out, device, false, 3);
-}
-
-int memo_membership_rows(const int64_t *rows3, uint64_t rows, int64_t qs, int64_t qe, int32_t k, int32_t num_docs, uint32_t *out_bits,
-                         int32_t device) {
-    if (rows && !rows3) return fail(MEMO_EINVAL, "rows pointer is NULL");
-    return one_shot(rows3, rows3 + 1, rows3 + 2, rows, qs, qe, k, num_docs, out_bits, device, true, 3);
-}
-
 int memo_synth_fill(memo_index_t *ix, uint64_t row_begin, uint64_t num, uint64_t den,
                     int32_t num_docs, uint64_t seed) {
     if (!ix) return fail(MEMO_EINVAL, "index is NULL");
     if (num == 0 || den == 0 || num_docs < 2) return fail(MEMO_EINVAL, "bad generator parameters");
-    if (!ix->has_wide) return fail(MEMO_EINVAL, "the int64 columns were dropped");
+    if (int rc = need_wide(ix)) return rc;
     DeviceGuard guard(ix->device);
-    drop_packed(ix);
+    rows_changed(ix, kLevelColumns);
     if (ix->rows) {
         hipLaunchKernelGGL(synth_rows_kernel, dim3(4096), dim3(256), 0, nullptr, ix->s, ix->e, ix->o,
                            ix->rows, row_begin, num, den, (uint64_t)(num_docs - 1), seed);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
     }
-    ix->finalized = 0;
     return MEMO_OK;
 }
 
@@ -1215,66 +922,6 @@ int memo_bin_conservation_dev(const uint16_t *d_vec, int64_t L, const int64_t *e
     if (err == hipSuccess) err = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, st);
     if (err == hipSuccess) err = hipStreamSynchronize(st);
     if (err != hipSuccess) return fail(MEMO_EHIP, "binning failed: %s", hipGetErrorString(err));
-    return MEMO_OK;
-}
-
-// wire layout: [count u32, cap u32, overflow u32, 4 B pad][nibbles: 4 * ceil(n / 8) B][exceptions: cap * 8 B]
-size_t memo_transport_bytes(int64_t n, uint32_t cap) {
-    return 16 + (size_t)((n + 7) / 8) * 4 + (size_t)cap * 8;
-}
-
-int memo_transport_pack_dev(const uint8_t *d_vec, int64_t n, uint32_t cap, void *d_wire, int32_t device,
-                            void *stream) {
-    if (n < 0 || (n > 0 && (!d_vec || !d_wire))) return fail(MEMO_EINVAL, "bad transport arguments");
-    if (((uintptr_t)d_vec & 7) || ((uintptr_t)d_wire & 7)) return fail(MEMO_EINVAL, "transport buffers must be 8-byte aligned");
-    DeviceGuard guard(device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *w = static_cast<char *>(d_wire);
-    HIP_TRY(hipMemsetAsync(w, 0, 16, st));  // count = 0; the kernel fills in the capacity (no host staging)
-    const int64_t groups = (n + 7) / 8;
-    {
-        const int64_t blocks = (groups + 256 * 16 - 1) / (256 * 16);  // 32768 positions per workgroup
-        if (blocks >= ((int64_t)1 << 31)) return fail(MEMO_EINVAL, "slice too long for one launch");
-        const unsigned grid = (unsigned)(blocks ? blocks : 1);  // (an empty slice still gets its header)
-        hipLaunchKernelGGL(nibble_pack_kernel, dim3(grid), dim3(256), 0, st, d_vec, n,
-                           reinterpret_cast<uint32_t *>(w + 16),
-                           reinterpret_cast<unsigned long long *>(w + 16 + groups * 4),
-                           reinterpret_cast<unsigned int *>(w), cap);
-        HIP_TRY(hipGetLastError());
-    }
-    return MEMO_OK;
-}
-
-int memo_transport_unpack_dev(const void *d_wire, int64_t n, uint8_t *d_vec, int32_t device, void *stream) {
-    if (n < 0 || (n > 0 && (!d_vec || !d_wire))) return fail(MEMO_EINVAL, "bad transport arguments");
-    if (((uintptr_t)d_vec & 7) || ((uintptr_t)d_wire & 7)) return fail(MEMO_EINVAL, "transport buffers must be 8-byte aligned");
-    DeviceGuard guard(device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const char *w = static_cast<const char *>(d_wire);
-    const int64_t groups = (n + 7) / 8;
-    if (groups) {
-        const unsigned grid = (unsigned)(groups / 256 + 1 < 8192 ? groups / 256 + 1 : 8192);
-        hipLaunchKernelGGL(nibble_unpack_kernel, dim3(grid), dim3(256), 0, st,
-                           reinterpret_cast<const uint32_t *>(w + 16), n, d_vec);
-        hipLaunchKernelGGL(nibble_exceptions_kernel, dim3(256), dim3(256), 0, st,
-                           reinterpret_cast<const unsigned long long *>(w + 16 + groups * 4),
-                           reinterpret_cast<const unsigned int *>(w), n, d_vec);
-        HIP_TRY(hipGetLastError());
-    }
-    return MEMO_OK;
-}
-
-// exceptions the sender found (host value; synchronises `stream`).  More than the wire's capacity
-// means the slice cannot travel in this coding.
-int memo_transport_exceptions(const void *d_wire, int32_t device, void *stream, uint32_t *found, uint32_t *cap) {
-    if (!d_wire || !found || !cap) return fail(MEMO_EINVAL, "NULL argument");
-    DeviceGuard guard(device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    uint32_t head[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(head, d_wire, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *found = head[2] ? 0xFFFFFFFFu : head[0];  // word 2: a workgroup overflowed its staging (more than an eighth exceptions)
-    *cap = head[1];
     return MEMO_OK;
 }
 

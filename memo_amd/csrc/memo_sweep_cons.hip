@@ -919,14 +919,14 @@ constexpr int kHaloLoads = 6;  // 16-byte loads in flight per lane
 template <typename OutT>
 static int long_rows_conservation(const memo_index *ix, int64_t qs, int64_t qe, int32_t k, int ncols,
                                   OutT *d_out, hipStream_t st) {
-    if (!ix->n_long || g_prepare_only) return MEMO_OK;
+    if (!ix->long_rows.n || g_prepare_only) return MEMO_OK;
     if (int prc = refuse_plan_pointer(d_out)) return prc;
     const int64_t fqs = ix->whole_set ? ix->whole_qs : qs, fqe = ix->whole_set ? ix->whole_qe : qe;
-    hipLaunchKernelGGL((long_rows_conservation_kernel<OutT>), dim3((unsigned)ix->n_long), dim3(256), 0, st,
-                       ix->ls, ix->le, ix->lo, qs, qe, k - 1, ncols, d_out, ix->d_status, fqs, fqe);
+    hipLaunchKernelGGL((long_rows_conservation_kernel<OutT>), dim3((unsigned)ix->long_rows.n), dim3(256), 0, st,
+                       ix->long_rows.s(), ix->long_rows.e(), ix->long_rows.o(), qs, qe, k - 1, ncols, d_out, ix->d_status, fqs, fqe);
     if ((qe - qs) % (4 / (int)sizeof(OutT)))
-        hipLaunchKernelGGL((long_rows_tail_kernel<OutT>), dim3(1), dim3(256), 0, st, ix->ls, ix->le, ix->lo,
-                           (uint64_t)ix->n_long, qs, qe, k - 1, ncols, d_out, ix->d_status, fqs, fqe);
+        hipLaunchKernelGGL((long_rows_tail_kernel<OutT>), dim3(1), dim3(256), 0, st, ix->long_rows.s(), ix->long_rows.e(), ix->long_rows.o(),
+                           (uint64_t)ix->long_rows.n, qs, qe, k - 1, ncols, d_out, ix->d_status, fqs, fqe);
     HIP_TRY(hipGetLastError());
     return MEMO_OK;
 }

@@ -463,10 +463,10 @@ __global__ void long_rows_membership_kernel(const int64_t *ls, const int64_t *le
 
 static int long_rows_membership(const memo_index *ix, int64_t qs, int64_t qe, int32_t k, int ncols, int nw,
                                 uint32_t *d_out, hipStream_t st) {
-    if (!ix->n_long || g_prepare_only) return MEMO_OK;
+    if (!ix->long_rows.n || g_prepare_only) return MEMO_OK;
     if (int prc = refuse_plan_pointer(d_out)) return prc;
-    hipLaunchKernelGGL(long_rows_membership_kernel, dim3((unsigned)ix->n_long), dim3(256), 0, st, ix->ls,
-                       ix->le, ix->lo, qs, qe, k - 1, ncols, nw, d_out, ix->d_status,
+    hipLaunchKernelGGL(long_rows_membership_kernel, dim3((unsigned)ix->long_rows.n), dim3(256), 0, st, ix->long_rows.s(),
+                       ix->long_rows.e(), ix->long_rows.o(), qs, qe, k - 1, ncols, nw, d_out, ix->d_status,
                        ix->whole_set ? ix->whole_qs : qs, ix->whole_set ? ix->whole_qe : qe);
     HIP_TRY(hipGetLastError());
     return MEMO_OK;

@@ -19,6 +19,10 @@
 //
 // Not on the reference's path (the reference has one process and no wire): it carries the input
 // of print_res (memo_query.py:65-71) from the ranks that computed it to the one that prints it.
+//
+// The FIRST coding lives at the end of this file (memo_transport_pack_dev / _unpack_dev / _exceptions /
+// _bytes, declared in include/memo_amd_transport.h with the others): one nibble per position, values of
+// 15 and more in an exception list -- lossless, half the bytes when few values reach 15 (bench.py: --coding nibble).
 #include "memo_common.h"
 
 using namespace memo;
@@ -691,6 +695,156 @@ int memo_transport_runs_stats(const void *d_wire, int32_t device, void *stream, 
     HIP_TRY(hipStreamSynchronize(st));
     *b_taken = head[0];
     *b_capacity = head[1];
+    return MEMO_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// the first coding: one nibble per position
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// Transport coding of uint8 conservation results for the multi-GPU gather: one nibble per position
+// (values >= 15 become 15 and go to an exception list as position << 8 | value).  Lossless; halves
+// what a slice puts on its xGMI link when few values reach 15.
+__global__ __launch_bounds__(256) void nibble_pack_kernel(const uint8_t *in, int64_t n, uint32_t *nib,
+                                                          unsigned long long *exc, unsigned int *count,
+                                                          unsigned int cap) {
+    // A workgroup codes 32768 consecutive positions (16 rounds of 256 threads x 8 positions).  Exceptions
+    // are collected in LDS -- no barrier between the rounds, LDS atomics order themselves -- and appended
+    // with ONE global atomic per workgroup: a quarter of a million same-address atomics would cost
+    // milliseconds, and round 1's version, which met at three barriers per round, ran at a fifth of its
+    // memory bound.  More than 4096 exceptions in 32768 positions (an eighth of them >= 15) is not data this
+    // coding is for: the count is saturated so that the receiver sees an incomplete slice.
+    constexpr int kRounds = 16, kHeld = 4096;
+    __shared__ unsigned long long held[kHeld];
+    __shared__ unsigned int n_held, base;
+    if (threadIdx.x == 0) n_held = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) count[1] = cap;  // header word 1
+    __syncthreads();
+    const int64_t groups = (n + 7) / 8;
+#pragma unroll 4
+    for (int r = 0; r < kRounds; ++r) {
+        const int64_t g = ((int64_t)blockIdx.x * kRounds + r) * 256 + threadIdx.x;
+        if (g >= groups) break;
+        unsigned long long eight = 0;  // 8 results in one load (the tail group byte by byte)
+        if (g * 8 + 8 <= n) {
+            eight = *reinterpret_cast<const unsigned long long *>(in + g * 8);
+        } else {
+            for (int i = 0; g * 8 + i < n; ++i) eight |= (unsigned long long)in[g * 8 + i] << (8 * i);
+        }
+        uint32_t word = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const uint32_t v = (uint32_t)(eight >> (8 * i)) & 0xFFu;
+            if (v >= 15u) {
+                const unsigned int slot = atomicAdd(&n_held, 1u);
+                if (slot < (unsigned)kHeld) held[slot] = ((unsigned long long)(g * 8 + i) << 8) | v;
+            }
+            word |= (v < 15u ? v : 15u) << (4 * i);
+        }
+        nib[g] = word;
+    }
+    __syncthreads();
+    const unsigned int mine = n_held;
+    if (!mine) return;
+    if (mine > (unsigned)kHeld) {
+        if (threadIdx.x == 0) count[2] = 1;  // header word 2: overflow -- the slice is incomplete, whatever the capacity
+        return;
+    }
+    if (threadIdx.x == 0) base = atomicAdd(count, mine);
+    __syncthreads();
+    for (unsigned int i = threadIdx.x; i < mine; i += 256)
+        if (base + i < cap) exc[base + i] = held[i];
+}
+
+__global__ void nibble_unpack_kernel(const uint32_t *nib, int64_t n, uint8_t *out) {
+    for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g * 8 < n;
+         g += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t word = nib[g];
+        unsigned long long eight = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) eight |= (unsigned long long)((word >> (4 * i)) & 15u) << (8 * i);
+        if (g * 8 + 8 <= n) {
+            *reinterpret_cast<unsigned long long *>(out + g * 8) = eight;
+        } else {
+            for (int i = 0; g * 8 + i < n; ++i) out[g * 8 + i] = (uint8_t)(eight >> (8 * i));
+        }
+    }
+}
+
+__global__ void nibble_exceptions_kernel(const unsigned long long *exc, const unsigned int *head, int64_t n,
+                                         uint8_t *out) {
+    const unsigned int count = head[0] < head[1] ? head[0] : head[1];  // found, capacity
+    for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const unsigned long long e = exc[i];
+        const int64_t p = (int64_t)(e >> 8);
+        if (p < n) out[p] = (uint8_t)(e & 0xFF);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// wire layout: [count u32, cap u32, overflow u32, 4 B pad][nibbles: 4 * ceil(n / 8) B][exceptions: cap * 8 B]
+size_t memo_transport_bytes(int64_t n, uint32_t cap) {
+    return 16 + (size_t)((n + 7) / 8) * 4 + (size_t)cap * 8;
+}
+
+int memo_transport_pack_dev(const uint8_t *d_vec, int64_t n, uint32_t cap, void *d_wire, int32_t device,
+                            void *stream) {
+    if (n < 0 || (n > 0 && (!d_vec || !d_wire))) return fail(MEMO_EINVAL, "bad transport arguments");
+    if (((uintptr_t)d_vec & 7) || ((uintptr_t)d_wire & 7)) return fail(MEMO_EINVAL, "transport buffers must be 8-byte aligned");
+    DeviceGuard guard(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *w = static_cast<char *>(d_wire);
+    HIP_TRY(hipMemsetAsync(w, 0, 16, st));  // count = 0; the kernel fills in the capacity (no host staging)
+    const int64_t groups = (n + 7) / 8;
+    {
+        const int64_t blocks = (groups + 256 * 16 - 1) / (256 * 16);  // 32768 positions per workgroup
+        if (blocks >= ((int64_t)1 << 31)) return fail(MEMO_EINVAL, "slice too long for one launch");
+        const unsigned grid = (unsigned)(blocks ? blocks : 1);  // (an empty slice still gets its header)
+        hipLaunchKernelGGL(nibble_pack_kernel, dim3(grid), dim3(256), 0, st, d_vec, n,
+                           reinterpret_cast<uint32_t *>(w + 16),
+                           reinterpret_cast<unsigned long long *>(w + 16 + groups * 4),
+                           reinterpret_cast<unsigned int *>(w), cap);
+        HIP_TRY(hipGetLastError());
+    }
+    return MEMO_OK;
+}
+
+int memo_transport_unpack_dev(const void *d_wire, int64_t n, uint8_t *d_vec, int32_t device, void *stream) {
+    if (n < 0 || (n > 0 && (!d_vec || !d_wire))) return fail(MEMO_EINVAL, "bad transport arguments");
+    if (((uintptr_t)d_vec & 7) || ((uintptr_t)d_wire & 7)) return fail(MEMO_EINVAL, "transport buffers must be 8-byte aligned");
+    DeviceGuard guard(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const char *w = static_cast<const char *>(d_wire);
+    const int64_t groups = (n + 7) / 8;
+    if (groups) {
+        const unsigned grid = (unsigned)(groups / 256 + 1 < 8192 ? groups / 256 + 1 : 8192);
+        hipLaunchKernelGGL(nibble_unpack_kernel, dim3(grid), dim3(256), 0, st,
+                           reinterpret_cast<const uint32_t *>(w + 16), n, d_vec);
+        hipLaunchKernelGGL(nibble_exceptions_kernel, dim3(256), dim3(256), 0, st,
+                           reinterpret_cast<const unsigned long long *>(w + 16 + groups * 4),
+                           reinterpret_cast<const unsigned int *>(w), n, d_vec);
+        HIP_TRY(hipGetLastError());
+    }
+    return MEMO_OK;
+}
+
+// exceptions the sender found (host value; synchronises `stream`).  More than the wire's capacity
+// means the slice cannot travel in this coding.
+int memo_transport_exceptions(const void *d_wire, int32_t device, void *stream, uint32_t *found, uint32_t *cap) {
+    if (!d_wire || !found || !cap) return fail(MEMO_EINVAL, "NULL argument");
+    DeviceGuard guard(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint32_t head[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(head, d_wire, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *found = head[2] ? 0xFFFFFFFFu : head[0];  // word 2: a workgroup overflowed its staging (more than an eighth exceptions)
+    *cap = head[1];
     return MEMO_OK;
 }
 

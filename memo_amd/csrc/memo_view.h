@@ -55,11 +55,41 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, RowS
 // ... the 4-byte words: their k-class view (+ their order)
 int packed_rows_for(memo_index *ix, int km1, int64_t window, bool membership, hipStream_t st, RowSource &src);
 int dense_compact(memo_index *ix);  // leave the rows that can never write out of the dense rows (see memo_index::boff3)
+// the views of one row source: the five- and six-row views of the dense rows, or the views of the 4-byte words
+template <typename Index, typename F>
+void each_view(Index *ix, bool dense, F f) {
+    if (dense) {
+        for (auto &v : ix->views) f(v);
+        for (auto &v : ix->views6) f(v);
+    } else {
+        for (auto &v : ix->pviews) f(v);
+    }
+}
+// The caller has the device drained: the views are freed, not retired.  The tile tables made for a dense view go with it, to the
+// retire list: none where the dense rows go too (rows_changed drops every table first), and MEMO_OPT_VIEWS = 0 flushes the list.
 void drop_dense_views(memo_index *ix);
 void drop_packed_views(memo_index *ix);
 void retire(memo_index *ix, void *p, uint64_t bytes);  // out of service now, freed once the device has drained
 void flush_retired(memo_index *ix);                    // ... which the caller guarantees (it synchronised the device)
 int order_words_now(memo_index *ix, int mode);  // waits for the device, orders ix->pk in place, waits again
+// one pass: run on `st` between two events, the caller's stream waited for (later queries may come on other streams)
+template <typename Build>
+int build_timed(hipStream_t st, float *ms, Build build) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_TRY(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        return fail(MEMO_EHIP, "hipEventCreate failed");
+    }
+    (void)hipEventRecord(e0, st);
+    const int rc = build();
+    (void)hipEventRecord(e1, st);
+    (void)hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+}
 extern thread_local int g_six_views;  // (AB library, memo_debug_six_views: -1 the library's choice, 0 five rows per group always, 1 six wherever they apply)
 extern thread_local int g_view_colouring;  // 1: the dense rows' k-class views may get their rows' places inside a group chosen against bank conflicts (memo_debug_view_colouring of the AB library turns it off)
 extern thread_local bool g_dense_keep_all;  // (AB library, memo_debug_dense_keep_all: dense_compact keeps every row)

@@ -25,10 +25,9 @@ int dense_compact(memo_index *ix) {
     if (rc == kNoRoom) rc = MEMO_OK;  // (no room for a second copy: every row stays)
     if (rc || !b.p3) return rc;
     DeviceGuard guard(ix->device);
-    drop_tile_tables(ix);
-    (void)hipFree(ix->p3);
-    ix->p3 = b.p3;
-    ix->boff3 = b.boff;
+    rows_changed(ix, kLevelDense);  // (the rows in full go; nothing can have been made of them yet)
+    ix->p3.adopt(b.p3);
+    ix->boff3.adopt(b.boff);
     ix->rows3 = b.rows;
     ix->padded3 = b.padded;
     return MEMO_OK;
@@ -56,15 +55,20 @@ static int ask_after_step(int x) { return x ? backoff_step(x) : 16; }
 
 // evicted: by the budget -- the class starts again, later (back-off: see DenseView); else the view is being replaced by another of
 // the same class (its places, its live copy, a new row order), which is as due as it was
-static void retire_view(memo_index *ix, memo_index::DenseView &v, bool evicted) {
-    for (size_t i = 0; i < ix->ttabs.size();) {  // the tile tables made for it go with it (a later allocation may land on its address)
-        if (ix->ttabs[i].rows_of == v.p3) {
+// the tile tables made for a view go with it (a later allocation may land on its address)
+static void retire_tables_of(memo_index *ix, const memo_index::DenseView &v) {
+    for (size_t i = 0; i < ix->ttabs.size();) {
+        if (ix->ttabs[i].rows_of == v.p3) {  // (never of a view that was not built: a table is made for rows)
             retire(ix, ix->ttabs[i].d, (uint64_t)ix->ttabs[i].n * 32);
             ix->ttabs.erase(ix->ttabs.begin() + (long)i);
         } else {
             ++i;
         }
     }
+}
+
+static void retire_view(memo_index *ix, memo_index::DenseView &v, bool evicted) {
+    retire_tables_of(ix, v);
     retire(ix, v.p3, v.bytes);
     retire(ix, v.boff, ix->nb * 8);
     const int backoff = evicted ? backoff_step(v.backoff) : v.backoff, ask = evicted ? ask_after_step(v.ask_after) : v.ask_after;
@@ -73,23 +77,17 @@ static void retire_view(memo_index *ix, memo_index::DenseView &v, bool evicted) 
     v.ask_after = ask;
 }
 
-// the views of one row source: the five- and six-row views of the dense rows, or the views of the 4-byte words
-template <typename F>
-static void each_view(memo_index *ix, bool dense, F f) {
-    if (dense) {
-        for (memo_index::DenseView &v : ix->views) f(v);
-        for (memo_index::DenseView &v : ix->views6) f(v);
-    } else {
-        for (memo_index::DenseView &v : ix->pviews) f(v);
-    }
-}
-
 static void free_view(memo_index::DenseView &v) {  // (the caller has the device drained)
     (void)hipFree(v.p3);
     (void)hipFree(v.boff);
     v = memo_index::DenseView();
 }
-void drop_dense_views(memo_index *ix) { each_view(ix, true, free_view); }
+void drop_dense_views(memo_index *ix) {
+    each_view(ix, true, [&](memo_index::DenseView &v) {
+        retire_tables_of(ix, v);
+        free_view(v);
+    });
+}
 void drop_packed_views(memo_index *ix) { each_view(ix, false, free_view); }
 
 // All the views of one row source together may take view_budget_pct percent (200 by default: memo_index_set_option) of the bytes
@@ -171,25 +169,6 @@ static void pass_measured(memo_index *ix, Pass pass, float ms, double units) {  
     if (units > 0) ix->pass_ns[pass] = ns / units > floor ? (ns / units < ceil ? ns / units : ceil) : floor;
 }
 
-// one pass: run on `st` between two events, the caller's stream waited for (later queries may come on other streams)
-template <typename Build>
-static int build_timed(hipStream_t st, float *ms, Build build) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        return fail(MEMO_EHIP, "hipEventCreate failed");
-    }
-    (void)hipEventRecord(e0, st);
-    const int rc = build();
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    (void)hipEventElapsedTime(ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-}
-
 // A class without its view (pass: kPassDenseView or kPassPackedView).  spared: the share of src_rows the view would leave out.
 static bool view_due(memo_index *ix, memo_index::DenseView &v, Pass pass, double src_rows, double spared, int64_t window, int km1) {
     if (g_prepare_only) return true;
@@ -263,8 +242,8 @@ static int order_words_on(memo_index *ix, int mode, hipStream_t st) {
     }
     for (memo_index::DenseView &v : ix->pviews)  // (views are subsets in the old order)
         if (v.p3) retire_view(ix, v, false);
-    retire(ix, ix->pk, bytes);
-    ix->pk = copy;
+    retire(ix, ix->pk.release(), bytes);
+    ix->pk.adopt(copy);
     ix->row_order = mode;
     ix->order_pending = 0;
     pass_measured(ix, kPassRowOrder, ms, (double)ix->rows);

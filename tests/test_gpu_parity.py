@@ -1989,6 +1989,105 @@ def test_prepare_builds_views_and_tables_now(memo, oracle):
         ix.check()
 
 
+def test_row_changes_drop_what_was_derived(memo, oracle):
+    """The derivation chain int64 columns -> 4-byte words -> dense rows -> views and tile tables (memo_index.hip: rows_changed), walked
+    with EVERY level resident: the index of test_prepare_builds_views_and_tables_now built with pack(keep_wide=True) and
+    pack_dense(keep_packed=True).  Each call that changes the rows (or may: memo_index_columns) leaves no words, no dense rows, no
+    view and no tile table behind, and -- all but a bare re-finalize -- an index that refuses queries until it is finalized again;
+    built up again, the index answers for the rows it now holds.  Rows A: the generator at its default seed, rows B: at another.
+    Pins what the library did before the row-change rule was written down in one place.  Letting the words go
+    (pack_dense(keep_packed=False)) does not by itself make a k = 101 query fail: while the int64 columns are kept they answer it
+    (memo_sweep.hip: pick_rows); the refusal (MEMO_EINVAL) needs an index that dropped them too, which the last step builds."""
+    import ctypes as C
+    from memo_amd import synth, _lib
+    n, L = 100, 2_000_000
+    num, den = synth.rows_per_position(n)
+    r0, r1 = synth.shard_rows(0, L, 64, num, den, L)
+    d16 = C.c_void_p()                                                    # the result of a 16-position query, for the bare return codes
+    _lib.check(_lib.lib().memo_dev_malloc(0, 64, C.byref(d16)))
+
+    def code(ix, k):
+        return _lib.lib().memo_query_conservation_dev(ix._h, 0, 16, k, n, d16, None)
+    m, half, seed_b = r1 - r0, (r1 - r0) // 2, 0x5EED
+    A = oracle.synth_rows(r0, m, num, den, n)
+    B = oracle.synth_rows(r0, m, num, den, n, seed=seed_b)
+    cut = slice(m // 3, m // 3 + 1_000_003)
+    mixed = tuple(np.concatenate((a[:cut.start], b[cut], a[cut.stop:])) for a, b in zip(A, B))
+    wants = {}
+
+    def answers(ix, name, rows):
+        if name not in wants:
+            wants[name] = (oracle.conservation(*rows, 0, L, 31, n, literal=False), oracle.conservation(*rows, 0, L, 17, n, literal=False),
+                           oracle.membership(*rows, 1000, 400_000, 31, n, literal=False))
+        assert np.array_equal(ix.conservation(0, L, 31, n), wants[name][0]), name
+        assert np.array_equal(ix.conservation(0, L, 17, n), wants[name][1]), name
+        assert np.array_equal(ix.membership(1000, 400_000, 31, n), wants[name][2]), name
+        ix.check()
+
+    def build_up(ix):
+        ix.pack(keep_wide=True)
+        ix.pack_dense(keep_packed=True)
+        ix.prepare(31, n)
+
+    def state_1():
+        ix = memo.DeviceIndex.synthetic(m, r0, num, den, n)
+        build_up(ix)
+        answers(ix, "A", A)
+        inf = ix.info()
+        print("state 1:", {f: inf[f] for f in ("views_resident", "tile_tables_resident", "dense_rows", "packed_format", "finalized")})
+        assert inf["views_resident"] > 0 and inf["tile_tables_resident"] > 0 and inf["dense_rows"] == 1 and inf["packed_format"] != 0
+        return ix
+
+    def upload(ix):
+        _lib.check(_lib.lib().memo_index_upload(ix._h, B[0].ctypes.data, B[1].ctypes.data, B[2].ctypes.data, m))
+
+    def synth_fill(ix):
+        _lib.check(_lib.lib().memo_synth_fill(ix._h, r0, num, den, n, seed_b))
+
+    changes = (("memo_index_upload", upload, "B", B),
+               ("memo_index_upload_rows", lambda ix: ix.upload_rows(cut.start, *(b[cut] for b in B)), "mixed", mixed),
+               ("memo_index_truncate", lambda ix: ix.truncate(half), "half", tuple(a[:half] for a in A)),
+               ("memo_index_columns", lambda ix: ix.columns(), "A", A),
+               ("memo_synth_fill", synth_fill, "B", B),
+               ("memo_index_finalize", lambda ix: ix.finalize(6, False), "A", A))
+    for call, change, name, rows in changes:
+        with state_1() as ix:
+            change(ix)
+            inf = ix.info()
+            print(call, {f: inf[f] for f in ("views_resident", "tile_tables_resident", "dense_rows", "packed_format", "finalized")})
+            assert (inf["packed_format"], inf["dense_rows"], inf["views_resident"], inf["tile_tables_resident"]) == (0, 0, 0, 0), call
+            if call != "memo_index_finalize":
+                assert inf["finalized"] == 0, call
+                assert code(ix, 31) == _lib.MEMO_ENOTREADY, call
+                ix.finalize()
+            else:
+                assert inf["finalized"] == 1 and inf["bucket_shift"] == 6   # (built up again on the buckets it now has)
+            build_up(ix)
+            answers(ix, name, rows)
+    with state_1() as ix:
+        ix.pack(keep_wide=True)                                           # once more: the words' allocation is reused
+        inf = ix.info()
+        assert inf["packed_format"] != 0 and (inf["dense_rows"], inf["views_resident"], inf["tile_tables_resident"]) == (0, 0, 0)
+        answers(ix, "A", A)
+        ix.pack_dense(keep_packed=True)
+        ix.prepare(31, n)
+        answers(ix, "A", A)
+        before = ix.info()["device_bytes"]
+        ix.pack_dense(keep_packed=False)                                  # on an index that has its dense rows: the words go, no more
+        inf = ix.info()
+        assert inf["dense_rows"] == 1 and inf["packed_format"] != 0 and inf["device_bytes"] < before
+        assert np.array_equal(ix.conservation(0, L, 31, n), wants["A"][0])
+        assert code(ix, 101) == _lib.MEMO_OK
+        assert np.array_equal(ix.conservation(0, L, 101, n), oracle.conservation(*A, 0, L, 101, n, literal=False))   # (the int64 columns answer)
+        ix.check()
+    with memo.DeviceIndex.synthetic(m, r0, num, den, n) as ix:             # ... and without them nothing can: refused
+        ix.pack(keep_wide=False)
+        ix.pack_dense(keep_packed=False)
+        assert np.array_equal(ix.conservation(0, L, 31, n), wants["A"][0])
+        assert code(ix, 101) == _lib.MEMO_EINVAL and b"int64 columns" in _lib.lib().memo_last_error()
+    _lib.lib().memo_dev_free(0, d16)
+
+
 def test_views_are_built_when_they_have_paid_for_themselves(memo, oracle):
     """no fixed "fifth query".  Every query of a k class that runs without its view adds what the view would
     have saved it (the rows of its window the view leaves out x what a sweep pays per row); the view is built by the query that finds
