@@ -57,19 +57,62 @@ size_t memo_emit_bed(const int32_t *rec, const int64_t *start, const int64_t *en
  *   crosses a $, so the MS against the text is the elementwise maximum over the pieces, and that is what the column
  *   receives (the first piece stores, the later ones take the maximum; other columns are never touched).
  *   piece_bytes <= 0: the cap is min(2^30, what the free device memory allows), raised to fit the longest string where
- *   memory allows; else a hard cap in [2, 2^31 - 2].  A string longer than the cap (len + 1 bytes with its $) is
+ *   memory allows (a coded handle first sets aside what its largest possible column takes: the piece's buffers stay while the
+ *   column is encoded); else a hard cap in [2, 2^31 - 2].  A string longer than the cap (len + 1 bytes with its $) is
  *   refused before anything is written.  *pieces (may be NULL): how many pieces ran (0 for nrec = 0: a zero column).
  * memo_ms_plan_pieces: the plan memo_ms_add_records follows (host only, no device): strings S_1 .. S_s, rc(S_1) ..
  *   rc(S_s) of rec_len[r] + 1 bytes each, greedily into pieces of at most `cap` bytes; piece_of_string (2 nrec
  *   entries) and *pieces may be NULL.
- * memo_ms_fetch: host copy of DAP rows [first, first + positions).
- * memo_ms_push_dap: memo_dap_push_dev of those rows (same device, same column count).
+ * memo_ms_create_layout: memo_ms_create with the DAP's layout chosen.  MEMO_MS_LAYOUT_DENSE is memo_ms_create (the same checks,
+ *   order and messages).  MEMO_MS_LAYOUT_CODED keeps no matrix: the walk fills one scratch column int32 [positions], and after a
+ *   genome's last piece that column is run-coded.  Matching statistics fall by at most one per position (MS[i] >= MS[i-1] - 1,
+ *   across record ends and after the maximum over pieces too), so with expect[i] = max(MS[i-1] - 1, 0), MS[-1] = 0, position i is
+ *   FLAGGED iff MS[i] != expect[i] or i is the first position of a coding block (`block` positions, a power of two:
+ *   memo_ms_layout_info), and a column is: one flag bit per position in 64-bit words (block / 64 words per coding block), the
+ *   int32 MS of every flagged position in position order, and one int64 per coding block, the rank of its first flag.
+ *   MS[i] = max(value[j] - (i - j), 0) with j the last flagged position <= i: exact, since every unflagged position equals its
+ *   expect.  A column holds, with nblocks = ceil(positions / block),
+ *       bytes = 4 * flagged + 8 * (block / 64) * nblocks + 8 * nblocks
+ *   of device memory, allocated when it is added (a column added again frees and replaces them; one never added holds none and
+ *   reads as zeros, as the dense matrix does).  When a column's buffers do not fit, the call fails with a message that names
+ *   the column, the bytes asked for and the bytes free; the column is then as one never added and the handle stays good.
+ *   MEMO_MS_LAYOUT_AUTO: dense wherever memo_ms_create would succeed, else coded; refused (before the pivot is read) when not
+ *   even the coded floor fits: scratch column + pivot + the flag words and block offsets of every column + the working set of a
+ *   1 MiB text that the dense check adds as well.  Everything else of the handle behaves alike in both layouts.
+ * memo_ms_plan_layout: that decision, host only (no device call): which layout a pivot of `positions` positions and `columns`
+ *   columns gets when `free_bytes` of device memory are free (*chosen; may be NULL) and the bytes that layout needs at creation
+ *   (*floor_bytes; may be NULL).  MEMO_EINVAL with "device memory" in the message when the asked-for layout (or, for AUTO,
+ *   neither) fits, and for a layout that is none of the three.
+ * memo_ms_layout_info: the handle's layout, its coding block, the device bytes now held for the DAP (dense: the matrix; coded:
+ *   scratch column + staging rows + what every column's three allocations hold, which equals the formula above), what the matrix would take (dense_bytes), the flagged
+ *   positions of all columns, and the device milliseconds so far of the encode and decode passes (0 for a dense handle).
+ * memo_ms_column_info: one column's flagged positions and the bytes its allocations hold (coded; never added: 0 and 0.  Dense: 0 and
+ *   4 * positions).  Either pointer may be NULL.
+ * memo_ms_fetch: host copy of DAP rows [first, first + positions) (coded: decoded on the device into a staging buffer [positions]
+ *   [columns] that the handle owns and that only grows, at most 256 MiB of it per step).
+ * memo_ms_push_dap: memo_dap_push_dev of those rows (same device, same column count).  A coded handle decodes them into that
+ *   staging buffer first, all of them at once: keep pushes moderate.
  * memo_ms_timings: device milliseconds so far of {suffix arrays, LCP + hierarchy, walks}, summed over pieces.
  * memo_suffix_array: the suffix array of text[0, n) on `device` into sa_out (n int32); a suffix that is a
  *   prefix of another sorts first. */
 typedef struct memo_ms memo_ms_t;
+enum { MEMO_MS_LAYOUT_AUTO = 0, MEMO_MS_LAYOUT_DENSE = 1, MEMO_MS_LAYOUT_CODED = 2 };
+typedef struct {
+    int32_t layout;         /* MEMO_MS_LAYOUT_DENSE or MEMO_MS_LAYOUT_CODED */
+    int32_t block;          /* positions per coding block */
+    uint64_t device_bytes;  /* held for the DAP now */
+    uint64_t dense_bytes;   /* positions * columns * 4 */
+    uint64_t flagged;       /* flagged positions, all columns */
+    float encode_ms, decode_ms;
+} memo_ms_layout_info_t;
 int memo_ms_create(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec, int32_t columns, int64_t chunk,
                    int32_t device, memo_ms_t **out);
+int memo_ms_create_layout(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec, int32_t columns, int64_t chunk,
+                          int32_t device, int32_t layout, memo_ms_t **out);
+int memo_ms_plan_layout(int64_t positions, int32_t columns, uint64_t free_bytes, int32_t layout, int32_t *chosen,
+                        int64_t *floor_bytes);
+int memo_ms_layout_info(memo_ms_t *h, memo_ms_layout_info_t *info);
+int memo_ms_column_info(memo_ms_t *h, int32_t column, uint64_t *flagged, uint64_t *bytes);
 int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t column);
 int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int32_t column,
                         int64_t piece_bytes, int32_t *pieces);

@@ -78,6 +78,9 @@ int memo_debug_set_stamp_buffer(uint64_t *d_buffer);
  * DAP matrix is not touched. */
 int memo_debug_ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes,
                              int32_t piece, uint8_t *out, int64_t out_cap, int64_t *out_n);
+/* this THREAD's later additions to coded matching-statistics handles (memo_ms_create_layout): every allocation of a coded column
+ * sees `bytes` of free device memory instead of what the device reports (< 0: off) -- the test of a column that does not fit */
+int memo_debug_ms_free_bytes(int64_t bytes);
 
 #ifdef __cplusplus
 }

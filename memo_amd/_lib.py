@@ -51,6 +51,12 @@ class IndexInfo(C.Structure):
                 ("last_view_rows_per_group", C.c_int32), ("last_tile_width", C.c_int32)]
 
 
+class MsLayoutInfo(C.Structure):
+    """memo_ms_layout_info_t (include/memo_amd_dap.h)"""
+    _fields_ = [("layout", C.c_int32), ("block", C.c_int32), ("device_bytes", C.c_uint64), ("dense_bytes", C.c_uint64),
+                ("flagged", C.c_uint64), ("encode_ms", C.c_float), ("decode_ms", C.c_float)]
+
+
 # every symbol the product headers declare: name -> (restype, argtypes)
 _P, _I32, _I64, _U64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 SYMBOLS = {
@@ -111,6 +117,10 @@ SYMBOLS = {
     "memo_dap_push_dev": (C.c_int, [_P, _P, _I64, C.POINTER(_U64)]),
     "memo_dap_destroy": (None, [_P]),
     "memo_ms_create": (C.c_int, [_P, _P, _I32, _I32, _I64, _I32, C.POINTER(_P)]),
+    "memo_ms_create_layout": (C.c_int, [_P, _P, _I32, _I32, _I64, _I32, _I32, C.POINTER(_P)]),
+    "memo_ms_plan_layout": (C.c_int, [_I64, _I32, _U64, _I32, C.POINTER(_I32), C.POINTER(_I64)]),
+    "memo_ms_layout_info": (C.c_int, [_P, C.POINTER(MsLayoutInfo)]),
+    "memo_ms_column_info": (C.c_int, [_P, _I32, C.POINTER(_U64), C.POINTER(_U64)]),
     "memo_ms_add_genome": (C.c_int, [_P, _P, _I64, _I32]),
     "memo_ms_add_records": (C.c_int, [_P, _P, _P, _I32, _I32, _I64, C.POINTER(_I32)]),
     "memo_ms_plan_pieces": (C.c_int, [_P, _I32, _I64, _P, C.POINTER(_I32)]),
@@ -154,6 +164,7 @@ DEBUG_SYMBOLS = {
     "memo_debug_one_shot_way": (C.c_int, [_I32]),
     "memo_debug_last_one_shot_sweep": (C.c_int, []),
     "memo_debug_set_stamp_buffer": (C.c_int, [_P]),
+    "memo_debug_ms_free_bytes": (C.c_int, [_I64]),
     "memo_debug_ms_piece_text": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _I64, C.POINTER(_I64)]),
 }
 

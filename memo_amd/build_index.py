@@ -17,6 +17,10 @@ statistics (MS) with MONI, genome by genome on the host.  Here every stage runs 
   3. MS of every pivot position against every genome text (memo_ms_*, memo_amd/csrc/memo_ms.hip: suffix array,
      LCP, MS walk per piece), straight into the DAP matrix [positions][genomes - 1] in HBM (index.sh:83).  No
      match crosses a $, so the elementwise maximum over the pieces is the MS against the whole text, exactly.
+     Where that matrix does not fit in the device's free memory (MEMO_INDEX_DAP_LAYOUT unset or `auto`; `dense` and
+     `coded` force one), every column is kept run-coded instead -- MS falls by at most one per position, so a flag
+     bit per position and the values of the flagged positions give it back exactly -- and stage 4 reads rows decoded
+     on the device a batch at a time.  The index is the same file either way.
   4. DAP -> index rows on the device (memo_dap_push_dev; --mem --overlap, plus --order for the conservation
      index: index.sh:86-103) -> DIR/PREFIX.parquet (f0 utf8, f1 f2 f3 int64, ZSTD: parquet_compress_bed.py).
 
@@ -25,8 +29,9 @@ reads them.
 
 Refused with a message (never a wrong result): gzip input, a NUL byte, a pivot record of length 0, a pivot
 record of 2^30 positions or more, a genome record of 2^31 - 2 bases or more (or longer than the piece cap less
-one byte), more than 4096 genomes besides the pivot, a DAP matrix or a piece's working set that does not fit in
-the device's free memory, a MEMO_INDEX_PIECE_BYTES that is not an integer in [2, 2^31 - 2].  A genome's whole
+one byte), more than 4096 genomes besides the pivot, a DAP that does not fit in the device's free memory even as
+coded columns, a piece's working set that does not, a MEMO_INDEX_PIECE_BYTES that is not an integer in
+[2, 2^31 - 2], a MEMO_INDEX_DAP_LAYOUT that is not auto, dense or coded.  A genome's whole
 text may exceed 2^31 bytes: a human assembly (~6.2 GB of text) runs in a handful of pieces.
 """
 import ctypes as C
@@ -60,6 +65,10 @@ MAX_RECORD = (1 << 30) - 1        # memo_dap: positions of one pivot record
 MAX_TEXT = (1 << 31) - 2          # memo_ms: int32 suffix array of one genome text (and of one piece)
 PIECE_ENV = "MEMO_INDEX_PIECE_BYTES"   # `memo index`: the piece cap (unset: the library's default)
 MAX_COLUMNS = 4096                # memo_dap: genomes besides the pivot
+LAYOUT_ENV = "MEMO_INDEX_DAP_LAYOUT"   # `memo index`: auto (unset) | dense | coded
+STATS_ENV = "MEMO_INDEX_STATS"         # `memo index`: a file that receives build_index's stats as one JSON line
+LAYOUTS = {"auto": 0, "dense": 1, "coded": 2}          # MEMO_MS_LAYOUT_*
+_LAYOUT_NAMES = {v: k for k, v in LAYOUTS.items()}
 
 
 class FastaError(ValueError):
@@ -117,9 +126,10 @@ def pivot_layout(records, path="<pivot>"):
 
 
 class MatchingStatistics:
-    """The DAP matrix int32 [positions][columns] of one pivot, resident on `device` (memo_ms_*)."""
+    """The DAP int32 [positions][columns] of one pivot, resident on `device` (memo_ms_*): as that matrix (layout "dense"),
+    as run-coded columns ("coded"), or dense where the matrix fits in the free device memory and coded where not ("auto")"""
 
-    def __init__(self, pivot, rec_begin, columns, device=0, chunk=0):
+    def __init__(self, pivot, rec_begin, columns, device=0, chunk=0, layout="auto"):
         self._h = C.c_void_p()
         self.rec_begin = np.ascontiguousarray(rec_begin, np.int64)
         self.positions = int(self.rec_begin[-1])
@@ -127,8 +137,24 @@ class MatchingStatistics:
         self._pivot = bytes(pivot)
         if len(self._pivot) != self.positions:
             raise ValueError(f"pivot has {len(self._pivot)} bytes, its records {self.positions}")
-        check(lib().memo_ms_create(self._pivot, self.rec_begin.ctypes.data, len(self.rec_begin) - 1, columns,
-                                   int(chunk), device, C.byref(self._h)))
+        check(lib().memo_ms_create_layout(self._pivot, self.rec_begin.ctypes.data, len(self.rec_begin) - 1, columns,
+                                          int(chunk), device, _layout_number(layout), C.byref(self._h)))
+
+    def layout_info(self):
+        """{"layout": "dense" | "coded", "block": positions per coding block, "device_bytes": held for the DAP now,
+        "dense_bytes": what the matrix takes, "flagged": flagged positions of all columns, "encode_ms", "decode_ms"}"""
+        from ._lib import MsLayoutInfo
+        info = MsLayoutInfo()
+        check(lib().memo_ms_layout_info(self._h, C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in MsLayoutInfo._fields_}
+        out["layout"] = _LAYOUT_NAMES[info.layout]
+        return out
+
+    def column_info(self, column):
+        """{"flagged", "bytes"} of one column (memo_ms_column_info)"""
+        flagged, nbytes = C.c_uint64(), C.c_uint64()
+        check(lib().memo_ms_column_info(self._h, column, C.byref(flagged), C.byref(nbytes)))
+        return {"flagged": flagged.value, "bytes": nbytes.value}
 
     def add(self, text, column):
         """matching statistics of the pivot against one genome text, into DAP column `column`"""
@@ -182,6 +208,32 @@ def plan_pieces(lengths, cap):
     return pieces.value, piece
 
 
+def _layout_number(layout):
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout {layout!r}: need one of {', '.join(LAYOUTS)}")
+    return LAYOUTS[layout]
+
+
+def plan_layout(positions, columns, free_bytes, layout="auto"):
+    """(layout name, bytes it needs at creation): memo_ms_create_layout's decision for a pivot of `positions` positions and
+    `columns` columns with `free_bytes` of device memory free (host only); MemoError ("device memory") when nothing fits"""
+    chosen, floor = C.c_int32(), C.c_int64()
+    number = layout if isinstance(layout, int) else _layout_number(layout)
+    check(lib().memo_ms_plan_layout(int(positions), int(columns), int(free_bytes), number, C.byref(chosen), C.byref(floor)))
+    return _LAYOUT_NAMES[chosen.value], floor.value
+
+
+def dap_layout_from_env(environ=os.environ):
+    """the DAP layout MEMO_INDEX_DAP_LAYOUT asks for ("auto" when unset or empty); FastaError when it is none of auto, dense,
+    coded (exactly so: no other case, no blanks)"""
+    raw = environ.get(LAYOUT_ENV, "")
+    if raw == "":
+        return "auto"
+    if raw not in LAYOUTS:
+        raise FastaError(f"{LAYOUT_ENV}={raw!r}: need one of {', '.join(LAYOUTS)}")
+    return raw
+
+
 def piece_bytes_from_env(environ=os.environ):
     """the piece cap MEMO_INDEX_PIECE_BYTES asks for (0: unset, the library's default); FastaError when it is not an
     integer in [2, 2^31 - 2]"""
@@ -222,18 +274,25 @@ def read_genome_list(path):
     return paths
 
 
-def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log=print, keep_ms=False, piece_bytes=0):
+def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log=print, keep_ms=False, piece_bytes=0,
+                layout="auto"):
     """index.sh end to end; returns per-stage seconds, the pieces of every genome's text (and the MS matrix when
-    keep_ms).  piece_bytes: the cap of a piece of genome text (<= 0: the library's default)"""
+    keep_ms).  piece_bytes: the cap of a piece of genome text (<= 0: the library's default).  layout: of the DAP on the
+    device, "auto" | "dense" | "coded" (stats: dap_layout, the one taken; dap_device_bytes, held for the DAP after the last
+    genome; per genome, flagged: its column's flagged positions, 0 in the dense layout).  Row batches go to the Parquet writer
+    as they are produced (each is written and dropped before the next is made), so the two stages interleave: dap_to_rows_s
+    is the time spent making batches, parquet_s the rest of that one loop."""
     from .dap_to_bed import DapConverter, write_parquet
     t0 = time.perf_counter()
     paths = read_genome_list(genome_list)
+    _layout_number(layout)
     names, pivot, rec_begin = pivot_layout(read_fasta(paths[0]), paths[0])
     stats = {"positions": int(rec_begin[-1]), "genomes": len(paths), "read_s": 0.0, "pieces": [], "per_genome": []}
     stats["read_s"] += time.perf_counter() - t0
     out_path = os.path.join(out_dir, prefix + ".parquet")
     os.makedirs(out_dir or ".", exist_ok=True)
-    with MatchingStatistics(pivot, rec_begin, len(paths) - 1, device, chunk) as ms:
+    with MatchingStatistics(pivot, rec_begin, len(paths) - 1, device, chunk, layout) as ms:
+        stats["dap_layout"] = ms.layout_info()["layout"]
         t1 = time.perf_counter()
         for c, path in enumerate(paths[1:]):
             tr = time.perf_counter()
@@ -252,26 +311,46 @@ def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log
             after = ms.timings()
             stats["per_genome"].append({"bases": sum(len(s) for _, s in records), "records": len(records),
                                         "pieces": stats["pieces"][-1], "read_s": read_s,
+                                        "flagged": ms.column_info(c)["flagged"],
                                         **{k: after[k] - before[k] for k in after}})
             del records
         stats["ms_s"] = time.perf_counter() - t1
         stats.update(ms.timings())
+        info = ms.layout_info()
+        stats["dap_device_bytes"] = info["device_bytes"]
+        stats["encode_ms"] = info["encode_ms"]
         if keep_ms:
             stats["ms"] = ms.fetch()
         log("Making membership index" if membership else "Making conservation index")
         t2 = time.perf_counter()
-        batches = []
         npos, C_ = ms.positions, ms.columns
         block = max(1024, (64 << 20) // C_)
-        with DapConverter(C_, rec_begin, not membership, True, device) as conv:
-            for first in range(0, npos, block):
-                batches.append(conv.push_ms(ms, first, min(block, npos - first)))
-            batches.append(conv.finish())
-        stats["dap_to_rows_s"] = time.perf_counter() - t2
-    log("Compressing index.")
-    t3 = time.perf_counter()
-    rows = write_parquet(out_path, ((names, b) for b in batches))
-    stats["parquet_s"] = time.perf_counter() - t3
+        made = [0.0]
+
+        def batches():
+            """every row batch once: written and dropped before the next is made"""
+            with DapConverter(C_, rec_begin, not membership, True, device) as conv:
+                for first in range(0, npos, block):
+                    tb = time.perf_counter()
+                    b = conv.push_ms(ms, first, min(block, npos - first))
+                    made[0] += time.perf_counter() - tb
+                    yield names, b
+                tb = time.perf_counter()
+                b = conv.finish()
+                made[0] += time.perf_counter() - tb
+                yield names, b
+        log("Compressing index.")
+        part_path = out_path + ".part"           # a failure while rows are made or written leaves no index behind
+        try:
+            rows = write_parquet(part_path, batches())
+            os.replace(part_path, out_path)
+        except BaseException:
+            if os.path.exists(part_path):
+                os.unlink(part_path)
+            raise
+        stats["decode_ms"] = ms.layout_info()["decode_ms"]
+        stats["dap_to_rows_s"] = made[0]
+        stats["parquet_s"] = time.perf_counter() - t2 - made[0]
     stats["rows"] = rows
     stats["total_s"] = time.perf_counter() - t0
     log("DONE")
@@ -298,8 +377,13 @@ def main(argv):
             raise FastaError("no output prefix: give one with -p")
         read_genome_list(val.get("-g", ""))          # refuse before the device is touched
         piece_bytes = piece_bytes_from_env()
-        build_index(val["-g"], val["-o"], val["-p"], "-m" in val, int(os.environ.get("MEMO_DEVICE", "0")),
-                    log=lambda s: print(s, flush=True), piece_bytes=piece_bytes)
+        layout = dap_layout_from_env()
+        stats = build_index(val["-g"], val["-o"], val["-p"], "-m" in val, int(os.environ.get("MEMO_DEVICE", "0")),
+                            log=lambda s: print(s, flush=True), piece_bytes=piece_bytes, layout=layout)
+        if os.environ.get(STATS_ENV):
+            import json
+            with open(os.environ[STATS_ENV], "w") as fh:
+                fh.write(json.dumps(stats) + "\n")
     except (FastaError, MemoError) as exc:
         sys.stderr.write(f"memo index: {exc}\n")
         sys.exit(1)

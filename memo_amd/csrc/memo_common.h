@@ -32,6 +32,9 @@ void dap_shape(const memo_dap_t *h, int *device, int *columns);
 // (its n bytes and the kPad zeros behind them, when out_cap holds them); returns the number of pieces (memo_debug_ms_piece_text)
 int ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes, int32_t piece,
                   uint8_t *out, int64_t out_cap, int64_t *out_n);
+// memo_ms.hip: >= 0: the allocations of this thread's later coded columns see this many bytes of free device memory instead of the
+// device's (AB library, memo_debug_ms_free_bytes: the test of a column that does not fit)
+extern thread_local int64_t g_ms_free_bytes;
 double pinned_alloc_ms_total();  // memo_hostcore.cpp: time this process has spent allocating pinned staging slots (MEMO_TIMING)
 
 struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the current device

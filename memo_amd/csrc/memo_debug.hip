@@ -134,4 +134,9 @@ int memo_debug_ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *re
     return ms_piece_text(h, seq, rec_begin, nrec, piece_bytes, piece, out, out_cap, out_n);
 }
 
+int memo_debug_ms_free_bytes(int64_t bytes) {
+    g_ms_free_bytes = bytes < 0 ? -1 : bytes;
+    return MEMO_OK;
+}
+
 }  // extern "C"

@@ -22,8 +22,10 @@
 //                     the later ones store max(M, l).  Every piece stays under the int32 suffix-array limit.
 //
 // MS columns are written straight into a device DAP matrix int32 [positions][columns] that memo_dap_push_dev
-// (memo_dap.hip) consumes in place.  Bad input sets a device error word that the host turns into an error;
-// nothing traps or spins.  rocPRIM lives in this translation unit only (its headers compile slowly).
+// (memo_dap.hip) consumes in place (the dense layout), or, where that matrix would not fit, into one scratch column
+// that is then run-coded (the coded layout, "coded columns" below) and decoded range by range into a staging matrix.
+// Bad input sets a device error word that the host turns into an error; nothing traps or spins.  rocPRIM lives in this
+// translation unit only (its headers compile slowly).
 #include <cstring>  // rocprim's texture iterator calls memset without including it
 
 #include <rocprim/rocprim.hpp>
@@ -420,6 +422,158 @@ struct DevBuf {  // device buffer that only ever grows
     }
 };
 
+// ---- coded columns ---------------------------------------------------------------------------------------
+//
+// MS[i] >= MS[i - 1] - 1 at every pivot position (inside a record, across record ends, and after the maximum over pieces),
+// so a column is known from the positions where it does not simply continue.  The run code of a column:
+//   expect[i] = max(MS[i - 1] - 1, 0), MS[-1] = 0;  i is flagged iff MS[i] != expect[i] or i is the first position of a
+//   coding block of kCodeBlock positions;  the column is one flag bit per position (64-bit words, bit l of word w = position
+//   64 w + l), the int32 MS of every flagged position in position order, and per coding block the rank of its first flag.
+//   MS[i] = max(value[j] - (i - j), 0) with j the last flagged position <= i: never further back than the block's start.
+// Exact by construction: between two flags every position equals its expect, which is what the decoder replays.
+
+constexpr int kCodeBlock = 2048;                // positions per coding block = per workgroup of the encode kernels
+constexpr int kCodeWords = kCodeBlock / 64;     // flag words per coding block
+constexpr int kTileCols = 64;                   // decode: columns per workgroup (one 64 x 64 tile through LDS)
+constexpr int64_t kLaunchGroups = (int64_t)1 << 22;  // workgroups along x per launch (grid x times block stays below 2^32)
+static_assert(kCodeBlock % kBlock == 0 && kBlock == 256 && kCodeWords <= 64, "the encode kernels' shape");
+
+struct CodedRef {  // one column as the decode kernel sees it; flags == nullptr: never added, zeros
+    const uint64_t *flags;
+    const int64_t *offs;
+    const int32_t *vals;
+};
+
+// (a) flags and per-block counts.  A workgroup covers one coding block, a wave 64 consecutive positions at a time, so the
+// ballot of the flag predicate is the flag word.  Words past the pivot's end are written as 0.
+__global__ void __launch_bounds__(kBlock) code_flag_kernel(const int32_t *S, int64_t npos, int64_t blk0, uint64_t *flags,
+                                                           int64_t *count) {
+    __shared__ int part[kBlock / 64];
+    const int64_t blk = blk0 + blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int mine = 0;
+    for (int k = 0; k < kCodeBlock / kBlock; ++k) {
+        const int64_t i = blk * kCodeBlock + k * kBlock + threadIdx.x;
+        bool f = false;
+        if (i < npos) {
+            const int32_t prev = i > 0 ? S[i - 1] : 0;
+            f = S[i] != (prev > 1 ? prev - 1 : 0) || (k == 0 && threadIdx.x == 0);
+        }
+        const uint64_t w = __ballot(f);
+        if (lane == 0) {
+            flags[blk * kCodeWords + k * (kBlock / 64) + wave] = w;
+            mine += __popcll(w);
+        }
+    }
+    if (lane == 0) part[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int w = 0; w < kBlock / 64; ++w) c += part[w];
+        count[blk] = c;
+    }
+}
+
+// (d) every flagged value to offs[block] + the flags before it in the block
+__global__ void __launch_bounds__(kBlock) code_scatter_kernel(const int32_t *S, int64_t blk0, const uint64_t *flags,
+                                                              const int64_t *offs, int32_t *vals) {
+    __shared__ int pre[kCodeWords];
+    const int64_t blk = blk0 + blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < kCodeWords) pre[threadIdx.x] = __popcll(flags[blk * kCodeWords + threadIdx.x]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int k = 0; k < kCodeWords; ++k) {
+            const int c = pre[k];
+            pre[k] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    const int64_t base = offs[blk];
+    for (int k = 0; k < kCodeBlock / kBlock; ++k) {
+        const int wi = k * (kBlock / 64) + wave;
+        const uint64_t w = flags[blk * kCodeWords + wi];
+        if ((w >> lane) & 1)  // a set bit lies inside the pivot (code_flag_kernel)
+            vals[base + pre[wi] + __popcll(w & (((uint64_t)1 << lane) - 1))] = S[blk * kCodeBlock + k * kBlock + threadIdx.x];
+    }
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+    const int lo = __shfl((int)(uint32_t)v, src), hi = __shfl((int)(uint32_t)(v >> 32), src);
+    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+// Positions [first, first + positions) of all columns into out[positions][C].  A workgroup takes the 64 positions of one flag
+// word (absolute, so a range may start and end anywhere) for kTileCols columns: each wave decodes a column at a time, lane =
+// position, into an LDS tile, which then goes out row by row -- consecutive threads write consecutive columns of a position.
+// The last flag at or before a position: in its own word by count-leading-zeros of the word masked to the lane; else in the
+// nearest earlier word of the block that has a bit (lane k holds word k of the block: one ballot finds it).  Its rank: the
+// block's offset + the bits of the words before + the bits of the masked word.
+__global__ void __launch_bounds__(kBlock) code_decode_kernel(const CodedRef *cols, int C, int64_t first, int64_t positions,
+                                                             int64_t tile0, int32_t *out) {
+    __shared__ int32_t tile[64 * (kTileCols + 1)];
+    const int64_t word = (first >> 6) + tile0 + blockIdx.x;
+    const int c0 = blockIdx.y * kTileCols;
+    const int nc = C - c0 < kTileCols ? C - c0 : kTileCols;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = word * 64 + lane;
+    const bool inside = i >= first && i < first + positions;
+    const int64_t blk = word / kCodeWords;
+    const int wi = (int)(word % kCodeWords);
+    for (int cc = wave; cc < nc; cc += kBlock / 64) {
+        const CodedRef col = cols[c0 + cc];
+        int32_t v = 0;
+        if (col.flags) {  // (the same for the whole wave)
+            const uint64_t wk = lane < kCodeWords ? col.flags[blk * kCodeWords + lane] : 0;
+            int before = lane < wi ? __popcll(wk) : 0;  // flags of the block ahead of this word
+            for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+            const uint64_t earlier = __ballot(lane < wi && wk != 0);
+            const int kk = earlier ? 63 - __clzll(earlier) : 0;
+            const uint64_t wprev = shfl64(wk, kk), w = shfl64(wk, wi);
+            const uint64_t m = w & (~(uint64_t)0 >> (63 - lane));
+            int64_t j = -1, rank = 0;
+            if (m) {
+                j = word * 64 + 63 - __clzll(m);
+                rank = before + __popcll(m) - 1;
+            } else if (earlier) {
+                j = (blk * kCodeWords + kk) * 64 + 63 - __clzll(wprev);
+                rank = before - 1;
+            }
+            if (inside && j >= 0) {  // (a block's first position is always flagged: j >= 0 wherever inside)
+                const int64_t val = (int64_t)col.vals[col.offs[blk] + rank] - (i - j);
+                v = val > 0 ? (int32_t)val : 0;
+            }
+        }
+        tile[lane * (kTileCols + 1) + cc] = v;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 64 * nc; idx += kBlock) {
+        const int p = idx / nc, cc = idx - p * nc;
+        const int64_t ii = word * 64 + p;
+        if (ii >= first && ii < first + positions) out[(ii - first) * C + c0 + cc] = tile[p * (kTileCols + 1) + cc];
+    }
+}
+
+// one coded column: the owner of its three allocations (the caller has the handle's device selected)
+struct CodedColumn {
+    DevPtr<uint64_t> flags;  // kCodeWords words per coding block
+    DevPtr<int64_t> offs;    // per coding block: the rank of its first flag
+    DevPtr<int32_t> vals;    // `flagged` values
+    int64_t flagged = 0;
+    int64_t n_flags = 0, n_offs = 0, n_vals = 0;  // elements allocated
+    uint64_t bytes() const { return (uint64_t)n_flags * 8 + (uint64_t)n_offs * 8 + (uint64_t)n_vals * 4; }
+    void reset() {
+        flags.reset(); offs.reset(); vals.reset();
+        flagged = n_flags = n_offs = n_vals = 0;
+    }
+};
+
+int64_t code_blocks(int64_t npos) { return (npos + kCodeBlock - 1) / kCodeBlock; }
+// device bytes of one coded column with `flagged` flagged positions: values, flag words, block offsets
+int64_t coded_column_bytes(int64_t npos, int64_t flagged) { return 4 * flagged + code_blocks(npos) * (8 * kCodeWords + 8); }
+
 int bits_for(uint64_t v) {  // bits to hold 0 .. v
     int b = 1;
     while (b < 64 && (v >> b)) ++b;
@@ -522,6 +676,17 @@ struct memo_ms {
     SaWork W;
     float ms_sa = 0.f, ms_lcp = 0.f, ms_walk = 0.f;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the coded layout (M stays empty): the walk's target, the columns, what the encode and decode passes work in
+    int layout = MEMO_MS_LAYOUT_DENSE;
+    int64_t nblocks = 0;               // coding blocks of the pivot
+    DevBuf<int32_t> scratch, stage;    // int32 [positions]: the column being built; [positions asked for][C]: decoded rows
+    DevBuf<int64_t> count;             // encode: flags per coding block
+    DevBuf<char> scan_tmp;
+    DevBuf<CodedRef> refs;             // the columns as the decode kernel reads them (uploaded when refs_stale)
+    std::vector<CodedColumn> cols;
+    bool refs_stale = true;
+    float ms_encode = 0.f, ms_decode = 0.f;
+    hipEvent_t cev[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -530,7 +695,11 @@ void release(memo_ms *h) {
     h->P.release(); h->T.release(); h->R.release(); h->rec_begin.release(); h->chunk_begin.release(); h->G.release();
     h->M.release(); h->SA.release(); h->ISA.release(); h->LCP.release(); h->levels.release(); h->err.release();
     h->W.release();
+    h->scratch.release(); h->stage.release(); h->count.release(); h->scan_tmp.release(); h->refs.release();
+    h->cols.clear();
     for (auto &e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : h->cev)
         if (e) (void)hipEventDestroy(e);
 }
 
@@ -625,7 +794,11 @@ int prepare_records(memo_ms *h, const uint8_t *seq, const int64_t *rec_begin, in
     if (cap <= 0) {  // min(2^30, what the free memory allows), raised to fit the longest string where memory allows
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t avail = (uint64_t)free_b + (uint64_t)resident_bytes(h);
+        uint64_t avail = (uint64_t)free_b + (uint64_t)resident_bytes(h);
+        if (h->layout == MEMO_MS_LAYOUT_CODED) {  // the piece's buffers stay while the column is encoded: leave room for the largest
+            const uint64_t keep = (uint64_t)coded_column_bytes(h->npos, h->npos) + (uint64_t)code_blocks(h->npos) * 8 + (16u << 20);
+            avail = avail > keep ? avail - keep : 0;  // column there can be (every position flagged), the block counts and the scan's scratch
+        }
         int64_t n_mem = avail > (64u << 20) ? (int64_t)((avail - (64u << 20)) * 8 / 547) : 0;  // text_bytes(n) ~ 68.375 n + 64 MiB
         while (n_mem > 0 && text_bytes(n_mem) > avail) --n_mem;
         n_mem = n_mem < kMaxPiece ? n_mem : kMaxPiece;
@@ -712,9 +885,10 @@ int ms_of_text(memo_ms *h, int64_t n, int32_t column, int merge, hipStream_t st)
     int64_t nchunks = 0;
     for (int r = 0; r < h->nrec; ++r) nchunks += (h->h_rec_begin[r + 1] - h->h_rec_begin[r] + h->chunk - 1) / h->chunk;
     A.nchunks = nchunks;
-    A.M = h->M.p;
-    A.C = h->C;
-    A.col = column;
+    const bool coded = h->layout == MEMO_MS_LAYOUT_CODED;  // the walk fills the scratch column; encode_column follows the last piece
+    A.M = coded ? h->scratch.p : h->M.p;
+    A.C = coded ? 1 : h->C;
+    A.col = coded ? 0 : column;
     A.merge = merge;
     A.err = h->err.p;
     HIP_TRY(hipMemsetAsync(h->err.p, 0, sizeof(int), st));
@@ -735,7 +909,143 @@ int ms_of_text(memo_ms *h, int64_t n, int32_t column, int merge, hipStream_t st)
     return MEMO_OK;
 }
 
+// ---- layouts ---------------------------------------------------------------------------------------------
+
+// what memo_ms_create asks of the free memory: the matrix, the pivot, the working set of a 1 MiB text
+int64_t dense_need(int64_t npos, int64_t columns) { return npos * columns * 4 + npos + (int64_t)sa_bytes(1 << 20); }
+// the least a coded handle can hold: the scratch column, the pivot, every column's flag words and block offsets (no values
+// yet), the same working set
+int64_t coded_floor(int64_t npos, int64_t columns) {
+    return npos * 4 + npos + kPad + columns * coded_column_bytes(npos, 0) + (int64_t)sa_bytes(1 << 20);
+}
+
+// The layout decision (memo_ms_plan_layout; memo_ms_create_layout with the device's figures).  total_bytes 0: not known.
+int plan_layout(int64_t npos, int32_t columns, uint64_t free_b, uint64_t total_b, int32_t layout, int32_t *chosen, int64_t *floor_bytes) {
+    if (layout != MEMO_MS_LAYOUT_AUTO && layout != MEMO_MS_LAYOUT_DENSE && layout != MEMO_MS_LAYOUT_CODED)
+        return fail(MEMO_EINVAL, "layout %d: 0 = auto, 1 = dense, 2 = coded", layout);
+    if (columns < 1 || columns > 4096) return fail(MEMO_EINVAL, "columns must be in [1, 4096], got %d", columns);
+    if (npos < 1 || npos >= ((int64_t)1 << 40)) return fail(MEMO_EINVAL, "pivot of %lld positions: need 1 .. 2^40 - 1", (long long)npos);
+    const int64_t dense = dense_need(npos, columns), floor = coded_floor(npos, columns);
+    const bool dense_fits = (uint64_t)dense <= free_b, coded_fits = (uint64_t)floor <= free_b;
+    int pick = layout;
+    if (layout == MEMO_MS_LAYOUT_AUTO) pick = dense_fits || !coded_fits ? MEMO_MS_LAYOUT_DENSE : MEMO_MS_LAYOUT_CODED;
+    const int64_t need = pick == MEMO_MS_LAYOUT_DENSE ? dense : floor;
+    if (chosen) *chosen = pick;
+    if (floor_bytes) *floor_bytes = need;
+    if (pick == MEMO_MS_LAYOUT_DENSE ? dense_fits : coded_fits) return MEMO_OK;
+    char of[48] = "";
+    if (total_b) snprintf(of, sizeof of, " (of %.2f GB)", total_b / 1e9);
+    if (layout == MEMO_MS_LAYOUT_AUTO)
+        return fail(MEMO_EINVAL, "the DAP needs %.2f GB of device memory even as coded columns (%.2f GB as a matrix), %.2f GB are free%s",
+                    floor / 1e9, dense / 1e9, free_b / 1e9, of);
+    return fail(MEMO_EINVAL, "%s needs %.2f GB of device memory, %.2f GB are free%s",
+                pick == MEMO_MS_LAYOUT_DENSE ? "the DAP matrix" : "the coded DAP (scratch column, flag words, block offsets)", need / 1e9,
+                free_b / 1e9, of);
+}
+
+// one allocation of coded column `column`: refused with the column, the bytes asked for and the bytes free when it does not fit
+template <typename T>
+int column_alloc(DevPtr<T> &buf, int64_t &held, int64_t n, int32_t column, const char *what) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (memo::g_ms_free_bytes >= 0) free_b = (size_t)memo::g_ms_free_bytes;  // (AB library: memo_debug_ms_free_bytes)
+    const uint64_t bytes = (uint64_t)(n > 0 ? n : 1) * sizeof(T);
+    if (bytes > free_b || buf.alloc((size_t)(n > 0 ? n : 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MEMO_EHIP, "coded column %d: its %s need %llu bytes of device memory, %llu bytes are free", column, what,
+                    (unsigned long long)bytes, (unsigned long long)free_b);
+    }
+    held = n > 0 ? n : 1;
+    return MEMO_OK;
+}
+
+int encode_passes(memo_ms *h, CodedColumn &col, int32_t column, hipStream_t st) {
+    const int64_t nb = h->nblocks;
+    int rc;
+    if ((rc = h->count.ensure((size_t)nb))) return rc;
+    if ((rc = column_alloc(col.flags, col.n_flags, nb * kCodeWords, column, "flag words")) ||
+        (rc = column_alloc(col.offs, col.n_offs, nb, column, "block offsets")))
+        return rc;
+    HIP_TRY(hipEventRecord(h->cev[0], st));
+    for (int64_t b0 = 0; b0 < nb; b0 += kLaunchGroups)
+        hipLaunchKernelGGL(code_flag_kernel, dim3((unsigned)(nb - b0 < kLaunchGroups ? nb - b0 : kLaunchGroups)), dim3(kBlock), 0, st,
+                           h->scratch.p, h->npos, b0, col.flags.p, h->count.p);
+    HIP_TRY(hipGetLastError());
+    size_t tmp = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, h->count.p, col.offs.p, (int64_t)0, (size_t)nb, rocprim::plus<int64_t>(), st));
+    if ((rc = h->scan_tmp.ensure(tmp ? tmp : 16))) return rc;
+    HIP_TRY(rocprim::exclusive_scan(h->scan_tmp.p, tmp, h->count.p, col.offs.p, (int64_t)0, (size_t)nb, rocprim::plus<int64_t>(), st));
+    int64_t last_off = 0, last_count = 0;
+    HIP_TRY(hipMemcpyAsync(&last_off, col.offs.p + nb - 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last_count, h->count.p + nb - 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t total = last_off + last_count;
+    if (total < nb || total > h->npos) return fail(MEMO_EHIP, "coded column %d: %lld flags counted over %lld positions", column, (long long)total, (long long)h->npos);
+    if ((rc = column_alloc(col.vals, col.n_vals, total, column, "flagged values"))) return rc;
+    for (int64_t b0 = 0; b0 < nb; b0 += kLaunchGroups)
+        hipLaunchKernelGGL(code_scatter_kernel, dim3((unsigned)(nb - b0 < kLaunchGroups ? nb - b0 : kLaunchGroups)), dim3(kBlock), 0, st,
+                           h->scratch.p, b0, col.flags.p, col.offs.p, col.vals.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->cev[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->cev[0], h->cev[1]));
+    h->ms_encode += ms;
+    col.flagged = total;
+    return MEMO_OK;
+}
+
+// the scratch column into coded column `column`, whose earlier content goes first; on failure the column is left as one never
+// added (zeros, no storage) and the handle stays good
+int encode_column(memo_ms *h, int32_t column, hipStream_t st) {
+    CodedColumn &col = h->cols[column];
+    col.reset();
+    h->refs_stale = true;
+    const int rc = encode_passes(h, col, column, st);
+    if (rc) col.reset();
+    return rc;
+}
+
+// a genome that matches nothing: a column of zeros
+int zero_column(memo_ms *h, int32_t column, hipStream_t st) {
+    if (h->layout == MEMO_MS_LAYOUT_CODED) {
+        HIP_TRY(hipMemsetAsync(h->scratch.p, 0, (size_t)h->npos * sizeof(int32_t), st));
+        return encode_column(h, column, st);
+    }
+    HIP_TRY(hipMemset2D(h->M.p + column, (size_t)h->C * 4, 0, 4, (size_t)h->npos));
+    return MEMO_OK;
+}
+
+// DAP rows [first, first + positions) of a coded handle into h->stage, done on return
+int decode_rows(memo_ms *h, int64_t first, int64_t positions, hipStream_t st) {
+    int rc;
+    if ((rc = h->stage.ensure((size_t)(positions * h->C > 0 ? positions * h->C : 1)))) return rc;
+    if (!positions) return MEMO_OK;
+    if (h->refs_stale) {
+        std::vector<CodedRef> refs(h->C);
+        for (int c = 0; c < h->C; ++c) refs[c] = CodedRef{h->cols[c].flags.p, h->cols[c].offs.p, h->cols[c].vals.p};
+        if ((rc = h->refs.ensure((size_t)h->C))) return rc;
+        HIP_TRY(hipMemcpy(h->refs.p, refs.data(), refs.size() * sizeof(CodedRef), hipMemcpyHostToDevice));
+        h->refs_stale = false;
+    }
+    const int64_t tiles = ((first + positions - 1) >> 6) - (first >> 6) + 1;
+    const unsigned groups = (unsigned)((h->C + kTileCols - 1) / kTileCols);
+    HIP_TRY(hipEventRecord(h->cev[0], st));
+    for (int64_t t0 = 0; t0 < tiles; t0 += kLaunchGroups)
+        hipLaunchKernelGGL(code_decode_kernel, dim3((unsigned)(tiles - t0 < kLaunchGroups ? tiles - t0 : kLaunchGroups), groups), dim3(kBlock),
+                           0, st, h->refs.p, h->C, first, positions, t0, h->stage.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->cev[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->cev[0], h->cev[1]));
+    h->ms_decode += ms;
+    return MEMO_OK;
+}
+
 }  // namespace
+
+thread_local int64_t memo::g_ms_free_bytes = -1;
 
 int memo::ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes, int32_t piece,
                         uint8_t *out, int64_t out_cap, int64_t *out_n) {
@@ -790,6 +1100,15 @@ void memo_ms_destroy(memo_ms_t *h) {
 
 int memo_ms_create(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec, int32_t columns, int64_t chunk,
                    int32_t device, memo_ms_t **out) {
+    return memo_ms_create_layout(pivot, rec_begin, nrec, columns, chunk, device, MEMO_MS_LAYOUT_DENSE, out);
+}
+
+int memo_ms_plan_layout(int64_t positions, int32_t columns, uint64_t free_bytes, int32_t layout, int32_t *chosen, int64_t *floor_bytes) {
+    return plan_layout(positions, columns, free_bytes, 0, layout, chosen, floor_bytes);
+}
+
+int memo_ms_create_layout(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec, int32_t columns, int64_t chunk,
+                          int32_t device, int32_t layout, memo_ms_t **out) {
     if (!out) return fail(MEMO_EINVAL, "out is NULL");
     *out = nullptr;
     if (columns < 1 || columns > 4096) return fail(MEMO_EINVAL, "columns must be in [1, 4096], got %d", columns);
@@ -806,9 +1125,12 @@ int memo_ms_create(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec,
     if (chunk > ((int64_t)1 << 30)) return fail(MEMO_EINVAL, "walk chunk %lld too long", (long long)chunk);
     DeviceGuard guard(device);
     if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
-    // the DAP matrix stays resident; every genome's working set comes on top of it
-    const int64_t dap_bytes = npos * (int64_t)columns * 4;
-    int rc = fits(dap_bytes + npos + (int64_t)(sa_bytes(1 << 20)), "the DAP matrix");
+    // the DAP (dense: the matrix; coded: the scratch column and every column's flags) stays resident; every genome's working set
+    // comes on top of it
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    int32_t chosen = 0;
+    int rc = plan_layout(npos, columns, free_b, total_b, layout, &chosen, nullptr);
     if (rc) return rc;
     if (!pivot) return fail(MEMO_EINVAL, "pivot is NULL");
     if (memchr(pivot, 0, (size_t)npos)) return fail(MEMO_EINVAL, "the pivot holds a NUL byte");
@@ -826,14 +1148,21 @@ int memo_ms_create(const uint8_t *pivot, const int64_t *rec_begin, int32_t nrec,
     rc = upload_padded(h->P, pivot, npos, st);
     if (!rc) rc = h->rec_begin.ensure((size_t)nrec + 1);
     if (!rc) rc = h->chunk_begin.ensure((size_t)nrec + 1);
-    if (!rc) rc = h->M.ensure((size_t)(npos * columns));
+    const bool coded = chosen == MEMO_MS_LAYOUT_CODED;
+    h->layout = chosen;
+    h->nblocks = code_blocks(npos);
+    if (coded) h->cols.resize((size_t)columns);  // (no device storage until a column is added)
+    if (!rc) rc = coded ? h->scratch.ensure((size_t)npos) : h->M.ensure((size_t)(npos * columns));
     if (!rc) rc = h->err.ensure(1);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpy(h->rec_begin.p, rec_begin, (nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
     if (!rc && e == hipSuccess) e = hipMemcpy(h->chunk_begin.p, cb.data(), (nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (!rc && e == hipSuccess) e = hipMemset(h->M.p, 0, (size_t)(npos * columns) * sizeof(int32_t));
+    if (!rc && e == hipSuccess)
+        e = coded ? hipMemset(h->scratch.p, 0, (size_t)npos * sizeof(int32_t)) : hipMemset(h->M.p, 0, (size_t)(npos * columns) * sizeof(int32_t));
     for (auto &ev : h->ev)
         if (!rc && e == hipSuccess) e = hipEventCreate(&ev);
+    for (auto &ev : h->cev)
+        if (!rc && e == hipSuccess && coded) e = hipEventCreate(&ev);
     if (!rc && e == hipSuccess) e = hipDeviceSynchronize();
     if (rc || e != hipSuccess) {
         memo_ms_destroy(h);
@@ -851,10 +1180,7 @@ int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t col
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
     hipStream_t st = nullptr;
-    if (n == 0) {  // an empty genome matches nothing: its column is zero
-        HIP_TRY(hipMemset2D(h->M.p + column, (size_t)h->C * 4, 0, 4, (size_t)h->npos));
-        return MEMO_OK;
-    }
+    if (n == 0) return zero_column(h, column, st);  // an empty genome matches nothing: its column is zero
     if (!text) return fail(MEMO_EINVAL, "text is NULL");
     // what is not allocated yet must fit (the buffers grow only)
     const int64_t need = (int64_t)text_bytes(n) - resident_bytes(h);
@@ -863,7 +1189,8 @@ int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t col
     if ((rc = upload_padded(h->T, text, n, st)) || (rc = h->SA.ensure(n)) || (rc = h->ISA.ensure(n)) ||
         (rc = h->LCP.ensure(n)))
         return rc;
-    return ms_of_text(h, n, column, 0, st);
+    if ((rc = ms_of_text(h, n, column, 0, st))) return rc;
+    return h->layout == MEMO_MS_LAYOUT_CODED ? encode_column(h, column, st) : MEMO_OK;
 }
 
 int memo_ms_plan_pieces(const int64_t *rec_len, int32_t nrec, int64_t cap, int32_t *piece_of_string, int32_t *pieces) {
@@ -881,13 +1208,13 @@ int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_beg
     int rc = prepare_records(h, seq, rec_begin, nrec, piece_bytes, first, st);
     if (rc) return rc;
     const int np = (int)first.size() - 1;
-    if (np == 0)  // no records: the text is empty and matches nothing
-        HIP_TRY(hipMemset2D(h->M.p + column, (size_t)h->C * 4, 0, 4, (size_t)h->npos));
+    if (np == 0 && (rc = zero_column(h, column, st))) return rc;  // no records: the text is empty and matches nothing
     for (int p = 0; p < np; ++p) {
         const int64_t n = assemble_piece(h, nrec, first, p, st);
         HIP_TRY(hipGetLastError());
         if ((rc = ms_of_text(h, n, column, p > 0, st))) return rc;
     }
+    if (np && h->layout == MEMO_MS_LAYOUT_CODED && (rc = encode_column(h, column, st))) return rc;
     if (pieces) *pieces = np;
     return MEMO_OK;
 }
@@ -900,6 +1227,15 @@ int memo_ms_fetch(memo_ms_t *h, int64_t first, int64_t positions, int32_t *out) 
     if (!positions) return MEMO_OK;
     if (!out) return fail(MEMO_EINVAL, "out is NULL");
     DeviceGuard guard(h->device);
+    if (h->layout == MEMO_MS_LAYOUT_CODED) {  // through the staging buffer, 256 MiB of rows at a time
+        const int64_t step = ((int64_t)64 << 20) / h->C;
+        for (int64_t done = 0; done < positions; done += step) {
+            const int64_t n = positions - done < step ? positions - done : step;
+            if (int rc = decode_rows(h, first + done, n, nullptr)) return rc;
+            HIP_TRY(hipMemcpy(out + done * h->C, h->stage.p, (size_t)(n * h->C) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        return MEMO_OK;
+    }
     HIP_TRY(hipMemcpy(out, h->M.p + first * h->C, (size_t)(positions * h->C) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MEMO_OK;
 }
@@ -914,7 +1250,43 @@ int memo_ms_push_dap(memo_ms_t *h, memo_dap_t *dap, int64_t first, int64_t posit
     if (dev != h->device || cols != h->C)
         return fail(MEMO_EINVAL, "the DAP handle has %d columns on device %d, the matching statistics %d on device %d", cols, dev,
                     h->C, h->device);
+    if (h->layout == MEMO_MS_LAYOUT_CODED) {  // decoded and waited for before the push reads it
+        DeviceGuard guard(h->device);
+        if (int rc = decode_rows(h, first, positions, nullptr)) return rc;
+        return memo_dap_push_dev(dap, h->stage.p, positions, out_rows);
+    }
     return memo_dap_push_dev(dap, h->M.p + first * h->C, positions, out_rows);
+}
+
+int memo_ms_layout_info(memo_ms_t *h, memo_ms_layout_info_t *info) {
+    if (!h || !info) return fail(MEMO_EINVAL, "NULL argument");
+    memset(info, 0, sizeof *info);
+    info->layout = h->layout;
+    info->block = kCodeBlock;
+    info->dense_bytes = (uint64_t)h->npos * (uint64_t)h->C * 4;
+    if (h->layout == MEMO_MS_LAYOUT_CODED) {
+        info->device_bytes = (uint64_t)(h->scratch.cap + h->stage.cap) * 4;
+        for (const CodedColumn &col : h->cols)
+            if (col.flags.p) {  // what the column's three allocations hold, not the formula
+                info->device_bytes += col.bytes();
+                info->flagged += (uint64_t)col.flagged;
+            }
+    } else {
+        info->device_bytes = (uint64_t)h->M.cap * 4;
+    }
+    info->encode_ms = h->ms_encode;
+    info->decode_ms = h->ms_decode;
+    return MEMO_OK;
+}
+
+int memo_ms_column_info(memo_ms_t *h, int32_t column, uint64_t *flagged, uint64_t *bytes) {
+    if (!h) return fail(MEMO_EINVAL, "handle is NULL");
+    if (column < 0 || column >= h->C) return fail(MEMO_EINVAL, "column %d outside [0, %d)", column, h->C);
+    const bool coded = h->layout == MEMO_MS_LAYOUT_CODED;
+    const bool held = coded && h->cols[column].flags.p;
+    if (flagged) *flagged = held ? (uint64_t)h->cols[column].flagged : 0;
+    if (bytes) *bytes = coded ? (held ? h->cols[column].bytes() : 0) : (uint64_t)h->npos * 4;
+    return MEMO_OK;
 }
 
 int memo_ms_timings(memo_ms_t *h, float *out3) {

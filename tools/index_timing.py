@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """`memo index` end to end on a generated pangenome, per stage, against the suffix-automaton MS of tools/ms_sam.cpp.
 
-    python tools/index_timing.py [--length 20000000] [--genomes 16] [--out build/index_timing]
+    python tools/index_timing.py [--length 20000000] [--genomes 16] [--layout auto] [--out build/index_timing]
 
 1. FASTA of a random pivot of --length bases and --genomes - 1 copies mutated as tools/realistic_index.py does
    (SNPs, short indels, inversions, translocations, a long deletion in every fifth genome);
 2. `memo index` (memo_amd.build_index.build_index, conservation) on them: wall seconds per stage (FASTA reading and
    text building, matching statistics, DAP -> rows, Parquet write) and the device milliseconds of the MS stages from
-   events (suffix arrays, LCP + hierarchy, walks);
+   events (suffix arrays, LCP + hierarchy, walks; with --layout coded also the encode and decode passes, the device bytes
+   held for the DAP and every genome's flagged positions);
 3. tools/ms_sam.cpp (g++ -O2) on the same genomes with MS_THREADS = memo_host_threads();
 4. the two MS matrices must be equal;
 5. one JSON line.  Needs the GPU for step 2.  Development tool."""
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--snp-hi", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=20260)
     ap.add_argument("--chunk", type=int, default=0, help="pivot positions per MS walk thread (0: the library's)")
+    ap.add_argument("--layout", default="auto", choices=["auto", "dense", "coded"], help="of the DAP on the device")
     ap.add_argument("--out", default="build/index_timing", help="working directory for the generated genomes (git-ignored)")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
@@ -73,7 +75,7 @@ def main():
     from memo_amd._lib import lib
     lib()
     st = build_index.build_index(lst, a.out, "index", False, int(os.environ.get("MEMO_DEVICE", "0")), chunk=a.chunk,
-                                 log=lambda s: None, keep_ms=True)
+                                 log=lambda s: None, keep_ms=True, layout=a.layout)
     ours = st.pop("ms")
 
     threads = C.c_int32()
