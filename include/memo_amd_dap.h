@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`), off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) and the reader of `memo view`: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -123,6 +123,27 @@ int memo_ms_timings(memo_ms_t *h, float *out3);
 void memo_ms_destroy(memo_ms_t *h);
 int memo_suffix_array(const uint8_t *text, int64_t n, int32_t *sa_out, int32_t device);
 
+
+/* ---- `memo view` reading: the text a conservation query wrote, parsed where it will be binned ----
+ * Stands in for src/plot_conservation.py:40-49 (fileReader + list(map(int, ...)): one integer per line).  d_text: the
+ * WHOLE file, nbytes bytes on `device` (16-byte aligned); d_vec[i] receives the value of line i (values of 65535 or
+ * more as 65535: memo_bin_conservation_dev counts them in no column and in the bin's width, as the reference's Counter
+ * does), *lines the number of lines.  cap: values d_vec holds; cap < *lines is MEMO_EINVAL (*lines is set), and
+ * cap = nbytes / 2 + 1 always suffices.
+ * The device reads the grammar `memo query` writes, with the usual hand edits: a line is [ \t]*[0-9]{1,9}[ \t]* -- at
+ * most 32 bytes -- ended by \n, \r\n or the end of the text.  Anything else is left to the caller, who reads the file
+ * as the reference does: *first_odd_offset is then the smallest offending byte offset (-1: none), d_vec unspecified,
+ * the return value still MEMO_OK.  What offends, and where: a byte that is no digit, blank, \t, \r or \n (a sign, an
+ * underscore, a NUL, anything >= 0x80), at its own offset; a \r that no \n follows directly (Python's text mode breaks
+ * the line there), at its own offset; and, at the offset of the line's terminator (nbytes for a last line without
+ * \n): an empty line or one of blanks only, blanks between digits, ten or more digits, a line longer than 32 bytes.
+ * Blocking (synchronises `stream`).  (Declared here, with the other text reader that is off the query path, memo_parse_ints: memo_amd.h
+ * keeps to the query path's 44 entry points.) */
+int memo_parse_conservation_text_dev(const char *d_text, int64_t nbytes, uint16_t *d_vec, int64_t cap, int64_t *lines,
+                                     int64_t *first_odd_offset, int32_t device, void *stream);
+/* memo_dev_upload for LARGE pageable host memory (a memory-mapped file): in pieces through the library's pinned ring, the
+ * worker threads filling the next piece while one crosses PCIe.  Blocking. */
+int memo_dev_upload_pipelined(int32_t device, void *dev, const void *host, size_t bytes);
 
 #ifdef __cplusplus
 }

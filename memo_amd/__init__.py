@@ -12,6 +12,8 @@ Layout (only what the path needs):
   shard.py         window sharding across ranks + gather (torch.distributed)
   dap_to_bed.py    DAP -> index rows on the GPU -> BED text or Parquet
   build_index.py   `memo index`: FASTA genomes -> matching statistics on the GPU -> Parquet index
+  view.py          `memo view` preprocessing: result text parsed and binned on the GPU, or a window binned from an index
+  view_cli.py      `memo view`: flags, usage, the table as TSV, the plot (matplotlib)
 
 Attributes are loaded on first use (PEP 562), so that `import memo_amd._fastquery` -- the CLI's cache-hit
 path -- does not pay for NumPy.
@@ -32,7 +34,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

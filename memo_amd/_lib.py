@@ -110,6 +110,8 @@ SYMBOLS = {
     "memo_emit_conservation": (_SZ, [_P, _I64, _P, _SZ]),
     "memo_emit_membership": (_SZ, [_P, _I64, _I32, _P, _SZ]),
     "memo_bin_conservation_dev": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P]),
+    "memo_parse_conservation_text_dev": (C.c_int, [_P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(_I64), _I32, _P]),
+    "memo_dev_upload_pipelined": (C.c_int, [_I32, _P, _P, _SZ]),
     "memo_dap_create": (C.c_int, [_I32, _P, _I32, _I32, _I32, _I32, C.POINTER(_P)]),
     "memo_dap_push": (C.c_int, [_P, _P, _I64, C.POINTER(_U64)]),
     "memo_dap_fetch": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -949,6 +949,13 @@ int memo_dev_upload(int32_t device, void *dev, const void *host, size_t bytes, v
     return MEMO_OK;
 }
 
+// large pageable host memory (a memory-mapped file): in pieces through the pinned ring
+int memo_dev_upload_pipelined(int32_t device, void *dev, const void *host, size_t bytes) {
+    if (bytes && (!dev || !host)) return fail(MEMO_EINVAL, "NULL buffer");
+    if (int rc = device_ok(device)) return rc;
+    return upload_pipelined(device, dev, host, bytes);
+}
+
 int memo_dev_download(int32_t device, void *host, const void *dev, size_t bytes, void *stream) {
     DeviceGuard guard(device);
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -324,10 +324,11 @@ def main():
         view_cases.append(dict(name=f"view{vi}", n_docs=n_docs, n_bins=n_bins, positions=npos))
     json.dump(view_cases, open(os.path.join(GOLD, "view", "manifest.json"), "w"))
 
-    # --- stdout of the reference's bash front end (usage banners; exit status 0 in all three)
+    # --- stdout of the reference's bash front end (usage banners; exit status 0 in all four)
     import subprocess
     os.makedirs(os.path.join(GOLD, "cli"))
-    for fname, argv in (("memo_usage.txt", []), ("memo_query_usage.txt", ["query"]), ("memo_bogus.txt", ["bogus"])):
+    for fname, argv in (("memo_usage.txt", []), ("memo_query_usage.txt", ["query"]), ("memo_bogus.txt", ["bogus"]),
+                        ("memo_view_usage.txt", ["view"])):
         r = subprocess.run(["bash", os.path.join(REF, "src", "memo")] + argv, capture_output=True)
         assert r.returncode == 0
         open(os.path.join(GOLD, "cli", fname), "wb").write(r.stdout)
