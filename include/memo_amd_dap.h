@@ -93,6 +93,13 @@ size_t memo_emit_bed(const int32_t *rec, const int64_t *start, const int64_t *en
  * memo_ms_push_dap: memo_dap_push_dev of those rows (same device, same column count).  A coded handle decodes them into that
  *   staging buffer first, all of them at once: keep pushes moderate.
  * memo_ms_timings: device milliseconds so far of {suffix arrays, LCP + hierarchy, walks}, summed over pieces.
+ * memo_ms_set_walk_budget: how many characters the walk extends a match one at a time before it looks the rest up by seed search
+ *   (a binary search over the suffix array, 8 bytes per compare), for the add calls that follow.  Long runs (N gaps, satellite
+ *   arrays) cost their length / 8 text reads that way instead of two binary searches per character.  0: seed at once; 2^30 or
+ *   more: never (a pivot record is shorter); negative: the default, 64.  The matching statistics are the same for every budget.
+ * memo_ms_walk_info: what the walks of the last memo_ms_add_genome / memo_ms_add_records read of the genome text, summed over its
+ *   pieces (all zeros before the first add).  A text read is one character fetched through the suffix array or one 8-byte word
+ *   compared.
  * memo_suffix_array: the suffix array of text[0, n) on `device` into sa_out (n int32); a suffix that is a
  *   prefix of another sorts first. */
 typedef struct memo_ms memo_ms_t;
@@ -120,6 +127,15 @@ int memo_ms_plan_pieces(const int64_t *rec_len, int32_t nrec, int64_t cap, int32
 int memo_ms_fetch(memo_ms_t *h, int64_t first, int64_t positions, int32_t *out);
 int memo_ms_push_dap(memo_ms_t *h, memo_dap_t *dap, int64_t first, int64_t positions, uint64_t *out_rows);
 int memo_ms_timings(memo_ms_t *h, float *out3);
+typedef struct {
+    uint64_t text_reads;            /* all walk threads */
+    uint64_t max_chunk_text_reads;  /* the most any one walk chunk read, in any piece */
+    uint64_t seeds;                 /* seed searches */
+    uint64_t seed_text_reads;       /* text reads spent in them */
+    int64_t budget;                 /* the budget the add ran with */
+} memo_ms_walk_info_t;
+int memo_ms_set_walk_budget(memo_ms_t *h, int64_t steps);
+int memo_ms_walk_info(memo_ms_t *h, memo_ms_walk_info_t *info);
 void memo_ms_destroy(memo_ms_t *h);
 int memo_suffix_array(const uint8_t *text, int64_t n, int32_t *sa_out, int32_t device);
 

@@ -57,6 +57,12 @@ class MsLayoutInfo(C.Structure):
                 ("flagged", C.c_uint64), ("encode_ms", C.c_float), ("decode_ms", C.c_float)]
 
 
+class MsWalkInfo(C.Structure):
+    """memo_ms_walk_info_t (include/memo_amd_dap.h)"""
+    _fields_ = [("text_reads", C.c_uint64), ("max_chunk_text_reads", C.c_uint64), ("seeds", C.c_uint64),
+                ("seed_text_reads", C.c_uint64), ("budget", C.c_int64)]
+
+
 # every symbol the product headers declare: name -> (restype, argtypes)
 _P, _I32, _I64, _U64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 SYMBOLS = {
@@ -129,6 +135,8 @@ SYMBOLS = {
     "memo_ms_fetch": (C.c_int, [_P, _I64, _I64, _P]),
     "memo_ms_push_dap": (C.c_int, [_P, _P, _I64, _I64, C.POINTER(_U64)]),
     "memo_ms_timings": (C.c_int, [_P, _P]),
+    "memo_ms_set_walk_budget": (C.c_int, [_P, _I64]),
+    "memo_ms_walk_info": (C.c_int, [_P, C.POINTER(MsWalkInfo)]),
     "memo_ms_destroy": (None, [_P]),
     "memo_suffix_array": (C.c_int, [_P, _I64, _P, _I32]),
     "memo_parse_ints": (C.c_int64, [_P, _SZ, _P, _SZ]),

@@ -31,7 +31,9 @@ Refused with a message (never a wrong result): gzip input, a NUL byte, a pivot r
 record of 2^30 positions or more, a genome record of 2^31 - 2 bases or more (or longer than the piece cap less
 one byte), more than 4096 genomes besides the pivot, a DAP that does not fit in the device's free memory even as
 coded columns, a piece's working set that does not, a MEMO_INDEX_PIECE_BYTES that is not an integer in
-[2, 2^31 - 2], a MEMO_INDEX_DAP_LAYOUT that is not auto, dense or coded.  A genome's whole
+[2, 2^31 - 2], a MEMO_INDEX_DAP_LAYOUT that is not auto, dense or coded, a MEMO_INDEX_WALK_BUDGET that is not an
+integer >= 0 (the characters a match is extended one at a time before the rest is looked up by seed search; unset: the
+library's default; 2^30 or more: never.  The index is the same file for every value).  A genome's whole
 text may exceed 2^31 bytes: a human assembly (~6.2 GB of text) runs in a handful of pieces.
 """
 import ctypes as C
@@ -66,6 +68,7 @@ MAX_TEXT = (1 << 31) - 2          # memo_ms: int32 suffix array of one genome te
 PIECE_ENV = "MEMO_INDEX_PIECE_BYTES"   # `memo index`: the piece cap (unset: the library's default)
 MAX_COLUMNS = 4096                # memo_dap: genomes besides the pivot
 LAYOUT_ENV = "MEMO_INDEX_DAP_LAYOUT"   # `memo index`: auto (unset) | dense | coded
+BUDGET_ENV = "MEMO_INDEX_WALK_BUDGET"  # `memo index`: the walk's budget (unset: the library's default)
 STATS_ENV = "MEMO_INDEX_STATS"         # `memo index`: a file that receives build_index's stats as one JSON line
 LAYOUTS = {"auto": 0, "dense": 1, "coded": 2}          # MEMO_MS_LAYOUT_*
 _LAYOUT_NAMES = {v: k for k, v in LAYOUTS.items()}
@@ -129,7 +132,7 @@ class MatchingStatistics:
     """The DAP int32 [positions][columns] of one pivot, resident on `device` (memo_ms_*): as that matrix (layout "dense"),
     as run-coded columns ("coded"), or dense where the matrix fits in the free device memory and coded where not ("auto")"""
 
-    def __init__(self, pivot, rec_begin, columns, device=0, chunk=0, layout="auto"):
+    def __init__(self, pivot, rec_begin, columns, device=0, chunk=0, layout="auto", walk_budget=None):
         self._h = C.c_void_p()
         self.rec_begin = np.ascontiguousarray(rec_begin, np.int64)
         self.positions = int(self.rec_begin[-1])
@@ -139,6 +142,25 @@ class MatchingStatistics:
             raise ValueError(f"pivot has {len(self._pivot)} bytes, its records {self.positions}")
         check(lib().memo_ms_create_layout(self._pivot, self.rec_begin.ctypes.data, len(self.rec_begin) - 1, columns,
                                           int(chunk), device, _layout_number(layout), C.byref(self._h)))
+        if walk_budget is not None:
+            try:
+                self.set_walk_budget(walk_budget)
+            except BaseException:
+                self.close()
+                raise
+
+    def set_walk_budget(self, steps):
+        """the characters the walks of the adds to come extend a match one at a time before the rest is looked up by seed
+        search: 0 seeds at once, 2^30 or more never, None or a negative value restores the default"""
+        check(lib().memo_ms_set_walk_budget(self._h, -1 if steps is None else int(steps)))
+
+    def walk_info(self):
+        """{"text_reads", "max_chunk_text_reads", "seeds", "seed_text_reads", "budget"} of the last add's walks
+        (memo_ms_walk_info; all zeros before the first add)"""
+        from ._lib import MsWalkInfo
+        info = MsWalkInfo()
+        check(lib().memo_ms_walk_info(self._h, C.byref(info)))
+        return {name: getattr(info, name) for name, _ in MsWalkInfo._fields_}
 
     def layout_info(self):
         """{"layout": "dense" | "coded", "block": positions per coding block, "device_bytes": held for the DAP now,
@@ -249,6 +271,17 @@ def piece_bytes_from_env(environ=os.environ):
     return cap
 
 
+def walk_budget_from_env(environ=os.environ):
+    """the walk budget MEMO_INDEX_WALK_BUDGET asks for (None: unset, the library's default); FastaError when it is not an
+    integer >= 0 (decimal digits only: no sign, no blanks)"""
+    raw = environ.get(BUDGET_ENV, "")
+    if raw == "":
+        return None
+    if not (raw.isascii() and raw.isdigit()) or len(raw) > 18:
+        raise FastaError(f"{BUDGET_ENV}={raw!r}: need an integer >= 0 (below 10^18)")
+    return int(raw)
+
+
 def matching_statistics(pivot, genomes, device=0, chunk=0):
     """MS matrix int32 [pivot positions][len(genomes)] of pivot records (list of bytes) against genomes (each a
     list of record bytes), by the rule in the module docstring"""
@@ -275,11 +308,12 @@ def read_genome_list(path):
 
 
 def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log=print, keep_ms=False, piece_bytes=0,
-                layout="auto"):
+                layout="auto", walk_budget=None):
     """index.sh end to end; returns per-stage seconds, the pieces of every genome's text (and the MS matrix when
     keep_ms).  piece_bytes: the cap of a piece of genome text (<= 0: the library's default).  layout: of the DAP on the
     device, "auto" | "dense" | "coded" (stats: dap_layout, the one taken; dap_device_bytes, held for the DAP after the last
-    genome; per genome, flagged: its column's flagged positions, 0 in the dense layout).  Row batches go to the Parquet writer
+    genome; per genome, flagged: its column's flagged positions, 0 in the dense layout).  walk_budget: MatchingStatistics' (None: the
+    default; stats: walk_budget, the one taken; per genome, seeds and max_chunk_text_reads of its walks).  Row batches go to the Parquet writer
     as they are produced (each is written and dropped before the next is made), so the two stages interleave: dap_to_rows_s
     is the time spent making batches, parquet_s the rest of that one loop."""
     from .dap_to_bed import DapConverter, write_parquet
@@ -287,11 +321,12 @@ def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log
     paths = read_genome_list(genome_list)
     _layout_number(layout)
     names, pivot, rec_begin = pivot_layout(read_fasta(paths[0]), paths[0])
-    stats = {"positions": int(rec_begin[-1]), "genomes": len(paths), "read_s": 0.0, "pieces": [], "per_genome": []}
+    stats = {"positions": int(rec_begin[-1]), "genomes": len(paths), "read_s": 0.0, "pieces": [], "per_genome": [],
+             "walk_budget": None}         # (the budget of the walks: no walk, no budget)
     stats["read_s"] += time.perf_counter() - t0
     out_path = os.path.join(out_dir, prefix + ".parquet")
     os.makedirs(out_dir or ".", exist_ok=True)
-    with MatchingStatistics(pivot, rec_begin, len(paths) - 1, device, chunk, layout) as ms:
+    with MatchingStatistics(pivot, rec_begin, len(paths) - 1, device, chunk, layout, walk_budget) as ms:
         stats["dap_layout"] = ms.layout_info()["layout"]
         t1 = time.perf_counter()
         for c, path in enumerate(paths[1:]):
@@ -309,9 +344,12 @@ def build_index(genome_list, out_dir, prefix, membership, device=0, chunk=0, log
                     raise
                 raise FastaError(f"{path}: record '{records[int(m.group(1))][0]}': {exc}") from None
             after = ms.timings()
+            walk = ms.walk_info()
+            stats["walk_budget"] = walk["budget"]
             stats["per_genome"].append({"bases": sum(len(s) for _, s in records), "records": len(records),
                                         "pieces": stats["pieces"][-1], "read_s": read_s,
                                         "flagged": ms.column_info(c)["flagged"],
+                                        "seeds": walk["seeds"], "max_chunk_text_reads": walk["max_chunk_text_reads"],
                                         **{k: after[k] - before[k] for k in after}})
             del records
         stats["ms_s"] = time.perf_counter() - t1
@@ -378,8 +416,10 @@ def main(argv):
         read_genome_list(val.get("-g", ""))          # refuse before the device is touched
         piece_bytes = piece_bytes_from_env()
         layout = dap_layout_from_env()
+        walk_budget = walk_budget_from_env()
         stats = build_index(val["-g"], val["-o"], val["-p"], "-m" in val, int(os.environ.get("MEMO_DEVICE", "0")),
-                            log=lambda s: print(s, flush=True), piece_bytes=piece_bytes, layout=layout)
+                            log=lambda s: print(s, flush=True), piece_bytes=piece_bytes, layout=layout,
+                            walk_budget=walk_budget)
         if os.environ.get(STATS_ENV):
             import json
             with open(os.environ[STATS_ENV], "w") as fh:

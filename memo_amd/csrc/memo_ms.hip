@@ -13,7 +13,11 @@
 //   MS walk           one thread per chunk of pivot positions inside one record, carrying the SA interval of
 //                     P[i, i + l): extend by two binary searches on T[SA[y] + l] (direct comparison once the
 //                     interval is one suffix), record MS[i] = l, advance through x = ISA[SA[lo] + 1] and the maximal
-//                     range around x with LCP >= l - 1.  Exact from any start, so chunks need no fix-up.
+//                     range around x with LCP >= l - 1.  Exact from any start, so chunks need no fix-up.  An extension
+//                     that has taken `budget` steps with more than one suffix left (an N run, a satellite array)
+//                     goes on by seed search: a binary search over the SA for the suffix that shares the most with
+//                     the rest of the record, 8 bytes per compare, every compare starting at the length the
+//                     candidates are known to share (seed_search below).  Same (l, interval), l / 8 reads.
 //
 //   pieces            a genome given as records (memo_ms_add_records) is uploaded once, back to back, and its text is
 //                     assembled on the device piece by piece: each piece a run of whole strings (records, then their
@@ -47,6 +51,7 @@ constexpr int kErrSearch = 1;     // device error bits: a hierarchy search ran o
 constexpr int kErrWalk = 2;       //   an MS walk loop hit its bound
 constexpr int kErrIsa = 4;        //   an advance step found no successor suffix
 constexpr int kBlock = 256;
+constexpr int64_t kWalkBudget = 64;              // extension steps before a seed search: the default
 
 unsigned grid_for(int64_t n, int block = kBlock) {  // n < 2^31: at most 2^23 blocks
     const int64_t g = (n + block - 1) / block;
@@ -61,10 +66,13 @@ __device__ __forceinline__ uint64_t load8(const uint8_t *T, int64_t p) {
     return s ? (lo >> s) | (w[1] << (64 - s)) : lo;
 }
 
-// common prefix of A[a, a + lim) and B[b, b + lim), 8 bytes per step; the buffers are padded by kPad
-__device__ __forceinline__ int64_t common_prefix(const uint8_t *A, int64_t a, const uint8_t *B, int64_t b, int64_t lim) {
+// common prefix of A[a, a + lim) and B[b, b + lim), 8 bytes per step; the buffers are padded by kPad.  words: += the 8-byte
+// words compared
+__device__ __forceinline__ int64_t common_prefix(const uint8_t *A, int64_t a, const uint8_t *B, int64_t b, int64_t lim,
+                                                 int64_t &words) {
     int64_t l = 0;
     for (int64_t step = 0; step <= (lim >> 3) && l < lim; ++step) {
+        ++words;
         const uint64_t x = load8(A, a + l) ^ load8(B, b + l);
         if (x) {
             l += __builtin_ctzll(x) >> 3;
@@ -73,6 +81,11 @@ __device__ __forceinline__ int64_t common_prefix(const uint8_t *A, int64_t a, co
         l += 8;
     }
     return l < lim ? l : lim;
+}
+
+__device__ __forceinline__ int64_t common_prefix(const uint8_t *A, int64_t a, const uint8_t *B, int64_t b, int64_t lim) {
+    int64_t words = 0;
+    return common_prefix(A, a, B, b, lim, words);
 }
 
 // ---- suffix array ------------------------------------------------------------------------------------
@@ -251,6 +264,11 @@ __device__ int64_t search_right(const Hierarchy &H, int64_t x, int32_t t, int *e
 
 // ---- the walk ------------------------------------------------------------------------------------------
 
+// what the walks of one add call read of the text; a text read is one char_at or one 8-byte word of a common_prefix
+struct WalkCounters {
+    unsigned long long text_reads, max_chunk_text_reads, seeds, seed_text_reads;
+};
+
 struct WalkArgs {
     const uint8_t *T;         // genome text (+ kPad zeros)
     const int32_t *SA, *ISA;
@@ -265,7 +283,9 @@ struct WalkArgs {
     int32_t *M;               // DAP [positions][C]
     int C, col;
     int merge;                // 0: store l (the first piece); 1: store max(M, l) (later pieces)
+    int64_t budget;           // extension steps at one position before a seed search takes over
     int *err;
+    WalkCounters *count;      // summed over the launches of one add call
 };
 
 // T[SA[y] + l] as a signed value; -1 past the end of the text (sorts first)
@@ -274,74 +294,158 @@ __device__ __forceinline__ int char_at(const WalkArgs &A, int64_t y, int64_t l) 
     return p < A.n ? (int)A.T[p] : -1;
 }
 
+// Seed search.  Every suffix of SA[lo, hi] shares its first l characters with P[i, re).  Returns the one that shares the most
+// (x) and sets l to that length: what extending one character at a time arrives at, for the price of l / 8 word compares.
+// A binary search over [a, b], which starts as [lo, hi].  `l` is what every suffix of [a, b] is known to share with P[i, re),
+// so the compare with the middle suffix m starts there and no character is compared twice.  When m shares k > l, the
+// suffixes that share less than k with m (outside the LCP >= k range around m, from the min hierarchy) share less than k
+// with the pivot too: [a, b] shrinks to that range and l becomes k.  Then the first characters that differ say on which
+// side of m the pivot sorts.  m leaves [a, b] every round and [a, b] at least halves, so 32 rounds do for n < 2^31
+// (the bound below allows one more).
+__device__ int64_t seed_search(const WalkArgs &A, int64_t i, int64_t re, int64_t lo, int64_t hi, int64_t &l, int64_t &reads,
+                               int *err) {
+    int64_t a = lo, b = hi, x = lo;
+    for (int round = 0; a <= b; ++round) {
+        if (round > 32) {
+            *err |= kErrWalk;
+            break;
+        }
+        const int64_t m = (a + b) >> 1;
+        const int64_t s = A.SA[m];
+        const int64_t lim = re - i < A.n - s ? re - i : A.n - s;  // >= l: suffix m shares l characters with P[i, re)
+        int64_t k = l;
+        if (k < lim) k += common_prefix(A.T, s + k, A.P, i + k, lim - k, reads);
+        if (k > l) {
+            x = m;
+            l = k;
+            if (k == re - i) break;  // the rest of the record occurs
+            const int64_t y0 = search_left(A.H, m, (int32_t)k, err);
+            const int64_t y1 = search_right(A.H, m + 1, (int32_t)k, err);
+            a = y0 > a ? y0 : a;
+            b = y1 - 1 < b ? y1 - 1 : b;
+        }
+        ++reads;
+        if ((int)A.P[i + k] < char_at(A, m, k)) b = m - 1; else a = m + 1;  // (a suffix that ends here sorts first)
+    }
+    return x;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
+        const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
 __global__ void __launch_bounds__(kBlock) ms_walk_kernel(const WalkArgs A) {
     const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (t >= A.nchunks) return;
-    int lo_r = 0, hi_r = A.nrec;  // record of this chunk: last r with chunk_begin[r] <= t
-    while (hi_r - lo_r > 1) {
-        const int mid = (lo_r + hi_r) >> 1;
-        if (A.chunk_begin[mid] <= t) lo_r = mid; else hi_r = mid;
-    }
-    const int64_t rb = A.rec_begin[lo_r], re = A.rec_begin[lo_r + 1];
-    const int64_t i0 = rb + (t - A.chunk_begin[lo_r]) * A.chunk;
-    const int64_t i1 = i0 + A.chunk < re ? i0 + A.chunk : re;
-    const int64_t n = A.n;
     int err = 0;
-    int64_t lo = 0, hi = n - 1, l = 0;  // SA interval of P[i, i + l)
-    for (int64_t i = i0; i < i1; ++i) {
-        // extend
-        for (int64_t step = 0; i + l < re; ++step) {
-            if (step > re - rb) {
-                err |= kErrWalk;
-                break;
-            }
-            if (lo == hi) {  // one suffix left: compare directly
-                const int64_t s = A.SA[lo];
-                const int64_t lim = (re - i < n - s ? re - i : n - s);
-                if (l < lim) l += common_prefix(A.T, s + l, A.P, i + l, lim - l);
-                break;
-            }
-            const int c = A.P[i + l];
-            int64_t a = lo, b = hi + 1;  // first y in [lo, hi] with char >= c
-            for (int k = 0; k < 33 && a < b; ++k) {
-                const int64_t mid = (a + b) >> 1;
-                if (char_at(A, mid, l) < c) a = mid + 1; else b = mid;
-            }
-            if (a > hi || char_at(A, a, l) != c) break;  // P[i, i + l] occurs nowhere
-            int64_t a2 = a, b2 = hi + 1;                  // first y in [a, hi] with char > c
-            for (int k = 0; k < 33 && a2 < b2; ++k) {
-                const int64_t mid = (a2 + b2) >> 1;
-                if (char_at(A, mid, l) <= c) a2 = mid + 1; else b2 = mid;
-            }
-            lo = a;
-            hi = a2 - 1;
-            ++l;
+    int64_t reads = 0, seeds = 0, seed_reads = 0;  // this chunk's text reads
+    if (t < A.nchunks) {
+        int lo_r = 0, hi_r = A.nrec;  // record of this chunk: last r with chunk_begin[r] <= t
+        while (hi_r - lo_r > 1) {
+            const int mid = (lo_r + hi_r) >> 1;
+            if (A.chunk_begin[mid] <= t) lo_r = mid; else hi_r = mid;
         }
-        int32_t *m = A.M + i * (int64_t)A.C + A.col;
-        *m = A.merge && *m > (int32_t)l ? *m : (int32_t)l;
-        // advance: P[i + 1, i + l) is the suffix after SA[lo], less its first character
-        if (l > 1) {
-            const int64_t s1 = (int64_t)A.SA[lo] + 1;
-            if (s1 >= n) {
-                err |= kErrIsa;
+        const int64_t rb = A.rec_begin[lo_r], re = A.rec_begin[lo_r + 1];
+        const int64_t i0 = rb + (t - A.chunk_begin[lo_r]) * A.chunk;
+        const int64_t i1 = i0 + A.chunk < re ? i0 + A.chunk : re;
+        const int64_t n = A.n;
+        int64_t lo = 0, hi = n - 1, l = 0;  // SA interval of P[i, i + l)
+        for (int64_t i = i0; i < i1; ++i) {
+            // extend
+            for (int64_t step = 0; i + l < re; ++step) {
+                if (step > re - rb) {
+                    err |= kErrWalk;
+                    break;
+                }
+                if (lo == hi) {  // one suffix left: compare directly
+                    const int64_t s = A.SA[lo];
+                    const int64_t lim = (re - i < n - s ? re - i : n - s);
+                    if (l < lim) l += common_prefix(A.T, s + l, A.P, i + l, lim - l, reads);
+                    break;
+                }
+                if (step >= A.budget) {  // still wide after `budget` characters: the rest by seed search
+                    const int64_t before = reads;
+                    const int64_t x = seed_search(A, i, re, lo, hi, l, reads, &err);
+                    ++seeds;
+                    seed_reads += reads - before;
+                    if (l > 0) {
+                        const int64_t y0 = search_left(A.H, x, (int32_t)l, &err);
+                        lo = y0 < 0 ? 0 : y0;
+                        hi = search_right(A.H, x + 1, (int32_t)l, &err) - 1;
+                    } else {
+                        lo = 0;
+                        hi = n - 1;
+                    }
+                    break;
+                }
+                const int c = A.P[i + l];
+                int64_t a = lo, b = hi + 1;  // first y in [lo, hi] with char >= c
+                for (int k = 0; k < 33 && a < b; ++k) {
+                    const int64_t mid = (a + b) >> 1;
+                    ++reads;
+                    if (char_at(A, mid, l) < c) a = mid + 1; else b = mid;
+                }
+                if (a > hi) break;  // P[i, i + l] occurs nowhere
+                ++reads;
+                if (char_at(A, a, l) != c) break;
+                int64_t a2 = a, b2 = hi + 1;  // first y in [a, hi] with char > c
+                for (int k = 0; k < 33 && a2 < b2; ++k) {
+                    const int64_t mid = (a2 + b2) >> 1;
+                    ++reads;
+                    if (char_at(A, mid, l) <= c) a2 = mid + 1; else b2 = mid;
+                }
+                lo = a;
+                hi = a2 - 1;
+                ++l;
+            }
+            int32_t *m = A.M + i * (int64_t)A.C + A.col;
+            *m = A.merge && *m > (int32_t)l ? *m : (int32_t)l;
+            // advance: P[i + 1, i + l) is the suffix after SA[lo], less its first character
+            if (l > 1) {
+                const int64_t s1 = (int64_t)A.SA[lo] + 1;
+                if (s1 >= n) {
+                    err |= kErrIsa;
+                    l = 0;
+                    lo = 0;
+                    hi = n - 1;
+                    continue;
+                }
+                const int64_t x = A.ISA[s1];
+                --l;
+                const int64_t y0 = search_left(A.H, x, (int32_t)l, &err);
+                const int64_t y1 = search_right(A.H, x + 1, (int32_t)l, &err);
+                lo = y0 < 0 ? 0 : y0;
+                hi = y1 - 1;
+            } else {
                 l = 0;
                 lo = 0;
                 hi = n - 1;
-                continue;
             }
-            const int64_t x = A.ISA[s1];
-            --l;
-            const int64_t y0 = search_left(A.H, x, (int32_t)l, &err);
-            const int64_t y1 = search_right(A.H, x + 1, (int32_t)l, &err);
-            lo = y0 < 0 ? 0 : y0;
-            hi = y1 - 1;
-        } else {
-            l = 0;
-            lo = 0;
-            hi = n - 1;
         }
     }
     if (err) atomicOr(A.err, err);
+    // the counters: summed (the largest chunk: maximised) over the wave, then one lane adds them
+    const unsigned long long r = wave_sum((unsigned long long)reads), rmax = wave_max((unsigned long long)reads);
+    const unsigned long long sd = wave_sum((unsigned long long)seeds), sr = wave_sum((unsigned long long)seed_reads);
+    if ((threadIdx.x & 63) == 0) {
+        WalkCounters *c = A.count;
+        if (r) atomicAdd(&c->text_reads, r);
+        if (rmax) atomicMax(&c->max_chunk_text_reads, rmax);
+        if (sd) atomicAdd(&c->seeds, sd);
+        if (sr) atomicAdd(&c->seed_text_reads, sr);
+    }
 }
 
 // ---- piece texts -----------------------------------------------------------------------------------------
@@ -675,6 +779,9 @@ struct memo_ms {
     DevBuf<int> err;
     SaWork W;
     float ms_sa = 0.f, ms_lcp = 0.f, ms_walk = 0.f;
+    int64_t budget = kWalkBudget;      // of the walks to come (memo_ms_set_walk_budget)
+    DevBuf<WalkCounters> walk_count;   // the walks of the add call under way
+    memo_ms_walk_info_t walk{};        // of the last add call
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // the coded layout (M stays empty): the walk's target, the columns, what the encode and decode passes work in
     int layout = MEMO_MS_LAYOUT_DENSE;
@@ -693,7 +800,7 @@ namespace {
 
 void release(memo_ms *h) {
     h->P.release(); h->T.release(); h->R.release(); h->rec_begin.release(); h->chunk_begin.release(); h->G.release();
-    h->M.release(); h->SA.release(); h->ISA.release(); h->LCP.release(); h->levels.release(); h->err.release();
+    h->M.release(); h->SA.release(); h->ISA.release(); h->LCP.release(); h->levels.release(); h->err.release(); h->walk_count.release();
     h->W.release();
     h->scratch.release(); h->stage.release(); h->count.release(); h->scan_tmp.release(); h->refs.release();
     h->cols.clear();
@@ -890,7 +997,9 @@ int ms_of_text(memo_ms *h, int64_t n, int32_t column, int merge, hipStream_t st)
     A.C = coded ? 1 : h->C;
     A.col = coded ? 0 : column;
     A.merge = merge;
+    A.budget = h->budget;
     A.err = h->err.p;
+    A.count = h->walk_count.p;
     HIP_TRY(hipMemsetAsync(h->err.p, 0, sizeof(int), st));
     hipLaunchKernelGGL(ms_walk_kernel, dim3(grid_for(nchunks)), dim3(kBlock), 0, st, A);
     HIP_TRY(hipGetLastError());
@@ -906,6 +1015,25 @@ int ms_of_text(memo_ms *h, int64_t n, int32_t column, int merge, hipStream_t st)
     h->ms_lcp += b;
     h->ms_walk += c;
     if (errw) return fail(MEMO_EHIP, "matching statistics of column %d: the walk kernel reported error bits 0x%x", column, errw);
+    return MEMO_OK;
+}
+
+// an add call's counters: cleared before its first piece, read after its last
+int begin_add(memo_ms *h, hipStream_t st) {
+    h->walk = memo_ms_walk_info_t{};
+    h->walk.budget = h->budget;
+    HIP_TRY(hipMemsetAsync(h->walk_count.p, 0, sizeof(WalkCounters), st));
+    return MEMO_OK;
+}
+
+int end_add(memo_ms *h, hipStream_t st) {
+    WalkCounters c{};
+    HIP_TRY(hipMemcpyAsync(&c, h->walk_count.p, sizeof c, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    h->walk.text_reads = c.text_reads;
+    h->walk.max_chunk_text_reads = c.max_chunk_text_reads;
+    h->walk.seeds = c.seeds;
+    h->walk.seed_text_reads = c.seed_text_reads;
     return MEMO_OK;
 }
 
@@ -1154,6 +1282,7 @@ int memo_ms_create_layout(const uint8_t *pivot, const int64_t *rec_begin, int32_
     if (coded) h->cols.resize((size_t)columns);  // (no device storage until a column is added)
     if (!rc) rc = coded ? h->scratch.ensure((size_t)npos) : h->M.ensure((size_t)(npos * columns));
     if (!rc) rc = h->err.ensure(1);
+    if (!rc) rc = h->walk_count.ensure(1);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpy(h->rec_begin.p, rec_begin, (nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
     if (!rc && e == hipSuccess) e = hipMemcpy(h->chunk_begin.p, cb.data(), (nrec + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
@@ -1180,16 +1309,17 @@ int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t col
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
     hipStream_t st = nullptr;
+    int rc = begin_add(h, st);
+    if (rc) return rc;
     if (n == 0) return zero_column(h, column, st);  // an empty genome matches nothing: its column is zero
     if (!text) return fail(MEMO_EINVAL, "text is NULL");
     // what is not allocated yet must fit (the buffers grow only)
     const int64_t need = (int64_t)text_bytes(n) - resident_bytes(h);
-    int rc = need > 0 ? fits(need, "this genome's suffix array and LCP") : MEMO_OK;
-    if (rc) return rc;
+    if (need > 0 && (rc = fits(need, "this genome's suffix array and LCP"))) return rc;
     if ((rc = upload_padded(h->T, text, n, st)) || (rc = h->SA.ensure(n)) || (rc = h->ISA.ensure(n)) ||
         (rc = h->LCP.ensure(n)))
         return rc;
-    if ((rc = ms_of_text(h, n, column, 0, st))) return rc;
+    if ((rc = ms_of_text(h, n, column, 0, st)) || (rc = end_add(h, st))) return rc;
     return h->layout == MEMO_MS_LAYOUT_CODED ? encode_column(h, column, st) : MEMO_OK;
 }
 
@@ -1206,7 +1336,7 @@ int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_beg
     hipStream_t st = nullptr;
     std::vector<int32_t> first;
     int rc = prepare_records(h, seq, rec_begin, nrec, piece_bytes, first, st);
-    if (rc) return rc;
+    if (rc || (rc = begin_add(h, st))) return rc;
     const int np = (int)first.size() - 1;
     if (np == 0 && (rc = zero_column(h, column, st))) return rc;  // no records: the text is empty and matches nothing
     for (int p = 0; p < np; ++p) {
@@ -1214,6 +1344,7 @@ int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_beg
         HIP_TRY(hipGetLastError());
         if ((rc = ms_of_text(h, n, column, p > 0, st))) return rc;
     }
+    if ((rc = end_add(h, st))) return rc;
     if (np && h->layout == MEMO_MS_LAYOUT_CODED && (rc = encode_column(h, column, st))) return rc;
     if (pieces) *pieces = np;
     return MEMO_OK;
@@ -1286,6 +1417,18 @@ int memo_ms_column_info(memo_ms_t *h, int32_t column, uint64_t *flagged, uint64_
     const bool held = coded && h->cols[column].flags.p;
     if (flagged) *flagged = held ? (uint64_t)h->cols[column].flagged : 0;
     if (bytes) *bytes = coded ? (held ? h->cols[column].bytes() : 0) : (uint64_t)h->npos * 4;
+    return MEMO_OK;
+}
+
+int memo_ms_set_walk_budget(memo_ms_t *h, int64_t steps) {
+    if (!h) return fail(MEMO_EINVAL, "handle is NULL");
+    h->budget = steps < 0 ? kWalkBudget : steps;  // (2^30 or more: no extension takes that many steps)
+    return MEMO_OK;
+}
+
+int memo_ms_walk_info(memo_ms_t *h, memo_ms_walk_info_t *info) {
+    if (!h || !info) return fail(MEMO_EINVAL, "NULL argument");
+    *info = h->walk;
     return MEMO_OK;
 }
 
