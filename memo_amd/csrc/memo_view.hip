@@ -427,7 +427,14 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, RowS
     const double spared = src_rows > kept ? 1.0 - kept / src_rows : 0.0;
     // six rows per group?  (5-bit starts and overlaps, 8-bit annots; the sweep's form for them has at most five level arrays)
     bool six = allow_six && ix->bshift == 5 && ix->max_annot <= 255 && km1 <= 31 && ix->view_rows != 5 && g_six_views != 0;
-    if (six && ix->view_rows != 6 && g_six_views != 1) six = kept >= 40.0 * (double)(ix->nb > 1 ? ix->nb - 1 : 1);
+    // The buckets the rows lie in, not the table's: the table starts at bucket 0 however far from the origin the first row is, and
+    // the buckets before it hold nothing to pad.  A table has nb = (last bucket) + 3 entries (memo_index_finalize), so for rows that
+    // begin in bucket 0 this is nb - 1 = (last bucket) + 2, what was counted before; never more than the table holds (an imported
+    // slice's nb is its caller's), never less than 1 (no rows: max_s = -1).
+    const int64_t table_buckets = ix->nb > 1 ? (int64_t)(ix->nb - 1) : 1;
+    int64_t spanned = (ix->max_s >> ix->bshift) - (ix->min_s >> ix->bshift) + 2;
+    if (spanned < 1 || spanned > table_buckets) spanned = table_buckets;
+    if (six && ix->view_rows != 6 && g_six_views != 1) six = kept >= 40.0 * (double)spanned;
     memo_index::DenseView *vp = six ? &ix->views6[slot] : &ix->views[slot];
     if (ix->view_rows == 0 && g_six_views < 0) {  // (the library's choice: whichever kind is there already)
         if (vp->state != 1 && allow_six && ix->bshift == 5 && km1 <= 31 && ix->views6[slot].state == 1) vp = &ix->views6[slot], six = true;
