@@ -609,10 +609,13 @@ int launch_tiles(SweepKernel kernel, SweepArgs &A, int w, int threads, size_t ld
 // ballots and packing have little to save; profiles/r07_live_rows.txt has the shares measured)
 constexpr double kLiveMinShare = 0.25;
 // A six-row view without flags at k - 1 in [16, 31] is swept on radix-4 arrays in wide tiles (R4) while a wide tile holds fewer than
-// kR4MaxGroups of its groups (MEMO_OPT_WIDE_TILES 0 keeps the doubling tiles); A's tile fields are rewritten for it.  Config 3 at
-// k = 31 (profiles/r09_wide_tiles.txt): the live copy, ~180 groups per wide tile, 0.095 against 0.122 ms; the placed view without
-// flags or copy, ~670, 0.200 against 0.188 -- its extra blocks per row cost more LDS cycles than the wider tile saves
-constexpr double kR4MaxGroups = 384.0;
+// kR4MaxGroups of its groups (MEMO_OPT_WIDE_TILES 0 keeps the doubling tiles); A's tile fields are rewritten for it.  Config 3's
+// generator at k = 31, wide against doubling tiles on one index (profiles/r13_three_block_rows.txt; tools/wide_tile_ab.py): the live
+// copy, 179 groups per wide tile, 0.095 against 0.125 ms; the copy at twice and three times the rows, 239 and 282 groups, -23 % and
+// -14 %; the placed view without flags or copy at 3/100 rows per genome-position, 412 groups, 0.131 against 0.144 ms (-8.5 %); the
+// same at config 3's 5/100, 674 groups, 0.186 against 0.188 ms -- inside the run-to-run spread of 1-1.5 %.  The constant: halfway
+// between the last two
+constexpr double kR4MaxGroups = 543.0;
 int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStream_t st, bool annot9 = false, bool all_write = false,
                   bool six = false, bool live = false);
 int pick_rows(const memo_index *ix, int32_t k, int &fmt);

@@ -72,7 +72,7 @@ __global__ void tile_table_kernel(const int64_t *boff, int64_t nb, int64_t bbase
 // launcher sets from the rows per tile (profiles/r06_headline.txt; masking the dead loads off with EXEC = 0 instead gained nothing).
 // LIVE (SIX only): the view's groups say which of them hold no live row (memo_view_build.hip: view_live_kernel) -- a dead group's lane
 // sits out its rows' atomics, a piece without a live group is skipped (memo_sweep_dense.h: live_pieces)
-// R4 (SIX, not LIVE, k - 1 in [16, 31]): radix-4 level arrays -- blocks of 16, 4 and 1 -- of kLS4 = 1664 cells in place of the five
+// R4 (SIX, not LIVE, k - 1 in [16, 31]): radix-4 level arrays -- blocks of 12, 4 and 1 -- of kLS4 = 1664 cells in place of the five
 // doubling arrays of 1024: the same 20 KiB per tile (eight tiles per CU), 1.69x the positions per tile at k = 31 (memo_sweep_dense.h:
 // group_rows4; the launcher takes it for six-row views with few rows per tile, launch_halo3t)
 template <int NLEV, typename OutT, int T, bool A9 = false, bool AW = false, bool SIX = false, bool SP = false, bool LIVE = false,
@@ -175,7 +175,8 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     // fold in registers + store (halo_fold_store_dpp of memo_sweep_cons.hip, unrolled for NLEV)
     OutT *out = static_cast<OutT *>(A.out);
     const int cells = HL + W;
-    constexpr int ctx = R4 ? 4 : (NLEV <= 1 ? 0 : (NLEV <= 3 ? 1 : 1 << (NLEV - 3)));
+    // context lanes of a chunk of 64 (R4: the fold of 12s reads two lanes to the left, the fold of 4s one more; 4 * ctx <= hl)
+    constexpr int ctx = R4 ? 3 : (NLEV <= 1 ? 0 : (NLEV <= 3 ? 1 : 1 << (NLEV - 3)));
     constexpr int valid = 64 - ctx;
     const int64_t a_rel = (int64_t)tabs * W - A.qs;  // the tile's first position, as an output index
     const int64_t ob = a_rel - HL;
@@ -187,11 +188,11 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
         u32x4 L[6];
         auto lv = [&](int i) { return make_uint4(L[i].x, L[i].y, L[i].z, L[i].w); };
         uint4 M;
-        if constexpr (R4) {  // blocks of 16 -> 4 -> positions (memo_sweep_fold.h)
+        if constexpr (R4) {  // blocks of 12 -> 4 -> positions (memo_sweep_fold.h)
             read_levels_r4(lds_base + 4u * (uint32_t)xr, L);
             M = lv(2);
             uint4 M4 = lv(1);
-            r4_fold16(M4, lv(0));
+            r4_fold12(M4, lv(0));
             r4_fold4(M, M4);
         } else {
             read_levels<NLEV>(lds_base + 4u * (uint32_t)xr, L);

@@ -315,37 +315,39 @@ __device__ __forceinline__ void live_pieces(const uint4 (&V)[NL], int lane, int 
 }
 
 // ---- R4: six-row views on RADIX-4 level arrays in wide tiles (k - 1 in [16, 31]; memo_sweep_cons3t.hip) -------------------------
-// Three arrays of kLS4 cells -- blocks of 16, 4 and 1 -- where the doubling arrays need five of 1024: 19 968 bytes, still eight tiles
+// Three arrays of kLS4 cells -- blocks of 12, 4 and 1 -- where the doubling arrays need five of 1024: 19 968 bytes, still eight tiles
 // per CU, and a tile of 1568 positions at k = 31 instead of 928.  A row's interval of n positions (n < 32) takes blocks of
-// S = 16 / 4 / 1 (the largest power of four <= n) at its first cell and at its end - S, plus one at first + S when n > 2S and one
-// at first + 2S when n > 3S (lanes past their row's block count masked off by v_cmpx): 2 to 4 ds_min per row instead of 2.
+// S = 12 (n >= 12) / 4 (n = 4 .. 11) / 1 (n < 4) at its first cell and at its end - S, plus one at first + S when n > 2S (lanes
+// whose two blocks cover their row masked off by v_cmpx): 2 or 3 ds_min per row instead of 2.  Three blocks of S cover every
+// n <= 3S: 3, 12 and 36 positions, and a six-row view holds no row of more than 31.
 constexpr int kLS4 = 1664;
+// The level of a row depends on n >> 2 alone (0: singles; 1, 2: blocks of 4; 3 .. 7: blocks of 12), so two nibble tables indexed by
+// n & 28 give it in one v_bfe_u32 each: kR4TabE, E = 2 * (2 - level) = 0 / 2 / 4 (the level's cell = BIAS + E * (-2 kLS4) + 4 start),
+// and kR4TabS, the block's cells 1 / 4 / 12.
+constexpr uint32_t kR4TabE = 0x44444220u, kR4TabS = 0xCCCCC441u;
 // operands: %0-%3 temporaries; %4-%9 LO of rows 0 .. 5; %10-%15 their D; %16 BIAS (the bias of the arrays + 4 * the cell of the group's
-// bucket); %17 km1 (SGPR), %18 -2 * kLS4 (SGPR); masked form: %19 the lane's group number, %20 groups left (SGPR).
-// E = 2 * (2 - level) = (~ffbh(n)) & 30 (v_bfi_b32): 4, 2, 0 for blocks of 16, 4, 1; the level's cell = BIAS + E * (-2 kLS4) + 4 start,
-// the block's bytes 4 << E.  EXEC is all ones again after every row (the mask by group number comes again in front of each).
+// bucket); %17 km1 (SGPR), %18 -2 * kLS4 (SGPR), %19 kR4TabE (SGPR), %20 kR4TabS (SGPR); masked form: %21 the lane's group number,
+// %22 groups left (SGPR).  %2: the row's end in its level's array, then end - S; %3: its first cell, then first + S.
+// EXEC is all ones again after every row (the mask by group number comes again in front of each).
 #define MEMO_ROW4_AT_(LO, D, TEST)                       \
     "v_bfe_u32 %0, " LO ", 5, 5\n\t"                     \
     "v_sub_u32 %0, %17, %0\n\t"                          \
     TEST                                                 \
-    "v_ffbh_u32 %1, %0\n\t"                              \
+    "v_and_b32 %1, 28, %0\n\t"                           \
     "v_and_b32 %3, 31, " LO "\n\t"                       \
-    "v_bfi_b32 %1, %1, 0, 30\n\t"                        \
-    "v_mad_i32_i24 %2, %1, %18, %16\n\t"                 \
+    "v_bfe_u32 %2, %19, %1, 4\n\t"                       \
+    "v_bfe_u32 %1, %20, %1, 4\n\t"                       \
+    "v_mad_i32_i24 %2, %2, %18, %16\n\t"                 \
     "v_lshl_add_u32 %2, %3, 2, %2\n\t"                   \
-    "v_lshlrev_b32_e64 %1, %1, 4\n\t"                    \
     "v_mad_i32_i24 %3, %0, -4, %2\n\t"                   \
-    "v_sub_u32 %2, %2, %1\n\t"                           \
+    "v_mad_i32_i24 %2, %1, -4, %2\n\t"                   \
     "ds_min_u32 %3, " D "\n\t"                           \
     "ds_min_u32 %2, " D "\n\t"                           \
-    "v_add_u32 %3, %3, %1\n\t"                           \
-    "v_cmpx_lt_u32 vcc, %3, %2\n\t"                      \
-    "ds_min_u32 %3, " D "\n\t"                           \
-    "v_add_u32 %3, %3, %1\n\t"                           \
+    "v_lshl_add_u32 %3, %1, 2, %3\n\t"                   \
     "v_cmpx_lt_u32 vcc, %3, %2\n\t"                      \
     "ds_min_u32 %3, " D "\n\t"                           \
     MEMO_ROW3_DONE
-#define MEMO_ROW4_MASK "v_cmpx_gt_u32 vcc, %20, %19\n\t"
+#define MEMO_ROW4_MASK "v_cmpx_gt_u32 vcc, %22, %21\n\t"
 #define MEMO_SIX_ROWS4(PRE, TEST)                                                                                              \
     PRE MEMO_ROW4_AT_("%4", "%10", TEST) PRE MEMO_ROW4_AT_("%5", "%11", TEST) PRE MEMO_ROW4_AT_("%6", "%12", TEST)                \
     PRE MEMO_ROW4_AT_("%7", "%13", TEST) PRE MEMO_ROW4_AT_("%8", "%14", TEST) PRE MEMO_ROW4_AT_("%9", "%15", TEST)
@@ -360,7 +362,7 @@ __device__ __forceinline__ void group_rows4(const uint4 &V, const SixConst &C, u
     uint32_t r0, r1, r2, r3;
     MEMO_EXEC_ALL_ONES(C.status);
 #define MEMO_SIX4_IN "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w), "v"(lo4), "v"(lo5), "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w), "v"(d4), "v"(d5), \
-                     "v"(bias), "s"(C.km1), "s"(C.ls4)
+                     "v"(bias), "s"(C.km1), "s"(C.ls4), "s"(kR4TabE), "s"(kR4TabS)
     if constexpr (MASKED && AW) {
         asm volatile(MEMO_SIX_ROWS4(MEMO_ROW4_MASK, "") MEMO_G3_OUT : MEMO_SIX4_IN, "v"(lg), "s"(left) : "memory", "vcc");
     } else if constexpr (MASKED) {

@@ -37,19 +37,15 @@ __device__ __forceinline__ void fold_step_dpp(uint4 &M, uint4 L, int lane) {
 // The radix-4 fold on a lane's four cells, for the six-row views' radix-4 arrays (memo_sweep_cons3t.hip: R4): the last two steps of
 // r4_fold_store and of the mixed arrays' fold (memo_sweep_cons.hip, which keep them inline: moved here, their code came out scheduled
 // differently), operands from the lanes to the left through DPP, one in-place asm block per step.
-// Blocks of 16 -> blocks of 4: cells x - 4, x - 8, x - 12 are the same component 1, 2, 3 lanes left.  B = min over two lanes in
-// place, P = B one lane left; M = min(M, B, P one more lane left).  (P of lane 0: whatever was there; a context lane.)
-#define MEMO_DPP_MOV(dst, src) "v_mov_b32_dpp " dst ", " src " wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-__device__ __forceinline__ void r4_fold16(uint4 &M, uint4 B) {
-    uint4 P;
+// Blocks of 12 -> blocks of 4: a block of 12 is three blocks of 4, at cells x, x - 4 and x - 8 -- the same component of this lane and
+// of the two to its left.  B = min over this lane and the one to the left, in place; M = min(M, B, B one lane left).  (Lane 0 keeps
+// what it had, lane 1 lacks its second neighbour: context lanes.)
+__device__ __forceinline__ void r4_fold12(uint4 &M, uint4 B) {
     asm("s_nop 1\n\t" MEMO_DPP_MIN("%4", "%4") MEMO_DPP_MIN("%5", "%5") MEMO_DPP_MIN("%6", "%6") MEMO_DPP_MIN("%7", "%7")
-        MEMO_DPP_MOV("%8", "%4") MEMO_DPP_MOV("%9", "%5") MEMO_DPP_MOV("%10", "%6") MEMO_DPP_MOV("%11", "%7")
         "v_min_u32 %0, %4, %0\n\tv_min_u32 %1, %5, %1\n\tv_min_u32 %2, %6, %2\n\tv_min_u32 %3, %7, %3\n\t"
-        MEMO_DPP_MIN("%0", "%8") MEMO_DPP_MIN("%1", "%9") MEMO_DPP_MIN("%2", "%10") MEMO_DPP_MIN("%3", "%11")
-        : "+v"(M.x), "+v"(M.y), "+v"(M.z), "+v"(M.w), "+v"(B.x), "+v"(B.y), "+v"(B.z), "+v"(B.w),
-          "=&v"(P.x), "=&v"(P.y), "=&v"(P.z), "=&v"(P.w));
+        MEMO_DPP_MIN("%0", "%4") MEMO_DPP_MIN("%1", "%5") MEMO_DPP_MIN("%2", "%6") MEMO_DPP_MIN("%3", "%7")
+        : "+v"(M.x), "+v"(M.y), "+v"(M.z), "+v"(M.w), "+v"(B.x), "+v"(B.y), "+v"(B.z), "+v"(B.w));
 }
-#undef MEMO_DPP_MOV
 
 // blocks of 4 -> positions: cell x takes the blocks at x, x - 1, x - 2, x - 3 (the last ones of the lane to the left)
 __device__ __forceinline__ void r4_fold4(uint4 &R, uint4 M) {

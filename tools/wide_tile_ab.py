@@ -3,8 +3,10 @@
 R4) against the doubling arrays (MEMO_OPT_WIDE_TILES 0).  Per k the class's view and its copy without dead groups are built first
 (MEMO_OPT_BUILD_COST_PCT 0); `--plain` sweeps the view without places instead (MEMO_OPT_VIEW_PLACES 0: no flags, no copy, 4x the
 rows per tile).  Then, per round and variant, `--launches` whole-window uint8 launches back to back, each between a HIP event pair;
-the median of the last `--keep`.  Variants alternate `--reps` times on the same index.  GPU box."""
+the median of the last `--keep`.  Variants alternate `--reps` times on the same index.  `--density` (rows per genome-position, a
+fraction; config 3 has 5/100) makes the rows per tile denser or sparser: the points the launcher's kR4MaxGroups stands between.  GPU box."""
 import argparse
+from fractions import Fraction
 import json
 import os
 import sys
@@ -20,6 +22,7 @@ def main():
     ap.add_argument("--launches", type=int, default=600)
     ap.add_argument("--keep", type=int, default=400)
     ap.add_argument("--plain", action="store_true")
+    ap.add_argument("--density", type=Fraction, default=Fraction(5, 100))
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -27,7 +30,7 @@ def main():
     num_docs, L = 100, 100_000_000
     out = torch.empty(L, dtype=torch.uint8, device="cuda:0")
     stream = torch.cuda.current_stream()
-    ix, _ = synth.device_index(0, L, 31, num_docs, L, pack="dense")
+    ix, _ = synth.device_index(0, L, 31, num_docs, L, density=a.density, pack="dense")
 
     def one(k):
         ix.conservation_u8_dev(0, L, k, num_docs, out, stream.cuda_stream)
@@ -56,7 +59,9 @@ def main():
                     ms = [e0.elapsed_time(e1) for e0, e1 in ev][-a.keep:]
                     print(json.dumps({"k": k, "rep": rep, "wide_tiles": wide, "ms": round(float(np.median(ms)), 5),
                                       "tile_width": inf["last_tile_width"], "variant": inf["last_variant"],
-                                      "rows_read": inf["last_rows_read"], "plain": a.plain}), flush=True)
+                                      "rows_read": inf["last_rows_read"], "plain": a.plain, "density": str(a.density),
+                                      "groups_per_tile": round(inf["last_rows_read"] / 6 * inf["last_tile_width"] / L, 1)}),
+                          flush=True)
             ix.set_option(7, 1)
 
 
