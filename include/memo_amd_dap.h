@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) and the reader of `memo view`: off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view` and the runs of `memo regions`: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -160,6 +160,39 @@ int memo_parse_conservation_text_dev(const char *d_text, int64_t nbytes, uint16_
 /* memo_dev_upload for LARGE pageable host memory (a memory-mapped file): in pieces through the library's pinned ring, the
  * worker threads filling the next piece while one crosses PCIe.  Blocking. */
 int memo_dev_upload_pipelined(int32_t device, void *dev, const void *host, size_t bytes);
+
+/* ---- `memo regions`: a result as intervals (no counterpart in the reference) ---------------------
+ * (Declared here, beside the `memo view` reader, with the other entry points that are not the query seam of memo_amd.h.)
+ * The maximal runs of positions with equal key of a result that is still on `device`, compacted there (count per tile,
+ * scan, scatter: memo_amd/csrc/memo_runs.hip), so that intervals instead of one line per position leave the device.
+ * starts[] are int64 offsets from the window start, ascending.  d_vec / d_bits must be 16-byte aligned (MEMO_EINVAL
+ * otherwise, before anything is launched) and is read from [0] to [L) ([L * W)) and nowhere else; L == 0 launches nothing.
+ *
+ * maximal runs of a conservation result that is on `device`.  mode 0 (value): starts[r], values[r];
+ * mode 1 (band, lo <= v <= hi): starts[] holds the boundaries, values is NULL.  *d_starts / *d_values are
+ * device buffers the call allocates (NULL when *runs == 0); free with memo_dev_free.  Blocking.
+ * Band boundaries: 2j opens an interval, 2j + 1 closes it; the position before the window counts as outside the
+ * band, and an odd *runs means that the last interval ends at L.  An allocation that fails returns MEMO_EHIP with the
+ * bytes asked for in memo_last_error and leaves nothing allocated. */
+int memo_runs_conservation_dev(const uint16_t *d_vec, int64_t L, int32_t mode, int32_t lo, int32_t hi,
+                               int64_t **d_starts, uint16_t **d_values, uint64_t *runs, int32_t device, void *stream);
+/* the same for a membership result (W = ceil(num_docs / 32) words per position; any W >= 1): a run is a stretch of equal
+ * rows, d_run_bits[r * W ...] its W words */
+int memo_runs_membership_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs,
+                             int64_t **d_starts, uint32_t **d_run_bits, uint64_t *runs, int32_t device, void *stream);
+/* positions per tile of the three passes, for tests that want lengths around it: words <= 0: a conservation result;
+ * else a membership result of that many words per position */
+int32_t memo_runs_tile(int32_t words);
+/* The text of the runs, HOST arrays in (what the two calls above returned, downloaded).  Coordinates are pivot positions
+ * qs + start, 0-based and half open; fields are tab-separated, lines end in '\n'; no runs: no bytes.
+ *   values != NULL   REC  start  end  value                                  (bedGraph)
+ *   values == NULL   REC  start  end     per band interval                   (BED3)
+ *   membership       REC  start  end  0110...   num_docs characters, genome 0 first
+ * Return the number of bytes the text needs; it is written only if it fits in cap. */
+size_t memo_emit_runs(const char *record, int64_t qs, int64_t L, const int64_t *starts, const uint16_t *values /* NULL: band */,
+                      uint64_t runs, char *buf, size_t cap);
+size_t memo_emit_membership_runs(const char *record, int64_t qs, int64_t L, const int64_t *starts, const uint32_t *run_bits,
+                                 uint64_t runs, int32_t num_docs, char *buf, size_t cap);
 
 #ifdef __cplusplus
 }

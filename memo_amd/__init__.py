@@ -14,6 +14,8 @@ Layout (only what the path needs):
   build_index.py   `memo index`: FASTA genomes -> matching statistics on the GPU -> Parquet index
   view.py          `memo view` preprocessing: result text parsed and binned on the GPU, or a window binned from an index
   view_cli.py      `memo view`: flags, usage, the table as TSV, the plot (matplotlib)
+  regions.py       `memo regions`: a result's runs of equal value compacted on the GPU, a window's runs from an index
+  regions_cli.py   `memo regions`: flags, usage, bedGraph / BED3 / BED + membership string
 
 Attributes are loaded on first use (PEP 562), so that `import memo_amd._fastquery` -- the CLI's cache-hit
 path -- does not pay for NumPy.
@@ -25,6 +27,7 @@ _LAZY = {
     "DeviceIndex": "index", "IndexBuilder": "index", "conservation": "index", "membership": "index",
     "conservation_rows": "index", "membership_rows": "index",
     "emit_conservation": "index", "emit_membership": "index",
+    "runs": "regions", "membership_runs": "regions", "region_runs": "regions",
 }
 
 
@@ -34,7 +37,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

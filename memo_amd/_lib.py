@@ -116,6 +116,11 @@ SYMBOLS = {
     "memo_emit_conservation": (_SZ, [_P, _I64, _P, _SZ]),
     "memo_emit_membership": (_SZ, [_P, _I64, _I32, _P, _SZ]),
     "memo_bin_conservation_dev": (C.c_int, [_P, _I64, _P, _I32, _I32, _P, _I32, _P]),
+    "memo_runs_conservation_dev": (C.c_int, [_P, _I64, _I32, _I32, _I32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_U64), _I32, _P]),
+    "memo_runs_membership_dev": (C.c_int, [_P, _I64, _I32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_U64), _I32, _P]),
+    "memo_runs_tile": (_I32, [_I32]),
+    "memo_emit_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _P, _SZ]),
+    "memo_emit_membership_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _I32, _P, _SZ]),
     "memo_parse_conservation_text_dev": (C.c_int, [_P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(_I64), _I32, _P]),
     "memo_dev_upload_pipelined": (C.c_int, [_I32, _P, _P, _SZ]),
     "memo_dap_create": (C.c_int, [_I32, _P, _I32, _I32, _I32, _I32, C.POINTER(_P)]),

@@ -35,6 +35,8 @@ int ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, in
 // memo_ms.hip: >= 0: the allocations of this thread's later coded columns see this many bytes of free device memory instead of the
 // device's (AB library, memo_debug_ms_free_bytes: the test of a column that does not fit)
 extern thread_local int64_t g_ms_free_bytes;
+// memo_text.hip: exclusive scan of ntiles uint32 tile counts into int64 bases, their sum into *d_total (one workgroup; queued on st)
+hipError_t scan_tile_counts(const uint32_t *d_counts, int64_t ntiles, int64_t *d_bases, int64_t *d_total, hipStream_t st);
 double pinned_alloc_ms_total();  // memo_hostcore.cpp: time this process has spent allocating pinned staging slots (MEMO_TIMING)
 
 struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the current device

@@ -47,6 +47,44 @@ void parallel_chunks(int64_t n, unsigned nt, F f) {  // f(chunk index, begin, en
 
 inline int dec_len(unsigned v) { return v < 10 ? 1 : v < 100 ? 2 : v < 1000 ? 3 : v < 10000 ? 4 : 5; }
 
+// str(v) of a Python int that fits 64 bits: its length, and its characters put at p (returns the end)
+inline size_t digits(long long v) {
+    size_t n = v < 0 ? 2 : 1;
+    for (unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v; u >= 10; u /= 10) ++n;
+    return n;
+}
+
+inline char *put(char *p, long long v) {
+    char tmp[24];
+    int n = 0;
+    unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+    do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
+    if (v < 0) *p++ = '-';
+    while (n) *p++ = tmp[--n];
+    return p;
+}
+
+// lines of different lengths: size(i) of every line summed per thread, then write(p, i) -> end from each thread's offset
+template <typename S, typename W>
+size_t emit_lines(int64_t lines, int64_t min_per_thread, char *buf, size_t cap, S size, W write) {
+    if (lines <= 0) return 0;
+    const unsigned nt = emit_threads(lines, min_per_thread);
+    std::vector<size_t> bytes(nt + 1, 0);
+    parallel_chunks(lines, nt, [&](unsigned t, int64_t b, int64_t e) {
+        size_t n = 0;
+        for (int64_t i = b; i < e; ++i) n += size(i);
+        bytes[t + 1] = n;
+    });
+    for (unsigned t = 0; t < nt; ++t) bytes[t + 1] += bytes[t];
+    const size_t need = bytes[nt];
+    if (need > cap || !buf) return need;
+    parallel_chunks(lines, nt, [&](unsigned t, int64_t b, int64_t e) {
+        char *p = buf + bytes[t];
+        for (int64_t i = b; i < e; ++i) p = write(p, i);
+    });
+    return need;
+}
+
 }  // namespace
 
 extern "C" {
@@ -159,20 +197,6 @@ size_t memo_emit_bed(const int32_t *rec, const int64_t *start, const int64_t *en
         nlen[r] = strlen(q);
         q += nlen[r] + 1;
     }
-    auto digits = [](long long v) {
-        size_t n = v < 0 ? 2 : 1;
-        for (unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v; u >= 10; u /= 10) ++n;
-        return n;
-    };
-    auto put = [](char *p, long long v) {
-        char tmp[24];
-        int n = 0;
-        unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
-        do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
-        if (v < 0) *p++ = '-';
-        while (n) *p++ = tmp[--n];
-        return p;
-    };
     const unsigned nt = emit_threads((int64_t)rows, 1 << 18);
     std::vector<size_t> bytes(nt + 1, 0);
     parallel_chunks((int64_t)rows, nt, [&](unsigned t, int64_t b, int64_t e) {
@@ -198,6 +222,54 @@ size_t memo_emit_bed(const int32_t *rec, const int64_t *start, const int64_t *en
         }
     });
     return need;
+}
+
+// ---- `memo regions`: the runs of memo_runs_*_dev as bedGraph / BED3 / BED + membership string (include/memo_amd_dap.h) ----
+size_t memo_emit_runs(const char *record, int64_t qs, int64_t L, const int64_t *starts, const uint16_t *values, uint64_t runs,
+                      char *buf, size_t cap) {
+    const size_t rlen = strlen(record);
+    const int64_t n = (int64_t)runs, step = values ? 1 : 2;  // a band's boundaries pair up: 2j opens, 2j + 1 closes
+    auto first = [&](int64_t i) { return qs + starts[i * step]; };
+    auto end = [&](int64_t i) { return qs + (i * step + 1 < n ? starts[i * step + 1] : L); };
+    return emit_lines((n + step - 1) / step, 1 << 17, buf, cap,
+                      [&](int64_t i) { return rlen + digits(first(i)) + digits(end(i)) + 3 + (values ? 1 + (size_t)dec_len(values[i]) : 0); },
+                      [&](char *p, int64_t i) {
+                          memcpy(p, record, rlen);
+                          p += rlen;
+                          *p++ = '\t';
+                          p = put(p, first(i));
+                          *p++ = '\t';
+                          p = put(p, end(i));
+                          if (values) {
+                              *p++ = '\t';
+                              p = put(p, values[i]);
+                          }
+                          *p++ = '\n';
+                          return p;
+                      });
+}
+
+size_t memo_emit_membership_runs(const char *record, int64_t qs, int64_t L, const int64_t *starts, const uint32_t *run_bits,
+                                 uint64_t runs, int32_t num_docs, char *buf, size_t cap) {
+    const size_t rlen = strlen(record), docs = num_docs > 0 ? (size_t)num_docs : 0;
+    const int64_t n = (int64_t)runs;
+    const int nw = (num_docs + 31) / 32;
+    auto end = [&](int64_t i) { return qs + (i + 1 < n ? starts[i + 1] : L); };
+    return emit_lines(n, ((int64_t)1 << 22) / (int64_t)(docs + 32) + 1, buf, cap,
+                      [&](int64_t i) { return rlen + digits(qs + starts[i]) + digits(end(i)) + docs + 4; },
+                      [&](char *p, int64_t i) {
+                          memcpy(p, record, rlen);
+                          p += rlen;
+                          *p++ = '\t';
+                          p = put(p, qs + starts[i]);
+                          *p++ = '\t';
+                          p = put(p, end(i));
+                          *p++ = '\t';
+                          const uint32_t *row = run_bits + i * nw;
+                          for (int g = 0; g < num_docs; ++g) *p++ = (char)('0' + ((row[g >> 5] >> (g & 31)) & 1u));
+                          *p++ = '\n';
+                          return p;
+                      });
 }
 
 }  // extern "C"

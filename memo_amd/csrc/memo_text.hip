@@ -181,6 +181,12 @@ __global__ __launch_bounds__(256) void text_parse_kernel(const char *__restrict_
 
 }  // namespace
 
+// the scan, for the other count / scan / scatter pass of the library (memo_runs.hip)
+hipError_t memo::scan_tile_counts(const uint32_t *d_counts, int64_t ntiles, int64_t *d_bases, int64_t *d_total, hipStream_t st) {
+    hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(1024), 0, st, d_counts, ntiles, d_bases, d_total);
+    return hipGetLastError();
+}
+
 extern "C" {
 
 int memo_parse_conservation_text_dev(const char *d_text, int64_t nbytes, uint16_t *d_vec, int64_t cap, int64_t *lines,
@@ -206,8 +212,7 @@ int memo_parse_conservation_text_dev(const char *d_text, int64_t nbytes, uint16_
     HIP_TRY(hipMemsetAsync(d_res, 0xFF, 16, st));
     hipLaunchKernelGGL(text_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, d_text, nbytes, d_counts, d_odd);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(1024), 0, st, d_counts, ntiles, d_bases, d_res);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(scan_tile_counts(d_counts, ntiles, d_bases, d_res, st));
     HIP_TRY(hipMemcpyAsync(lines, d_res, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (cap < *lines) return fail(MEMO_EINVAL, "the text has %lld lines: d_vec holds %lld", (long long)*lines, (long long)cap);

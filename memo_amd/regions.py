@@ -1,0 +1,186 @@
+"""`memo regions`: a query result as intervals, run-coded on the GPU.
+
+No counterpart in the reference: its users run-length the text of `memo query` (src/memo_query.py:65-71) on the host.  Here
+the sweep's result stays in HBM, memo_runs_*_dev (memo_amd/csrc/memo_runs.hip) compacts its maximal runs of equal key there,
+and only the runs are downloaded.  Three keys:
+
+  value   runs of equal conservation value       starts [R] int64, values [R] uint16          (lossless)
+  band    lo <= value <= hi                      boundaries [R] int64: 2j opens an interval, 2j + 1 closes it,
+                                                 an odd R leaves the last interval to end at L
+  bits    runs of equal membership rows          starts [R] int64, run_bits [R, W] uint32
+
+Starts are offsets from the window start.  The text forms (bedGraph, BED3, BED + one character per genome) are written by
+memo_emit_runs / memo_emit_membership_runs (memo_amd/csrc/memo_emit.cpp); the flags are memo_amd/regions_cli.py.
+"""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib
+from .index import words
+
+Runs = collections.namedtuple("Runs", "record qs L starts values run_bits num_docs")
+Runs.__doc__ = """region_runs' result: `starts` as runs() / membership_runs() return them; values is None for a band and for
+membership, run_bits is None for conservation"""
+
+
+def tile(words_per_position=0):
+    """positions per tile of the three passes (0: a conservation result): the lengths a test wants to straddle"""
+    return int(lib().memo_runs_tile(int(words_per_position)))
+
+
+def _on_device(host_or_pair, dtype, device):
+    """(device pointer, L, buffer to free or None) of a host array, or of a (device pointer, L) pair as it is"""
+    if isinstance(host_or_pair, tuple):
+        return C.c_void_p(int(host_or_pair[0])), int(host_or_pair[1]), None
+    host = np.ascontiguousarray(host_or_pair, dtype)
+    tmp = C.c_void_p()
+    check(lib().memo_dev_malloc(device, host.nbytes, C.byref(tmp)))
+    try:
+        check(lib().memo_dev_upload(device, tmp, host.ctypes.data, host.nbytes, None))
+    except BaseException:
+        lib().memo_dev_free(device, tmp)
+        raise
+    return tmp, len(host), tmp
+
+
+def _download(device, d_ptr, shape, dtype):
+    """a device buffer the runs calls allocated, as a host array; the buffer is freed"""
+    out = np.empty(shape, dtype)
+    try:
+        if d_ptr and out.nbytes:
+            check(lib().memo_dev_download(device, out.ctypes.data, d_ptr, out.nbytes, None))
+    finally:
+        if d_ptr:
+            lib().memo_dev_free(device, d_ptr)
+    return out
+
+
+def runs(vec, mode="value", lo=None, hi=None, device=0, stream=None):
+    """Runs of a conservation vector: a host uint16 array, or (device pointer, L).  mode "value": (starts, values); mode
+    "band": the boundaries of lo <= value <= hi (one int64 array)."""
+    if mode not in ("value", "band"):
+        raise ValueError("mode must be 'value' or 'band'")
+    band = mode == "band"
+    if band and (lo is None or hi is None):
+        raise ValueError("a band needs lo and hi")
+    d_vec, L, tmp = _on_device(vec, np.uint16, device)
+    d_starts, d_values, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+    try:
+        check(lib().memo_runs_conservation_dev(d_vec, L, 1 if band else 0, int(lo) if band else 0, int(hi) if band else 0,
+                                               C.byref(d_starts), None if band else C.byref(d_values), C.byref(n), device,
+                                               None if stream is None else C.c_void_p(int(stream))))
+    finally:
+        if tmp is not None:
+            lib().memo_dev_free(device, tmp)
+    try:
+        starts = _download(device, d_starts, n.value, np.int64)
+    except BaseException:
+        if d_values:
+            lib().memo_dev_free(device, d_values)
+        raise
+    return starts if band else (starts, _download(device, d_values, n.value, np.uint16))
+
+
+def membership_runs(bits, num_docs, device=0, stream=None):
+    """Runs of equal rows of a membership result: a host uint32 array [L, W], or (device pointer, L).  (starts, run_bits [R, W])."""
+    W = words(num_docs)
+    if not isinstance(bits, tuple):
+        bits = np.ascontiguousarray(bits, np.uint32).reshape(-1, W)
+    d_bits, L, tmp = _on_device(bits, np.uint32, device)
+    d_starts, d_rows, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+    try:
+        check(lib().memo_runs_membership_dev(d_bits, L, num_docs, C.byref(d_starts), C.byref(d_rows), C.byref(n), device,
+                                             None if stream is None else C.c_void_p(int(stream))))
+    finally:
+        if tmp is not None:
+            lib().memo_dev_free(device, tmp)
+    try:
+        starts = _download(device, d_starts, n.value, np.int64)
+    except BaseException:
+        if d_rows:
+            lib().memo_dev_free(device, d_rows)
+        raise
+    return starts, _download(device, d_rows, (n.value, W), np.uint32)
+
+
+def band_intervals(boundaries, L):
+    """(begin, end) offsets of a band's intervals from its boundaries"""
+    b = np.asarray(boundaries, np.int64)
+    if len(b) & 1:
+        b = np.append(b, np.int64(L))
+    return b[0::2], b[1::2]
+
+
+def expand(starts, values, L):
+    """the vector (or the rows) the runs came from"""
+    lengths = np.diff(np.append(np.asarray(starts, np.int64), np.int64(L)))
+    return np.repeat(values, lengths, axis=0)
+
+
+def region_runs(index_path, region, k, n_docs, membership=False, lo=None, hi=None, device=0):
+    """The runs of a window of a Parquet index, without the vector in between: the sweep's result stays in HBM and is
+    run-coded there; only the runs leave the device.  `region` is CHR:START-END as `memo query -r` takes it, and what is
+    wrong with it raises what memo_query.main raises.  lo and / or hi: the band lo <= value <= hi (lo defaults to 0, hi to
+    n_docs); membership: runs of equal rows.  One device.  Returns Runs."""
+    from . import memo_query
+    if membership and (lo is not None or hi is not None):
+        raise ValueError("a band is a question about conservation values, not about membership rows")
+    record, start_end = region.split(':')                  # exactly one ':' and one '-'
+    qs, qe = map(int, start_end.split('-'))
+    if qe < qs:
+        raise ValueError("negative dimensions are not allowed")          # np.zeros of memo_init, as `memo query` raises it
+    band = lo is not None or hi is not None
+    index = memo_query.region_index(index_path, record, qs, qe + k, device=device, k=k, num_docs=n_docs, membership=membership)
+    with index:
+        L = qe - qs
+        d_vec = C.c_void_p()
+        check(lib().memo_dev_malloc(device, L * (4 * words(n_docs) if membership else 2), C.byref(d_vec)))
+        try:
+            if membership:
+                index.membership_dev(qs, qe, k, n_docs, d_vec.value)
+                index.check()
+                starts, rows = membership_runs((d_vec.value, L), n_docs, device)
+                return Runs(record, qs, L, starts, None, rows, n_docs)
+            index.conservation_dev(qs, qe, k, n_docs, d_vec.value)
+            index.check()
+            if band:
+                starts = runs((d_vec.value, L), "band", 0 if lo is None else lo, n_docs if hi is None else hi, device)
+                return Runs(record, qs, L, starts, None, None, n_docs)
+            starts, values = runs((d_vec.value, L), "value", device=device)
+            return Runs(record, qs, L, starts, values, None, n_docs)
+        finally:
+            lib().memo_dev_free(device, d_vec)
+
+
+def _emit(call):
+    """the text as a writable byte buffer: sized by a first call, written by the second"""
+    need = call(None, 0)
+    buf = np.empty(need, np.uint8)
+    if need:
+        call(buf.ctypes.data, need)
+    return buf
+
+
+def emit_runs(record, qs, L, starts, values=None):
+    """bedGraph lines (values given) or BED3 lines of a band's intervals (values None), as a uint8 array"""
+    s = np.ascontiguousarray(starts, np.int64)
+    v = None if values is None else np.ascontiguousarray(values, np.uint16)
+    return _emit(lambda buf, cap: lib().memo_emit_runs(record.encode(), qs, L, s.ctypes.data, None if v is None else v.ctypes.data,
+                                                       len(s), buf, cap))
+
+
+def emit_membership_runs(record, qs, L, starts, run_bits, num_docs):
+    """REC start end 0110... lines (num_docs characters, genome 0 first), as a uint8 array"""
+    s = np.ascontiguousarray(starts, np.int64)
+    b = np.ascontiguousarray(run_bits, np.uint32)
+    return _emit(lambda buf, cap: lib().memo_emit_membership_runs(record.encode(), qs, L, s.ctypes.data, b.ctypes.data, len(s),
+                                                                  num_docs, buf, cap))
+
+
+def emit(result):
+    """the text of a region_runs result"""
+    if result.run_bits is not None:
+        return emit_membership_runs(result.record, result.qs, result.L, result.starts, result.run_bits, result.num_docs)
+    return emit_runs(result.record, result.qs, result.L, result.starts, result.values)
