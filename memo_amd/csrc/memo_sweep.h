@@ -55,8 +55,27 @@ struct SweepArgs {
 typedef uint32_t __attribute__((aligned(1))) u32_any;
 typedef uint64_t __attribute__((aligned(2))) u64_any;
 __device__ __forceinline__ void store_four(uint8_t *p, uint32_t v) { *reinterpret_cast<u32_any *>(p) = v; }
-__device__ __forceinline__ void store_four(uint16_t *p, uint32_t lo, uint32_t hi) {
-    *reinterpret_cast<u64_any *>(p) = (uint64_t)lo | ((uint64_t)hi << 32);
+__device__ __forceinline__ void store_four(uint16_t *p, uint2 v) {
+    *reinterpret_cast<u64_any *>(p) = (uint64_t)v.x | ((uint64_t)v.y << 32);
+}
+
+// Four level cells -> the 4 or 8 bytes of their results (what store_four takes).  TOP != 0: a cell holds its order from bit TOP up.
+// The one place that knows how cells become output bytes: an order in the top byte (TOP 24) comes out by v_perm_b32, one per two
+// cells; other fields by shifts.
+template <typename OutT, int TOP>
+__device__ __forceinline__ auto pack_cells4(uint4 R) {
+    if constexpr (TOP == 24 && sizeof(OutT) == 1) {
+        return __builtin_amdgcn_perm(R.y, R.x, 0x0c0c0703u) | __builtin_amdgcn_perm(R.w, R.z, 0x07030c0cu);  // [x3 y3 0 0] | [0 0 z3 w3]
+    } else if constexpr (TOP == 24) {
+        return make_uint2(__builtin_amdgcn_perm(R.y, R.x, 0x0c070c03u), __builtin_amdgcn_perm(R.w, R.z, 0x0c070c03u));
+    } else {
+        if constexpr (sizeof(OutT) == 1) {
+            if (TOP) R = make_uint4(R.x >> TOP, R.y >> TOP, R.z >> TOP, R.w >> TOP);
+            return R.x | (R.y << 8) | (R.z << 16) | (R.w << 24);
+        } else {  // (shifted pair by pair: the order the nine-bit table-driven kernels had)
+            return make_uint2((R.x >> TOP) | ((R.y >> TOP) << 16), (R.z >> TOP) | ((R.w >> TOP) << 16));
+        }
+    }
 }
 
 // Diagnostic builds only (never in the product library): wave 0 of every workgroup stores the
@@ -357,6 +376,13 @@ struct PackedRows {
     }
 };
 
+// The two pieces of a scatter block (memo_sweep_cons.hip) that depend on the row format, as asm text on the block's named operands:
+// the SDWA selector of the length byte in `v_sub_u32_sdwa n, km1, w`, and start - a -- [rel] = rel_start([w], [key]).
+#define MEMO_ROW8_LEN_SEL "src1_sel:BYTE_2"
+#define MEMO_ROW8_REL_START "v_sub_u16 %[rel], %[w], %[key]\n\t"
+#define MEMO_ROW12_LEN_SEL "src1_sel:BYTE_0"
+#define MEMO_ROW12_REL_START "v_sub_u32 %[rel], %[w], %[key]\n\tv_bfe_u32 %[rel], %[rel], 8, 12\n\t"
+
 // Dense rows (memo_index_pack_dense): start mod 2^10, min(end - start, 63), annot (8 bits) -- 24 bits per
 // row, FIVE rows per 16-byte group (3.2 B per row), one aligned global_load_dwordx4 per lane and group:
 //     dword j = B_j | X_j << 16 | A_j << 24   (j = 0 .. 3)      B = (start & 1023) << 6 | min(end - start, 63)
@@ -504,25 +530,21 @@ __device__ __forceinline__ void store_conservation(const SweepArgs &A, const Til
                     v.z = min(v.z, min(u.z, u.y));
                     v.w = min(v.w, min(u.w, u.z));
                 }
-                if (TOP && TOP != 24) v = make_uint4(v.x >> TOP, v.y >> TOP, v.z >> TOP, v.w >> TOP);
-                if (TOP == 24) {  // byte 3 of each word -> the packed result, one v_perm_b32 per two words
-                    if (sizeof(OutT) == 1) {
-                        const uint32_t lo = __builtin_amdgcn_perm(v.y, v.x, 0x0C0C0703u);  // [x3, y3, 0, 0]
-                        const uint32_t hi = __builtin_amdgcn_perm(v.w, v.z, 0x07030C0Cu);  // [0, 0, z3, w3]
-                        *reinterpret_cast<uint32_t *>(out + g) = lo | hi;
-                    } else {
-                        *reinterpret_cast<uint2 *>(out + g) = make_uint2(__builtin_amdgcn_perm(v.y, v.x, 0x0C070C03u),
-                                                                         __builtin_amdgcn_perm(v.w, v.z, 0x0C070C03u));
-                    }
+                // The cells read one by one below come out of one() with the order already taken out of them, so both branches meet
+                // in one pack of plain orders (pack_cells4<OutT, 0>) and the shift by TOP happens here -- except TOP 24, whose pack
+                // is the v_perm_b32 pair on the cells as they are.  (One pack per branch instead: every kernel that stores through
+                // here compiles to other code, the clipped ones included; this shape leaves them as they were.)
+                if (TOP == 24) {
+                    const auto bytes = pack_cells4<OutT, TOP>(v);
+                    *reinterpret_cast<std::remove_const_t<decltype(bytes)> *>(out + g) = bytes;  // (g is a multiple of four: an aligned store)
                     continue;
                 }
+                if (TOP) v = make_uint4(v.x >> TOP, v.y >> TOP, v.z >> TOP, v.w >> TOP);
             } else {
                 v = make_uint4(one(x), one(x + 1), one(x + 2), one(x + 3));
             }
-            if (sizeof(OutT) == 1)
-                *reinterpret_cast<uint32_t *>(out + g) = v.x | (v.y << 8) | (v.z << 16) | (v.w << 24);
-            else
-                *reinterpret_cast<uint2 *>(out + g) = make_uint2(v.x | (v.y << 16), v.z | (v.w << 16));
+            const auto bytes = pack_cells4<OutT, 0>(v);  // (the orders themselves by now)
+            *reinterpret_cast<std::remove_const_t<decltype(bytes)> *>(out + g) = bytes;  // (g is a multiple of four: an aligned store)
         } else {
             for (int i = 0; i < 4; ++i)
                 if (g + i >= o_lo && g + i < o_hi) out[g + i] = (OutT)one(x + i);

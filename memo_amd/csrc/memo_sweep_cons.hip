@@ -150,33 +150,28 @@ __device__ __forceinline__ void halo_fold_store(const SweepArgs &A, const Tile &
 // the cascade  M_top = L_top,  M_(j-1)[x] = min(L_(j-1)[x], M_j[x], M_j[x - 2^(j-1)])  runs on a lane's four cells
 // with the shifted operand taken from the lanes to its left: through the DPP operand of v_min_u32 itself for one
 // lane, through ds_bpermute (the LDS crossbar, no bank access) for more; the result goes straight to the output.
-// No intermediate level is written back and no barrier separates the steps.  A wave covers 256 cells of which the
-// leftmost 2^(nlev-3) lanes only supply context (their own results would need cells of the previous wave), so
-// consecutive waves overlap by that much; wave 0's context lanes hold the first cells of the left halo, whose own
-// results nobody stores and left of which no block can start -- every lane reads real cells, no ds_read is
-// conditional.  Needs the tile grid aligned with the output (t.a - qs a multiple of 4: the lanes' cells are aligned
-// in the level arrays); the caller falls back to halo_fold_store otherwise.
+// No intermediate level is written back and no barrier separates the steps.  The leftmost 2^(nlev-3) lanes of a chunk
+// of 64 only supply context; the walk over the arrays in chunks that overlap by that much, the drop of those lanes
+// and the store of the rest (any window: store_four takes the address as it comes) are fold_store_chunks, which the
+// radix-4, the mixed and the table-driven sweeps share (memo_sweep_fold.h) -- every lane reads real cells, no ds_read
+// is conditional.
 // History (profiles/r02_fold_in_registers.txt): the compiler's rendering of this fold (lane_shr1() + min3: a copy,
 // a v_mov_dpp and a share of a min3 per shifted operand, all-ones stand-ins for lanes left of the array) took
 // ~100 VALU instructions per wave at k = 31 -- 30 % of a sweep whose VALU is 70 % busy -- and lost to the LDS
 // passes from six levels up; written as below it takes ~40, is 2-5 % of the whole sweep faster at k = 21 / 31,
 // and wins up to seven levels (k = 64: 0.53 -> 0.48 ms; k = 101 / 128 on doubling arrays: -2 / -3 %).
 // (fold_step_dpp<J>: memo_sweep_fold.h)
-
 template <typename OutT, int T, int TOP>
 __device__ __forceinline__ void halo_fold_store_dpp(const SweepArgs &A, const Tile &t, const uint32_t *lds) {
     const int LS = A.ls, HL = A.hl, W = A.w, nlev = A.nlev;
     const int cells = HL + W;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int NW = T / 64;
-    const int ctx = nlev <= 1 ? 0 : (nlev <= 3 ? 1 : 1 << (nlev - 3));  // context lanes at the left of a wave
-    const int valid = 64 - ctx;
+    const int ctx = nlev <= 1 ? 0 : (nlev <= 3 ? 1 : 1 << (nlev - 3));  // context lanes at the left of a chunk
     OutT *out = static_cast<OutT *>(A.out);
     const int64_t ob = t.a - A.qs - HL;  // output index of cell 0
     const int64_t o_lo = t.a - A.qs + t.x_lo, o_hi = t.a - A.qs + t.x_hi;
-    for (int base = wave * 4 * valid; base + 4 * ctx < cells; base += NW * 4 * valid) {
-        const int x0 = base + 4 * lane;             // this lane's cells x0 .. x0 + 3
-        const uint32_t *p = lds + min(x0, LS - 4);  // (past the array: lanes whose results are dropped below)
+    fold_store_chunks<OutT, T, TOP>(out, ob, o_lo, o_hi, cells, LS, lane, wave, ctx, [&](int xr) {
+        const uint32_t *p = lds + xr;
         uint4 M = *reinterpret_cast<const uint4 *>(p);
         // blocks of 2^J fold in when that level exists (wave-uniform branches around straight-line steps)
         if (nlev >= 7) fold_step_dpp<5>(M, *reinterpret_cast<const uint4 *>(p + (nlev - 6) * LS), lane);
@@ -185,24 +180,8 @@ __device__ __forceinline__ void halo_fold_store_dpp(const SweepArgs &A, const Ti
         if (nlev >= 4) fold_step_dpp<2>(M, *reinterpret_cast<const uint4 *>(p + (nlev - 3) * LS), lane);
         if (nlev >= 3) fold_step_dpp<1>(M, *reinterpret_cast<const uint4 *>(p + (nlev - 2) * LS), lane);
         if (nlev >= 2) fold_step_dpp<0>(M, *reinterpret_cast<const uint4 *>(p + (nlev - 1) * LS), lane);
-        if (lane < ctx || x0 >= cells) continue;
-        const int64_t g = ob + x0;
-        if (g >= o_lo && g + 4 <= o_hi) {
-            if constexpr (sizeof(OutT) == 1 && TOP == 24) {  // the four top bytes, two v_perm_b32 and an or
-                store_four(out + g, __builtin_amdgcn_perm(M.y, M.x, 0x0c0c0703u) | __builtin_amdgcn_perm(M.w, M.z, 0x07030c0cu));
-            } else {
-                if (TOP) M = make_uint4(M.x >> TOP, M.y >> TOP, M.z >> TOP, M.w >> TOP);
-                if constexpr (sizeof(OutT) == 1)
-                    store_four(out + g, M.x | (M.y << 8) | (M.z << 16) | (M.w << 24));
-                else
-                    store_four(out + g, M.x | (M.y << 16), M.z | (M.w << 16));
-            }
-        } else {
-            const uint32_t v[4] = {M.x >> TOP, M.y >> TOP, M.z >> TOP, M.w >> TOP};
-            for (int i = 0; i < 4; ++i)
-                if (g + i >= o_lo && g + i < o_hi) out[g + i] = (OutT)v[i];
-        }
-    }
+        return M;
+    });
 }
 
 template <typename OutT, int T, int TOP>
@@ -242,8 +221,7 @@ void sweep_conservation_halo_kernel(const SweepArgs A) {
     uint4 V[U];
     uint2 N[U];
     Rows::template issue<T, U>(A, t, 0, V, N);
-    const uint32_t sent = (uint32_t)(A.ncols - 1);
-    halo_clear<T>(A, lds, TOP ? (sent << TOP) | ((1u << TOP) - 1u) : sent);
+    halo_clear<T>(A, lds, cell_sentinel<TOP>(A));
     MEMO_STAMP(1);  // issue of the loads + LDS clear + barrier
 
     const int km1 = A.km1;
@@ -256,42 +234,32 @@ void sweep_conservation_halo_kernel(const SweepArgs A) {
     auto scatter = [&](uint32_t w, uint32_t col) {  // n, the test, start - a, the two cells, both ds_min: one block
         uint32_t r0, r1, r2, nn;
         MEMO_EXEC_ALL_ONES(A.status);
+#define MEMO_HALO_BLOCK(LEN_SEL, REL_START)                                                                           \
+        asm volatile(                                                                                                \
+            "v_sub_u32_sdwa %[n], %[km1], %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD " LEN_SEL "\n\t"    \
+            "v_cmpx_lt_i32 vcc, 0, %[n]\n\t"                                                                         \
+            REL_START                                                                                                \
+            "v_ffbh_u32 %[f], %[n]\n\t"                                                                              \
+            "v_mad_u32_u24 %[a2], %[f], %[ls4], %[bias4]\n\t"                                                        \
+            "v_lshl_add_u32 %[a2], %[rel], 2, %[a2]\n\t"                                                             \
+            "v_mad_i32_i24 %[rel], %[n], -4, %[a2]\n\t"                                                              \
+            "v_ashrrev_i32 %[f], %[f], %[top_bit]\n\t"                                                               \
+            "v_lshl_add_u32 %[a2], %[f], 2, %[a2]\n\t"                                                               \
+            "ds_min_u32 %[rel], %[data]\n\t"                                                                         \
+            "ds_min_u32 %[a2], %[data]\n\t"                                                                          \
+            "s_mov_b64 exec, -1"                                                                                     \
+            : [f] "=&v"(r0), [rel] "=&v"(r1), [a2] "=&v"(r2), [n] "=&v"(nn)                                          \
+            : [w] "v"(w), [km1] "s"(km1), [key] "v"(key), [ls4] "s"(ls4), [bias4] "v"(bias4), [top_bit] "v"(top_bit), \
+              [data] "v"(TOP ? w : col)                                                                              \
+            : "memory", "vcc")
         if constexpr (!Rows::kW12)
-            asm volatile(
-                "v_sub_u32_sdwa %3, %5, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                "v_sub_u16 %1, %4, %6\n\t"
-                "v_ffbh_u32 %0, %3\n\t"
-                "v_mad_u32_u24 %2, %0, %7, %8\n\t"
-                "v_lshl_add_u32 %2, %1, 2, %2\n\t"
-                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                "v_ashrrev_i32 %0, %0, %9\n\t"
-                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                "ds_min_u32 %1, %10\n\t"
-                "ds_min_u32 %2, %10\n\t"
-                "s_mov_b64 exec, -1"
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(nn)
-                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                : "memory", "vcc");
+            MEMO_HALO_BLOCK(MEMO_ROW8_LEN_SEL, MEMO_ROW8_REL_START);
         else
-            asm volatile(
-                "v_sub_u32_sdwa %3, %5, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                "v_sub_u32 %1, %4, %6\n\t"
-                "v_bfe_u32 %1, %1, 8, 12\n\t"
-                "v_ffbh_u32 %0, %3\n\t"
-                "v_mad_u32_u24 %2, %0, %7, %8\n\t"
-                "v_lshl_add_u32 %2, %1, 2, %2\n\t"
-                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                "v_ashrrev_i32 %0, %0, %9\n\t"
-                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                "ds_min_u32 %1, %10\n\t"
-                "ds_min_u32 %2, %10\n\t"
-                "s_mov_b64 exec, -1"
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(nn)
-                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                : "memory", "vcc");
+            MEMO_HALO_BLOCK(MEMO_ROW12_LEN_SEL, MEMO_ROW12_REL_START);
+#undef MEMO_HALO_BLOCK
     };
+    // (batch 0, then the rest: written out in each of the four kernels.  Behind one shared helper the doubling kernels came out
+    // waiting for all of a tile's rows -- s_waitcnt vmcnt(0) -- before the clear of the level arrays: profiles/fold_tail_device_code.txt)
     Rows::template consume<T, U>(A, t, 0, V, N, scatter);
     for (uint32_t b = 1, nb = Rows::template batches<T, U>(t); b < nb; ++b) {  // a dense tile: the rest
         Rows::template issue<T, U>(A, t, b, V, N);
@@ -329,7 +297,7 @@ void sweep_conservation_halo3_kernel(const SweepArgs A) {
     if (!locate_tile_w(A, t, W)) return;
     uint4 V[U];
     Rows::template issue<T, U>(A, t, 0, V);
-    halo_clear<T>(A, lds, ((uint32_t)(A.ncols - 1) << TOP) | ((1u << TOP) - 1u));
+    halo_clear<T>(A, lds, cell_sentinel<TOP>(A));
 
     const int km1 = A.km1;
     const uint32_t ls4 = 4u * (uint32_t)LS;
@@ -387,8 +355,8 @@ void sweep_conservation_halo3_kernel(const SweepArgs A) {
 // ------------------------------------------------------------------------------------------
 template <typename OutT, int T, int TOP>
 __device__ __forceinline__ void r4_fold_store(const SweepArgs &A, const Tile &t, uint32_t *lds) {
-    const int LS = A.ls, HL = A.hl, W = A.w, m = A.nlev;
-    const int cells = HL + W;
+    const int LS = A.ls, HL = A.hl, m = A.nlev;
+    const int cells = HL + A.w;
     // levels above 16 fold down through LDS (shifts of 16 cells and more are not a DPP's reach).  (The mixed arrays have a fold of
     // their own since round 4: plan_fold_store.)
     // Radix-4 levels: slot s holds blocks of 4^(m-1-s); after this loop slot m-3 (blocks of 16) has everything
@@ -413,65 +381,22 @@ __device__ __forceinline__ void r4_fold_store(const SweepArgs &A, const Tile &t,
         }
         lds_barrier();
     }
-    // 16 -> 4 and 4 -> 1 in registers, as in halo_fold_store_dpp: four cells per lane, lane 0 of a wave on cell
-    // `base` (wave 0's context lanes hold the first cells of the left halo), operands from the lanes to the left
-    // through DPP, one in-place asm block per step (s_nop 1: the two wait states a DPP source written by the
-    // instruction before needs).
+    // 16 -> 4 and 4 -> 1 in registers (memo_sweep_fold.h)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int NW = T / 64;
     const int ctx = m >= 3 ? 4 : (m == 2 ? 1 : 0);  // context lanes: 15 / 3 / 0 cells to the left
-    const int valid = 64 - ctx;
     OutT *out = static_cast<OutT *>(A.out);
     const int64_t ob = t.a - A.qs - HL;  // output index of cell 0
     const int64_t o_lo = t.a - A.qs + t.x_lo, o_hi = t.a - A.qs + t.x_hi;
-#define MEMO_DPP_MIN(dst, src) "v_min_u32_dpp " dst ", " src ", " dst " wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-#define MEMO_DPP_MOV(dst, src) "v_mov_b32_dpp " dst ", " src " wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-    for (int base = wave * 4 * valid; base + 4 * ctx < cells; base += NW * 4 * valid) {
-        const int x0 = base + 4 * lane;             // this lane's cells x0 .. x0 + 3
-        const uint32_t *p = lds + min(x0, LS - 4);  // (past the array: lanes whose results are dropped below)
+    fold_store_chunks<OutT, T, TOP>(out, ob, o_lo, o_hi, cells, LS, lane, wave, ctx, [&](int xr) {
+        const uint32_t *p = lds + xr;
         uint4 R = *reinterpret_cast<const uint4 *>(p + (m - 1) * LS);  // blocks of 1
         if (m >= 2) {
             uint4 M = *reinterpret_cast<const uint4 *>(p + (m - 2) * LS);  // blocks of 4
-            if (m >= 3) {
-                // blocks of 16 -> blocks of 4: cells x - 4, x - 8, x - 12 are the same component 1, 2, 3 lanes left.
-                // B = min over two lanes in place, P = B one lane left; M = min(M, B, P one more lane left)
-                uint4 B = *reinterpret_cast<const uint4 *>(p + (m - 3) * LS), P;
-                asm("s_nop 1\n\t" MEMO_DPP_MIN("%4", "%4") MEMO_DPP_MIN("%5", "%5") MEMO_DPP_MIN("%6", "%6") MEMO_DPP_MIN("%7", "%7")
-                    MEMO_DPP_MOV("%8", "%4") MEMO_DPP_MOV("%9", "%5") MEMO_DPP_MOV("%10", "%6") MEMO_DPP_MOV("%11", "%7")
-                    "v_min_u32 %0, %4, %0\n\tv_min_u32 %1, %5, %1\n\tv_min_u32 %2, %6, %2\n\tv_min_u32 %3, %7, %3\n\t"
-                    MEMO_DPP_MIN("%0", "%8") MEMO_DPP_MIN("%1", "%9") MEMO_DPP_MIN("%2", "%10") MEMO_DPP_MIN("%3", "%11")
-                    : "+v"(M.x), "+v"(M.y), "+v"(M.z), "+v"(M.w), "+v"(B.x), "+v"(B.y), "+v"(B.z), "+v"(B.w),
-                      "=&v"(P.x), "=&v"(P.y), "=&v"(P.z), "=&v"(P.w));  // (P of lane 0: whatever was there; a context lane)
-            }
-            // blocks of 4 -> positions: cell x takes the blocks at x, x - 1, x - 2, x - 3 (the last ones of the lane to the left)
-            asm("s_nop 1\n\t"
-                "v_min3_u32 %3, %3, %7, %6\n\tv_min3_u32 %3, %3, %5, %4\n\t"
-                "v_min3_u32 %2, %2, %6, %5\n\tv_min_u32 %2, %2, %4\n\t"
-                "v_min3_u32 %1, %1, %5, %4\n\tv_min_u32 %0, %0, %4\n\t"
-                MEMO_DPP_MIN("%2", "%7") MEMO_DPP_MIN("%1", "%7") MEMO_DPP_MIN("%0", "%7")
-                MEMO_DPP_MIN("%1", "%6") MEMO_DPP_MIN("%0", "%6") MEMO_DPP_MIN("%0", "%5")
-                : "+v"(R.x), "+v"(R.y), "+v"(R.z), "+v"(R.w) : "v"(M.x), "v"(M.y), "v"(M.z), "v"(M.w));
+            if (m >= 3) r4_fold16(M, *reinterpret_cast<const uint4 *>(p + (m - 3) * LS));
+            r4_fold4(R, M);
         }
-        if (lane < ctx || x0 >= cells) continue;
-        const int64_t g = ob + x0;
-        if (g >= o_lo && g + 4 <= o_hi) {
-            if constexpr (sizeof(OutT) == 1 && TOP == 24) {  // the four top bytes, two v_perm_b32 and an or
-                store_four(out + g, __builtin_amdgcn_perm(R.y, R.x, 0x0c0c0703u) | __builtin_amdgcn_perm(R.w, R.z, 0x07030c0cu));
-            } else {
-                if (TOP) R = make_uint4(R.x >> TOP, R.y >> TOP, R.z >> TOP, R.w >> TOP);
-                if constexpr (sizeof(OutT) == 1)
-                    store_four(out + g, R.x | (R.y << 8) | (R.z << 16) | (R.w << 24));
-                else
-                    store_four(out + g, R.x | (R.y << 16), R.z | (R.w << 16));
-            }
-        } else {  // window edges
-            const uint32_t v[4] = {R.x >> TOP, R.y >> TOP, R.z >> TOP, R.w >> TOP};
-            for (int i = 0; i < 4; ++i)
-                if (g + i >= o_lo && g + i < o_hi) out[g + i] = (OutT)v[i];
-        }
-    }
-#undef MEMO_DPP_MIN
-#undef MEMO_DPP_MOV
+        return R;
+    });
 }
 
 template <typename Rows, int U, int T, typename OutT, int TOP>
@@ -485,8 +410,7 @@ void sweep_conservation_r4_kernel(const SweepArgs A) {
     uint4 V[U];
     uint2 N[U];
     Rows::template issue<T, U>(A, t, 0, V, N);
-    const uint32_t sent = (uint32_t)(A.ncols - 1);
-    halo_clear<T>(A, lds, TOP ? (sent << TOP) | ((1u << TOP) - 1u) : sent);
+    halo_clear<T>(A, lds, cell_sentinel<TOP>(A));
 
     const int km1 = A.km1;
     // LDS byte address of tile slot x on level i (blocks of 4^i):  level0 - i * 4 LS + 4 x
@@ -506,30 +430,31 @@ void sweep_conservation_r4_kernel(const SweepArgs A) {
         MEMO_EXEC_ALL_ONES(A.status);
 #define MEMO_R4_BLOCK(LEN_SEL, REL_START)                                                                           \
         asm volatile(                                                                                               \
-            "v_mov_b32 %4, 0\n\t"                 /* q = 0 where the row does not write */                          \
-            "v_sub_u32_sdwa %0, %7, %6 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" LEN_SEL "\n\t" \
-            "v_cmpx_lt_i32 vcc, 0, %0\n\t"                                                                          \
+            "v_mov_b32 %[q], 0\n\t"                      /* q = 0 where the row does not write */                   \
+            "v_sub_u32_sdwa %[n], %[km1], %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD " LEN_SEL "\n\t"   \
+            "v_cmpx_lt_i32 vcc, 0, %[n]\n\t"                                                                        \
             REL_START                                                                                               \
-            "v_ffbh_u32 %4, %0\n\t"                                                                                 \
-            "v_lshrrev_b32 %4, 1, %4\n\t"        /* i' = 15 - i */                                                  \
-            "v_mad_u32_u24 %1, %4, %9, %10\n\t"  /* level i */                                                      \
-            "v_lshl_add_u32 %2, %5, 2, %1\n\t"   /* cell `start` on level i (%5 = start - a) */                     \
-            "v_mad_i32_i24 %1, %0, -4, %2\n\t"   /* a1: cell start - n */                                           \
-            "v_lshl_add_u32 %4, %4, 1, -1\n\t"   /* 2 i' - 1 = 29 - 2 i */                                          \
-            "v_lshrrev_b32 %3, %4, %12\n\t"      /* 4 S (bytes) */                                                  \
-            "v_sub_u32 %2, %2, %3\n\t"           /* a2: cell start - S */                                           \
-            "ds_min_u32 %1, %11\n\t"                                                                                \
-            "ds_min_u32 %2, %11\n\t"                                                                                \
-            "v_sub_u32 %4, 29, %4\n\t"           /* 2 i */                                                          \
-            "v_lshrrev_b32 %4, %4, %0\n\t"       /* q */                                                            \
+            "v_ffbh_u32 %[q], %[n]\n\t"                                                                             \
+            "v_lshrrev_b32 %[q], 1, %[q]\n\t"            /* i' = 15 - i */                                          \
+            "v_mad_u32_u24 %[a1], %[q], %[ls4], %[levelK]\n\t" /* level i */                                        \
+            "v_lshl_add_u32 %[a2], %[rel], 2, %[a1]\n\t" /* cell `start` on level i */                              \
+            "v_mad_i32_i24 %[a1], %[n], -4, %[a2]\n\t"   /* a1: cell start - n */                                   \
+            "v_lshl_add_u32 %[q], %[q], 1, -1\n\t"       /* 2 i' - 1 = 29 - 2 i */                                  \
+            "v_lshrrev_b32 %[s4], %[q], %[top_bit]\n\t"  /* 4 S (bytes) */                                          \
+            "v_sub_u32 %[a2], %[a2], %[s4]\n\t"          /* a2: cell start - S */                                   \
+            "ds_min_u32 %[a1], %[data]\n\t"                                                                         \
+            "ds_min_u32 %[a2], %[data]\n\t"                                                                         \
+            "v_sub_u32 %[q], 29, %[q]\n\t"               /* 2 i */                                                  \
+            "v_lshrrev_b32 %[q], %[q], %[n]\n\t"         /* q */                                                    \
             "s_mov_b64 exec, -1"                                                                                    \
-            : "=&v"(tmp), "=&v"(a1), "=&v"(a2), "=&v"(s4), "=&v"(q), "=&v"(dd)                                      \
-            : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(levelK), "v"(TOP ? w : col), "v"(top_bit)                   \
+            : [n] "=&v"(tmp), [a1] "=&v"(a1), [a2] "=&v"(a2), [s4] "=&v"(s4), [q] "=&v"(q), [rel] "=&v"(dd)         \
+            : [w] "v"(w), [km1] "s"(km1), [key] "v"(key), [ls4] "s"(ls4), [levelK] "v"(levelK),                     \
+              [data] "v"(TOP ? w : col), [top_bit] "v"(top_bit)                                                     \
             : "memory", "vcc")
         if constexpr (!Rows::kW12)
-            MEMO_R4_BLOCK("BYTE_2", "v_sub_u16 %5, %6, %8\n\t");
+            MEMO_R4_BLOCK(MEMO_ROW8_LEN_SEL, MEMO_ROW8_REL_START);
         else
-            MEMO_R4_BLOCK("BYTE_0", "v_sub_u32 %5, %6, %8\n\tv_bfe_u32 %5, %5, 8, 12\n\t");
+            MEMO_R4_BLOCK(MEMO_ROW12_LEN_SEL, MEMO_ROW12_REL_START);
 #undef MEMO_R4_BLOCK
         if (q >= 2) {
             const uint32_t data = TOP ? w : col;
@@ -660,66 +585,24 @@ __device__ __forceinline__ void plan_fold_store(const SweepArgs &A, const Tile &
         }
         lds_barrier();
     }
-    // 16 -> 4 and 4 -> 1 in registers (r4_fold_store's last part; arrays that do not exist read as "no row")
+    // 16 -> 4 and 4 -> 1 in registers, as in r4_fold_store.  Arrays the plan does not have are read where the blocks of 16 are -- one
+    // unconditional 16-byte read each -- and replaced by "no row" afterwards.
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int NW = T / 64;
-    constexpr int ctx = 4, valid = 64 - ctx;  // context lanes: 15 cells to the left
     OutT *out = static_cast<OutT *>(A.out);
     const int64_t ob = t.a - A.qs - HL;  // output index of cell 0
     const int64_t o_lo = t.a - A.qs + t.x_lo, o_hi = t.a - A.qs + t.x_hi;
-    // (arrays the plan does not have are read where the blocks of 16 are -- one unconditional 16-byte read each -- and
-    // replaced by "no row" afterwards)
     const uint32_t *L16 = lds + P.s16() * LS, *L4 = lds + (P.has4 ? P.s4() : P.s16()) * LS,
                    *L1 = lds + (P.has1 ? P.s1() : P.s16()) * LS;
-#define MEMO_DPP_MIN(dst, src) "v_min_u32_dpp " dst ", " src ", " dst " wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-#define MEMO_DPP_MOV(dst, src) "v_mov_b32_dpp " dst ", " src " wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-    for (int base = wave * 4 * valid; base + 4 * ctx < cells; base += NW * 4 * valid) {
-        const int x0 = base + 4 * lane;             // this lane's cells x0 .. x0 + 3
-        const int xr = min(x0, LS - 4);             // (past the array: lanes whose results are dropped below)
+    fold_store_chunks<OutT, T, TOP>(out, ob, o_lo, o_hi, cells, LS, lane, wave, Int<4>{}, [&](int xr) {
         const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
         uint4 R = *reinterpret_cast<const uint4 *>(L1 + xr);  // blocks of 1
         uint4 M = *reinterpret_cast<const uint4 *>(L4 + xr);  // blocks of 4
         if (!P.has1) R = ones;
         if (!P.has4) M = ones;
-        {
-            // blocks of 16 -> blocks of 4: cells x - 4, x - 8, x - 12 are the same component 1, 2, 3 lanes left.
-            // B = min over two lanes in place, P = B one lane left; M = min(M, B, P one more lane left)
-            uint4 B = *reinterpret_cast<const uint4 *>(L16 + xr), Q;
-            asm("s_nop 1\n\t" MEMO_DPP_MIN("%4", "%4") MEMO_DPP_MIN("%5", "%5") MEMO_DPP_MIN("%6", "%6") MEMO_DPP_MIN("%7", "%7")
-                MEMO_DPP_MOV("%8", "%4") MEMO_DPP_MOV("%9", "%5") MEMO_DPP_MOV("%10", "%6") MEMO_DPP_MOV("%11", "%7")
-                "v_min_u32 %0, %4, %0\n\tv_min_u32 %1, %5, %1\n\tv_min_u32 %2, %6, %2\n\tv_min_u32 %3, %7, %3\n\t"
-                MEMO_DPP_MIN("%0", "%8") MEMO_DPP_MIN("%1", "%9") MEMO_DPP_MIN("%2", "%10") MEMO_DPP_MIN("%3", "%11")
-                : "+v"(M.x), "+v"(M.y), "+v"(M.z), "+v"(M.w), "+v"(B.x), "+v"(B.y), "+v"(B.z), "+v"(B.w),
-                  "=&v"(Q.x), "=&v"(Q.y), "=&v"(Q.z), "=&v"(Q.w));  // (Q of lane 0: whatever was there; a context lane)
-        }
-        // blocks of 4 -> positions: cell x takes the blocks at x, x - 1, x - 2, x - 3 (the last ones of the lane to the left)
-        asm("s_nop 1\n\t"
-            "v_min3_u32 %3, %3, %7, %6\n\tv_min3_u32 %3, %3, %5, %4\n\t"
-            "v_min3_u32 %2, %2, %6, %5\n\tv_min_u32 %2, %2, %4\n\t"
-            "v_min3_u32 %1, %1, %5, %4\n\tv_min_u32 %0, %0, %4\n\t"
-            MEMO_DPP_MIN("%2", "%7") MEMO_DPP_MIN("%1", "%7") MEMO_DPP_MIN("%0", "%7")
-            MEMO_DPP_MIN("%1", "%6") MEMO_DPP_MIN("%0", "%6") MEMO_DPP_MIN("%0", "%5")
-            : "+v"(R.x), "+v"(R.y), "+v"(R.z), "+v"(R.w) : "v"(M.x), "v"(M.y), "v"(M.z), "v"(M.w));
-        if (lane < ctx || x0 >= cells) continue;
-        const int64_t g = ob + x0;
-        if (g >= o_lo && g + 4 <= o_hi) {
-            if constexpr (sizeof(OutT) == 1 && TOP == 24) {  // the four top bytes, two v_perm_b32 and an or
-                store_four(out + g, __builtin_amdgcn_perm(R.y, R.x, 0x0c0c0703u) | __builtin_amdgcn_perm(R.w, R.z, 0x07030c0cu));
-            } else {
-                if (TOP) R = make_uint4(R.x >> TOP, R.y >> TOP, R.z >> TOP, R.w >> TOP);
-                if constexpr (sizeof(OutT) == 1)
-                    store_four(out + g, R.x | (R.y << 8) | (R.z << 16) | (R.w << 24));
-                else
-                    store_four(out + g, R.x | (R.y << 16), R.z | (R.w << 16));
-            }
-        } else {  // window edges
-            const uint32_t v[4] = {R.x >> TOP, R.y >> TOP, R.z >> TOP, R.w >> TOP};
-            for (int i = 0; i < 4; ++i)
-                if (g + i >= o_lo && g + i < o_hi) out[g + i] = (OutT)v[i];
-        }
-    }
-#undef MEMO_DPP_MIN
-#undef MEMO_DPP_MOV
+        r4_fold16(M, *reinterpret_cast<const uint4 *>(L16 + xr));
+        r4_fold4(R, M);
+        return R;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -747,8 +630,7 @@ void sweep_conservation_mixed_kernel(const SweepArgs A) {
     uint4 V[U];
     uint2 N[U];
     Rows::template issue<T, U>(A, t, 0, V, N);
-    const uint32_t sent = (uint32_t)(A.ncols - 1);
-    plan_clear<T>(A, lds, TOP ? (sent << TOP) | ((1u << TOP) - 1u) : sent);
+    plan_clear<T>(A, lds, cell_sentinel<TOP>(A));
 
     const int km1 = A.km1;
     // slot of the blocks of 2^(31-f), f = clz(n) <= 27:  f - ftop (the range: see the level plan above);
@@ -767,43 +649,30 @@ void sweep_conservation_mixed_kernel(const SweepArgs A) {
         int n;
         uint32_t r0, r1, r2, d;
         MEMO_EXEC_ALL_ONES(A.status);
+#define MEMO_MIXED_BLOCK(LEN_SEL, REL_START)                                                                        \
+        asm volatile(                                                                                               \
+            "v_sub_u32_sdwa %[n], %[km1], %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD " LEN_SEL "\n\t"   \
+            REL_START                                                                                               \
+            "v_ffbh_u32 %[f], %[n]\n\t"                                                                             \
+            "v_cmpx_lt_i32 vcc, 0, %[n]\n\t"                                                                        \
+            "v_cmpx_gt_u32 vcc, 28, %[f]\n\t"                                                                       \
+            "v_mad_u32_u24 %[a2], %[f], %[ls4], %[bias4]\n\t"                                                       \
+            "v_lshl_add_u32 %[a2], %[rel], 2, %[a2]\n\t"                                                            \
+            "v_mad_i32_i24 %[a1], %[n], -4, %[a2]\n\t"                                                              \
+            "v_ashrrev_i32 %[f], %[f], %[top_bit]\n\t"                                                              \
+            "v_lshl_add_u32 %[a2], %[f], 2, %[a2]\n\t"                                                              \
+            "ds_min_u32 %[a1], %[data]\n\t"                                                                         \
+            "ds_min_u32 %[a2], %[data]\n\t"                                                                         \
+            "s_mov_b64 exec, -1"                                                                                    \
+            : [f] "=&v"(r0), [a1] "=&v"(r1), [a2] "=&v"(r2), [n] "=&v"(n), [rel] "=&v"(d)                           \
+            : [w] "v"(w), [km1] "s"(km1), [key] "v"(key), [ls4] "s"(ls4), [bias4] "v"(bias4), [top_bit] "v"(top_bit), \
+              [data] "v"(TOP ? w : col)                                                                             \
+            : "memory", "vcc")
         if constexpr (!Rows::kW12)
-            asm volatile(
-                "v_sub_u32_sdwa %3, %6, %5 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                "v_sub_u16 %4, %5, %7\n\t"
-                "v_ffbh_u32 %0, %3\n\t"
-                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                "v_cmpx_gt_u32 vcc, 28, %0\n\t"
-                "v_mad_u32_u24 %2, %0, %8, %9\n\t"
-                "v_lshl_add_u32 %2, %4, 2, %2\n\t"
-                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                "v_ashrrev_i32 %0, %0, %10\n\t"
-                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                "ds_min_u32 %1, %11\n\t"
-                "ds_min_u32 %2, %11\n\t"
-                "s_mov_b64 exec, -1"
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(n), "=&v"(d)
-                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                : "memory", "vcc");
+            MEMO_MIXED_BLOCK(MEMO_ROW8_LEN_SEL, MEMO_ROW8_REL_START);
         else
-            asm volatile(
-                "v_sub_u32_sdwa %3, %6, %5 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-                "v_sub_u32 %4, %5, %7\n\t"
-                "v_bfe_u32 %4, %4, 8, 12\n\t"
-                "v_ffbh_u32 %0, %3\n\t"
-                "v_cmpx_lt_i32 vcc, 0, %3\n\t"
-                "v_cmpx_gt_u32 vcc, 28, %0\n\t"
-                "v_mad_u32_u24 %2, %0, %8, %9\n\t"
-                "v_lshl_add_u32 %2, %4, 2, %2\n\t"
-                "v_mad_i32_i24 %1, %3, -4, %2\n\t"
-                "v_ashrrev_i32 %0, %0, %10\n\t"
-                "v_lshl_add_u32 %2, %0, 2, %2\n\t"
-                "ds_min_u32 %1, %11\n\t"
-                "ds_min_u32 %2, %11\n\t"
-                "s_mov_b64 exec, -1"
-                : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(n), "=&v"(d)
-                : "v"(w), "s"(km1), "v"(key), "s"(ls4), "v"(bias4), "v"(top_bit), "v"(TOP ? w : col)
-                : "memory", "vcc");
+            MEMO_MIXED_BLOCK(MEMO_ROW12_LEN_SEL, MEMO_ROW12_REL_START);
+#undef MEMO_MIXED_BLOCK
         if ((uint32_t)(n - 1) < 15u) {  // 0 < n < 16: blocks of S = 4 (n >= 4) or 1 at start - n and start - S; two more while n >= 2S, 3S
             const uint32_t data = TOP ? w : col;
             const bool four = n >= 4;

@@ -86,7 +86,7 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     constexpr int LSZ = R4 ? kLS4 : kLS;  // cells per level array
     constexpr int SH = A9 ? 23 : 24;  // a cell = order << SH | tie-breaking bits
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    constexpr int NW = T / 64, NL = kStageGroups / T;  // waves; 16-byte groups per lane and batch
+    constexpr int NL = kStageGroups / T;  // 16-byte groups per lane and batch
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t blk = blockIdx.x;
     const uint32_t tile = (blk & 7u) * (uint32_t)A.tiles_per_xcd + (blk >> 3);  // each XCD group: a contiguous run of tiles
@@ -128,7 +128,7 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     issue(0);
     const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)lds;
     const int HL = A.hl, W = A.w;
-    clear_levels<NLEV, T>(lds_base, ((uint32_t)(A.ncols - 1) << SH) | ((1u << SH) - 1u));  // (R4: 3 x 6656 B inside the 20 KiB of five)
+    clear_levels<NLEV, T>(lds_base, cell_sentinel<SH>(A));  // (R4: 3 x 6656 B inside the 20 KiB of five)
     RowConst C;
     C.km1 = A.km1;
     C.status = A.status;
@@ -172,51 +172,52 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     }
     barrier_lds();  // (lgkmcnt(0): the ds_min above are invisible to the compiler)
 
-    // fold in registers + store (halo_fold_store_dpp of memo_sweep_cons.hip, unrolled for NLEV)
+    // fold in registers + store
     OutT *out = static_cast<OutT *>(A.out);
     const int cells = HL + W;
     // context lanes of a chunk of 64 (R4: the fold of 12s reads two lanes to the left, the fold of 4s one more; 4 * ctx <= hl)
     constexpr int ctx = R4 ? 3 : (NLEV <= 1 ? 0 : (NLEV <= 3 ? 1 : 1 << (NLEV - 3)));
-    constexpr int valid = 64 - ctx;
     const int64_t a_rel = (int64_t)tabs * W - A.qs;  // the tile's first position, as an output index
     const int64_t ob = a_rel - HL;
     const int64_t o_lo = a_rel + (tile == 0 ? A.x_lo_first : 0);
     const int64_t o_hi = a_rel + (tile == (uint32_t)A.ntiles - 1u ? A.x_hi_last : W);
-    for (int base = wave * 4 * valid; base + 4 * ctx < cells; base += NW * 4 * valid) {
-        const int x0 = base + 4 * lane;
-        const int xr = x0 < LSZ - 4 ? x0 : LSZ - 4;  // (past the array: lanes whose results are dropped below)
-        u32x4 L[6];
-        auto lv = [&](int i) { return make_uint4(L[i].x, L[i].y, L[i].z, L[i].w); };
-        uint4 M;
-        if constexpr (R4) {  // blocks of 12 -> 4 -> positions (memo_sweep_fold.h)
+    u32x4 L[6];
+    auto lv = [&](int i) { return make_uint4(L[i].x, L[i].y, L[i].z, L[i].w); };
+    if constexpr (R4) {  // blocks of 12 -> 4 -> positions, in the chunk loop every register fold shares (memo_sweep_fold.h)
+        fold_store_chunks<OutT, T, SH>(out, ob, o_lo, o_hi, cells, LSZ, lane, wave, Int<ctx>{}, [&](int xr) {
             read_levels_r4(lds_base + 4u * (uint32_t)xr, L);
-            M = lv(2);
-            uint4 M4 = lv(1);
+            uint4 M = lv(2), M4 = lv(1);
             r4_fold12(M4, lv(0));
             r4_fold4(M, M4);
-        } else {
+            return M;
+        });
+    } else {
+        // The doubling arrays: halo_fold_store_dpp of memo_sweep_cons.hip unrolled for NLEV, with the loop and the store of
+        // fold_store_chunks / store_cells4 (memo_sweep_fold.h) written out as they were; only the pack is the shared one.  Through
+        // the shared loop these kernels came out as the same instructions under another register allocation, and the six-row
+        // kernel on config 3's view at k = 31 then took 0.12488 against 0.12255 ms, +1.9 % where the parent's own rounds spread by
+        // 1.35 % (k = 9 / 17 / 21: +0.4 / +0.3 / -0.5 %, inside the spread): profiles/fold_tail_refactor.txt, first run.  Written
+        // like this every one of them is the parent's code to the instruction (profiles/fold_tail_device_code.txt).
+        constexpr int NW = T / 64, valid = 64 - ctx;
+        for (int base = wave * 4 * valid; base + 4 * ctx < cells; base += NW * 4 * valid) {
+            const int x0 = base + 4 * lane;
+            const int xr = x0 < LSZ - 4 ? x0 : LSZ - 4;  // (past the array: lanes whose results are dropped below)
             read_levels<NLEV>(lds_base + 4u * (uint32_t)xr, L);
-            M = lv(0);
+            uint4 M = lv(0);
             if constexpr (NLEV >= 6) fold_step_dpp<4>(M, lv(NLEV - 5), lane);
             if constexpr (NLEV >= 5) fold_step_dpp<3>(M, lv(NLEV - 4), lane);
             if constexpr (NLEV >= 4) fold_step_dpp<2>(M, lv(NLEV - 3), lane);
             if constexpr (NLEV >= 3) fold_step_dpp<1>(M, lv(NLEV - 2), lane);
             if constexpr (NLEV >= 2) fold_step_dpp<0>(M, lv(NLEV - 1), lane);
-        }
-        if (lane < ctx || x0 >= cells) continue;
-        const int64_t o = ob + x0;
-        if (o >= o_lo && o + 4 <= o_hi) {
-            if constexpr (A9) {  // (store_four, memo_sweep.h: the address is whatever the window's start makes of it)
-                store_four(out + o, (M.x >> 23) | ((M.y >> 23) << 16), (M.z >> 23) | ((M.w >> 23) << 16));
-            } else if constexpr (sizeof(OutT) == 1) {
-                store_four(out + o, __builtin_amdgcn_perm(M.y, M.x, 0x0c0c0703u) | __builtin_amdgcn_perm(M.w, M.z, 0x07030c0cu));
+            if (lane < ctx || x0 >= cells) continue;
+            const int64_t o = ob + x0;
+            if (o >= o_lo && o + 4 <= o_hi) {
+                store_four(out + o, pack_cells4<OutT, SH>(M));
             } else {
-                store_four(out + o, __builtin_amdgcn_perm(M.y, M.x, 0x0c070c03u), __builtin_amdgcn_perm(M.w, M.z, 0x0c070c03u));
+                const uint32_t v[4] = {M.x >> SH, M.y >> SH, M.z >> SH, M.w >> SH};
+                for (int i = 0; i < 4; ++i)
+                    if (o + i >= o_lo && o + i < o_hi) out[o + i] = (OutT)v[i];
             }
-        } else {
-            const uint32_t v[4] = {M.x >> SH, M.y >> SH, M.z >> SH, M.w >> SH};
-            for (int i = 0; i < 4; ++i)
-                if (o + i >= o_lo && o + i < o_hi) out[o + i] = (OutT)v[i];
         }
     }
 }
