@@ -67,6 +67,13 @@ int memo_debug_one_shot_way(int32_t way);
  * swept (the one-shot forms destroy their index before they return): which kernel family -- hence which row format --
  * answered it */
 int memo_debug_last_one_shot_sweep(void);
+/* the plan of this index's last memo_query_membership_dev, as its launcher recorded it on the host: out6[0] the algorithm (2 = doubling,
+ * 3 = runs, 4 = planes on the 4- / 6-byte rows, 5 = planes on the dense rows; 0 = none yet, or the fill of k <= 1 / an empty index),
+ * [1] the tile width in positions, [2] threads per tile, [3] the MW of the planes' row block (0, 2, 3, 4 or 8: the most words a run reaches
+ * past its first; -1 where the kernel has none), [4] 1 where the planes' group skew (SK) is on, [5] result words per launch (the
+ * slice of genome words; all of them except where the runs kernel sweeps more than 64).  memo_index_info_t.last_sweep says 7 for
+ * doubling, runs and planes alike. */
+int memo_debug_last_membership(const memo_index_t *ix, int32_t *out6);
 /* one pass that reads the three int64 columns exactly once (24 B/row) with the sweep's access
  * shape, to calibrate the FETCH_SIZE counter on a known byte count */
 int memo_debug_stream_rows(memo_index_t *ix, void *stream);

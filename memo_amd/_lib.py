@@ -178,6 +178,7 @@ DEBUG_SYMBOLS = {
     "memo_debug_dense_keep_all": (C.c_int, [_I32]),
     "memo_debug_one_shot_way": (C.c_int, [_I32]),
     "memo_debug_last_one_shot_sweep": (C.c_int, []),
+    "memo_debug_last_membership": (C.c_int, [_P, C.POINTER(_I32)]),
     "memo_debug_set_stamp_buffer": (C.c_int, [_P]),
     "memo_debug_ms_free_bytes": (C.c_int, [_I64]),
     "memo_debug_ms_piece_text": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _I64, C.POINTER(_I64)]),

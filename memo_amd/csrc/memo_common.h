@@ -246,6 +246,10 @@ struct memo_index {
     int last_arrays = 0;         // mixed level arrays (last_sweep 4): how many of them the sweep's level plan allocated
     int last_variant = 0;        // ... 2 table-driven on five-row groups (memo_sweep_cons3t.hip), 3 on a view of six rows per group; 0 no table
     int last_tile_w = 0;         // ... and its tile width (info.last_tile_width: 1568 at k = 31 on the radix-4 arrays, 928 on the doubling ones)
+    // the plan of the last membership sweep (memo_debug_last_membership of the AB library): the algorithm (2 doubling, 3 runs, 4 planes on the
+    // 4- / 6-byte rows, 5 planes on the dense rows; 0 none yet, or the k <= 1 fill), the tile width, threads per tile, the row block's MW
+    // (-1: a kernel without one), SK, result words per launch.  Host side only: no kernel reads it.
+    int last_memb[6] = {0, 0, 0, -1, 0, 0};
     int has_wide = 1;          // the three int64 columns are still resident
     // rows with end < start (never written by the reference's index builder, but legal input to
     // memo_query.py): copied aside at finalize and applied by long_rows_kernel after each sweep

@@ -119,6 +119,12 @@ int memo_debug_stream_rows(memo_index_t *ix, void *stream) {
 
 int memo_debug_last_one_shot_sweep(void) { return g_last_one_shot_sweep; }
 
+int memo_debug_last_membership(const memo_index_t *ix, int32_t *out6) {
+    if (!ix || !out6) return fail(MEMO_EINVAL, "index or out6 is NULL");
+    for (int i = 0; i < 6; ++i) out6[i] = ix->last_memb[i];
+    return MEMO_OK;
+}
+
 int memo_debug_set_stamp_buffer(uint64_t *d_buffer) {
 #ifdef MEMO_STAMPS
     g_stamp_buffer = reinterpret_cast<unsigned long long *>(d_buffer);

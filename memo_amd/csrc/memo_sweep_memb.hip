@@ -501,8 +501,13 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     DeviceGuard guard(ix->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nw = (num_docs + 31) / 32;
+    const auto record = [&](int algo, int tw, int threads, int mw, int sk, int slice) {  // memo_index::last_memb
+        const int plan[6] = {algo, tw, threads, mw, sk, slice};
+        for (int i = 0; i < 6; ++i) ix->last_memb[i] = plan[i];
+    };
     if (k <= 1 || ix->rows == 0) {
         if (g_prepare_only) return MEMO_OK;
+        record(0, 0, 0, -1, 0, nw);
         if ((rc = refuse_plan_pointer(d_out))) return rc;
         hipLaunchKernelGGL(fill_membership_kernel, dim3(2048), dim3(256), 0, st, d_out,
                            (qe - qs) * nw, nw, num_docs);
@@ -525,7 +530,7 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     const int km1 = k - 1, bw = 1 << ix->bshift;
     const int64_t len = qe - qs;
     SweepKernel kern = nullptr;
-    int tw = 0, threads = 256, slice = nw;
+    int tw = 0, threads = 256, slice = nw, plan_algo = 0, plan_mw = -1, plan_sk = 0;
     size_t lds = 0;
     // The dense rows where an index holds no 4- / 6-byte rows and they can answer: the planes kernel on them (k - 1 <= 63,
     // at most 255 genomes, every annot inside the matrix, an index of >= 1 row per position like the other unclipped
@@ -544,7 +549,8 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     if (dense) {
         lds = planes_tile(A, tw, km1, bw, nw);
         // (k - 1 <= 63 here: a run reaches at most two words past its first)
-        kern = pick_int<0, 2>(km1 <= 31 ? 0 : 2, [&](auto MW) {
+        plan_algo = 5, plan_mw = km1 <= 31 ? 0 : 2, plan_sk = A.hl != 0;
+        kern = pick_int<0, 2>(plan_mw, [&](auto MW) {
             return pick_bool(A.hl != 0, [&](auto SK) {
                 return (SweepKernel)sweep_membership_planes3_kernel<PackedRows3::kLoads, 256, MW, SK>;
             });
@@ -585,6 +591,7 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
                 threads = T;
                 // the row block by the most words a run can reach past its first: 0 = the two-word block (k - 1 <= 31), else 2, 3, 4 or 8
                 const int reach = (km1 + 30) / 32, mw = km1 <= 31 ? 0 : (reach <= 2 ? 2 : reach <= 3 ? 3 : reach <= 4 ? 4 : 8);
+                plan_algo = 4, plan_mw = mw, plan_sk = A.hl != 0;
                 kern = pick_packed<false>(fmt, [&](auto R) {
                     return pick_int<64, 256>(T, [&](auto TT) {
                         return pick_int<0, 2, 3, 4, 8>(mw, [&](auto MW) {
@@ -600,6 +607,7 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
             if (!waves) waves = 4;
             threads = 64 * waves;
             const bool runs = algo == 3 || algo == 4;
+            plan_algo = runs ? 3 : 2, plan_mw = -1, plan_sk = 0;
             if (runs) {
                 // 4 * nw bytes of LDS per position: beyond 2048 genomes even a 256-position tile is too big,
                 // so the genome words are swept in slices of 64 (the rows are read once per slice; every
@@ -653,6 +661,7 @@ int memo_query_membership_dev(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     } else if ((rc = use_words(ix, A, fmt, true, st))) {
         return rc;
     }
+    record(plan_algo, tw, threads, plan_mw, plan_sk, slice);
     for (int base = 0; base < nw; base += slice) {
         A.word_base = base;
         A.nwords = nw - base < slice ? nw - base : slice;

@@ -166,6 +166,12 @@ class DeviceIndex:
         check(lib().memo_debug_set_tuning(self._h, tile_w, waves, membership_algo, row_source, scatter))
         return self
 
+    def debug_last_membership(self):
+        """memo_debug_last_membership: the plan of the last membership sweep, as the launcher recorded it"""
+        out = (C.c_int32 * 6)()
+        check(lib().memo_debug_last_membership(self._h, out))
+        return dict(zip(("algorithm", "tile_width", "threads", "mw", "sk", "slice"), (int(v) for v in out)))
+
     def check(self, stream=None):
         check(lib().memo_query_check(self._h, _ptr(stream)))
 
