@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view` and the runs of `memo regions`: off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions` and the matrix of `memo matrix`: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -193,6 +193,27 @@ size_t memo_emit_runs(const char *record, int64_t qs, int64_t L, const int64_t *
                       uint64_t runs, char *buf, size_t cap);
 size_t memo_emit_membership_runs(const char *record, int64_t qs, int64_t L, const int64_t *starts, const uint32_t *run_bits,
                                  uint64_t runs, int32_t num_docs, char *buf, size_t cap);
+
+/* ---- `memo matrix`: pairwise k-mer sharing between genomes (no counterpart in the reference) ---------------------
+ * (Declared here, beside the `memo regions` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The co-occurrence matrix of a membership result that is still on `device` (memo_amd/csrc/memo_cooc.hip): d_bits is uint32
+ * [L][W], W = ceil(num_docs / 32), as memo_query_membership_dev writes it (bit g & 31 of word g >> 5: genome g holds the k-mer;
+ * genome 0 is the pivot).  d_bits must be 16-byte aligned (MEMO_EINVAL otherwise, before anything is launched) and is read from
+ * [0] to [L * W) and nowhere else; bits at or above num_docs are masked, whatever they hold.  Any num_docs >= 1.  Scratch memory
+ * on the device: at most 64 MiB, freed before the call returns; an allocation that fails returns MEMO_EHIP with the bytes asked
+ * for in memo_last_error and leaves nothing allocated.
+ *
+ * C[g][h] += #{p : bit g and bit h set} for a membership result on `device`; d_counts is uint64 [num_docs][num_docs],
+ * ADDED to (the caller zeroes it; several windows or slices accumulate).  Blocking. */
+int memo_cooccurrence_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, uint64_t *d_counts, int32_t device, void *stream);
+/* positions per tile, for tests that want lengths around it */
+int32_t memo_cooccurrence_tile(int32_t words);
+/* memo_query_membership_dev of the slice [qs, qe) of the window [whole_qs, whole_qe), so that the slices of a window laid end to
+ * end are the window's result: rows with end < start pass the reference's filter by the whole window, not by the slice (they
+ * reach any distance left of their start; memo_amd_multi.h sweeps its sub-windows alike).  d_out: the slice's rows, uint32
+ * [qe - qs][W].  Queued on `stream` as memo_query_membership_dev queues it; check with memo_query_check. */
+int memo_query_membership_slice_dev(memo_index_t *ix, int64_t whole_qs, int64_t whole_qe, int64_t qs, int64_t qe, int32_t k,
+                                    int32_t num_docs, uint32_t *d_out, void *stream);
 
 #ifdef __cplusplus
 }

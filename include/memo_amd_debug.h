@@ -88,6 +88,14 @@ int memo_debug_ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *re
 /* this THREAD's later additions to coded matching-statistics handles (memo_ms_create_layout): every allocation of a coded column
  * sees `bytes` of free device memory instead of what the device reports (< 0: off) -- the test of a column that does not fit */
 int memo_debug_ms_free_bytes(int64_t bytes);
+/* this THREAD's later memo_cooccurrence_dev calls: how the workgroups' 32-bit counts reach the 64-bit matrix: 0 (the default, the
+ * product's way) = a partials buffer and a reduce launch, 1 = one 64-bit atomic per pair, mirror and workgroup (the A/B of
+ * DESIGN.md 10.4).  The matrix is the same either way. */
+int memo_debug_cooc_flush(int32_t way);
+/* this THREAD's later memo_cooccurrence_dev calls put event pairs around their launches (on = 1; each launch is then waited for)
+ * or do not (0); out2 (may be NULL) receives the device milliseconds of the last timed call: [0] the sweep launches, [1] the
+ * reduce launches (0 with atomics: the flush is part of the sweep).  tools/matrix_timing.py reads them. */
+int memo_debug_cooc_times(int32_t on, float *out2);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,8 @@ Layout (only what the path needs):
   view_cli.py      `memo view`: flags, usage, the table as TSV, the plot (matplotlib)
   regions.py       `memo regions`: a result's runs of equal value compacted on the GPU, a window's runs from an index
   regions_cli.py   `memo regions`: flags, usage, bedGraph / BED3 / BED + membership string
+  matrix.py        `memo matrix`: a membership result's co-occurrence matrix counted on the GPU, a window's in slices
+  matrix_cli.py    `memo matrix`: flags, usage, counts or Jaccard distances as tab-separated text
 
 Attributes are loaded on first use (PEP 562), so that `import memo_amd._fastquery` -- the CLI's cache-hit
 path -- does not pay for NumPy.
@@ -28,6 +30,7 @@ _LAZY = {
     "conservation_rows": "index", "membership_rows": "index",
     "emit_conservation": "index", "emit_membership": "index",
     "runs": "regions", "membership_runs": "regions", "region_runs": "regions",
+    "cooccurrence": "matrix", "region_matrix": "matrix",
 }
 
 
@@ -37,7 +40,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

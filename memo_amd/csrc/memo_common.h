@@ -37,6 +37,9 @@ int ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, in
 extern thread_local int64_t g_ms_free_bytes;
 // memo_text.hip: exclusive scan of ntiles uint32 tile counts into int64 bases, their sum into *d_total (one workgroup; queued on st)
 hipError_t scan_tile_counts(const uint32_t *d_counts, int64_t ntiles, int64_t *d_bases, int64_t *d_total, hipStream_t st);
+extern thread_local int g_cooc_flush;  // memo_cooc.hip (AB library, memo_debug_cooc_flush: 1 = atomics instead of partials)
+extern thread_local int g_cooc_timed;  // ... memo_debug_cooc_times: event pairs around the launches of memo_cooccurrence_dev
+extern thread_local float g_cooc_ms[2];
 double pinned_alloc_ms_total();  // memo_hostcore.cpp: time this process has spent allocating pinned staging slots (MEMO_TIMING)
 
 struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the current device

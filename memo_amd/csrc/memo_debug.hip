@@ -145,4 +145,16 @@ int memo_debug_ms_free_bytes(int64_t bytes) {
     return MEMO_OK;
 }
 
+int memo_debug_cooc_flush(int32_t way) {
+    if (way < 0 || way > 1) return fail(MEMO_EINVAL, "co-occurrence flush: 0 partials and a reduce launch, 1 atomics");
+    g_cooc_flush = way;
+    return MEMO_OK;
+}
+
+int memo_debug_cooc_times(int32_t on, float *out2) {
+    g_cooc_timed = on ? 1 : 0;
+    if (out2) out2[0] = g_cooc_ms[0], out2[1] = g_cooc_ms[1];
+    return MEMO_OK;
+}
+
 }  // extern "C"

@@ -151,6 +151,10 @@ class DeviceIndex:
     def membership_dev(self, qs, qe, k, num_docs, out, stream=None):
         check(lib().memo_query_membership_dev(self._h, qs, qe, k, num_docs, _ptr(out), _ptr(stream)))
 
+    def membership_slice_dev(self, whole_qs, whole_qe, qs, qe, k, num_docs, out, stream=None):
+        """membership_dev of the slice [qs, qe) of the window [whole_qs, whole_qe): the slices of a window are the window's result"""
+        check(lib().memo_query_membership_slice_dev(self._h, whole_qs, whole_qe, qs, qe, k, num_docs, _ptr(out), _ptr(stream)))
+
     # ---- include/memo_amd_debug.h: only with _lib.use_ab() (libmemo_amd_ab.so) ----
     def debug_stream_rows(self, stream=None):
         check(lib().memo_debug_stream_rows(self._h, _ptr(stream)))
