@@ -32,7 +32,10 @@ extern "C" {
  *   level arrays with a halo, 3 = unclipped into radix-4 level arrays, 4 = unclipped into mixed level arrays
  *   (blocks of 1, 4, 16, then doubling; k - 1 >= 16) with every array a k - 1 of that size can need (rounds 2-3), 5 = the mixed
  *   arrays with the library's level plan (only the arrays some row of the index can write to) -- 2 .. 5 only when every annot of
- *   the index is inside the result matrix, else 1. */
+ *   the index is inside the result matrix, else 1.  Bits 8 .. 10 of scatter, added to any of these, switch parts of the wide-tile
+ *   sweep's shortened chain OFF (memo_sweep_cons3t.hip; profiles/tile_chain.txt): 256 = the kernel entry whose head arrives in
+ *   registers, 512 = a wave's two fold chunks in flight together, 1024 = the store without the window test in tiles off the
+ *   window's edges; all three off is the kernel as it was before them. */
 int memo_debug_set_tuning(memo_index_t *ix, int32_t tile_w, int32_t waves, int32_t membership_algo,
                           int32_t row_source, int32_t scatter);
 /* Order of the 4-byte rows inside a start bucket (memo_amd/csrc/memo_interleave.hip): 0 = the library's choice (3 for conservation, 4 for membership: whichever kind of query pays for the pass), 1 = start order (as the packers write them), 2 = chunks of four rows dealt round-robin

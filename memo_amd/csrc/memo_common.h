@@ -128,6 +128,9 @@ struct memo_tuning {
     int no_all_write = 0;  // dense rows: 1 = the row blocks keep their "this row writes" test on a view of exactly the writing rows (A/B)
     int force_packed = 0;  // 1 = read the 4-byte rows even when the dense rows are resident and could answer (they are
                            //     the faster source for the conservation sweep: profiles/r02_dense_rows_ab.txt)
+    int chain_off = 0;     // wide-tile sweep (memo_sweep_cons3t.hip: R4), parts of its shortened chain switched OFF (A/B): 1 = the entry with
+                           //     the head in registers, 2 = a wave's two fold chunks in flight together, 4 = the store without the window
+                           //     test in tiles off the window's edges
     int row_order = 0;     // order of the 4-byte rows inside a bucket (memo_interleave.hip): 0 = the library's (kRowOrderDefault),
                            //     1 = start order as packed, 2 = chunks of four dealt over the starts, 3 = the same with the rows of a
                            //     start ordered by overlap mod 32 (the conservation order), 4 = dealt over annot mod 32 (membership)

@@ -42,6 +42,8 @@ int memo_debug_set_tuning(memo_index_t *ix, int32_t tile_w, int32_t waves, int32
                                  "the 4- / 6-byte rows, else the int64 columns), 1 (int64 columns), 2 (same as 0), 3 (4- / 6-byte "
                                  "rows even where the dense rows could answer), 5 (dense rows, every wave works its tile out), 8, 9, 10 or 13 "
                                  "(include/memo_amd_debug.h; 4, 6, 7, 11, 12 were round 3's persistent sweeps: profiles/r03_persistent_sweep.txt)");
+    const int32_t chain_off = (scatter >> 8) & 7;  // (bits 8 .. 10: the wide-tile sweep's parts, include/memo_amd_debug.h)
+    scatter &= ~(7 << 8);
     if (scatter < 0 || scatter > 5)
         return fail(MEMO_EINVAL, "scatter must be 0 (choose), 1 (clipped), 2 (unclipped, doubling levels), 3 (unclipped, radix-4 levels) "
                                  "4 (unclipped, mixed levels, every array) or 5 (mixed levels, the arrays of the library's level plan)");
@@ -54,6 +56,7 @@ int memo_debug_set_tuning(memo_index_t *ix, int32_t tile_w, int32_t waves, int32
     ix->tune.no_views = row_source == 9 || row_source == 5;
     ix->tune.no_all_write = row_source == 13;
     ix->tune.scatter = scatter;
+    ix->tune.chain_off = chain_off;
     return MEMO_OK;
 }
 

@@ -11,6 +11,19 @@
 // later query's waves fetch their tile with ONE s_load_dwordx8.  The rest of the tile body is the lean one of
 // memo_sweep_dense.h: clear, level reads and fold unrolled for the number of level arrays (template parameter), four
 // row loads in a row, rows masked by number only in the pieces that straddle an end of the slice.
+//
+// The wide tiles (R4) run a kernel of their own, sweep_conservation_wide_kernel, whose time follows the chain a tile walks while it
+// holds its 20 KiB, not its instruction count.  Three links of that chain are gone (profiles/tile_chain.txt: -6.7 ... -7.1 % at
+// k = 31, 21, 17, each part alone faster than the kernel before on every run):
+//   - the head: the six values a wave needs before its row loads, and six more it needs before the barrier, are leading scalar
+//     kernel parameters, which gfx950 delivers in SGPRs at wave launch (kernel-argument preload, 14 dwords; this file is compiled
+//     with -amdgpu-kernarg-preload-count=16); the tile descriptor then comes with ONE s_load_dwordx8 -- one scalar round trip in
+//     front of the row loads where there were several;
+//   - the fold: a wave with two chunks of the level arrays reads both before it waits (fold_chunks_once_or_twice);
+//   - the store: a tile that touches neither edge of the window keeps the lanes right of the left halo and stores their four
+//     results at a scalar base plus a 32-bit lane offset; the per-cell 64-bit window test is left to the window's first and last
+//     tile.  The wave-uniform choice is made once, in front of two straight tails (made per store it cost what it saved).
+// memo_debug_set_tuning (scatter bits 8 .. 10) switches each part off; all off is sweep_conservation_halo3t_kernel<..., R4>.
 #include "memo_sweep_dense.h"
 
 using namespace memo;
@@ -222,6 +235,193 @@ void sweep_conservation_halo3t_kernel(const SweepArgs A) {
     }
 }
 
+// What a wave of a wide tile needs before its row loads and before its barrier, behind one set of names: the leading scalar
+// parameters of sweep_conservation_wide_kernel, which gfx950 hands over in SGPRs at wave launch (FlatHead), or the fields of SweepArgs,
+// each read where it is used as the kernel above reads them (ArgsHead: sweep_conservation_wide_args_kernel, the A/B of the head).
+struct ArgsHead {
+    const SweepArgs &A;
+    __device__ __forceinline__ const TileDesc *ttab() const { return static_cast<const TileDesc *>(A.ttab); }
+    __device__ __forceinline__ const uint4 *rows() const { return reinterpret_cast<const uint4 *>(A.p3); }
+    __device__ __forceinline__ uint32_t ntiles() const { return (uint32_t)A.ntiles; }
+    __device__ __forceinline__ uint32_t tiles_per_xcd() const { return (uint32_t)A.tiles_per_xcd; }
+    __device__ __forceinline__ uint32_t tile_abs0() const { return (uint32_t)A.tile_abs0; }
+    __device__ __forceinline__ uint32_t ntab() const { return (uint32_t)A.ntab; }
+    __device__ __forceinline__ int hl() const { return A.hl; }
+    __device__ __forceinline__ int w() const { return A.w; }
+    __device__ __forceinline__ int km1() const { return A.km1; }
+    __device__ __forceinline__ int ncols() const { return A.ncols; }
+    __device__ __forceinline__ int x_lo_first() const { return A.x_lo_first; }
+    __device__ __forceinline__ int x_hi_last() const { return A.x_hi_last; }
+};
+
+struct FlatHead {
+    const TileDesc *ttab_;
+    const uint4 *rows_;
+    uint32_t ntiles_, tiles_per_xcd_, tile_abs0_, ntab_;
+    int hl_, w_, km1_, ncols_, x_lo_first_, x_hi_last_;
+    __device__ __forceinline__ const TileDesc *ttab() const { return ttab_; }
+    __device__ __forceinline__ const uint4 *rows() const { return rows_; }
+    __device__ __forceinline__ uint32_t ntiles() const { return ntiles_; }
+    __device__ __forceinline__ uint32_t tiles_per_xcd() const { return tiles_per_xcd_; }
+    __device__ __forceinline__ uint32_t tile_abs0() const { return tile_abs0_; }
+    __device__ __forceinline__ uint32_t ntab() const { return ntab_; }
+    __device__ __forceinline__ int hl() const { return hl_; }
+    __device__ __forceinline__ int w() const { return w_; }
+    __device__ __forceinline__ int km1() const { return km1_; }
+    __device__ __forceinline__ int ncols() const { return ncols_; }
+    __device__ __forceinline__ int x_lo_first() const { return x_lo_first_; }
+    __device__ __forceinline__ int x_hi_last() const { return x_hi_last_; }
+};
+
+// the parts of the wide-tile kernel's shortened chain (CH; launch_halo3t, memo_tuning.chain_off)
+constexpr int kChainFold2 = 1;     // a wave's two fold chunks in flight together
+constexpr int kChainInterior = 2;  // tiles off the window's edges store without the window test
+
+// The wide tile's body (R4 of the kernel above: radix-4 arrays, six-row views without flags) with the shortened chain, for both of its
+// entries.  FLAT: the head came in registers -- the descriptor is then fetched by ONE scalar load of its 32 bytes (written as asm: left
+// to itself the compiler splits it, or turns to a vector load and v_readfirstlane).  It is a body of its own: the kernel above, put
+// behind a shared __device__ function, came out as other code in every doubling instance (the batch loop counted another way, other
+// registers; profiles/tile_chain.txt), and those must stay what they were.
+template <typename OutT, bool AW, bool SP, int CH, typename Head>
+__device__ __forceinline__ void wide_tile(const SweepArgs &A, const Head &H) {
+    constexpr bool FLAT = std::is_same<Head, FlatHead>::value;
+    static_assert((FLAT || CH > 0) && CH >= 0 && CH <= (kChainFold2 | kChainInterior), "no part of the chain: the kernel above");
+    constexpr int T = 256, LSZ = kLS4, SH = 24;  // (as the kernel above has them for R4)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    constexpr int NL = kStageGroups / T;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t blk = blockIdx.x;
+    const uint32_t tile = (blk & 7u) * H.tiles_per_xcd() + (blk >> 3);
+    if (tile >= H.ntiles()) return;
+    const uint32_t tabs = H.tile_abs0() + tile;
+    const TileDesc *dp = H.ttab() + (tabs < H.ntab() ? tabs : H.ntab() - 1u);
+    uint4 d0;
+    uint32_t d_wrap;  // (the wide tiles mask by group alone: the slice's rows first .. end come with the same load, unused)
+    if constexpr (FLAT) {
+        typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+        u32x8 d;
+        asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(d) : "s"(dp) : "memory");
+        d0 = make_uint4(d[0], d[1], d[2], d[3]);
+        d_wrap = d[5];
+    } else {
+        d0 = *reinterpret_cast<const uint4 *>(dp);
+        d_wrap = dp->g_wrap;
+    }
+    const uint32_t ng = d0.z;
+    if (ng == 0xFFFFFFFFu) {
+        if (tid == 0) atomicOr(A.status, kStatusHugeSlice);
+        return;
+    }
+    const uint4 *src0 = H.rows() + (((uint64_t)d0.y << 32) | d0.x);
+    uint4 V[NL];
+    auto issue = [&](uint32_t batch) {  // (the kernel above says what shaped this)
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+            const uint32_t pg = batch * kStageGroups + (uint32_t)(j * T + wave * 64);
+            uint4 &v = V[j];
+            const uint32_t at = pg + (uint32_t)lane;
+            if constexpr (SP) {
+                if (pg < ng) v = src0[at];
+            } else {
+                v = src0[pg < ng ? at : 0u];
+            }
+        }
+    };
+    issue(0);
+    const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)lds;
+    const int HL = H.hl(), W = H.w();
+    clear_levels<5, T>(lds_base, cell_sentinel<SH>(H.ncols()));  // (3 x 6656 B inside the 20 KiB of five)
+    SixConst C6;
+    C6.km1 = H.km1();
+    C6.status = A.status;
+    C6.ls4 = (uint32_t)(-2 * LSZ);
+    C6.bias4 = (uint32_t)pin_vgpr((int)(lds_base + 4u * (uint32_t)HL + 8u * (uint32_t)LSZ));
+    C6.top_bit = (uint32_t)pin_vgpr((int)0x80000000u);
+    C6.nega = (uint32_t)pin_vgpr((int)((0u - tabs * (uint32_t)W) & 1023u));
+    barrier_lds();  // the level arrays are clear
+
+    const uint32_t nbatch = (ng + kStageGroups - 1) / kStageGroups;
+    for (uint32_t batch = 0; batch == 0 || batch < nbatch; ++batch) {
+        if (batch) issue(batch);
+        const uint32_t gbase = batch * kStageGroups;
+        const uint32_t gleft = ng > gbase ? ng - gbase : 0;
+        r4_pieces<T, NL, AW>(V, lane, wave, gleft, d_wrap > gbase ? d_wrap - gbase : 0u, C6);
+    }
+    barrier_lds();  // (lgkmcnt(0): the ds_min above are invisible to the compiler)
+
+    // fold in registers + store
+    OutT *out = static_cast<OutT *>(A.out);
+    const int cells = HL + W;
+    constexpr int ctx = 3;
+    const int64_t a_rel = (int64_t)tabs * W - A.qs;  // the tile's first position, as an output index
+    const int64_t ob = a_rel - HL;
+    const int64_t o_lo = a_rel + (tile == 0 ? H.x_lo_first() : 0);
+    const int64_t o_hi = a_rel + (tile == H.ntiles() - 1u ? H.x_hi_last() : W);
+    u32x4 L[6];
+    auto lv = [&](int i) { return make_uint4(L[i].x, L[i].y, L[i].z, L[i].w); };
+    auto fold1 = [&](int xr) {
+        read_levels_r4(lds_base + 4u * (uint32_t)xr, L);
+        uint4 M = lv(2), M4 = lv(1);
+        r4_fold12(M4, lv(0));
+        r4_fold4(M, M4);
+        return M;
+    };
+    if constexpr (CH == 0) {
+        fold_store_chunks<OutT, T, SH>(out, ob, o_lo, o_hi, cells, LSZ, lane, wave, Int<ctx>{}, fold1);
+    } else {
+        // The shortened tail.  A wide tile's cells (at most kLS4) are at most two chunks per wave: a wave that has two reads both
+        // chunks' levels before it waits (kChainFold2).  A tile that touches neither edge of the window keeps a lane's quartet iff
+        // it lies right of the left halo -- hl, w and a chunk's first cell are multiples of four, no quartet straddles an end --
+        // and stores it at a scalar base plus the lane's 32-bit cell number (kChainInterior).
+        static_assert(2 * (T / 64) * 4 * (64 - ctx) + 4 * ctx >= kLS4, "a wave of a wide tile: two chunks at the most");
+        const bool edge = (tile == 0 && H.x_lo_first() != 0) || (tile == H.ntiles() - 1u && H.x_hi_last() != W);
+        OutT *const out_b = out + ob;
+        auto fold2 = [&](int xa, int xb, uint4 &Ra, uint4 &Rb) {
+            read_levels_r4x2(lds_base + 4u * (uint32_t)xa, lds_base + 4u * (uint32_t)xb, L);
+            uint4 M4a = lv(1), M4b = lv(4);
+            Ra = lv(2);
+            Rb = lv(5);
+            r4_fold12(M4a, lv(0));
+            r4_fold12(M4b, lv(3));
+            r4_fold4(Ra, M4a);
+            r4_fold4(Rb, M4b);
+        };
+        auto tail = [&](auto store) {
+            fold_chunks_once_or_twice<T, (CH & kChainFold2) != 0>(cells, LSZ, lane, wave, Int<ctx>{}, fold1, fold2, store);
+        };
+        auto store_edge = [&](int x0, uint4 R) { store_cells4<OutT, SH>(out, ob + x0, o_lo, o_hi, R); };
+        if constexpr ((CH & kChainInterior) != 0) {  // (the wave-uniform choice once, in front of two straight tails)
+            if (edge) {
+                tail(store_edge);
+            } else {
+                tail([&](int x0, uint4 R) {
+                    if (x0 >= HL) store_four(out_b + (uint32_t)x0, pack_cells4<OutT, SH>(R));
+                });
+            }
+        } else {
+            tail(store_edge);
+        }
+    }
+}
+
+// The wide tiles' own entry (R4).  The leading parameters are flat scalars -- a struct by value is not preloaded -- in the order
+// of FlatHead: this file is compiled with -amdgpu-kernarg-preload-count=16 (Makefile), and what fits the user SGPRs arrives with
+// the wave instead of by a scalar load (a fallback prologue loads it where the firmware does not preload).  FLAT false: the same
+// tail parts behind the doubling kernels' signature (A/B: memo_tuning.chain_off).
+template <typename OutT, bool AW, bool SP, int CH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void sweep_conservation_wide_kernel(const TileDesc *ttab, const uint4 *rows, uint32_t ntiles, uint32_t tiles_per_xcd, uint32_t tile_abs0,
+                                    uint32_t ntab, int hl, int w, int km1, int ncols, int x_lo_first, int x_hi_last, const SweepArgs A) {
+    const FlatHead H = {ttab, rows, ntiles, tiles_per_xcd, tile_abs0, ntab, hl, w, km1, ncols, x_lo_first, x_hi_last};
+    wide_tile<OutT, AW, SP, CH>(A, H);
+}
+
+template <typename OutT, bool AW, bool SP, int CH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void sweep_conservation_wide_args_kernel(const SweepArgs A) {
+    wide_tile<OutT, AW, SP, CH>(A, ArgsHead{A});
+}
+
 }  // namespace
 
 namespace memo {
@@ -329,6 +529,9 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     // 0.203 ms at k = 31, 0.168 against 0.154 at k = 17) and 1-4 % slower on all the rows; profiles/r03_views.txt.  Sixteen
     // waves per CU hide the scatter's LDS latency worse than thirty-two, whatever they save in instructions.)
     const bool sp = groups_per_tile(tw) < 768.0;
+    // the wide tiles' shortened chain, part by part (memo_tuning.chain_off: all of it in the product)
+    const bool flat = r4 && !(ix->tune.chain_off & 1);
+    const int chain = r4 ? (~ix->tune.chain_off >> 1) & (kChainFold2 | kChainInterior) : 0;
     SweepKernel kern = pick_int<1, 2, 3, 4, 5, 6>(A.nlev, [&](auto N) {
         return pick_bool(all_write, [&](auto AW) {
             return pick_bool(sp, [&](auto SP) -> SweepKernel {
@@ -337,7 +540,15 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
                 auto of = [&](auto O) -> SweepKernel {
                     using OutT = typename decltype(O)::type;
                     if constexpr (decltype(N)::value == 5) {
-                        if (r4) return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, 256, false, AW, true, SP, false, true>;
+                        if (r4)  // (the flat entry goes through the picker under the doubling kernels' type: cast back at the launch)
+                            return pick_int<0, 1, 2, 3>(chain, [&](auto CH) -> SweepKernel {
+                                if (flat) return reinterpret_cast<SweepKernel>(reinterpret_cast<void (*)()>(sweep_conservation_wide_kernel<OutT, AW, SP, CH>));
+                                if constexpr (decltype(CH)::value == 0) {
+                                    return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, 256, false, AW, true, SP, false, true>;
+                                } else {
+                                    return (SweepKernel)sweep_conservation_wide_args_kernel<OutT, AW, SP, CH>;
+                                }
+                            });
                     }
                     if constexpr (decltype(N)::value <= 5) {
                         if (six)
@@ -355,7 +566,16 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     ix->last_tile_w = tw;
     if (g_prepare_only) return MEMO_OK;  // memo_index_prepare: the table is built, nothing is launched
     if (int prc = refuse_plan_pointer(A.out)) return prc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(A.tiles_per_xcd * 8)), dim3(256), (size_t)A.nlev * 4096, st, A);
+    if (flat) {  // (launch_halo3t's own checks above: the four counts fit 32 bits)
+        using WideKernel = void (*)(const TileDesc *, const uint4 *, uint32_t, uint32_t, uint32_t, uint32_t, int, int, int, int, int, int,
+                                    const SweepArgs);
+        hipLaunchKernelGGL(reinterpret_cast<WideKernel>(reinterpret_cast<void (*)()>(kern)), dim3((unsigned)(A.tiles_per_xcd * 8)), dim3(256), (size_t)A.nlev * 4096, st,
+                           static_cast<const TileDesc *>(A.ttab), reinterpret_cast<const uint4 *>(A.p3), (uint32_t)A.ntiles,
+                           (uint32_t)A.tiles_per_xcd, (uint32_t)A.tile_abs0, (uint32_t)A.ntab, A.hl, A.w, A.km1, A.ncols, A.x_lo_first,
+                           A.x_hi_last, A);
+    } else {
+        hipLaunchKernelGGL(kern, dim3((unsigned)(A.tiles_per_xcd * 8)), dim3(256), (size_t)A.nlev * 4096, st, A);
+    }
     HIP_TRY(hipGetLastError());
     return MEMO_OK;
 }

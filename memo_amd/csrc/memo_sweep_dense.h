@@ -394,7 +394,13 @@ __device__ __forceinline__ void read_levels_r4(uint32_t addr, u32x4 (&L)[6]) {
     asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %3 offset:6656\n\tds_read_b128 %2, %3 offset:13312\n\ts_waitcnt lgkmcnt(0)"
                  : "=&v"(L[0]), "=&v"(L[1]), "=&v"(L[2]) : "v"(addr) : "memory");
 }
-static_assert(kLS4 * 4 == 6656, "read_levels_r4: the arrays' offsets");
+// the same at two cells -- a wave's two fold chunks -- in L[0 .. 2] and L[3 .. 5]: six reads in flight, one wait
+__device__ __forceinline__ void read_levels_r4x2(uint32_t addr_a, uint32_t addr_b, u32x4 (&L)[6]) {
+    asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:6656\n\tds_read_b128 %2, %6 offset:13312\n\t"
+                 "ds_read_b128 %3, %7\n\tds_read_b128 %4, %7 offset:6656\n\tds_read_b128 %5, %7 offset:13312\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(L[0]), "=&v"(L[1]), "=&v"(L[2]), "=&v"(L[3]), "=&v"(L[4]), "=&v"(L[5]) : "v"(addr_a), "v"(addr_b) : "memory");
+}
+static_assert(kLS4 * 4 == 6656, "read_levels_r4, read_levels_r4x2: the arrays' offsets");
 
 // the J-th group of a lane, already in registers (MODE 1 / 2)
 template <int J, int T = 256, bool A9 = false, bool AW = false>

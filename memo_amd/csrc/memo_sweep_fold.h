@@ -80,9 +80,13 @@ __device__ __forceinline__ void r4_fold4(uint4 &R, uint4 M) {
 // What every level cell starts at: the sentinel column N (memo_query.py:53-54).  TOP != 0: the cells hold whole row words whose bits
 // from TOP up are the order -- the sentinel on top, all ones below it.
 template <int TOP>
-__device__ __forceinline__ uint32_t cell_sentinel(const SweepArgs &A) {
-    const uint32_t sent = (uint32_t)(A.ncols - 1);
+__device__ __forceinline__ uint32_t cell_sentinel(int ncols) {
+    const uint32_t sent = (uint32_t)(ncols - 1);
     return TOP ? (sent << TOP) | ((1u << TOP) - 1u) : sent;
+}
+template <int TOP>
+__device__ __forceinline__ uint32_t cell_sentinel(const SweepArgs &A) {
+    return cell_sentinel<TOP>(A.ncols);
 }
 
 // A lane's four cells to results g .. g + 3 of the window [o_lo, o_hi): one store for a whole quartet (at whatever address the window's
@@ -116,6 +120,34 @@ __device__ __forceinline__ void fold_store_chunks(OutT *out, int64_t ob, int64_t
         const uint4 R = fold(min(x0, LS - 4));
         if (lane < ctx || x0 >= cells) continue;
         store_cells4<OutT, TOP>(out, ob + x0, o_lo, o_hi, R);
+    }
+}
+
+// The same walk for a kernel whose waves have at most two chunks (the wide tiles of memo_sweep_cons3t.hip), with the store handed in:
+// store(x0, R) gets the four folded cells of every lane that is no context lane and lies inside the cells in use.  TWO: a wave with
+// two chunks has both in flight -- fold2(xa, xb, Ra, Rb) reads both chunks' levels, waits once and folds both (the chunks share no
+// cell a fold writes; the LDS round trip of the second is not paid behind the first's fold and store).  A wave with one chunk, and
+// every wave without TWO, goes chunk by chunk through fold1 as above.
+template <int T, bool TWO, typename Ctx, typename Fold1, typename Fold2, typename Store>
+__device__ __forceinline__ void fold_chunks_once_or_twice(int cells, int LS, int lane, int wave, Ctx ctx, Fold1 fold1, Fold2 fold2,
+                                                          Store store) {
+    constexpr int NW = T / 64;
+    const int valid = 64 - ctx, step = NW * 4 * valid;
+    const int base = wave * 4 * valid;
+    if (TWO && base + step + 4 * ctx < cells) {  // (wave-uniform.  Both chunks begin inside the array; only the second can leave it)
+        const int x0 = base + 4 * lane, x1 = x0 + step;
+        uint4 Ra, Rb;
+        fold2(x0, min(x1, LS - 4), Ra, Rb);
+        if (lane < ctx) return;
+        store(x0, Ra);
+        if (x1 < cells) store(x1, Rb);
+        return;
+    }
+    for (int b = base; b + 4 * ctx < cells; b += step) {
+        const int x0 = b + 4 * lane;
+        const uint4 R = fold1(min(x0, LS - 4));
+        if (lane < ctx || x0 >= cells) continue;
+        store(x0, R);
     }
 }
 

@@ -11,7 +11,7 @@ CXX="-O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -I../../include"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $CXX $FLAGS -c memo_sweep_memb.hip -o /tmp/memb_$NAME.o &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $CXX $FLAGS -c memo_sweep.hip -o /tmp/sweep_$NAME.o &      # (fill_args, the stamp buffer)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $CXX $FLAGS -c memo_debug.hip -o /tmp/debug_$NAME.o &
-/opt/rocm/bin/hipcc --offload-arch=gfx950 $CXX $FLAGS -c memo_sweep_cons3t.hip -o /tmp/cons3t_$NAME.o &
+/opt/rocm/bin/hipcc --offload-arch=gfx950 $CXX $FLAGS -mllvm -amdgpu-kernarg-preload-count=16 -c memo_sweep_cons3t.hip -o /tmp/cons3t_$NAME.o &
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../libmemo_amd_${NAME}_ab.so \
   /tmp/sweep_$NAME.o /tmp/cons_$NAME.o /tmp/cons3t_$NAME.o /tmp/memb_$NAME.o memo_interleave.o memo_view.o memo_view_build.o memo_index.o memo_oneshot.o memo_hostpack.o memo_hostcore.o memo_multi.o memo_transport.o memo_sort.o memo_dap.o memo_ms.o memo_emit.o /tmp/debug_$NAME.o

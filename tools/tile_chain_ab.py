@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""A/B of the parts of the wide-tile sweep's shortened chain (memo_sweep_cons3t.hip: sweep_conservation_wide_kernel) on config 3's live
+copy, inside ONE library: memo_debug_set_tuning's scatter bits 8 .. 10 switch parts OFF (256 the entry whose head arrives in registers,
+512 both fold chunks in flight, 1024 the store without the window test in interior tiles); all three off is the kernel as it was before
+them.  Per k the class's view and its copy are built first; then, per round and variant, `--launches` whole-window uint8 launches back
+to back, each between a HIP event pair; the median of the last `--keep`.  Variants alternate `--reps` times on the same index.  Needs
+libmemo_amd_ab.so.  GPU box."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VARIANTS = (("none (the kernel before)", 7), ("head", 6), ("fold", 5), ("store", 3), ("head + fold", 4), ("all", 0))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ks", default="31")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--launches", type=int, default=600)
+    ap.add_argument("--keep", type=int, default=400)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from memo_amd import _lib, synth
+    _lib.use_ab()
+    num_docs, L = 100, 100_000_000
+    out = torch.empty(L, dtype=torch.uint8, device="cuda:0")
+    first = None
+    stream = torch.cuda.current_stream()
+    ix, _ = synth.device_index(0, L, 31, num_docs, L, pack="dense")
+
+    def one(k):
+        ix.conservation_u8_dev(0, L, k, num_docs, out, stream.cuda_stream)
+
+    with ix:
+        ix.set_option(3, 0)                       # MEMO_OPT_BUILD_COST_PCT: the first query of a class builds
+        for k in [int(x) for x in a.ks.split(",")]:
+            ix.prepare(k, num_docs)
+            for _ in range(3):                    # (the view, its places, the copy)
+                one(k)
+            torch.cuda.synchronize()
+            first = None
+            for rep in range(a.reps):
+                for name, off in VARIANTS:
+                    ix.debug_set_tuning(scatter=off << 8)
+                    one(k)
+                    torch.cuda.synchronize()
+                    same = True
+                    if first is None:
+                        first = out.clone()
+                    else:
+                        same = bool(torch.equal(first, out))
+                    inf = ix.info()
+                    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.launches)]
+                    for e0, e1 in ev:
+                        e0.record(stream)
+                        one(k)
+                        e1.record(stream)
+                    torch.cuda.synchronize()
+                    ms = [e0.elapsed_time(e1) for e0, e1 in ev][-a.keep:]
+                    print(json.dumps({"k": k, "rep": rep, "parts": name, "off_mask": off, "ms": round(float(np.median(ms)), 5),
+                                      "tile_width": inf["last_tile_width"], "variant": inf["last_variant"],
+                                      "same_bytes_as_first": same}), flush=True)
+            ix.debug_set_tuning()
+
+
+if __name__ == "__main__":
+    main()
