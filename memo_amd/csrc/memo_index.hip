@@ -662,7 +662,9 @@ int memo_index_pack(memo_index_t *ix, int32_t keep_wide) {
         ix->max_annot = h[5];
         if (fmt != 6) ix->pa.reset();  // (only format 6 has the annot column)
         ix->row_order = 0;
-        if (const int mode = row_order_mode(ix); mode && (fmt == 4 || fmt == 12) && ix->rows) {  // the order inside a bucket (memo_interleave.hip)
+        int mode = row_order_mode(ix);
+        if (mode == 3 && ix->bshift != 5) mode = 2;  // (what interleave_words makes of it, and order_words_now records)
+        if (mode && (fmt == 4 || fmt == 12) && ix->rows) {  // the order inside a bucket (memo_interleave.hip)
             if (int r = interleave_words(ix->pk, ix->boff, ix->nb, ix->bshift, fmt, mode, st, ix->d_scratch)) return r;
             ix->row_order = mode;
         }
