@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions` and the matrix of `memo matrix`: off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix` and the lengths of `memo maxk`: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -214,6 +214,32 @@ int32_t memo_cooccurrence_tile(int32_t words);
  * [qe - qs][W].  Queued on `stream` as memo_query_membership_dev queues it; check with memo_query_check. */
 int memo_query_membership_slice_dev(memo_index_t *ix, int64_t whole_qs, int64_t whole_qe, int64_t qs, int64_t qe, int32_t k,
                                     int32_t num_docs, uint32_t *d_out, void *stream);
+
+/* ---- `memo maxk`: the longest shared k-mer per position, every k in one pass (no counterpart in the reference) ----------
+ * (Declared here, beside the `memo matrix` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * For the window [qs, qs + L), a cap CAP in [1, 2^31 - 1] and a row predicate -- mode 0: 0 <= annot < arg ("fewer than arg genomes
+ * share it": a conservation index, arg = T), mode 1: annot == arg (a membership index, arg = the genome) --
+ *     out[p - qs] = min( CAP, max( 0, min{ end_i - p : pred(annot_i), p < start_i, qs < start_i < qs + L + CAP } ) )       uint32
+ * and CAP where no row bounds p.  For rows with end >= start: conservation(p, k) >= T, or bit G of the membership row of p, holds
+ * exactly when k <= out[p - qs] (for k <= CAP).  Rows with end < start are legal and take the formula literally (the result can be
+ * 0); for them equality with a per-k query is NOT promised.  annot is compared as the int64 it is.  Rows with start <= qs or
+ * start >= qs + L + CAP are ignored by the kernel itself, whatever the caller passes; rows need not be sorted.
+ *
+ * d_cells is uint32 [L] on `device`, 16-byte aligned; the columns are device pointers, 8-byte aligned (MEMO_EINVAL otherwise, before
+ * anything is launched; so are L > 2^31, CAP = 0 or above 2^31 - 1, |qs| > 2^61).  begin fills the cells with the identity
+ * L - 1 + CAP; rows accumulates one chunk of rows into them (atomic min: any number of calls, any cut, any order -- the same cells);
+ * finish turns the cells into out[] in place (scratch: 4 bytes per memo_maxk_tile() cells, freed before it returns; an allocation
+ * that fails is MEMO_EHIP with the bytes asked for).  The same L and CAP go to all three.  L == 0 or rows == 0 launches nothing.
+ * Nothing is read outside the `rows` elements of each column or outside d_cells[0 .. L).  Blocking (each synchronises `stream`). */
+int memo_maxk_begin_dev(uint32_t *d_cells, int64_t L, uint32_t cap, int32_t device, void *stream);
+int memo_maxk_rows_dev(const int64_t *d_start, const int64_t *d_end, const int64_t *d_annot, uint64_t rows, int64_t qs, int64_t L,
+                       uint32_t cap, int32_t mode, int64_t arg, uint32_t *d_cells, int32_t device, void *stream);
+int memo_maxk_finish_dev(uint32_t *d_cells, int64_t L, uint32_t cap, int32_t device, void *stream);
+/* cells per tile of finish's scan, for tests that want lengths around it */
+int32_t memo_maxk_tile(void);
+/* the text of `memo maxk`: one decimal integer and '\n' per position; L <= 0 is no text at all.  Returns the number of bytes the
+ * text needs; it is written only if it fits in cap (nothing is written past cap). */
+size_t memo_emit_u32(const uint32_t *vec, int64_t L, char *buf, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -99,6 +99,14 @@ int memo_debug_cooc_flush(int32_t way);
  * or do not (0); out2 (may be NULL) receives the device milliseconds of the last timed call: [0] the sweep launches, [1] the
  * reduce launches (0 with atomics: the flush is part of the sweep).  tools/matrix_timing.py reads them. */
 int memo_debug_cooc_times(int32_t on, float *out2);
+/* this THREAD's later memo_maxk_rows_dev calls: how the rows' bounds reach the cells: 0 (the default, the product's way) =
+ * wave-aggregated: a segmented min over the lanes that hit the same cell leaves one atomic min per run of equal cells and wave,
+ * 1 = one atomic min per row (the A/B of DESIGN.md 10.5).  The cells are the same either way. */
+int memo_debug_maxk_rows(int32_t way);
+/* this THREAD's later memo_maxk_*_dev calls put event pairs around their launches (on = 1; each launch is then waited for) or do
+ * not (0); out5 (may be NULL) receives the device milliseconds of the last timed launch of each kind: [0] the fill of begin, [1] the
+ * row pass, [2] the tile minima, [3] their scan, [4] the apply launch of finish.  tools/maxk_timing.py reads them. */
+int memo_debug_maxk_times(int32_t on, float *out5);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,8 @@ Layout (only what the path needs):
   regions_cli.py   `memo regions`: flags, usage, bedGraph / BED3 / BED + membership string
   matrix.py        `memo matrix`: a membership result's co-occurrence matrix counted on the GPU, a window's in slices
   matrix_cli.py    `memo matrix`: flags, usage, counts or Jaccard distances as tab-separated text
+  maxk.py          `memo maxk`: the longest shared k per position, all k in one pass over the rows, a window's from a Parquet index
+  maxk_cli.py      `memo maxk`: flags, usage, one integer per line
 
 Attributes are loaded on first use (PEP 562), so that `import memo_amd._fastquery` -- the CLI's cache-hit
 path -- does not pay for NumPy.
@@ -31,6 +33,7 @@ _LAZY = {
     "emit_conservation": "index", "emit_membership": "index",
     "runs": "regions", "membership_runs": "regions", "region_runs": "regions",
     "cooccurrence": "matrix", "region_matrix": "matrix",
+    "region_maxk": "maxk", "index_maxk": "maxk",          # (maxk.maxk keeps its module's name: memo_amd.maxk is the module)
 }
 
 
@@ -40,7 +43,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "maxk", "maxk_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

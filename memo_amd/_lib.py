@@ -122,6 +122,11 @@ SYMBOLS = {
     "memo_cooccurrence_dev": (C.c_int, [_P, _I64, _I32, _P, _I32, _P]),
     "memo_cooccurrence_tile": (_I32, [_I32]),
     "memo_query_membership_slice_dev": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _I32, _P, _P]),
+    "memo_maxk_begin_dev": (C.c_int, [_P, _I64, C.c_uint32, _I32, _P]),
+    "memo_maxk_rows_dev": (C.c_int, [_P, _P, _P, _U64, _I64, _I64, C.c_uint32, _I32, _I64, _P, _I32, _P]),
+    "memo_maxk_finish_dev": (C.c_int, [_P, _I64, C.c_uint32, _I32, _P]),
+    "memo_maxk_tile": (_I32, []),
+    "memo_emit_u32": (_SZ, [_P, _I64, _P, _SZ]),
     "memo_emit_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _P, _SZ]),
     "memo_emit_membership_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _I32, _P, _SZ]),
     "memo_parse_conservation_text_dev": (C.c_int, [_P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(_I64), _I32, _P]),
@@ -186,6 +191,8 @@ DEBUG_SYMBOLS = {
     "memo_debug_ms_free_bytes": (C.c_int, [_I64]),
     "memo_debug_cooc_flush": (C.c_int, [_I32]),
     "memo_debug_cooc_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
+    "memo_debug_maxk_rows": (C.c_int, [_I32]),
+    "memo_debug_maxk_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_ms_piece_text": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _I64, C.POINTER(_I64)]),
 }
 

@@ -160,4 +160,17 @@ int memo_debug_cooc_times(int32_t on, float *out2) {
     return MEMO_OK;
 }
 
+int memo_debug_maxk_rows(int32_t way) {
+    if (way < 0 || way > 1) return fail(MEMO_EINVAL, "maxk row pass: 0 wave-aggregated atomics, 1 one atomic per row");
+    g_maxk_rows_way = way;
+    return MEMO_OK;
+}
+
+int memo_debug_maxk_times(int32_t on, float *out5) {
+    g_maxk_timed = on ? 1 : 0;
+    if (out5)
+        for (int i = 0; i < 5; ++i) out5[i] = g_maxk_ms[i];
+    return MEMO_OK;
+}
+
 }  // extern "C"

@@ -272,4 +272,14 @@ size_t memo_emit_membership_runs(const char *record, int64_t qs, int64_t L, cons
                       });
 }
 
+// ---- `memo maxk`: one unsigned integer per line (include/memo_amd_dap.h); no line at all for an empty vector ----
+size_t memo_emit_u32(const uint32_t *vec, int64_t L, char *buf, size_t cap) {
+    return emit_lines(L, 1 << 20, buf, cap, [&](int64_t i) { return digits((long long)vec[i]) + 1; },
+                      [&](char *p, int64_t i) {
+                          p = put(p, (long long)vec[i]);
+                          *p++ = '\n';
+                          return p;
+                      });
+}
+
 }  // extern "C"
