@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix` and the lengths of `memo maxk`: off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix`, the curves of `memo collect` and the lengths of `memo maxk`: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -214,6 +214,25 @@ int32_t memo_cooccurrence_tile(int32_t words);
  * [qe - qs][W].  Queued on `stream` as memo_query_membership_dev queues it; check with memo_query_check. */
 int memo_query_membership_slice_dev(memo_index_t *ix, int64_t whole_qs, int64_t whole_qe, int64_t qs, int64_t qe, int32_t k,
                                     int32_t num_docs, uint32_t *d_out, void *stream);
+
+/* ---- `memo collect`: core and covered k-mer curves over genome orders (no counterpart in the reference) ----------------
+ * (Declared here, beside the `memo matrix` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The collector's curves of a membership result that is still on `device` (memo_amd/csrc/memo_collect.hip): d_bits as
+ * memo_cooccurrence_dev takes it (uint32 [L][W], 16-byte aligned, read from [0] to [L * W) and nowhere else, bits at or above
+ * num_docs masked).  orders_host is a HOST pointer, uint16 [num_orders][steps], every entry a genome id below num_docs; repeats and
+ * genome 0 are legal.  For order q and step j
+ *     d_core   [q][j] += #{p : bit orders[q][i] of row p is set for every i <= j}
+ *     d_covered[q][j] += #{p : bit orders[q][i] of row p is set for some  i <= j}          uint64 [num_orders][steps] on `device`
+ * ADDED to (the caller zeroes them; several windows or slices accumulate).  MEMO_EINVAL before anything is launched: d_bits not
+ * 16-byte aligned, an entry >= num_docs, steps outside [1, num_docs], num_orders outside [0, 65535], num_docs outside [1, 2048],
+ * an output that is NULL or not 8-byte aligned.  L == 0 or num_orders == 0 launches nothing and leaves the outputs as they were.
+ * The library uploads the orders itself.  Scratch memory on the device: the orders and at most 64 MiB, freed before the call
+ * returns; an allocation that fails returns MEMO_EHIP with the bytes asked for in memo_last_error and leaves nothing allocated.
+ * Blocking. */
+int memo_collect_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, const uint16_t *orders_host, int32_t num_orders, int32_t steps,
+                     uint64_t *d_core, uint64_t *d_covered, int32_t device, void *stream);
+/* positions per tile at `words` genome words (512 up to 16 words, 256 up to 32, 128 above), for tests that want lengths around it */
+int32_t memo_collect_tile(int32_t words);
 
 /* ---- `memo maxk`: the longest shared k-mer per position, every k in one pass (no counterpart in the reference) ----------
  * (Declared here, beside the `memo matrix` block: memo_amd.h keeps to the query path's 44 entry points.)

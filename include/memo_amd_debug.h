@@ -107,6 +107,10 @@ int memo_debug_maxk_rows(int32_t way);
  * not (0); out5 (may be NULL) receives the device milliseconds of the last timed launch of each kind: [0] the fill of begin, [1] the
  * row pass, [2] the tile minima, [3] their scan, [4] the apply launch of finish.  tools/maxk_timing.py reads them. */
 int memo_debug_maxk_times(int32_t on, float *out5);
+/* this THREAD's later memo_collect_dev calls put event pairs around their launches (on = 1; each launch is then waited for) or do
+ * not (0); out2 (may be NULL) receives the device milliseconds of the last timed call: [0] the sweep launches, [1] the reduce
+ * launches.  tools/collect_timing.py reads them. */
+int memo_debug_collect_times(int32_t on, float *out2);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,8 @@ Layout (only what the path needs):
   regions_cli.py   `memo regions`: flags, usage, bedGraph / BED3 / BED + membership string
   matrix.py        `memo matrix`: a membership result's co-occurrence matrix counted on the GPU, a window's in slices
   matrix_cli.py    `memo matrix`: flags, usage, counts or Jaccard distances as tab-separated text
+  collect.py       `memo collect`: core and covered k-mer curves over genome orders, reduced on the GPU, a window's in slices
+  collect_cli.py   `memo collect`: flags, usage, the curve, the band over random orders or every order as tab-separated text
   maxk.py          `memo maxk`: the longest shared k per position, all k in one pass over the rows, a window's from a Parquet index
   maxk_cli.py      `memo maxk`: flags, usage, one integer per line
 
@@ -33,6 +35,7 @@ _LAZY = {
     "emit_conservation": "index", "emit_membership": "index",
     "runs": "regions", "membership_runs": "regions", "region_runs": "regions",
     "cooccurrence": "matrix", "region_matrix": "matrix",
+    "region_curves": "collect",
     "region_maxk": "maxk", "index_maxk": "maxk",          # (maxk.maxk keeps its module's name: memo_amd.maxk is the module)
 }
 
@@ -43,7 +46,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "maxk", "maxk_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

@@ -13,7 +13,7 @@
 //
 // One tile = 512 positions = 16 position words.  Per tile a workgroup
 //   1. stages: one lane per (staged genome word s, position word P) loads the 32 row words of its 32 x 32 block, masks the bits at
-//      or above num_docs, transposes the block in registers (transpose32: memo_sweep_memb.hip's, copied) and writes the 32 plane
+//      or above num_docs, transposes the block in registers (transpose32: memo_planes.h, shared with memo_collect.hip) and writes the 32 plane
 //      words -- plane[P][genome] holds 32 positions of one genome -- to LDS with eight 16-byte stores.  A block is 36 words apart
 //      from the next and a position word's row 36 x staged + 4: the 16-byte stores of the lanes then fall on all banks alike.
 //      A triangle workgroup stages only the words up to that of its largest b.
@@ -41,7 +41,7 @@
 // accumulate a window slice by slice (memo_amd/matrix.py: region_matrix) and get the window's matrix.
 #include <algorithm>
 
-#include "memo_common.h"
+#include "memo_planes.h"
 
 using namespace memo;
 
@@ -55,7 +55,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kTile = 512, kPW = kTile / 32;  // positions per tile, its position words
-constexpr int kBlockPitch = 36;               // LDS words from one staged genome word to the next
+constexpr int kBlockPitch = kPlaneBlockPitch;  // LDS words from one staged genome word to the next
 constexpr int kMaxStaged = 16;                // genome words a launch stages at most (both chunks together)
 constexpr int kMaxGridX = 1024;               // workgroups along the positions at most
 constexpr size_t kScratchCap = (size_t)64 << 20;
@@ -71,37 +71,6 @@ struct CoocArgs {
     uint32_t *partials;      // nullptr: atomics
     uint64_t *counts;
 };
-
-// (memo_sweep_memb.hip's transpose32, copied: that file's generated code stays as it is)
-template <int J>
-__device__ __forceinline__ void transpose32_stage(uint32_t (&m)[32]) {
-    constexpr uint32_t mask = J == 4 ? 0x0F0F0F0Fu : J == 2 ? 0x33333333u : 0x55555555u;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        if ((k & J) == 0) {
-            const uint32_t a = m[k], b = m[k + J];
-            if (J == 16) {
-                m[k] = __builtin_amdgcn_perm(b, a, 0x05040100u);      // a.lo16 | b.lo16 << 16
-                m[k + J] = __builtin_amdgcn_perm(b, a, 0x07060302u);  // a.hi16 | b.hi16 << 16
-            } else if (J == 8) {
-                m[k] = __builtin_amdgcn_perm(b, a, 0x06020400u);      // bytes a0 b0 a2 b2
-                m[k + J] = __builtin_amdgcn_perm(b, a, 0x07030501u);  // bytes a1 b1 a3 b3
-            } else {
-                const uint32_t bs = b << J, as = a >> J;
-                asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(m[k]) : "s"(mask), "v"(a), "v"(bs));
-                asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(m[k + J]) : "s"(mask), "v"(as), "v"(b));
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void transpose32(uint32_t (&m)[32]) {  // m[j] bit i  <-  m[i] bit j
-    transpose32_stage<16>(m);
-    transpose32_stage<8>(m);
-    transpose32_stage<4>(m);
-    transpose32_stage<2>(m);
-    transpose32_stage<1>(m);
-}
 
 // the two groups of unit u (u < A.units)
 __device__ __forceinline__ void unit_groups(const CoocArgs &A, int u, int &a, int &b) {

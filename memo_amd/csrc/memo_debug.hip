@@ -173,4 +173,10 @@ int memo_debug_maxk_times(int32_t on, float *out5) {
     return MEMO_OK;
 }
 
+int memo_debug_collect_times(int32_t on, float *out2) {
+    g_collect_timed = on ? 1 : 0;
+    if (out2) out2[0] = g_collect_ms[0], out2[1] = g_collect_ms[1];
+    return MEMO_OK;
+}
+
 }  // extern "C"
