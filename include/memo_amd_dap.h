@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix`, the curves of `memo collect` and the lengths of `memo maxk`: off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix`, the curves of `memo collect`, the lengths of `memo maxk` and the per-genome lengths of `memo lengths`: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -259,6 +259,53 @@ int32_t memo_maxk_tile(void);
 /* the text of `memo maxk`: one decimal integer and '\n' per position; L <= 0 is no text at all.  Returns the number of bytes the
  * text needs; it is written only if it fits in cap (nothing is written past cap). */
 size_t memo_emit_u32(const uint32_t *vec, int64_t L, char *buf, size_t cap);
+
+/* ---- `memo lengths`: every genome's match length from a membership index, and the T-th largest (no counterpart in the reference) ----
+ * (Declared here, beside the `memo maxk` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * For the window [qs, qs + L), num_docs = N genomes in [1, 2048] and a cap CAP in [1, 2^31 - 1] (memo_amd/csrc/memo_lengths.hip)
+ *     len[g][p - qs] = min( CAP, max( 0, min{ end_i - p : annot_i = g, p < start_i, qs < start_i < qs + L + CAP } ) )     0 <= g < N
+ *     sel_T[p - qs]  = the T-th largest of { len[g][p - qs] : 0 <= g < N }                                                  1 <= T <= N
+ * and CAP where no row bounds p: len[g] is what the memo_maxk_*_dev calls give in mode 1 with arg = g, for every g in one pass over
+ * the rows.  For rows with end >= start and k <= CAP: bit g of the membership row of p is set exactly when k <= len[g][p - qs], and
+ * that row has at least T bits set exactly when k <= sel_T[p - qs].  Rows with end < start take the formula literally.  Rows whose
+ * annot is outside [0, N) are ignored; rows need not be sorted.
+ *
+ * d_cells is uint32 [N][pitch] on `device`, genome-major: 16-byte aligned, pitch a multiple of 4 and at least L, N * pitch below 2^32.
+ * The cells [L, pitch) of a plane are never read or written.  MEMO_EINVAL before anything is launched: the above, N outside [1, 2048],
+ * L > 2^31, CAP = 0 or above 2^31 - 1, |qs| > 2^61, columns or a carry that are not 8-byte aligned, a threshold outside [1, N], a
+ * d_out that is not 4-byte aligned.  L == 0 or rows == 0 launches nothing.  Nothing is read outside the `rows` elements of each
+ * column.  Blocking (each call synchronises `stream`).
+ *   begin   fills [0, L) of every plane with the identity L - 1 + CAP; with d_carry (int64 [N] on the device, INT64_MAX: none; NULL:
+ *           no carry) cell L - 1 of plane g then holds carry[g] relative to qs, as if a row with that end started right of the window
+ *   rows    accumulates one chunk of rows into the planes (one atomic min per row: any number of calls, any cut, any order, repeats)
+ *   carry   d_carry[annot] = min(d_carry[annot], end) over the rows with lo < start < hi and 0 <= annot < N (the caller fills d_carry
+ *           with INT64_MAX first).  With it a window runs in slices from the right, every row read once: seed the carry with the rows
+ *           qe < start < qe + CAP; then for every slice [a, b): begin(qs = a, L = b - a, d_carry), rows with the rows a < start <= b,
+ *           carry(lo = a, hi = b + 1) with the same rows, finish.  The planes of the slices laid end to end are the window's.
+ *   finish  turns the cells into len[][] in place (scratch: 4 bytes per memo_lengths_tile() cells and plane, freed before it returns;
+ *           an allocation that fails is MEMO_EHIP with the bytes asked for)
+ *   select  d_out[i] = the threshold-th largest over g of min(d_cells[g][i], CAP), uint32 [L]; d_cells is not changed.  LDS: N rows of
+ *           memo_lengths_select_tile(N) positions (with the kernel's static words at most 120 KiB). */
+int memo_lengths_begin_dev(uint32_t *d_cells, int64_t L, int64_t pitch, int32_t num_docs, uint32_t cap, int64_t qs, const int64_t *d_carry,
+                           int32_t device, void *stream);
+int memo_lengths_rows_dev(const int64_t *d_start, const int64_t *d_end, const int64_t *d_annot, uint64_t rows, int64_t qs, int64_t L,
+                          int64_t pitch, int32_t num_docs, uint32_t cap, uint32_t *d_cells, int32_t device, void *stream);
+int memo_lengths_carry_dev(const int64_t *d_start, const int64_t *d_end, const int64_t *d_annot, uint64_t rows, int64_t lo, int64_t hi,
+                           int32_t num_docs, int64_t *d_carry, int32_t device, void *stream);
+int memo_lengths_finish_dev(uint32_t *d_cells, int64_t L, int64_t pitch, int32_t num_docs, uint32_t cap, int32_t device, void *stream);
+int memo_lengths_select_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t num_docs, uint32_t cap, int32_t threshold,
+                            uint32_t *d_out, int32_t device, void *stream);
+/* cells per tile of finish's scan, and positions per tile of select at num_docs genomes (256, 128 ... 8; 0: num_docs outside
+ * [1, 2048]), for tests that want lengths around them */
+int32_t memo_lengths_tile(void);
+int32_t memo_lengths_select_tile(int32_t num_docs);
+/* the text of `memo lengths -a`, HOST planes in (uint32 [n][pitch], genome-major; [0, L) of each is read): line p is
+ * planes[0][p] ... planes[n - 1][p], blank-separated, and '\n'; L <= 0 or n <= 0 is no text at all.  Returns the number of bytes the text
+ * needs; it is written only if it fits in cap (nothing is written past cap). */
+size_t memo_emit_u32_rows(const uint32_t *planes, int64_t L, int64_t pitch, int32_t n, char *buf, size_t cap);
+/* the threads memo_emit_u32_rows splits the lines of that shape over (one per 2^20 integers, at most the process's CPU budget or
+ * MEMO_EMIT_THREADS, read per call; 0 for an empty text), for tests that want the threaded path and must know that they got it */
+int32_t memo_emit_u32_rows_threads(int64_t L, int32_t n);
 
 #ifdef __cplusplus
 }

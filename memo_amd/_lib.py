@@ -129,6 +129,15 @@ SYMBOLS = {
     "memo_maxk_finish_dev": (C.c_int, [_P, _I64, C.c_uint32, _I32, _P]),
     "memo_maxk_tile": (_I32, []),
     "memo_emit_u32": (_SZ, [_P, _I64, _P, _SZ]),
+    "memo_lengths_begin_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, _I64, _P, _I32, _P]),
+    "memo_lengths_rows_dev": (C.c_int, [_P, _P, _P, _U64, _I64, _I64, _I64, _I32, C.c_uint32, _P, _I32, _P]),
+    "memo_lengths_carry_dev": (C.c_int, [_P, _P, _P, _U64, _I64, _I64, _I32, _P, _I32, _P]),
+    "memo_lengths_finish_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, _I32, _P]),
+    "memo_lengths_select_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, _I32, _P, _I32, _P]),
+    "memo_lengths_tile": (_I32, []),
+    "memo_lengths_select_tile": (_I32, [_I32]),
+    "memo_emit_u32_rows": (_SZ, [_P, _I64, _I64, _I32, _P, _SZ]),
+    "memo_emit_u32_rows_threads": (_I32, [_I64, _I32]),
     "memo_emit_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _P, _SZ]),
     "memo_emit_membership_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _I32, _P, _SZ]),
     "memo_parse_conservation_text_dev": (C.c_int, [_P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(_I64), _I32, _P]),
@@ -196,6 +205,7 @@ DEBUG_SYMBOLS = {
     "memo_debug_maxk_rows": (C.c_int, [_I32]),
     "memo_debug_maxk_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_collect_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
+    "memo_debug_lengths_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_ms_piece_text": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _I64, C.POINTER(_I64)]),
 }
 

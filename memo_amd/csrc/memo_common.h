@@ -45,6 +45,8 @@ extern thread_local int g_maxk_timed;     // ... memo_debug_maxk_times: event pa
 extern thread_local float g_maxk_ms[5];
 extern thread_local int g_collect_timed;  // memo_collect.hip (AB library, memo_debug_collect_times: event pairs around the launches of memo_collect_dev)
 extern thread_local float g_collect_ms[2];
+extern thread_local int g_lengths_timed;  // memo_lengths.hip (AB library, memo_debug_lengths_times: event pairs around the launches of the memo_lengths_*_dev calls)
+extern thread_local float g_lengths_ms[7];
 double pinned_alloc_ms_total();  // memo_hostcore.cpp: time this process has spent allocating pinned staging slots (MEMO_TIMING)
 
 struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the current device

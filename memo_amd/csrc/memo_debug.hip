@@ -179,4 +179,11 @@ int memo_debug_collect_times(int32_t on, float *out2) {
     return MEMO_OK;
 }
 
+int memo_debug_lengths_times(int32_t on, float *out7) {
+    g_lengths_timed = on ? 1 : 0;
+    if (out7)
+        for (int i = 0; i < 7; ++i) out7[i] = g_lengths_ms[i];
+    return MEMO_OK;
+}
+
 }  // extern "C"

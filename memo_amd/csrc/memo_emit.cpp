@@ -282,4 +282,45 @@ size_t memo_emit_u32(const uint32_t *vec, int64_t L, char *buf, size_t cap) {
                       });
 }
 
+// ---- `memo lengths -a`: n unsigned integers per line out of genome-major planes (include/memo_amd_dap.h).  A thread walks its lines in
+// blocks of kBlock positions, genome by genome inside a block, so that every plane is read in runs of kBlock values ----
+int32_t memo_emit_u32_rows_threads(int64_t L, int32_t n) { return L <= 0 || n <= 0 ? 0 : (int32_t)emit_threads(L * (int64_t)n, 1 << 20); }
+
+size_t memo_emit_u32_rows(const uint32_t *planes, int64_t L, int64_t pitch, int32_t n, char *buf, size_t cap) {
+    if (L <= 0 || n <= 0) return 0;
+    constexpr int64_t kBlock = 64;
+    const unsigned nt = (unsigned)memo_emit_u32_rows_threads(L, n);
+    std::vector<size_t> bytes(nt + 1, 0);
+    parallel_chunks(L, nt, [&](unsigned t, int64_t b, int64_t e) {
+        size_t total = (size_t)(e - b) * (size_t)n;  // the blanks and the newline
+        for (int32_t g = 0; g < n; ++g) {
+            const uint32_t *plane = planes + (int64_t)g * pitch;
+            for (int64_t i = b; i < e; ++i) total += digits((long long)plane[i]);
+        }
+        bytes[t + 1] = total;
+    });
+    for (unsigned t = 0; t < nt; ++t) bytes[t + 1] += bytes[t];
+    const size_t need = bytes[nt];
+    if (need > cap || !buf) return need;
+    parallel_chunks(L, nt, [&](unsigned t, int64_t b, int64_t e) {
+        char *p = buf + bytes[t];
+        std::vector<uint32_t> block((size_t)(kBlock * n));  // [position][genome] of one block
+        for (int64_t i0 = b; i0 < e; i0 += kBlock) {
+            const int64_t m = e - i0 < kBlock ? e - i0 : kBlock;
+            for (int32_t g = 0; g < n; ++g) {
+                const uint32_t *plane = planes + (int64_t)g * pitch + i0;
+                for (int64_t i = 0; i < m; ++i) block[(size_t)(i * n + g)] = plane[i];
+            }
+            for (int64_t i = 0; i < m; ++i) {
+                const uint32_t *row = block.data() + i * n;
+                for (int32_t g = 0; g < n; ++g) {
+                    p = put(p, (long long)row[g]);
+                    *p++ = g + 1 < n ? ' ' : '\n';
+                }
+            }
+        }
+    });
+    return need;
+}
+
 }  // extern "C"
