@@ -35,7 +35,9 @@ extern "C" {
  *   the index is inside the result matrix, else 1.  Bits 8 .. 10 of scatter, added to any of these, switch parts of the wide-tile
  *   sweep's shortened chain OFF (memo_sweep_cons3t.hip; profiles/tile_chain.txt): 256 = the kernel entry whose head arrives in
  *   registers, 512 = a wave's two fold chunks in flight together, 1024 = the store without the window test in tiles off the
- *   window's edges; all three off is the kernel as it was before them. */
+ *   window's edges; all three off is the kernel as it was before them.  Bit 11 (2048) switches OFF the wide tiles' pair kernel (two
+ *   tiles per workgroup behind one head, sweep_conservation_wide_pair_kernel; profiles/tile_pairs.txt): every workgroup then
+ *   does one tile, as before it. */
 int memo_debug_set_tuning(memo_index_t *ix, int32_t tile_w, int32_t waves, int32_t membership_algo,
                           int32_t row_source, int32_t scatter);
 /* Order of the 4-byte rows inside a start bucket (memo_amd/csrc/memo_interleave.hip): 0 = the library's choice (3 for conservation, 4 for membership: whichever kind of query pays for the pass), 1 = start order (as the packers write them), 2 = chunks of four rows dealt round-robin
@@ -77,6 +79,8 @@ int memo_debug_last_one_shot_sweep(void);
  * slice of genome words; all of them except where the runs kernel sweeps more than 64).  memo_index_info_t.last_sweep says 7 for
  * doubling, runs and planes alike. */
 int memo_debug_last_membership(const memo_index_t *ix, int32_t *out6);
+/* tiles per workgroup of this index's last table-driven conservation sweep: 2 where the wide tiles' pair kernel answered it, else 1 */
+int memo_debug_last_tiles_per_group(const memo_index_t *ix, int32_t *out);
 /* one pass that reads the three int64 columns exactly once (24 B/row) with the sweep's access
  * shape, to calibrate the FETCH_SIZE counter on a known byte count */
 int memo_debug_stream_rows(memo_index_t *ix, void *stream);

@@ -137,7 +137,8 @@ struct memo_tuning {
                            //     the faster source for the conservation sweep: profiles/r02_dense_rows_ab.txt)
     int chain_off = 0;     // wide-tile sweep (memo_sweep_cons3t.hip: R4), parts of its shortened chain switched OFF (A/B): 1 = the entry with
                            //     the head in registers, 2 = a wave's two fold chunks in flight together, 4 = the store without the window
-                           //     test in tiles off the window's edges
+                           //     test in tiles off the window's edges, 8 = two tiles per workgroup behind one head
+                           //     (sweep_conservation_wide_pair_kernel)
     int row_order = 0;     // order of the 4-byte rows inside a bucket (memo_interleave.hip): 0 = the library's (kRowOrderDefault),
                            //     1 = start order as packed, 2 = chunks of four dealt over the starts, 3 = the same with the rows of a
                            //     start ordered by overlap mod 32 (the conservation order), 4 = dealt over annot mod 32 (membership)
@@ -258,6 +259,7 @@ struct memo_index {
     int last_sweep = 0;          // level arrays of the last conservation sweep (memo_index_info_t.last_sweep)
     int last_arrays = 0;         // mixed level arrays (last_sweep 4): how many of them the sweep's level plan allocated
     int last_variant = 0;        // ... 2 table-driven on five-row groups (memo_sweep_cons3t.hip), 3 on a view of six rows per group; 0 no table
+    int last_tiles_per_group = 1;  // tiles a workgroup of the last table-driven sweep did (2: the wide tiles' pair kernel; memo_debug_last_tiles_per_group)
     int last_tile_w = 0;         // ... and its tile width (info.last_tile_width: 1568 at k = 31 on the radix-4 arrays, 928 on the doubling ones)
     // the plan of the last membership sweep (memo_debug_last_membership of the AB library): the algorithm (2 doubling, 3 runs, 4 planes on the
     // 4- / 6-byte rows, 5 planes on the dense rows; 0 none yet, or the k <= 1 fill), the tile width, threads per tile, the row block's MW

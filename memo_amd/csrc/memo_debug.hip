@@ -42,8 +42,8 @@ int memo_debug_set_tuning(memo_index_t *ix, int32_t tile_w, int32_t waves, int32
                                  "the 4- / 6-byte rows, else the int64 columns), 1 (int64 columns), 2 (same as 0), 3 (4- / 6-byte "
                                  "rows even where the dense rows could answer), 5 (dense rows, every wave works its tile out), 8, 9, 10 or 13 "
                                  "(include/memo_amd_debug.h; 4, 6, 7, 11, 12 were round 3's persistent sweeps: profiles/r03_persistent_sweep.txt)");
-    const int32_t chain_off = (scatter >> 8) & 7;  // (bits 8 .. 10: the wide-tile sweep's parts, include/memo_amd_debug.h)
-    scatter &= ~(7 << 8);
+    const int32_t chain_off = (scatter >> 8) & 15;  // (bits 8 .. 11: the wide-tile sweep's parts, include/memo_amd_debug.h)
+    scatter &= ~(15 << 8);
     if (scatter < 0 || scatter > 5)
         return fail(MEMO_EINVAL, "scatter must be 0 (choose), 1 (clipped), 2 (unclipped, doubling levels), 3 (unclipped, radix-4 levels) "
                                  "4 (unclipped, mixed levels, every array) or 5 (mixed levels, the arrays of the library's level plan)");
@@ -125,6 +125,12 @@ int memo_debug_last_one_shot_sweep(void) { return g_last_one_shot_sweep; }
 int memo_debug_last_membership(const memo_index_t *ix, int32_t *out6) {
     if (!ix || !out6) return fail(MEMO_EINVAL, "index or out6 is NULL");
     for (int i = 0; i < 6; ++i) out6[i] = ix->last_memb[i];
+    return MEMO_OK;
+}
+
+int memo_debug_last_tiles_per_group(const memo_index_t *ix, int32_t *out) {
+    if (!ix || !out) return fail(MEMO_EINVAL, "index or out is NULL");
+    *out = ix->last_tiles_per_group;
     return MEMO_OK;
 }
 

@@ -1128,6 +1128,7 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     // -- the rows, the launch, the record
     int variant = 0;
     if (doubling_tile) ix->last_variant = ix->last_tile_w = 0;
+    ix->last_tiles_per_group = 1;  // (launch_halo3t says otherwise)
     if (three) {
         if ((rc = sweep_dense_rows(ix, A, tw, (int)sizeof(OutT), top8, top9, st, &variant))) return rc;
     } else if ((rc = use_words(ix, A, fmt, false, st))) {

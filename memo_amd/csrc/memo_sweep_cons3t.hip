@@ -24,6 +24,8 @@
 //     results at a scalar base plus a 32-bit lane offset; the per-cell 64-bit window test is left to the window's first and last
 //     tile.  The wave-uniform choice is made once, in front of two straight tails (made per store it cost what it saved).
 // memo_debug_set_tuning (scatter bits 8 .. 10) switches each part off; all off is sweep_conservation_halo3t_kernel<..., R4>.
+// Where the wide tiles hold few groups a workgroup sweeps TWO of them behind one head (sweep_conservation_wide_pair_kernel,
+// profiles/tile_pairs.txt; scatter bit 11 switches that off).
 #include "memo_sweep_dense.h"
 
 using namespace memo;
@@ -276,6 +278,10 @@ struct FlatHead {
 // the parts of the wide-tile kernel's shortened chain (CH; launch_halo3t, memo_tuning.chain_off)
 constexpr int kChainFold2 = 1;     // a wave's two fold chunks in flight together
 constexpr int kChainInterior = 2;  // tiles off the window's edges store without the window test
+// The pair kernel is taken below this many groups per PAIR of wide tiles (launch_halo3t).  Config 3's live copy at k = 31, pairs against
+// one tile per workgroup on one index: 179 groups per tile -4.2 %, 239 (10 rows per 100 genome-positions) +0.6 %, 282 (15 per 100)
+// +2.1 % -- the threshold stands between the first two (profiles/tile_pairs.txt, section 6).
+constexpr double kPairMaxGroups = 418.0;
 
 // The wide tile's body (R4 of the kernel above: radix-4 arrays, six-row views without flags) with the shortened chain, for both of its
 // entries.  FLAT: the head came in registers -- the descriptor is then fetched by ONE scalar load of its 32 bytes (written as asm: left
@@ -290,6 +296,9 @@ __device__ __forceinline__ void wide_tile(const SweepArgs &A, const Head &H) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     constexpr int NL = kStageGroups / T;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef MEMO_STAMPS
+    unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime();  // entry
+#endif
     const uint32_t blk = blockIdx.x;
     const uint32_t tile = (blk & 7u) * H.tiles_per_xcd() + (blk >> 3);
     if (tile >= H.ntiles()) return;
@@ -312,6 +321,7 @@ __device__ __forceinline__ void wide_tile(const SweepArgs &A, const Head &H) {
         if (tid == 0) atomicOr(A.status, kStatusHugeSlice);
         return;
     }
+    MEMO_STAMP(0);  // the descriptor has arrived
     const uint4 *src0 = H.rows() + (((uint64_t)d0.y << 32) | d0.x);
     uint4 V[NL];
     auto issue = [&](uint32_t batch) {  // (the kernel above says what shaped this)
@@ -339,6 +349,13 @@ __device__ __forceinline__ void wide_tile(const SweepArgs &A, const Head &H) {
     C6.top_bit = (uint32_t)pin_vgpr((int)0x80000000u);
     C6.nega = (uint32_t)pin_vgpr((int)((0u - tabs * (uint32_t)W) & 1023u));
     barrier_lds();  // the level arrays are clear
+    MEMO_STAMP(1);  // first barrier
+#ifdef MEMO_STAMPS
+    // (wave 0 stamps.  SP: it holds only the loads of its live pieces, one at config 3's ~180 groups per tile, so the wait for all of
+    // them is the wait in front of its first group_rows4)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    MEMO_STAMP(2);  // the wave's first row piece is available
+#endif
 
     const uint32_t nbatch = (ng + kStageGroups - 1) / kStageGroups;
     for (uint32_t batch = 0; batch == 0 || batch < nbatch; ++batch) {
@@ -348,6 +365,7 @@ __device__ __forceinline__ void wide_tile(const SweepArgs &A, const Head &H) {
         r4_pieces<T, NL, AW>(V, lane, wave, gleft, d_wrap > gbase ? d_wrap - gbase : 0u, C6);
     }
     barrier_lds();  // (lgkmcnt(0): the ds_min above are invisible to the compiler)
+    MEMO_STAMP(3);  // second barrier
 
     // fold in registers + store
     OutT *out = static_cast<OutT *>(A.out);
@@ -402,6 +420,10 @@ __device__ __forceinline__ void wide_tile(const SweepArgs &A, const Head &H) {
             tail(store_edge);
         }
     }
+    MEMO_STAMP(4);  // end (the stores issued, not waited for)
+#ifdef MEMO_STAMPS
+    if (threadIdx.x == 0 && A.stamps) A.stamps[8ull * blockIdx.x + 7] = 1;
+#endif
 }
 
 // The wide tiles' own entry (R4).  The leading parameters are flat scalars -- a struct by value is not preloaded -- in the order
@@ -420,6 +442,143 @@ template <typename OutT, bool AW, bool SP, int CH>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void sweep_conservation_wide_args_kernel(const SweepArgs A) {
     wide_tile<OutT, AW, SP, CH>(A, ArgsHead{A});
+}
+
+// Two wide tiles per workgroup behind one head: the workgroup of pair j sweeps the tiles 2 j and 2 j + 1 of the PIVOT raster (a pair is
+// one 64-byte block of the tile table, fetched by one scalar load), one after the other in the same 20 KiB.  Both tiles' rows are
+// requested at once, each slice into half of the registers a single tile's batch uses (half a batch, kStageGroups / 2 groups, each;
+// every piece begins at its own slice's first group, so the row blocks run as they do in sweep_conservation_wide_kernel, masked in a
+// slice's last piece only); then tile A is cleared, scattered, folded and stored, and tile B after it.  One wave launch, one
+// descriptor round trip and one round trip of the rows to memory for two tiles; the workgroups stay independent, eight of them
+// resident per CU.  A half whose tile lies outside the window (the first pair of a window that starts at an odd tile, the last pair
+// of one that ends at an even one) loads, scatters and stores nothing.  A pair with a slice of more than half a batch does its tiles
+// as sweep_conservation_wide_kernel does, each with its own loads batch by batch.  The leading parameters are FlatHead's with
+// pairs_per_xcd in the place of tiles_per_xcd.  (profiles/tile_pairs.txt: ONE request for the pair's groups, scattered twice under a
+// mask, was measured first and is slower than one tile per workgroup -- B's slice begins inside a piece.)
+template <typename OutT, bool AW, bool SP, int CH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void sweep_conservation_wide_pair_kernel(const TileDesc *ttab, const uint4 *rows, uint32_t ntiles, uint32_t pairs_per_xcd, uint32_t tile_abs0,
+                                         uint32_t ntab, int hl, int w, int km1, int ncols, int x_lo_first, int x_hi_last, const SweepArgs A) {
+    static_assert(SP && CH == (kChainFold2 | kChainInterior), "pairs: few rows per tile, the whole shortened chain");
+    constexpr int T = 256, LSZ = kLS4, SH = 24, NL = kStageGroups / T, NH = NL / 2, ctx = 3;
+    constexpr uint32_t kHalf = (uint32_t)(NH * T);  // groups of a slice that fit its registers
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t blk = blockIdx.x;
+    const uint32_t pair = (blk & 7u) * pairs_per_xcd + (blk >> 3);
+    const uint32_t tabs_a = ((tile_abs0 >> 1) + pair) << 1;  // the pair's first tile in pivot coordinates
+    const uint32_t rel_a = tabs_a - tile_abs0;               // ... and in the window (2^32 - 1: the tile before its first)
+    const bool has_a = rel_a < ntiles, has_b = rel_a + 1u < ntiles;
+    if (!has_a && !has_b) return;
+    // (ntab is even: tiles past the table's end are its last PAIR, two empty slices)
+    const TileDesc *dp = ttab + (tabs_a < ntab - 1u ? tabs_a : ntab - 2u);
+    typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+    u32x16 d;
+    asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(d) : "s"(dp) : "memory");
+    const uint32_t ng_a = d[2], ng_b = d[10], wrap_a = d[5], wrap_b = d[13];
+    if ((has_a && ng_a == 0xFFFFFFFFu) || (has_b && ng_b == 0xFFFFFFFFu)) {
+        if (tid == 0) atomicOr(A.status, kStatusHugeSlice);
+        return;
+    }
+    const uint4 *src_a = rows + (((uint64_t)d[1] << 32) | d[0]), *src_b = rows + (((uint64_t)d[9] << 32) | d[8]);
+    // the window's tiles of this pair, first and (where both halves are present) second: slice, groups, g_wrap
+    const uint32_t nh = has_a && has_b ? 2u : 1u;
+    const uint4 *src = has_a ? src_a : src_b;
+    uint32_t n = has_a ? ng_a : ng_b, wleft = has_a ? wrap_a : wrap_b;
+    const bool both = n <= kHalf && (nh == 1u || ng_b <= kHalf);  // the slices fit their registers: requested here, both at once
+    uint4 V[NH], VB[NH];  // V: the slice of the tile being swept
+    if (both) {
+#pragma unroll
+        for (int j = 0; j < NH; ++j) {
+            const uint32_t pg = (uint32_t)(j * T + wave * 64);
+            if (pg < n) V[j] = src[pg + (uint32_t)lane];
+        }
+#pragma unroll
+        for (int j = 0; j < NH; ++j) {
+            const uint32_t pg = (uint32_t)(j * T + wave * 64);
+            if (nh == 2u && pg < ng_b) VB[j] = src_b[pg + (uint32_t)lane];
+        }
+    }
+    const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)lds;
+    const int HL = hl, W = w;
+    const uint32_t sent = cell_sentinel<SH>(ncols);
+    SixConst C6;
+    C6.km1 = km1;
+    C6.status = A.status;
+    C6.ls4 = (uint32_t)(-2 * LSZ);
+    C6.bias4 = (uint32_t)pin_vgpr((int)(lds_base + 4u * (uint32_t)HL + 8u * (uint32_t)LSZ));
+    C6.top_bit = (uint32_t)pin_vgpr((int)0x80000000u);
+    OutT *out = static_cast<OutT *>(A.out);
+    const int cells = HL + W;
+    u32x4 L[6];
+    auto lv = [&](int i) { return make_uint4(L[i].x, L[i].y, L[i].z, L[i].w); };
+    auto fold1 = [&](int xr) {
+        read_levels_r4(lds_base + 4u * (uint32_t)xr, L);
+        uint4 M = lv(2), M4 = lv(1);
+        r4_fold12(M4, lv(0));
+        r4_fold4(M, M4);
+        return M;
+    };
+    auto fold2 = [&](int xa, int xb, uint4 &Ra, uint4 &Rb) {
+        read_levels_r4x2(lds_base + 4u * (uint32_t)xa, lds_base + 4u * (uint32_t)xb, L);
+        uint4 M4a = lv(1), M4b = lv(4);
+        Ra = lv(2);
+        Rb = lv(5);
+        r4_fold12(M4a, lv(0));
+        r4_fold12(M4b, lv(3));
+        r4_fold4(Ra, M4a);
+        r4_fold4(Rb, M4b);
+    };
+    // One tile of the pair per round, from the clear to the store (tabs: its number in pivot coordinates, rel: in the window; V: its
+    // slice's groups where they were requested above, else loaded here batch by batch from src).  A loop, not two copies of the body:
+    // the row blocks stand once in the code, in front of the fold.
+    uint32_t tabs = has_a ? tabs_a : tabs_a + 1u, rel = tabs - tile_abs0;
+#pragma unroll 1
+    for (uint32_t half = 0; half < nh; ++half) {
+        if (half) barrier_lds();  // every wave has read what it folds of the first tile: the arrays may be cleared again
+        clear_levels<5, T>(lds_base, sent);
+        C6.nega = (uint32_t)pin_vgpr((int)((0u - tabs * (uint32_t)W) & 1023u));
+        barrier_lds();  // the level arrays are clear
+        if (both) {
+            r4_pieces<T, NH, AW>(V, lane, wave, n, wleft, C6);
+        } else {
+            uint4 VF[NL];
+            const uint32_t nbatch = (n + kStageGroups - 1) / kStageGroups;
+            for (uint32_t batch = 0; batch < nbatch; ++batch) {
+                const uint32_t gbase = batch * kStageGroups, gleft = n - gbase;
+#pragma unroll
+                for (int j = 0; j < NL; ++j) {
+                    const uint32_t pg = (uint32_t)(j * T + wave * 64);
+                    VF[j] = src[pg < gleft ? gbase + pg + (uint32_t)lane : 0u];
+                }
+                r4_pieces<T, NL, AW>(VF, lane, wave, gleft, wleft > gbase ? wleft - gbase : 0u, C6);
+            }
+        }
+        barrier_lds();  // (lgkmcnt(0): the ds_min above are invisible to the compiler)
+        const int64_t a_rel = (int64_t)tabs * W - A.qs;  // the tile's first position, as an output index
+        const int64_t ob = a_rel - HL;
+        const int64_t o_lo = a_rel + (rel == 0 ? x_lo_first : 0);
+        const int64_t o_hi = a_rel + (rel == ntiles - 1u ? x_hi_last : W);
+        const bool edge = (rel == 0 && x_lo_first != 0) || (rel == ntiles - 1u && x_hi_last != W);
+        OutT *const out_b = out + ob;
+        auto tail = [&](auto store) { fold_chunks_once_or_twice<T, true>(cells, LSZ, lane, wave, Int<ctx>{}, fold1, fold2, store); };
+        if (edge) {
+            tail([&](int x0, uint4 R) { store_cells4<OutT, SH>(out, ob + x0, o_lo, o_hi, R); });
+        } else {
+            tail([&](int x0, uint4 R) {
+                if (x0 >= HL) store_four(out_b + (uint32_t)x0, pack_cells4<OutT, SH>(R));
+            });
+        }
+        if (half + 1u < nh) {  // the second tile's
+#pragma unroll
+            for (int j = 0; j < NH; ++j) V[j] = VB[j];
+            src = src_b;
+            n = ng_b;
+            wleft = wrap_b;
+            ++tabs;
+            ++rel;
+        }
+    }
 }
 
 }  // namespace
@@ -443,7 +602,8 @@ static int tile_table(memo_index *ix, const void *rows_of, const int64_t *boff, 
         if (t.d && t.w == w && t.km1 == km1 && t.rows_of == rows_of) slot = &t;
     if (!slot) {
         const int64_t top = ix->max_s < 0 ? 0 : ix->max_s;
-        const int64_t n = (top + km1 + ((int64_t)1 << ix->bshift)) / w + 3;  // past the last row: empty slices
+        // past the last row: empty slices; an even number of them (the pair kernel fetches the tiles 2 j and 2 j + 1 as one 64-byte block)
+        const int64_t n = ((top + km1 + ((int64_t)1 << ix->bshift)) / w + 3 + 1) & ~(int64_t)1;
         if (n >= ((int64_t)1 << 31)) return 1;
         if (ix->ttabs.size() >= kMaxTileTables) {
             size_t lru = 0;
@@ -456,6 +616,10 @@ static int tile_table(memo_index *ix, const void *rows_of, const int64_t *boff, 
         const hipError_t aerr = side_alloc(&d, (size_t)n * sizeof(TileDesc));
         if (aerr == hipErrorOutOfMemory) return kNoRoom;  // (the caller takes the kernel that needs no table)
         HIP_TRY(aerr);
+        if ((uintptr_t)d % 64) {  // (device allocations are aligned far beyond this)
+            (void)hipFree(d);
+            return fail(MEMO_EHIP, "tile table: allocation not aligned to 64 bytes");
+        }
         hipLaunchKernelGGL(tile_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, boff, (int64_t)ix->nb, ix->bbase,
                            ix->bshift, w, km1, n, static_cast<TileDesc *>(d), rpg);
         hipError_t err = hipGetLastError();
@@ -532,6 +696,10 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     // the wide tiles' shortened chain, part by part (memo_tuning.chain_off: all of it in the product)
     const bool flat = r4 && !(ix->tune.chain_off & 1);
     const int chain = r4 ? (~ix->tune.chain_off >> 1) & (kChainFold2 | kChainInterior) : 0;
+    // two tiles per workgroup behind one head, where the tiles hold few groups (chain_off & 8: off)
+    const bool pairs = flat && chain == (kChainFold2 | kChainInterior) && sp && !(ix->tune.chain_off & 8) && groups_per_tile(2 * tw) < kPairMaxGroups;
+    const int64_t npairs = ((q + ntiles + 1) >> 1) - (q >> 1);
+    const int64_t per_xcd = pairs ? (npairs + 7) / 8 : A.tiles_per_xcd;  // (workgroups per XCD: of pairs, or of tiles)
     SweepKernel kern = pick_int<1, 2, 3, 4, 5, 6>(A.nlev, [&](auto N) {
         return pick_bool(all_write, [&](auto AW) {
             return pick_bool(sp, [&](auto SP) -> SweepKernel {
@@ -542,6 +710,9 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
                     if constexpr (decltype(N)::value == 5) {
                         if (r4)  // (the flat entry goes through the picker under the doubling kernels' type: cast back at the launch)
                             return pick_int<0, 1, 2, 3>(chain, [&](auto CH) -> SweepKernel {
+                                if constexpr (decltype(CH)::value == (kChainFold2 | kChainInterior) && decltype(SP)::value) {
+                                    if (pairs) return reinterpret_cast<SweepKernel>(reinterpret_cast<void (*)()>(sweep_conservation_wide_pair_kernel<OutT, AW, true, CH>));
+                                }
                                 if (flat) return reinterpret_cast<SweepKernel>(reinterpret_cast<void (*)()>(sweep_conservation_wide_kernel<OutT, AW, SP, CH>));
                                 if constexpr (decltype(CH)::value == 0) {
                                     return (SweepKernel)sweep_conservation_halo3t_kernel<5, OutT, 256, false, AW, true, SP, false, true>;
@@ -564,14 +735,15 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     });
     if (!kern) return no(1);
     ix->last_tile_w = tw;
+    ix->last_tiles_per_group = pairs ? 2 : 1;
     if (g_prepare_only) return MEMO_OK;  // memo_index_prepare: the table is built, nothing is launched
     if (int prc = refuse_plan_pointer(A.out)) return prc;
     if (flat) {  // (launch_halo3t's own checks above: the four counts fit 32 bits)
         using WideKernel = void (*)(const TileDesc *, const uint4 *, uint32_t, uint32_t, uint32_t, uint32_t, int, int, int, int, int, int,
                                     const SweepArgs);
-        hipLaunchKernelGGL(reinterpret_cast<WideKernel>(reinterpret_cast<void (*)()>(kern)), dim3((unsigned)(A.tiles_per_xcd * 8)), dim3(256), (size_t)A.nlev * 4096, st,
+        hipLaunchKernelGGL(reinterpret_cast<WideKernel>(reinterpret_cast<void (*)()>(kern)), dim3((unsigned)(per_xcd * 8)), dim3(256), (size_t)A.nlev * 4096, st,
                            static_cast<const TileDesc *>(A.ttab), reinterpret_cast<const uint4 *>(A.p3), (uint32_t)A.ntiles,
-                           (uint32_t)A.tiles_per_xcd, (uint32_t)A.tile_abs0, (uint32_t)A.ntab, A.hl, A.w, A.km1, A.ncols, A.x_lo_first,
+                           (uint32_t)per_xcd, (uint32_t)A.tile_abs0, (uint32_t)A.ntab, A.hl, A.w, A.km1, A.ncols, A.x_lo_first,
                            A.x_hi_last, A);
     } else {
         hipLaunchKernelGGL(kern, dim3((unsigned)(A.tiles_per_xcd * 8)), dim3(256), (size_t)A.nlev * 4096, st, A);

@@ -176,6 +176,12 @@ class DeviceIndex:
         check(lib().memo_debug_last_membership(self._h, out))
         return dict(zip(("algorithm", "tile_width", "threads", "mw", "sk", "slice"), (int(v) for v in out)))
 
+    def debug_last_tiles_per_group(self):
+        """memo_debug_last_tiles_per_group: 2 where the wide tiles' pair kernel answered the last conservation sweep, else 1"""
+        out = C.c_int32(0)
+        check(lib().memo_debug_last_tiles_per_group(self._h, C.byref(out)))
+        return int(out.value)
+
     def check(self, stream=None):
         check(lib().memo_query_check(self._h, _ptr(stream)))
 
