@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix`, the curves of `memo collect`, the lengths of `memo maxk` and the per-genome lengths of `memo lengths`: off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix`, the curves of `memo collect`, the lengths of `memo maxk`, the per-genome lengths of `memo lengths` and the matrix `memo convert` makes of them: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -306,6 +306,21 @@ size_t memo_emit_u32_rows(const uint32_t *planes, int64_t L, int64_t pitch, int3
 /* the threads memo_emit_u32_rows splits the lines of that shape over (one per 2^20 integers, at most the process's CPU budget or
  * MEMO_EMIT_THREADS, read per call; 0 for an empty text), for tests that want the threaded path and must know that they got it */
 int32_t memo_emit_u32_rows_threads(int64_t L, int32_t n);
+
+/* ---- `memo convert`: a conservation index from a membership index (no counterpart in the reference) ----------------------------------
+ * (Declared here, after the `memo lengths` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The step between the planes of the memo_lengths_*_dev calls and memo_dap_push_dev (memo_amd/csrc/memo_convert.hip): positions
+ * [first, first + positions) of the genome-major planes d_cells (uint32 [N][pitch] on `device`, 16-byte aligned, pitch a multiple of 4)
+ * become the position-major matrix the row builder reads, clipped at the end of the record, `remaining` positions from `first`:
+ *     d_dap[i][g - 1] = min( d_cells[g][first + i], remaining - i )        0 <= i < positions, 1 <= g < N        int32 [positions][N - 1]
+ * Plane 0, the pivot, is not read, and nothing outside [first, first + positions) of the other planes; nothing is written outside the
+ * positions * (N - 1) integers of d_dap.  MEMO_EINVAL before anything is launched: N outside [2, 2048], pitch % 4 != 0,
+ * first + positions > pitch, remaining < positions, remaining > 2^31 - 1, d_cells not 16-byte aligned, d_dap not 4-byte aligned, a
+ * negative count.  positions == 0 launches nothing.  Blocking (synchronises `stream`). */
+int memo_convert_dap_dev(const uint32_t *d_cells, int64_t pitch, int32_t num_docs, int64_t first, int64_t positions, int64_t remaining,
+                         int32_t *d_dap, int32_t device, void *stream);
+/* positions per tile of that kernel (tiles lie at multiples of it in the plane), for tests that want lengths around it */
+int32_t memo_convert_tile(void);
 
 #ifdef __cplusplus
 }

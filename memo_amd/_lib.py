@@ -136,6 +136,8 @@ SYMBOLS = {
     "memo_lengths_select_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, _I32, _P, _I32, _P]),
     "memo_lengths_tile": (_I32, []),
     "memo_lengths_select_tile": (_I32, [_I32]),
+    "memo_convert_dap_dev": (C.c_int, [_P, _I64, _I32, _I64, _I64, _I64, _P, _I32, _P]),
+    "memo_convert_tile": (_I32, []),
     "memo_emit_u32_rows": (_SZ, [_P, _I64, _I64, _I32, _P, _SZ]),
     "memo_emit_u32_rows_threads": (_I32, [_I64, _I32]),
     "memo_emit_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _P, _SZ]),
