@@ -81,6 +81,16 @@ int memo_debug_last_one_shot_sweep(void);
 int memo_debug_last_membership(const memo_index_t *ix, int32_t *out6);
 /* tiles per workgroup of this index's last table-driven conservation sweep: 2 where the wide tiles' pair kernel answered it, else 1 */
 int memo_debug_last_tiles_per_group(const memo_index_t *ix, int32_t *out);
+/* what the plan step and the kernel pickers of this index's last conservation query decided, as the launchers recorded it on the host
+ * (memo_sweep_cons.hip: query_conservation; memo_sweep_cons3t.hip: launch_halo3t): the first min(n, 19) of
+ *   [0] the kernel family, numbered as memo_index_info_t.last_sweep (0: none yet, or the fill of k <= 1 / an empty index),
+ *   [1] the row format (0 int64 columns, 4, 12, 6 the 4- / 6-byte rows, 3 the dense rows), [2] CHECKED, [3] TOP (24, 20 or 0),
+ *   [4] threads per workgroup, [5] the clipped tile width / cells of a level array / width of a table-driven tile, [6] level arrays,
+ *   [7] sizeof(OutT); of the table-driven sweep [8] nlev, [9] AW (all rows write), [10] SP (few groups per tile), [11] six, [12] live,
+ *   [13] r4, [14] the chain value, [15] pairs, [16] A9 (256 .. 511 genomes); [17] 1 where sweep_conservation_halo3_kernel (no table)
+ *   answered; [18] which table-driven kernel: 1 halo3t, 2 wide_args, 3 wide, 4 wide_pair, 0 none.
+ * Returns how many values the record has (19). */
+int memo_debug_last_pick(const memo_index_t *ix, int32_t *out, int32_t n);
 /* one pass that reads the three int64 columns exactly once (24 B/row) with the sweep's access
  * shape, to calibrate the FETCH_SIZE counter on a known byte count */
 int memo_debug_stream_rows(memo_index_t *ix, void *stream);

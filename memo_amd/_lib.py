@@ -201,7 +201,8 @@ DEBUG_SYMBOLS = {
     "memo_debug_last_one_shot_sweep": (C.c_int, []),
     "memo_debug_last_membership": (C.c_int, [_P, C.POINTER(_I32)]),
     "memo_debug_last_tiles_per_group": (C.c_int, [_P, C.POINTER(_I32)]),
-    "memo_debug_set_stamp_buffer": (C.c_int, [_P]),
+    "memo_debug_last_pick": (C.c_int, [_P, C.POINTER(_I32), _I32]),
+    "memo_debug_set_stamp_buffer":(C.c_int, [_P]),
     "memo_debug_ms_free_bytes": (C.c_int, [_I64]),
     "memo_debug_cooc_flush": (C.c_int, [_I32]),
     "memo_debug_cooc_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),

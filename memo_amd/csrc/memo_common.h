@@ -260,6 +260,22 @@ struct memo_index {
     int last_arrays = 0;         // mixed level arrays (last_sweep 4): how many of them the sweep's level plan allocated
     int last_variant = 0;        // ... 2 table-driven on five-row groups (memo_sweep_cons3t.hip), 3 on a view of six rows per group; 0 no table
     int last_tiles_per_group = 1;  // tiles a workgroup of the last table-driven sweep did (2: the wide tiles' pair kernel; memo_debug_last_tiles_per_group)
+    // what the plan step and the pickers of the last conservation sweep decided (memo_debug_last_pick of the AB library): the template
+    // arguments of the kernel launched, as the picker's lambdas saw them.  All int32, in the order memo_amd_debug.h lists; host side
+    // only: no kernel reads it.  family 0: none yet, or the fill of k <= 1 / an empty index.
+    struct SweepPick {
+        int32_t family = 0;     // last_sweep's numbering: 1 clipped, 2 doubling, 3 radix-4, 4 mixed, 5 the dense rows
+        int32_t format = 0;     // 0 int64 columns, 4, 12, 6 the 4- / 6-byte rows, 3 the dense rows
+        int32_t checked = 0;    // PackedRows' CHECKED (0 for the int64 columns and the dense rows)
+        int32_t top = 0;        // TOP of the unclipped families on 4-byte rows: 24, 20 or 0
+        int32_t threads = 0;    // per workgroup
+        int32_t width = 0;      // clipped: W; unclipped: cells of a level array; table-driven: the tile width
+        int32_t arrays = 0;     // level arrays in LDS
+        int32_t out_bytes = 0;  // sizeof(OutT)
+        int32_t nlev = 0, aw = 0, sp = 0, six = 0, live = 0, r4 = 0, chain = 0, pairs = 0, a9 = 0;  // the table-driven sweep's (launch_halo3t)
+        int32_t halo3 = 0;      // 1: sweep_conservation_halo3_kernel (no table) answered
+        int32_t kernel = 0;     // table-driven: 1 halo3t, 2 wide_args, 3 wide, 4 wide_pair; else 0
+    } last_pick;
     int last_tile_w = 0;         // ... and its tile width (info.last_tile_width: 1568 at k = 31 on the radix-4 arrays, 928 on the doubling ones)
     // the plan of the last membership sweep (memo_debug_last_membership of the AB library): the algorithm (2 doubling, 3 runs, 4 planes on the
     // 4- / 6-byte rows, 5 planes on the dense rows; 0 none yet, or the k <= 1 fill), the tile width, threads per tile, the row block's MW

@@ -134,6 +134,15 @@ int memo_debug_last_tiles_per_group(const memo_index_t *ix, int32_t *out) {
     return MEMO_OK;
 }
 
+int memo_debug_last_pick(const memo_index_t *ix, int32_t *out, int32_t n) {
+    constexpr int32_t kFields = (int32_t)(sizeof(memo_index::SweepPick) / sizeof(int32_t));
+    static_assert(kFields == 19 && sizeof(memo_index::SweepPick) == 19 * sizeof(int32_t), "memo_amd_debug.h lists the fields");
+    if (!ix || !out || n < 0) return fail(MEMO_EINVAL, "index or out is NULL, or n < 0");
+    const int32_t *p = reinterpret_cast<const int32_t *>(&ix->last_pick);
+    for (int32_t i = 0; i < n && i < kFields; ++i) out[i] = p[i];
+    return kFields;
+}
+
 int memo_debug_set_stamp_buffer(uint64_t *d_buffer) {
 #ifdef MEMO_STAMPS
     g_stamp_buffer = reinterpret_cast<unsigned long long *>(d_buffer);

@@ -955,6 +955,7 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     if (k <= 1 || ix->rows == 0) {
         if (g_prepare_only) return MEMO_OK;
         if ((rc = refuse_plan_pointer(d_out))) return rc;
+        ix->last_pick = memo_index::SweepPick();  // (no sweep: the fill)
         hipLaunchKernelGGL((fill_conservation_kernel<OutT>), dim3(2048), dim3(256), 0, st, d_out,
                            qe - qs, (OutT)num_docs);
         HIP_TRY(hipGetLastError());
@@ -1008,6 +1009,8 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     int sweep = 0, tw = 0, arrays = 0;
     size_t lds = 0;
     bool three = false, top9 = false, top8 = false, doubling_tile = false;
+    memo_index::SweepPick pick;  // what the pickers below were handed (memo_index::last_pick; launch_halo3t adds the table-driven sweep's)
+    pick.out_bytes = (int32_t)sizeof(OutT);
     // Mixed levels (sweep_conservation_mixed_kernel): 1, 4, 16, then doubling -- of which only the arrays some row of the index
     // can write to exist (level_plan; the debug switch scatter = 4 asks for all of them, the layout of rounds 2-3).  k - 1 >= 16.
     if (levels == 3 || (levels == 4 && km1 >= 16)) {
@@ -1035,6 +1038,7 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
                 using Rows = typename decltype(R)::type;
                 return pick_top<Rows>(num_docs, [&](auto TOP) {
                     return pick_int<512, 256, 64>(threads_of(waves), [&](auto T) {
+                        pick.top = TOP, pick.threads = T;
                         return levels == 3 ? (SweepKernel)sweep_conservation_r4_kernel<Rows, kHaloLoads, T, OutT, TOP>
                                            : (SweepKernel)sweep_conservation_mixed_kernel<Rows, kHaloLoads, T, OutT, TOP>;
                     });
@@ -1080,6 +1084,7 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
                 sweep = three ? 5 : 2;
                 lds = (size_t)A.nlev * A.ls * 4;
                 kern = pick_int<512, 256, 64>(threads_of(waves), [&](auto T) -> SweepKernel {
+                    pick.threads = T;
                     if (three) {  // (no tile table: no room, a negative window start)
                         if constexpr (sizeof(OutT) == 2) {
                             if (top9)  // (256 .. 511 genomes)
@@ -1090,6 +1095,7 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
                     return pick_packed<false>(fmt, [&](auto R) {
                         using Rows = typename decltype(R)::type;
                         return pick_top<Rows>(num_docs, [&](auto TOP) {
+                            pick.top = TOP;
                             return (SweepKernel)sweep_conservation_halo_kernel<Rows, kHaloLoads, T, OutT, TOP>;
                         });
                     });
@@ -1118,6 +1124,7 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
             using Rows = typename decltype(R)::type;
             return pick_int<256, 512, 1024, 2048, 4096>(w, [&](auto W) {
                 return pick_int<256, 64>(clipped_threads_of(waves), [&](auto T) {
+                    pick.threads = T, pick.width = W;
                     return (SweepKernel)sweep_conservation_kernel<Rows, W, Rows::kLoads, T, OutT>;
                 });
             });
@@ -1129,12 +1136,20 @@ static int query_conservation(memo_index_t *ix, int64_t qs, int64_t qe, int32_t 
     int variant = 0;
     if (doubling_tile) ix->last_variant = ix->last_tile_w = 0;
     ix->last_tiles_per_group = 1;  // (launch_halo3t says otherwise)
+    pick.family = sweep;
+    pick.format = three ? 3 : fmt;
+    pick.checked = sweep == 1 && fmt && checked;  // (pick_rows_clipped; every other family is handed CHECKED = false)
+    if (sweep != 1) pick.width = A.ls;
+    pick.arrays = sweep == 3 || sweep == 4 ? arrays : A.nlev;
+    pick.a9 = three && top9;
+    ix->last_pick = pick;
     if (three) {
         if ((rc = sweep_dense_rows(ix, A, tw, (int)sizeof(OutT), top8, top9, st, &variant))) return rc;
     } else if ((rc = use_words(ix, A, fmt, false, st))) {
         return rc;
     }
     if (!variant && (rc = launch_tiles(kern, A, tw, 64 * waves, lds, st))) return rc;
+    if (three && !variant) ix->last_pick.halo3 = 1;
     ix->last_sweep = sweep;
     if (sweep == 4) ix->last_arrays = arrays;
     if (variant) ix->last_variant = variant;

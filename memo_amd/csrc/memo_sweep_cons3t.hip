@@ -700,9 +700,15 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     const bool pairs = flat && chain == (kChainFold2 | kChainInterior) && sp && !(ix->tune.chain_off & 8) && groups_per_tile(2 * tw) < kPairMaxGroups;
     const int64_t npairs = ((q + ntiles + 1) >> 1) - (q >> 1);
     const int64_t per_xcd = pairs ? (npairs + 7) / 8 : A.tiles_per_xcd;  // (workgroups per XCD: of pairs, or of tiles)
+    // p: the template arguments as the picker's lambdas are handed them (memo_index::last_pick; kernel: 1 halo3t, 2 wide_args, 3 wide,
+    // 4 wide_pair; the caller filled the family, the row format and OutT)
+    memo_index::SweepPick p = ix->last_pick;
+    p.threads = 256, p.width = tw, p.arrays = A.nlev, p.halo3 = 0;
     SweepKernel kern = pick_int<1, 2, 3, 4, 5, 6>(A.nlev, [&](auto N) {
         return pick_bool(all_write, [&](auto AW) {
             return pick_bool(sp, [&](auto SP) -> SweepKernel {
+                p.nlev = N, p.aw = AW, p.sp = SP, p.kernel = 1;
+                p.a9 = annot9;
                 if (annot9)  // (256 .. 511 genomes: nine-bit orders, uint16 results)
                     return (SweepKernel)sweep_conservation_halo3t_kernel<N, uint16_t, 256, true, AW, false, SP>;
                 auto of = [&](auto O) -> SweepKernel {
@@ -710,7 +716,10 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
                     if constexpr (decltype(N)::value == 5) {
                         if (r4)  // (the flat entry goes through the picker under the doubling kernels' type: cast back at the launch)
                             return pick_int<0, 1, 2, 3>(chain, [&](auto CH) -> SweepKernel {
+                                p.six = p.r4 = 1, p.chain = CH;
+                                p.kernel = flat ? 3 : decltype(CH)::value == 0 ? 1 : 2;
                                 if constexpr (decltype(CH)::value == (kChainFold2 | kChainInterior) && decltype(SP)::value) {
+                                    if (pairs) p.pairs = 1, p.kernel = 4;
                                     if (pairs) return reinterpret_cast<SweepKernel>(reinterpret_cast<void (*)()>(sweep_conservation_wide_pair_kernel<OutT, AW, true, CH>));
                                 }
                                 if (flat) return reinterpret_cast<SweepKernel>(reinterpret_cast<void (*)()>(sweep_conservation_wide_kernel<OutT, AW, SP, CH>));
@@ -724,6 +733,7 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
                     if constexpr (decltype(N)::value <= 5) {
                         if (six)
                             return pick_bool(live, [&](auto LIVE) {
+                                p.six = 1, p.live = LIVE;
                                 return (SweepKernel)sweep_conservation_halo3t_kernel<N, OutT, 256, false, AW, true, SP, LIVE>;
                             });
                     }
@@ -736,6 +746,7 @@ int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStrea
     if (!kern) return no(1);
     ix->last_tile_w = tw;
     ix->last_tiles_per_group = pairs ? 2 : 1;
+    ix->last_pick = p;
     if (g_prepare_only) return MEMO_OK;  // memo_index_prepare: the table is built, nothing is launched
     if (int prc = refuse_plan_pointer(A.out)) return prc;
     if (flat) {  // (launch_halo3t's own checks above: the four counts fit 32 bits)

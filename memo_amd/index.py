@@ -182,6 +182,17 @@ class DeviceIndex:
         check(lib().memo_debug_last_tiles_per_group(self._h, C.byref(out)))
         return int(out.value)
 
+    PICK_FIELDS = ("family", "format", "checked", "top", "threads", "width", "arrays", "out_bytes", "nlev", "aw", "sp", "six", "live",
+                   "r4", "chain", "pairs", "a9", "halo3", "kernel")
+
+    def debug_last_pick(self):
+        """memo_debug_last_pick: what the plan step and the kernel pickers of the last conservation query decided"""
+        out = (C.c_int32 * len(self.PICK_FIELDS))()
+        n = check(lib().memo_debug_last_pick(self._h, out, len(out)))
+        if n != len(out):
+            raise RuntimeError(f"memo_debug_last_pick has {n} fields, the binding {len(out)}")
+        return dict(zip(self.PICK_FIELDS, (int(v) for v in out)))
+
     def check(self, stream=None):
         check(lib().memo_query_check(self._h, _ptr(stream)))
 
