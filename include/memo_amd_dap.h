@@ -126,6 +126,11 @@ int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_beg
 int memo_ms_plan_pieces(const int64_t *rec_len, int32_t nrec, int64_t cap, int32_t *piece_of_string, int32_t *pieces);
 int memo_ms_fetch(memo_ms_t *h, int64_t first, int64_t positions, int32_t *out);
 int memo_ms_push_dap(memo_ms_t *h, memo_dap_t *dap, int64_t first, int64_t positions, uint64_t *out_rows);
+/* memo_ms_rows_dev: DAP rows [first, first + positions) where they lie on the device, int32 [positions][columns] (`memo add` reads
+ *   them beside the columns it reads back from an index: memo_add_dap_dev).  A dense handle: a pointer into the matrix.  A coded handle:
+ *   the rows are decoded into the staging buffer first, all of them at once, as memo_ms_push_dap does.  *d_rows is valid until the next
+ *   call on the handle.  positions == 0: *d_rows = NULL and MEMO_OK; a range outside the pivot: MEMO_EINVAL, *d_rows untouched. */
+int memo_ms_rows_dev(memo_ms_t *h, int64_t first, int64_t positions, const int32_t **d_rows);
 int memo_ms_timings(memo_ms_t *h, float *out3);
 typedef struct {
     uint64_t text_reads;            /* all walk threads */
@@ -321,6 +326,24 @@ int memo_convert_dap_dev(const uint32_t *d_cells, int64_t pitch, int32_t num_doc
                          int32_t *d_dap, int32_t device, void *stream);
 /* positions per tile of that kernel (tiles lie at multiples of it in the plane), for tests that want lengths around it */
 int32_t memo_convert_tile(void);
+
+/* ---- `memo add`: a membership index grown by new genomes, without the old ones (no counterpart in the reference) -----------------------
+ * (Declared here, after the `memo convert` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The row builder's matrix from two sources (memo_amd/csrc/memo_add.hip): the old genomes' columns from the planes d_cells exactly as
+ * memo_convert_dap_dev takes them (uint32 [N][pitch] on `device`, 16-byte aligned, pitch a multiple of 4), the new genomes' columns from
+ * d_new, int32 [positions][new_cols] on `device`, contiguous and 4-byte aligned (memo_ms_rows_dev), row i of it beside position first + i
+ * of the planes.  With W = N - 1 + new_cols and room = remaining - i:
+ *     d_dap[i][c] = min( d_cells[c + 1][first + i], room )                    0 <= c < N - 1         0 <= i < positions
+ *     d_dap[i][c] = min( (uint32) d_new[i][c - (N - 1)], room )               N - 1 <= c < W         int32 [positions][W]
+ * Plane 0 is not read, and nothing outside [first, first + positions) of the other planes; nothing is read outside d_new[0 ..
+ * positions * new_cols); nothing is written outside the positions * W integers of d_dap, each of which is written once.  MEMO_EINVAL
+ * before anything is launched: N outside [2, 2047], new_cols outside [1, 2047], W > 2047, pitch % 4 != 0, first + positions > pitch,
+ * remaining < positions, remaining > 2^31 - 1, d_cells not 16-byte aligned, d_new or d_dap not 4-byte aligned, a negative count, a NULL
+ * pointer with positions > 0.  positions == 0 launches nothing.  Blocking (synchronises `stream`). */
+int memo_add_dap_dev(const uint32_t *d_cells, int64_t pitch, int32_t num_docs, int64_t first, int64_t positions, int64_t remaining,
+                     const int32_t *d_new, int32_t new_cols, int32_t *d_dap, int32_t device, void *stream);
+/* positions per tile of that kernel (tiles lie at multiples of it in the plane), for tests that want lengths around it */
+int32_t memo_add_tile(void);
 
 #ifdef __cplusplus
 }

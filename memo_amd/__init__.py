@@ -26,6 +26,8 @@ Layout (only what the path needs):
   lengths_cli.py   `memo lengths`: flags, usage, one integer per line or one per genome and line
   convert.py       `memo convert`: a membership index's lengths fed to the row builder: the conservation index, or the canonical membership index
   convert_cli.py   `memo convert`: flags, usage, the Parquet index written beside its name and renamed
+  add.py           `memo add`: new genomes' matching statistics beside a membership index's lengths, fed to the row builder once
+  add_cli.py       `memo add`: flags, usage, the grown membership and conservation indexes written beside their names and renamed
 
 Attributes are loaded on first use (PEP 562), so that `import memo_amd._fastquery` -- the CLI's cache-hit
 path -- does not pay for NumPy.
@@ -43,6 +45,7 @@ _LAZY = {
     "region_maxk": "maxk", "index_maxk": "maxk",          # (maxk.maxk keeps its module's name: memo_amd.maxk is the module)
     "region_planes": "lengths", "region_kth": "lengths",
     "convert_index": "convert",
+    "add_index": "add",
 }
 
 
@@ -52,7 +55,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "convert", "convert_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "convert", "convert_cli", "add", "add_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

@@ -138,6 +138,8 @@ SYMBOLS = {
     "memo_lengths_select_tile": (_I32, [_I32]),
     "memo_convert_dap_dev": (C.c_int, [_P, _I64, _I32, _I64, _I64, _I64, _P, _I32, _P]),
     "memo_convert_tile": (_I32, []),
+    "memo_add_dap_dev": (C.c_int, [_P, _I64, _I32, _I64, _I64, _I64, _P, _I32, _P, _I32, _P]),
+    "memo_add_tile": (_I32, []),
     "memo_emit_u32_rows": (_SZ, [_P, _I64, _I64, _I32, _P, _SZ]),
     "memo_emit_u32_rows_threads": (_I32, [_I64, _I32]),
     "memo_emit_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _P, _SZ]),
@@ -160,6 +162,7 @@ SYMBOLS = {
     "memo_ms_plan_pieces": (C.c_int, [_P, _I32, _I64, _P, C.POINTER(_I32)]),
     "memo_ms_fetch": (C.c_int, [_P, _I64, _I64, _P]),
     "memo_ms_push_dap": (C.c_int, [_P, _P, _I64, _I64, C.POINTER(_U64)]),
+    "memo_ms_rows_dev": (C.c_int, [_P, _I64, _I64, C.POINTER(_P)]),
     "memo_ms_timings": (C.c_int, [_P, _P]),
     "memo_ms_set_walk_budget": (C.c_int, [_P, _I64]),
     "memo_ms_walk_info": (C.c_int, [_P, C.POINTER(MsWalkInfo)]),

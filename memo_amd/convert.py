@@ -137,18 +137,26 @@ class _RowBuilder:
         self._conv.close()
 
 
-def _record_rows(feed, length, n_docs, builder, device, slice_positions, batch_positions):
+def _record_rows(feed, length, n_docs, builder, device, slice_positions, batch_positions, columns=None, matrix=None):
     """Yields the (rec, start, end, annot) rows of one record of `length` positions, batch by batch, in the index's order.  feed(lo, hi)
-    yields (d_start, d_end, d_annot, rows) chunks of device columns that hold at least the rows with lo < start < hi."""
+    yields (d_start, d_end, d_annot, rows) chunks of device columns that hold at least the rows with lo < start < hi.
+    The step that makes a batch's matrix is a parameter (memo_amd/add.py puts new columns beside the ones read back): `columns`, the
+    matrix's width (default: N - 1), and matrix(d_cells, pitch, at, first, positions, remaining, d_dap), which writes int32
+    [positions][columns] at d_dap from positions [first, first + positions) of the slice's planes; `at` is the batch's first position
+    in the record (default: memo_convert_dap_dev).  What builder.push_dev(d_dap, positions) returns is what is yielded."""
     from .lengths import _DevBuffer, _pitch, _slices
     L_ = lib()
     cap = min(length, L_MAX)
     reach = length + cap
     slices = _slices(0, length, n_docs, slice_positions)              # from the right
-    batch = default_batch_positions(n_docs) if batch_positions is None else batch_positions
+    columns = n_docs - 1 if columns is None else columns
+    if matrix is None:
+        def matrix(d_cells, pitch, at, first, positions, remaining, d_dap):
+            check(L_.memo_convert_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_dap, device, None))
+    batch = default_batch_positions(columns + 1) if batch_positions is None else batch_positions
     longest = max(b - a for a, b in slices)
     with _DevBuffer(device, 4 * n_docs * _pitch(longest)) as cells, _DevBuffer(device, 8 * n_docs if len(slices) > 1 else 0) as carry, \
-            _DevBuffer(device, 4 * (n_docs - 1) * min(batch, longest)) as d_dap:
+            _DevBuffer(device, 4 * columns * min(batch, longest)) as d_dap:
         saved = {}
         if len(slices) > 1:                                            # pass A: every slice's carry, from the right
             none = np.full(n_docs, _NO_CARRY, np.int64)
@@ -175,7 +183,7 @@ def _record_rows(feed, length, n_docs, builder, device, slice_positions, batch_p
             check(L_.memo_lengths_finish_dev(cells.d, Ls, pitch, n_docs, cap, device, None))
             for first in range(0, Ls, batch):
                 positions = min(batch, Ls - first)
-                check(L_.memo_convert_dap_dev(cells.d, pitch, n_docs, first, positions, length - a - first, d_dap.d, device, None))
+                matrix(cells.d, pitch, a + first, first, positions, length - a - first, d_dap.d)
                 yield builder.push_dev(d_dap.d, positions)
 
 

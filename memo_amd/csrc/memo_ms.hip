@@ -1389,6 +1389,23 @@ int memo_ms_push_dap(memo_ms_t *h, memo_dap_t *dap, int64_t first, int64_t posit
     return memo_dap_push_dev(dap, h->M.p + first * h->C, positions, out_rows);
 }
 
+int memo_ms_rows_dev(memo_ms_t *h, int64_t first, int64_t positions, const int32_t **d_rows) {
+    if (!h || !d_rows) return fail(MEMO_EINVAL, "NULL argument");
+    if (first < 0 || positions < 0 || first + positions > h->npos)
+        return fail(MEMO_EINVAL, "positions [%lld, %lld) outside the pivot's %lld", (long long)first,
+                    (long long)(first + positions), (long long)h->npos);
+    *d_rows = nullptr;
+    if (!positions) return MEMO_OK;
+    if (h->layout == MEMO_MS_LAYOUT_CODED) {  // decoded and waited for before the caller reads it
+        DeviceGuard guard(h->device);
+        if (int rc = decode_rows(h, first, positions, nullptr)) return rc;
+        *d_rows = h->stage.p;
+        return MEMO_OK;
+    }
+    *d_rows = h->M.p + first * h->C;
+    return MEMO_OK;
+}
+
 int memo_ms_layout_info(memo_ms_t *h, memo_ms_layout_info_t *info) {
     if (!h || !info) return fail(MEMO_EINVAL, "NULL argument");
     memset(info, 0, sizeof *info);

@@ -160,20 +160,39 @@ def convert(dap_path, fai_path, order, overlap, device=0):
             conv.close()
 
 
+class RowWriter:
+    """the index file `memo index` ends with, one row batch at a time: columns f0 utf8, f1 f2 f3 int64, ZSTD
+    (parquet_compress_bed.py:19-38); .rows: the rows written so far"""
+
+    def __init__(self, out_path, codec="ZSTD"):
+        import pyarrow as pa
+        import pyarrow.parquet as pq
+        self._schema = pa.schema([("f0", pa.utf8()), ("f1", pa.int64()), ("f2", pa.int64()), ("f3", pa.int64())])
+        self._w = pq.ParquetWriter(out_path, self._schema, compression=codec)
+        self.rows = 0
+
+    def write(self, names, batch):
+        import pyarrow as pa
+        rec, start, end, annot = batch
+        if len(rec):
+            f0 = pa.DictionaryArray.from_arrays(pa.array(rec, pa.int32()), pa.array(names, pa.utf8())).cast(pa.utf8())
+            self._w.write_table(pa.table({"f0": f0, "f1": start, "f2": end, "f3": annot.astype(np.int64)}, schema=self._schema))
+            self.rows += len(rec)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self._w.close()
+
+
 def write_parquet(out_path, batches, codec="ZSTD"):
-    """(names, (rec, start, end, annot)) row batches -> the index file `memo index` ends with: columns f0 utf8,
-    f1 f2 f3 int64, ZSTD (parquet_compress_bed.py:19-38).  Returns the number of rows."""
-    import pyarrow as pa
-    import pyarrow.parquet as pq
-    schema = pa.schema([("f0", pa.utf8()), ("f1", pa.int64()), ("f2", pa.int64()), ("f3", pa.int64())])
-    rows = 0
-    with pq.ParquetWriter(out_path, schema, compression=codec) as w:
-        for names, (rec, start, end, annot) in batches:
-            if len(rec):
-                f0 = pa.DictionaryArray.from_arrays(pa.array(rec, pa.int32()), pa.array(names, pa.utf8())).cast(pa.utf8())
-                w.write_table(pa.table({"f0": f0, "f1": start, "f2": end, "f3": annot.astype(np.int64)}, schema=schema))
-                rows += len(rec)
-    return rows
+    """(names, (rec, start, end, annot)) row batches -> the index file `memo index` ends with (RowWriter).  Returns the
+    number of rows."""
+    with RowWriter(out_path, codec) as w:
+        for names, batch in batches:
+            w.write(names, batch)
+    return w.rows
 
 
 def dap_to_parquet(dap_path, fai_path, out_path, order, device=0, codec="ZSTD"):
