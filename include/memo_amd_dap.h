@@ -1,5 +1,5 @@
 /*
- * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix`, the curves of `memo collect`, the lengths of `memo maxk`, the per-genome lengths of `memo lengths` and the matrix `memo convert` makes of them: off the query path.
+ * memo_amd_dap.h -- index-row construction (the dap_to_bed.py step of `memo index`) the reader of `memo view`, the runs of `memo regions`, the matrix of `memo matrix`, the curves of `memo collect`, the lengths of `memo maxk`, the per-genome lengths of `memo lengths` and the matrices `memo convert`, `memo add` and `memo merge` make of them: off the query path.
  * Part of the C ABI of libmemo_amd.so (see memo_amd.h for conventions: plain C types, 0 or a negative
  * code, memo_last_error()).
  */
@@ -344,6 +344,24 @@ int memo_add_dap_dev(const uint32_t *d_cells, int64_t pitch, int32_t num_docs, i
                      const int32_t *d_new, int32_t new_cols, int32_t *d_dap, int32_t device, void *stream);
 /* positions per tile of that kernel (tiles lie at multiples of it in the plane), for tests that want lengths around it */
 int32_t memo_add_tile(void);
+
+/* ---- `memo merge`: an index of chosen genomes from indexes on one pivot (no counterpart in the reference) ------------------------------
+ * (Declared here, after the `memo add` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The row builder's matrix through a column map (memo_amd/csrc/memo_merge.hip): d_cells holds `planes` planes stacked with one pitch
+ * (uint32 [planes][pitch] on `device`, 16-byte aligned, pitch a multiple of 4: the blocks of several memo_lengths_*_dev runs one after
+ * another), d_plane_of `cols` int32 on `device`, 4-byte aligned: the plane of every column.  With room = remaining - i:
+ *     d_dap[i][c] = min( d_cells[d_plane_of[c]][first + i], room )            0 <= i < positions, 0 <= c < cols        int32 [positions][cols]
+ * A plane may be named by any number of columns; nothing is skipped (the caller leaves the pivots' planes out of the map).  An entry
+ * outside [0, planes) reads nothing and its column is 0: no content of the map makes the call read outside the planes.  Nothing is read
+ * outside [first, first + positions) of a named plane or outside the `cols` entries of the map; nothing is written outside the
+ * positions * cols integers of d_dap, each of which is written once.  MEMO_EINVAL before anything is launched: planes outside
+ * [1, 65 536], cols outside [1, 2047], pitch % 4 != 0, first + positions > pitch, remaining < positions, remaining > 2^31 - 1, d_cells
+ * not 16-byte aligned, d_plane_of or d_dap not 4-byte aligned, a negative count, a NULL pointer with positions > 0.  positions == 0
+ * launches nothing.  Blocking (synchronises `stream`). */
+int memo_merge_dap_dev(const uint32_t *d_cells, int64_t pitch, int32_t planes, const int32_t *d_plane_of, int32_t cols, int64_t first,
+                       int64_t positions, int64_t remaining, int32_t *d_dap, int32_t device, void *stream);
+/* positions per tile of that kernel (tiles lie at multiples of it in the plane), for tests that want lengths around it */
+int32_t memo_merge_tile(void);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,8 @@ Layout (only what the path needs):
   convert_cli.py   `memo convert`: flags, usage, the Parquet index written beside its name and renamed
   add.py           `memo add`: new genomes' matching statistics beside a membership index's lengths, fed to the row builder once
   add_cli.py       `memo add`: flags, usage, the grown membership and conservation indexes written beside their names and renamed
+  merge.py         `memo merge`: the lengths of chosen genomes of one or more membership indexes on one pivot, fed to the row builder once
+  merge_cli.py     `memo merge`: flags (per input and for the outputs), usage, the indexes and the genome list written beside their names
 
 Attributes are loaded on first use (PEP 562), so that `import memo_amd._fastquery` -- the CLI's cache-hit
 path -- does not pay for NumPy.
@@ -46,6 +48,7 @@ _LAZY = {
     "region_planes": "lengths", "region_kth": "lengths",
     "convert_index": "convert",
     "add_index": "add",
+    "merge_index": "merge",
 }
 
 
@@ -55,7 +58,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "convert", "convert_cli", "add", "add_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

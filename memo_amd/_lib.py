@@ -140,6 +140,8 @@ SYMBOLS = {
     "memo_convert_tile": (_I32, []),
     "memo_add_dap_dev": (C.c_int, [_P, _I64, _I32, _I64, _I64, _I64, _P, _I32, _P, _I32, _P]),
     "memo_add_tile": (_I32, []),
+    "memo_merge_dap_dev": (C.c_int, [_P, _I64, _I32, _P, _I32, _I64, _I64, _I64, _P, _I32, _P]),
+    "memo_merge_tile": (_I32, []),
     "memo_emit_u32_rows": (_SZ, [_P, _I64, _I64, _I32, _P, _SZ]),
     "memo_emit_u32_rows_threads": (_I32, [_I64, _I32]),
     "memo_emit_runs": (_SZ, [C.c_char_p, _I64, _I64, _P, _P, _U64, _P, _SZ]),
