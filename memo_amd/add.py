@@ -29,7 +29,7 @@ import re
 import numpy as np
 
 from ._lib import MemoError, check, lib
-from .convert import L_MAX, _RowBuilder, _docs, _record_rows, _setting, check_rows, record_length, scan_index
+from .convert import L_MAX, _Builders, _dap, _docs, _record_rows, _same_file, _setting, check_rows, record_length, scan_index
 
 N_MAX = 2048                 # genomes after the addition, the pivot included
 HOLD_BYTES = 2 << 30         # new genomes whose FASTA files are larger together are read twice: once to refuse, once to add
@@ -50,27 +50,6 @@ def _sizes(n_docs, new):
     if n_docs + new > N_MAX:
         raise ValueError(f"{n_docs} genomes and {new} new ones are {n_docs + new}: the limit is {N_MAX}")
     return _docs(n_docs), new
-
-
-class _Builders:
-    """one row builder per requested output, all fed the same matrix"""
-
-    def __init__(self, columns, rec_begin, orders, device):
-        self._stack = contextlib.ExitStack()
-        try:
-            self._each = [self._stack.enter_context(_RowBuilder(columns, rec_begin, order, device)) for order in orders]
-        except BaseException:
-            self._stack.close()
-            raise
-
-    def push_dev(self, d_dap, positions):
-        return [b.push_dev(d_dap, positions) for b in self._each]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self._stack.close()
 
 
 def _add_genomes(ms, genomes, piece_bytes, label=lambda j: f"new genome {j}"):
@@ -94,7 +73,7 @@ def _grown_rows(ms, base, feed, length, n_docs, builders, device, slice_position
         d_new = C.c_void_p()
         check(L_.memo_ms_rows_dev(ms._h, base + at, positions, C.byref(d_new)))
         check(L_.memo_add_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_new, new, d_dap, device, None))
-    return _record_rows(feed, length, n_docs, builders, device, slice_positions, batch_positions, columns=n_docs - 1 + new, matrix=matrix)
+    return _record_rows([(feed, n_docs)], length, builders, device, slice_positions, batch_positions, n_docs - 1 + new, matrix)
 
 
 def rows(start, end, annot, n_docs, record, genomes, *, order=True, device=0, slice_positions=None, batch_positions=None,
@@ -142,29 +121,10 @@ def dap(planes, new, first, positions, remaining, device=0, pitch=None):
     if new.shape[0] != positions:
         raise ValueError(f"new has {new.shape[0]} rows for {positions} positions")
     n_docs, m = _sizes(planes.shape[0], new.shape[1])
-    L = planes.shape[1]
-    pitch = (L + 3) & ~3 if pitch is None else int(pitch)
-    if pitch < L:
-        raise ValueError("pitch is below the planes' length")
-    from .lengths import _DevBuffer
-    padded = np.zeros((n_docs, pitch), np.uint32)
-    padded[:, :L] = planes
-    out = np.empty((positions, n_docs - 1 + m), np.int32)
-    with _DevBuffer(device, max(padded.nbytes, 16)) as cells, _DevBuffer(device, max(new.nbytes, 16)) as d_new, \
-            _DevBuffer(device, max(out.nbytes, 16)) as d_out:
-        for d, host in ((cells, padded), (d_new, new)):
-            if host.nbytes:
-                check(lib().memo_dev_upload(device, d.d, host.ctypes.data, host.nbytes, None))
-        check(lib().memo_add_dap_dev(cells.d, pitch, n_docs, int(first), positions, int(remaining), d_new.d, m, d_out.d, device, None))
-        if out.nbytes:
-            check(lib().memo_dev_download(device, out.ctypes.data, d_out.d, out.nbytes, None))
-    return out
 
-
-def _same_file(a, b):
-    if os.path.exists(a) and os.path.exists(b):
-        return os.path.samefile(a, b)
-    return os.path.abspath(a) == os.path.abspath(b)
+    def call(d_cells, pitch, d_new, first, positions, remaining, d_out):
+        return lib().memo_add_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_new, m, d_out, device, None)
+    return _dap(call, n_docs - 1 + m, planes, first, positions, remaining, device, pitch, new)
 
 
 def _match_pivot(in_path, n_docs, pivot_path):
@@ -199,7 +159,7 @@ def add_index(in_path, genome_list, n_docs, out_path=None, cons_path=None, devic
     from .build_index import MatchingStatistics, _layout_number, read_fasta, read_genome_list
     from .dap_to_bed import RowWriter
     from .lengths import _region_feed
-    from .view_cli import _replace_into
+    from .view_cli import _replace_all_into
     outputs = [(path, order) for path, order in ((out_path, False), (cons_path, True)) if path]
     if not outputs:
         raise ValueError("no output: give the membership index's path, the conservation index's, or both")
@@ -243,12 +203,5 @@ def add_index(in_path, genome_list, n_docs, out_path=None, cons_path=None, devic
         return [w.rows for w in writers]
 
     written = []
-
-    def nest(at, tmps):
-        """every output beside its name; renamed from the last to the first once all are whole"""
-        if at == len(outputs):
-            written.extend(write(tmps))
-        else:
-            _replace_into(outputs[at][0], lambda tmp: nest(at + 1, tmps + [tmp]))
-    nest(0, [])
+    _replace_all_into([path for path, _ in outputs], lambda tmps: written.extend(write(tmps)))
     return {"positions": int(rec_begin[-1]), "new": new, "rows": written}

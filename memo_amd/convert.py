@@ -20,6 +20,7 @@ more than one slice runs in two passes over its rows:
 One memo_dap_t serves a whole file: the records follow one another without a gap, and a slice never straddles a record.  The result
 depends neither on the slice nor on the batch length.  One device.  The flags are memo_amd/convert_cli.py.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -137,54 +138,117 @@ class _RowBuilder:
         self._conv.close()
 
 
-def _record_rows(feed, length, n_docs, builder, device, slice_positions, batch_positions, columns=None, matrix=None):
-    """Yields the (rec, start, end, annot) rows of one record of `length` positions, batch by batch, in the index's order.  feed(lo, hi)
-    yields (d_start, d_end, d_annot, rows) chunks of device columns that hold at least the rows with lo < start < hi.
-    The step that makes a batch's matrix is a parameter (memo_amd/add.py puts new columns beside the ones read back): `columns`, the
-    matrix's width (default: N - 1), and matrix(d_cells, pitch, at, first, positions, remaining, d_dap), which writes int32
-    [positions][columns] at d_dap from positions [first, first + positions) of the slice's planes; `at` is the batch's first position
-    in the record (default: memo_convert_dap_dev).  What builder.push_dev(d_dap, positions) returns is what is yielded."""
+class _Builders:
+    """one row builder per requested output, all fed the same matrix"""
+
+    def __init__(self, columns, rec_begin, orders, device):
+        self._stack = contextlib.ExitStack()
+        try:
+            self._each = [self._stack.enter_context(_RowBuilder(columns, rec_begin, order, device)) for order in orders]
+        except BaseException:
+            self._stack.close()
+            raise
+
+    def push_dev(self, d_dap, positions):
+        return [b.push_dev(d_dap, positions) for b in self._each]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._stack.close()
+
+
+def _same_file(a, b):
+    if os.path.exists(a) and os.path.exists(b):
+        return os.path.samefile(a, b)
+    return os.path.abspath(a) == os.path.abspath(b)
+
+
+def _record_rows(sources, length, builder, device, slice_positions, batch_positions, columns, matrix):
+    """Yields what builder.push_dev(d_dap, positions) returns for one record of `length` positions, batch by batch, in the index's
+    order.  sources = [(feed, n_docs), ...]: feed(lo, hi) yields (d_start, d_end, d_annot, rows) chunks of device columns that hold at
+    least that source's rows with lo < start < hi.  The sources' planes lie stacked in one buffer with one pitch, source s in planes
+    [base_s, base_s + N_s), each with its own carries; the slices are cut for the sum of the N_s.
+    The step that makes a batch's matrix is the caller's: `columns`, the matrix's width, and matrix(d_cells, pitch, at, first,
+    positions, remaining, d_dap), which writes int32 [positions][columns] at d_dap from positions [first, first + positions) of the
+    slice's stack; `at` is the batch's first position in the record."""
     from .lengths import _DevBuffer, _pitch, _slices
     L_ = lib()
+    sizes = [n for _, n in sources]
+    total = sum(sizes)
+    bases = np.concatenate([[0], np.cumsum(sizes)]).tolist()
     cap = min(length, L_MAX)
     reach = length + cap
-    slices = _slices(0, length, n_docs, slice_positions)              # from the right
-    columns = n_docs - 1 if columns is None else columns
-    if matrix is None:
-        def matrix(d_cells, pitch, at, first, positions, remaining, d_dap):
-            check(L_.memo_convert_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_dap, device, None))
+    slices = _slices(0, length, total, slice_positions)               # from the right; cut for the whole stack
     batch = default_batch_positions(columns + 1) if batch_positions is None else batch_positions
     longest = max(b - a for a, b in slices)
-    with _DevBuffer(device, 4 * n_docs * _pitch(longest)) as cells, _DevBuffer(device, 8 * n_docs if len(slices) > 1 else 0) as carry, \
+    with _DevBuffer(device, 4 * total * _pitch(longest)) as cells, _DevBuffer(device, 8 * total if len(slices) > 1 else 0) as carry, \
             _DevBuffer(device, 4 * columns * min(batch, longest)) as d_dap:
         saved = {}
-        if len(slices) > 1:                                            # pass A: every slice's carry, from the right
-            none = np.full(n_docs, _NO_CARRY, np.int64)
-            check(L_.memo_dev_upload(device, carry.d, none.ctypes.data, none.nbytes, None))
-            for chunk in feed(length, reach):                          # (the rows right of the record: none in an index `memo index` wrote)
-                check(L_.memo_lengths_carry_dev(*chunk, length, reach, n_docs, carry.d, device, None))
-            for a, b in slices:
-                saved[a] = np.empty(n_docs, np.int64)
-                check(L_.memo_dev_download(device, saved[a].ctypes.data, carry.d, saved[a].nbytes, None))
-                if a:                                                  # (nothing lies left of the first slice)
-                    for chunk in feed(a, b + 1):
-                        check(L_.memo_lengths_carry_dev(*chunk, a, b + 1, n_docs, carry.d, device, None))
+        if len(slices) > 1:                                            # pass A: every slice's carry, from the right, source by source
+            for s, (feed, n) in enumerate(sources):
+                d_carry = carry.at(8 * bases[s])
+                none = np.full(n, _NO_CARRY, np.int64)
+                check(L_.memo_dev_upload(device, d_carry, none.ctypes.data, none.nbytes, None))
+                for chunk in feed(length, reach):                      # (the rows right of the record: none in an index `memo index` wrote)
+                    check(L_.memo_lengths_carry_dev(*chunk, length, reach, n, d_carry, device, None))
+                for a, b in slices:
+                    saved[s, a] = np.empty(n, np.int64)
+                    check(L_.memo_dev_download(device, saved[s, a].ctypes.data, d_carry, saved[s, a].nbytes, None))
+                    if a:                                              # (nothing lies left of the first slice)
+                        for chunk in feed(a, b + 1):
+                            check(L_.memo_lengths_carry_dev(*chunk, a, b + 1, n, d_carry, device, None))
         for a, b in slices[::-1]:                                      # pass B: the planes, left to right
             Ls, pitch = b - a, _pitch(b - a)
-            if len(slices) > 1:
-                check(L_.memo_dev_upload(device, carry.d, saved[a].ctypes.data, saved[a].nbytes, None))
-                check(L_.memo_lengths_begin_dev(cells.d, Ls, pitch, n_docs, cap, a, carry.d, device, None))
-                chunks = feed(a, b + 1)
-            else:                                                      # the whole record: the row pass's own filter is the definition's
-                check(L_.memo_lengths_begin_dev(cells.d, Ls, pitch, n_docs, cap, a, None, device, None))
-                chunks = feed(0, reach)
-            for chunk in chunks:
-                check(L_.memo_lengths_rows_dev(*chunk, a, Ls, pitch, n_docs, cap, cells.d, device, None))
-            check(L_.memo_lengths_finish_dev(cells.d, Ls, pitch, n_docs, cap, device, None))
+            for s, (feed, n) in enumerate(sources):
+                block = cells.at(4 * bases[s] * pitch)                 # (pitch % 4 == 0: every block is 16-byte aligned)
+                if len(slices) > 1:
+                    d_carry = carry.at(8 * bases[s])
+                    check(L_.memo_dev_upload(device, d_carry, saved[s, a].ctypes.data, saved[s, a].nbytes, None))
+                    check(L_.memo_lengths_begin_dev(block, Ls, pitch, n, cap, a, d_carry, device, None))
+                    chunks = feed(a, b + 1)
+                else:                                                  # the whole record: the row pass's own filter is the definition's
+                    check(L_.memo_lengths_begin_dev(block, Ls, pitch, n, cap, a, None, device, None))
+                    chunks = feed(0, reach)
+                for chunk in chunks:
+                    check(L_.memo_lengths_rows_dev(*chunk, a, Ls, pitch, n, cap, block, device, None))
+                check(L_.memo_lengths_finish_dev(block, Ls, pitch, n, cap, device, None))
             for first in range(0, Ls, batch):
                 positions = min(batch, Ls - first)
                 matrix(cells.d, pitch, a + first, first, positions, length - a - first, d_dap.d)
                 yield builder.push_dev(d_dap.d, positions)
+
+
+def _converted_rows(feed, length, n_docs, builder, device, slice_positions, batch_positions):
+    """_record_rows of one source, its N - 1 columns as they lie (convert_dap_kernel)"""
+    def matrix(d_cells, pitch, at, first, positions, remaining, d_dap):
+        check(lib().memo_convert_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_dap, device, None))
+    return _record_rows([(feed, n_docs)], length, builder, device, slice_positions, batch_positions, n_docs - 1, matrix)
+
+
+def _dap(call, width, planes, first, positions, remaining, device, pitch, side=None):
+    """One planes-to-matrix kernel alone on host values: the uint32 planes [P, L], padded to `pitch` (default: L rounded up to 4), and
+    the kernel's other host array `side` (or None) go up, call(d_cells, pitch, d_side, first, positions, remaining, d_out) runs, and
+    int32 [positions, width] comes back."""
+    from .lengths import _DevBuffer
+    count, L = planes.shape
+    pitch = (L + 3) & ~3 if pitch is None else int(pitch)
+    if pitch < L:
+        raise ValueError("pitch is below the planes' length")
+    padded = np.zeros((count, pitch), np.uint32)
+    padded[:, :L] = planes
+    positions = int(positions)
+    out = np.empty((max(positions, 0), width), np.int32)
+    with _DevBuffer(device, max(padded.nbytes, 16)) as cells, _DevBuffer(device, 0 if side is None else max(side.nbytes, 16)) as d_side, \
+            _DevBuffer(device, max(out.nbytes, 16)) as d_out:
+        for d, host in ((cells, padded), (d_side, side)):
+            if host is not None and host.nbytes:
+                check(lib().memo_dev_upload(device, d.d, host.ctypes.data, host.nbytes, None))
+        check(call(cells.d, pitch, d_side.d, int(first), positions, int(remaining), d_out.d))
+        if out.nbytes:
+            check(lib().memo_dev_download(device, out.ctypes.data, d_out.d, out.nbytes, None))
+    return out
 
 
 def rows(start, end, annot, n_docs, *, length=None, order=True, device=0, slice_positions=None, batch_positions=None):
@@ -204,7 +268,7 @@ def rows(start, end, annot, n_docs, *, length=None, order=True, device=0, slice_
         from .lengths import _host_feed
         feed, buf = _host_feed(*cols, None, device, (0, L + min(L, L_MAX)))
         with buf, _RowBuilder(n_docs - 1, [0, L], order, device) as builder:
-            for _rec, s, e, a in _record_rows(feed, L, n_docs, builder, device, slice_positions, batch_positions):
+            for _rec, s, e, a in _converted_rows(feed, L, n_docs, builder, device, slice_positions, batch_positions):
                 for column, part in zip(out, (s, e, a)):
                     column.append(part.astype(np.int64))
     return tuple(np.concatenate(column) for column in out)
@@ -216,21 +280,11 @@ def dap(planes, first, positions, remaining, device=0, pitch=None):
     planes = np.asarray(planes, np.uint32)
     if planes.ndim != 2:
         raise ValueError("planes must be [n_docs, positions]")
-    n_docs, L = _docs(planes.shape[0]), planes.shape[1]
-    pitch = (L + 3) & ~3 if pitch is None else int(pitch)
-    if pitch < L:
-        raise ValueError("pitch is below the planes' length")
-    from .lengths import _DevBuffer
-    padded = np.zeros((n_docs, pitch), np.uint32)
-    padded[:, :L] = planes
-    out = np.empty((max(int(positions), 0), n_docs - 1), np.int32)
-    with _DevBuffer(device, max(padded.nbytes, 16)) as cells, _DevBuffer(device, max(out.nbytes, 16)) as d_out:
-        if padded.nbytes:
-            check(lib().memo_dev_upload(device, cells.d, padded.ctypes.data, padded.nbytes, None))
-        check(lib().memo_convert_dap_dev(cells.d, pitch, n_docs, int(first), int(positions), int(remaining), d_out.d, device, None))
-        if out.nbytes:
-            check(lib().memo_dev_download(device, out.ctypes.data, d_out.d, out.nbytes, None))
-    return out
+    n_docs = _docs(planes.shape[0])
+
+    def call(d_cells, pitch, _d_side, first, positions, remaining, d_out):
+        return lib().memo_convert_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_out, device, None)
+    return _dap(call, n_docs - 1, planes, first, positions, remaining, device, pitch)
 
 
 def scan_index(in_path, n_docs, fai=None):
@@ -285,7 +339,7 @@ def convert_index(in_path, out_path, n_docs, order=True, fai=None, device=0, log
         for name, L in kept:
             feed, buf = _region_feed(in_path, name, device)
             with buf:
-                for part in _record_rows(feed, L, n_docs, builder, device, slice_positions, batch_positions):
+                for part in _converted_rows(feed, L, n_docs, builder, device, slice_positions, batch_positions):
                     yield names, part
             log(f"{name}: {L} positions")
 

@@ -26,12 +26,10 @@ import contextlib
 import numpy as np
 
 from ._lib import check, lib
-from .add import _Builders, _same_file
-from .convert import L_MAX, _docs, _setting, check_rows, default_batch_positions, record_length, scan_index
+from .convert import L_MAX, _Builders, _dap, _docs, _record_rows, _same_file, _setting, check_rows, record_length, scan_index
 
 N_MAX = 2048                 # genomes of one input, and of the output, the pivot included
 PLANES_MAX = 65536           # genomes of all inputs together, their pivots included
-_NO_CARRY = np.iinfo(np.int64).max
 
 
 def tile():
@@ -90,56 +88,20 @@ def _plan(sizes, selections):
     return sizes, chosen, plane_of
 
 
-def _merged_rows(feeds, length, sizes, plane_of, builders, device, slice_positions, batch_positions):
-    """convert._record_rows over several sources: yields what builders.push_dev returns for one record of `length` positions, batch by
-    batch, in the index's order.  feeds[s](lo, hi) yields (d_start, d_end, d_annot, rows) chunks of input s that hold at least its rows
-    with lo < start < hi; sizes[s] is its N_s; plane_of names the plane of every output column in the stack of all inputs."""
-    from .lengths import _DevBuffer, _pitch, _slices
+@contextlib.contextmanager
+def _mapped(sizes, plane_of, device):
+    """The column map on the device for a run: yields (columns, matrix), _record_rows' batch step through merge_dap_kernel.  sizes: the
+    N_s of the sources whose planes make the stack; plane_of names the plane of every output column in it."""
+    from .lengths import _DevBuffer
     L_ = lib()
     total, width = int(sum(sizes)), len(plane_of)
-    bases = np.concatenate([[0], np.cumsum(sizes)]).tolist()
-    cap = min(length, L_MAX)
-    reach = length + cap
-    slices = _slices(0, length, total, slice_positions)               # from the right; cut for the whole stack
-    batch = default_batch_positions(width + 1) if batch_positions is None else batch_positions
-    longest = max(b - a for a, b in slices)
     plane_of = np.ascontiguousarray(plane_of, np.int32)
-    with _DevBuffer(device, 4 * total * _pitch(longest)) as cells, _DevBuffer(device, 8 * total if len(slices) > 1 else 0) as carry, \
-            _DevBuffer(device, 4 * width) as d_map, _DevBuffer(device, 4 * width * min(batch, longest)) as d_dap:
+    with _DevBuffer(device, 4 * width) as d_map:
         check(L_.memo_dev_upload(device, d_map.d, plane_of.ctypes.data, plane_of.nbytes, None))
-        saved = {}
-        if len(slices) > 1:                                            # pass A: every slice's carry, from the right, input by input
-            for s, (feed, n) in enumerate(zip(feeds, sizes)):
-                d_carry = carry.at(8 * bases[s])
-                none = np.full(n, _NO_CARRY, np.int64)
-                check(L_.memo_dev_upload(device, d_carry, none.ctypes.data, none.nbytes, None))
-                for chunk in feed(length, reach):
-                    check(L_.memo_lengths_carry_dev(*chunk, length, reach, n, d_carry, device, None))
-                for a, b in slices:
-                    saved[s, a] = np.empty(n, np.int64)
-                    check(L_.memo_dev_download(device, saved[s, a].ctypes.data, d_carry, saved[s, a].nbytes, None))
-                    if a:                                              # (nothing lies left of the first slice)
-                        for chunk in feed(a, b + 1):
-                            check(L_.memo_lengths_carry_dev(*chunk, a, b + 1, n, d_carry, device, None))
-        for a, b in slices[::-1]:                                      # pass B: the planes, left to right
-            Ls, pitch = b - a, _pitch(b - a)
-            for s, (feed, n) in enumerate(zip(feeds, sizes)):
-                block = cells.at(4 * bases[s] * pitch)                 # (pitch % 4 == 0: every block is 16-byte aligned)
-                if len(slices) > 1:
-                    d_carry = carry.at(8 * bases[s])
-                    check(L_.memo_dev_upload(device, d_carry, saved[s, a].ctypes.data, saved[s, a].nbytes, None))
-                    check(L_.memo_lengths_begin_dev(block, Ls, pitch, n, cap, a, d_carry, device, None))
-                    chunks = feed(a, b + 1)
-                else:                                                  # the whole record: the row pass's own filter is the definition's
-                    check(L_.memo_lengths_begin_dev(block, Ls, pitch, n, cap, a, None, device, None))
-                    chunks = feed(0, reach)
-                for chunk in chunks:
-                    check(L_.memo_lengths_rows_dev(*chunk, a, Ls, pitch, n, cap, block, device, None))
-                check(L_.memo_lengths_finish_dev(block, Ls, pitch, n, cap, device, None))
-            for first in range(0, Ls, batch):
-                positions = min(batch, Ls - first)
-                check(L_.memo_merge_dap_dev(cells.d, pitch, total, d_map.d, width, first, positions, length - a - first, d_dap.d, device, None))
-                yield builders.push_dev(d_dap.d, positions)
+
+        def matrix(d_cells, pitch, at, first, positions, remaining, d_dap):
+            check(L_.memo_merge_dap_dev(d_cells, pitch, total, d_map.d, width, first, positions, remaining, d_dap, device, None))
+        yield width, matrix
 
 
 def rows(sources, length=None, *, order=True, device=0, slice_positions=None, batch_positions=None):
@@ -173,7 +135,8 @@ def rows(sources, length=None, *, order=True, device=0, slice_positions=None, ba
                 stack.enter_context(buf)
                 feeds.append(feed)
             builders = stack.enter_context(_Builders(len(plane_of), [0, L], [order], device))
-            for ((_rec, s, e, a),) in _merged_rows(feeds, L, sizes, plane_of, builders, device, slice_positions, batch_positions):
+            mapped = stack.enter_context(_mapped(sizes, plane_of, device))
+            for ((_rec, s, e, a),) in _record_rows(list(zip(feeds, sizes)), L, builders, device, slice_positions, batch_positions, *mapped):
                 for column, part in zip(out, (s, e, a)):
                     column.append(part.astype(np.int64))
     return tuple(np.concatenate(column) for column in out)
@@ -186,7 +149,7 @@ def dap(planes, plane_of, first, positions, remaining, device=0, pitch=None):
     planes = np.asarray(planes, np.uint32)
     if planes.ndim != 2:
         raise ValueError("planes must be [planes, positions]")
-    count, L = planes.shape
+    count = planes.shape[0]
     if not 1 <= count <= PLANES_MAX:
         raise ValueError(f"the planes must be 1 to {PLANES_MAX} (got {count})")
     plane_of = np.asarray(plane_of)
@@ -195,23 +158,10 @@ def dap(planes, plane_of, first, positions, remaining, device=0, pitch=None):
     if len(plane_of) and (plane_of.min() < -2 ** 31 or plane_of.max() > 2 ** 31 - 1):
         raise ValueError("plane_of must hold int32 values")
     plane_of = np.ascontiguousarray(plane_of, np.int32)
-    positions = max(int(positions), 0)
-    pitch = (L + 3) & ~3 if pitch is None else int(pitch)
-    if pitch < L:
-        raise ValueError("pitch is below the planes' length")
-    from .lengths import _DevBuffer
-    padded = np.zeros((count, pitch), np.uint32)
-    padded[:, :L] = planes
-    out = np.empty((positions, len(plane_of)), np.int32)
-    with _DevBuffer(device, max(padded.nbytes, 16)) as cells, _DevBuffer(device, max(plane_of.nbytes, 16)) as d_map, \
-            _DevBuffer(device, max(out.nbytes, 16)) as d_out:
-        for d, host in ((cells, padded), (d_map, plane_of)):
-            if host.nbytes:
-                check(lib().memo_dev_upload(device, d.d, host.ctypes.data, host.nbytes, None))
-        check(lib().memo_merge_dap_dev(cells.d, pitch, count, d_map.d, len(plane_of), int(first), positions, int(remaining), d_out.d, device, None))
-        if out.nbytes:
-            check(lib().memo_dev_download(device, out.ctypes.data, d_out.d, out.nbytes, None))
-    return out
+
+    def call(d_cells, pitch, d_map, first, positions, remaining, d_out):
+        return lib().memo_merge_dap_dev(d_cells, pitch, count, d_map, len(plane_of), first, positions, remaining, d_out, device, None)
+    return _dap(call, len(plane_of), planes, first, max(int(positions), 0), remaining, device, pitch, plane_of)
 
 
 def read_list(path, n_docs):
@@ -242,7 +192,7 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
     Returns {"positions", "genomes", "rows": [per output, -o first]}."""
     from .dap_to_bed import RowWriter
     from .lengths import _region_feed
-    from .view_cli import _replace_into
+    from .view_cli import _replace_all_into
     inputs = [tuple(i) + (None,) * (4 - len(i)) for i in inputs]
     outputs = [(path, order) for path, order in ((out_path, False), (cons_path, True)) if path]
     if not outputs:
@@ -286,6 +236,7 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
             writers = [stack.enter_context(RowWriter(tmp)) for tmp in tmps[:len(outputs)]]
             if kept:
                 builders = stack.enter_context(_Builders(len(plane_of), rec_begin, [order for _, order in outputs], device))
+                mapped = stack.enter_context(_mapped(sizes, plane_of, device))
             for name, L in kept:
                 with contextlib.ExitStack() as record:
                     feeds = []
@@ -293,7 +244,7 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
                         feed, buf = _region_feed(path, name, device)
                         record.enter_context(buf)
                         feeds.append(feed)
-                    for parts in _merged_rows(feeds, L, sizes, plane_of, builders, device, slice_positions, batch_positions):
+                    for parts in _record_rows(list(zip(feeds, sizes)), L, builders, device, slice_positions, batch_positions, *mapped):
                         for writer, part in zip(writers, parts):
                             writer.write(names, part)
                 log(f"{name}: {L} positions")
@@ -303,12 +254,5 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
         return [w.rows for w in writers]
 
     written = []
-
-    def nest(at, tmps):
-        """every file beside its name; renamed from the last to the first once all are whole"""
-        if at == len(written_paths):
-            written.extend(write(tmps))
-        else:
-            _replace_into(written_paths[at], lambda tmp: nest(at + 1, tmps + [tmp]))
-    nest(0, [])
+    _replace_all_into(written_paths, lambda tmps: written.extend(write(tmps)))
     return {"positions": int(rec_begin[-1]), "genomes": len(plane_of) + 1, "rows": written}

@@ -58,6 +58,17 @@ def _replace_into(path, write):
         raise
 
 
+def _replace_all_into(paths, write):
+    """write([tmp, ...]), one beside every path, and then rename from the last to the first: no file is replaced before all are
+    whole, and nothing is left behind"""
+    def nest(at, tmps):
+        if at == len(paths):
+            write(tmps)
+        else:
+            _replace_into(paths[at], lambda tmp: nest(at + 1, tmps + [tmp]))
+    nest(0, [])
+
+
 def write_tsv(table, path):
     """the table as text: one header line, rows in melt order, floats by repr"""
     def write(tmp):

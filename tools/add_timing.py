@@ -160,7 +160,7 @@ def main():
         t1 = time.perf_counter()
         rows = 0
         with buf, convert._RowBuilder(W, rec_begin, False, 0) as builder:
-            for part in convert._record_rows(feed, a.length, n, Push(builder), 0, None, None, columns=W, matrix=matrix):
+            for part in convert._record_rows([(feed, n)], a.length, Push(builder), 0, None, None, W, matrix):
                 rows += len(part[0])
         pipe_s = time.perf_counter() - t1
     whole = [i for i, p in enumerate(sizes) if p == max(sizes)]       # the batches of full length

@@ -7,7 +7,7 @@ In one process, on the index's own int64 columns (memo_index_columns), medians o
   - convert_dap_kernel and the memo_dap_push_dev it feeds, batch by batch as the product runs them (the default batch: a matrix of about
     128 MiB), each between a pair of events on the stream the library launches on.  Both calls block, so a pair holds the launches and the
     waits between them and nothing else.  The kernel against the time its 8 (N - 1) positions bytes take at 8 TB/s, and against the push;
-  - the whole device pipeline (memo_amd.convert._record_rows on the device columns: both passes, every batch's rows fetched to the host),
+  - the whole device pipeline (memo_amd.convert._converted_rows on the device columns: both passes, every batch's rows fetched to the host),
     launch to last row on the host clock.  No Parquet file is read or written here."""
 import argparse
 import ctypes as C
@@ -126,7 +126,7 @@ def main():
                 t0 = time.perf_counter()
                 total = 0
                 with convert._RowBuilder(n - 1, [0, M], order, 0) as builder:
-                    for part in convert._record_rows(feed, M, n, builder, 0, None, None):
+                    for part in convert._converted_rows(feed, M, n, builder, 0, None, None):
                         total += len(part[0])
                 print(f"-- the device pipeline, {'conservation' if order else 'membership'} order: {time.perf_counter() - t0:.2f} s on the host clock for "
                       f"{M} positions in {-(-M // step)} slices, {total} rows out (every slice's rows where they lie in device memory; no Parquet)", flush=True)

@@ -108,7 +108,7 @@ def main():
 
     # ---- the kernel beside convert_dap_kernel
     import torch  # (before the library: both then share one HIP runtime) -- the event pairs, and what the runtime says the device is
-    from memo_amd import _lib, add, convert, lengths, merge
+    from memo_amd import _lib, convert, lengths, merge
     lib, check = _lib.lib, _lib.check
 
     def timed(call):
@@ -197,8 +197,8 @@ def main():
     t1 = time.perf_counter()
     lib().memo_merge_dap_dev = timed_kernel
     try:
-        with bufs[0], bufs[1], add._Builders(W, [0, L], [False, True], 0) as builders:
-            for parts in merge._merged_rows(feeds, L, sizes_in, plane_of, Push(builders), 0, None, None):
+        with bufs[0], bufs[1], convert._Builders(W, [0, L], [False, True], 0) as builders, merge._mapped(sizes_in, plane_of, 0) as mapped:
+            for parts in convert._record_rows(list(zip(feeds, sizes_in)), L, Push(builders), 0, None, None, *mapped):
                 for i, part in enumerate(parts):
                     rows[i] += len(part[0])
     finally:
