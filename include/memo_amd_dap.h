@@ -312,6 +312,34 @@ size_t memo_emit_u32_rows(const uint32_t *planes, int64_t L, int64_t pitch, int3
  * MEMO_EMIT_THREADS, read per call; 0 for an empty text), for tests that want the threaded path and must know that they got it */
 int32_t memo_emit_u32_rows_threads(int64_t L, int32_t n);
 
+/* ---- `memo spectrum`: the conservation histogram of a window at every k, one pass (no counterpart in the reference) -----------------
+ * (Declared here, beside the `memo lengths` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * From the finished planes of the memo_lengths_*_dev calls, run with cap = KMAX (memo_amd/csrc/memo_spectrum.hip): d_cells is uint32
+ * [N][pitch] on `device`, genome-major, 16-byte aligned, pitch a multiple of 4 and at least L, N * pitch below 2^32; a cell above KMAX is
+ * taken as KMAX; the cells [L, pitch) of a plane are never read.  With num_docs = N in [1, 2048] and KMAX in [1, 1024]
+ *     sel_T[p]    = the T-th largest of d_cells[0 .. N)[p]                      mode 1: the planes of a membership index
+ *     sel_T[p]    = min{ d_cells[a][p] : 0 <= a < T }                           mode 0: the planes of a conservation index (annot = plane)
+ *     cons(p, k)  = max({ T : sel_T[p] >= k } + {0})                            1 <= k <= KMAX
+ *     exact[k][v] = #{ p : cons(p, k) = v }                                     0 <= v <= N
+ * For rows with end >= start exact[k] is the histogram of what `memo query -k k` writes for the window on a conservation index, and of
+ * the one-bit counts of what `memo query -m -k k` writes on a membership index.
+ *   scratch_bytes  the bytes of the scratch at that shape, (N + 1)(KMAX + 1) 64-bit counters (0: a shape outside the limits)
+ *   begin          zeroes the scratch
+ *   add            adds the L positions of one slice into the scratch; any number of calls, in any order; L == 0 launches nothing.  Every
+ *                  call of one begin ... finish takes the same N, KMAX and mode.
+ *   finish         writes d_exact, uint64 [KMAX][N + 1] on `device` (row k - 1 is k); the scratch is not changed, more adds may follow
+ *   tile           positions per tile of add at that shape (mode 0: 256; mode 1: 256, 128, 64 or 32; 0: a shape or a mode outside the
+ *                  limits), for tests that want lengths around it
+ * MEMO_EINVAL before anything is launched: N outside [1, 2048], KMAX outside [1, 1024], a mode other than 0 or 1, L > 2^31, pitch < L,
+ * pitch % 4 != 0, N * pitch >= 2^32, cells that are not 16-byte aligned, a scratch or a result that is NULL or not 8-byte aligned.
+ * Blocking (each call synchronises `stream`). */
+size_t memo_spectrum_scratch_bytes(int32_t num_docs, int32_t kmax);
+int memo_spectrum_begin_dev(uint64_t *d_scratch, int32_t num_docs, int32_t kmax, int32_t device, void *stream);
+int memo_spectrum_add_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t num_docs, int32_t kmax, int32_t mode, uint64_t *d_scratch,
+                          int32_t device, void *stream);
+int memo_spectrum_finish_dev(const uint64_t *d_scratch, int32_t num_docs, int32_t kmax, uint64_t *d_exact, int32_t device, void *stream);
+int32_t memo_spectrum_tile(int32_t num_docs, int32_t kmax, int32_t mode);
+
 /* ---- `memo convert`: a conservation index from a membership index (no counterpart in the reference) ----------------------------------
  * (Declared here, after the `memo lengths` block: memo_amd.h keeps to the query path's 44 entry points.)
  * The step between the planes of the memo_lengths_*_dev calls and memo_dap_push_dev (memo_amd/csrc/memo_convert.hip): positions

@@ -130,6 +130,12 @@ int memo_debug_collect_times(int32_t on, float *out2);
  * carry's cells), [1] the row pass, [2] the carry pass, [3] the tile minima, [4] their scan, [5] the apply launch of finish, [6] the
  * selection.  tools/lengths_timing.py reads them. */
 int memo_debug_lengths_times(int32_t on, float *out7);
+/* this THREAD's later memo_spectrum_add_dev / memo_spectrum_finish_dev calls put event pairs around their launches (on & 1; each launch
+ * is then waited for) and count the global atomics of an add in a device counter (on & 2: one more atomic beside each), or do neither
+ * (0).  out2 (may be NULL) receives the device milliseconds of the last timed add and finish; *private_table (may be NULL) whether the
+ * last add of this thread accumulated in the workgroup-private table in LDS (1) or merged equal updates per wave before global atomics
+ * (0; -1: no add yet); *atomics (may be NULL) the global atomics the last counted add issued.  tools/spectrum_timing.py reads them. */
+int memo_debug_spectrum_times(int32_t on, float *out2, int32_t *private_table, uint64_t *atomics);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,8 @@ Layout (only what the path needs):
   maxk_cli.py      `memo maxk`: flags, usage, one integer per line
   lengths.py       `memo lengths`: every genome's match length per position from a membership index, and the T-th largest, in slices
   lengths_cli.py   `memo lengths`: flags, usage, one integer per line or one per genome and line
+  spectrum.py      `memo spectrum`: a window's conservation histogram at every k from either kind of index, reduced on the GPU, in slices
+  spectrum_cli.py  `memo spectrum`: flags, usage, the table as tab-separated text
   convert.py       `memo convert`: a membership index's lengths fed to the row builder: the conservation index, or the canonical membership index
   convert_cli.py   `memo convert`: flags, usage, the Parquet index written beside its name and renamed
   add.py           `memo add`: new genomes' matching statistics beside a membership index's lengths, fed to the row builder once
@@ -46,6 +48,7 @@ _LAZY = {
     "region_curves": "collect",
     "region_maxk": "maxk", "index_maxk": "maxk",          # (maxk.maxk keeps its module's name: memo_amd.maxk is the module)
     "region_planes": "lengths", "region_kth": "lengths",
+    "region_exact": "spectrum",
     "convert_index": "convert",
     "add_index": "add",
     "merge_index": "merge",
@@ -58,7 +61,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

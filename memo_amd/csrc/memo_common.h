@@ -47,6 +47,10 @@ extern thread_local int g_collect_timed;  // memo_collect.hip (AB library, memo_
 extern thread_local float g_collect_ms[2];
 extern thread_local int g_lengths_timed;  // memo_lengths.hip (AB library, memo_debug_lengths_times: event pairs around the launches of the memo_lengths_*_dev calls)
 extern thread_local float g_lengths_ms[7];
+extern thread_local int g_spectrum_timed;  // memo_spectrum.hip (AB library, memo_debug_spectrum_times: bit 0 event pairs around the launches, bit 1 the global atomics counted)
+extern thread_local float g_spectrum_ms[2];
+extern thread_local int g_spectrum_private;
+extern thread_local uint64_t g_spectrum_atomics;
 double pinned_alloc_ms_total();  // memo_hostcore.cpp: time this process has spent allocating pinned staging slots (MEMO_TIMING)
 
 struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the current device

@@ -201,4 +201,12 @@ int memo_debug_lengths_times(int32_t on, float *out7) {
     return MEMO_OK;
 }
 
+int memo_debug_spectrum_times(int32_t on, float *out2, int32_t *private_table, uint64_t *atomics) {
+    g_spectrum_timed = on & 3;
+    if (out2) out2[0] = g_spectrum_ms[0], out2[1] = g_spectrum_ms[1];
+    if (private_table) *private_table = g_spectrum_private;
+    if (atomics) *atomics = g_spectrum_atomics;
+    return MEMO_OK;
+}
+
 }  // extern "C"
