@@ -239,6 +239,25 @@ int memo_collect_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, const 
 /* positions per tile at `words` genome words (512 up to 16 words, 256 up to 32, 128 above), for tests that want lengths around it */
 int32_t memo_collect_tile(int32_t words);
 
+/* ---- `memo tracks`: per-genome k-mer presence along the pivot, binned (no counterpart in the reference) -----------------
+ * (Declared here, beside the `memo collect` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The presence counts of a membership result that is still on `device` (memo_amd/csrc/memo_tracks.hip): d_bits as
+ * memo_cooccurrence_dev takes it (uint32 [L][W], 16-byte aligned, read from [0] to [L * W) and nowhere else, bits at or above
+ * num_docs masked); it holds the positions first .. first + L of a window.  edges_host is a HOST pointer, int64 [bins + 1], bin
+ * edges in the window's coordinates, non-decreasing (two equal edges are an empty bin, which counts nothing); the library uploads
+ * them itself.
+ *     d_counts[g][b] += #{p in [first, first + L) : edges[b] <= p < edges[b + 1] and bit g of row p - first is set}
+ * uint64 [num_docs][bins] on `device`, ADDED to (the caller zeroes it; the slices of a window and several windows accumulate, and
+ * the table does not depend on where the slices are cut).  MEMO_EINVAL before anything is launched: d_bits not 16-byte aligned,
+ * d_counts NULL or not 8-byte aligned, num_docs outside [1, 2048], bins outside [1, 2^20], edges that decrease somewhere,
+ * first < edges[0], first + L > edges[bins].  L == 0 launches nothing and leaves the table as it was.  Scratch memory on the device:
+ * the edges, (bins + 1) x 8 bytes, freed before the call returns; an allocation that fails returns MEMO_EHIP with the bytes asked
+ * for in memo_last_error and leaves nothing allocated.  Blocking. */
+int memo_tracks_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, int64_t first, const int64_t *edges_host, int32_t bins,
+                    uint64_t *d_counts, int32_t device, void *stream);
+/* positions per tile at `words` genome words (512 up to 16 words, 256 up to 32, 128 above), for tests that want lengths around it */
+int32_t memo_tracks_tile(int32_t words);
+
 /* ---- `memo maxk`: the longest shared k-mer per position, every k in one pass (no counterpart in the reference) ----------
  * (Declared here, beside the `memo matrix` block: memo_amd.h keeps to the query path's 44 entry points.)
  * For the window [qs, qs + L), a cap CAP in [1, 2^31 - 1] and a row predicate -- mode 0: 0 <= annot < arg ("fewer than arg genomes

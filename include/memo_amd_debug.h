@@ -113,6 +113,10 @@ int memo_debug_cooc_flush(int32_t way);
  * or do not (0); out2 (may be NULL) receives the device milliseconds of the last timed call: [0] the sweep launches, [1] the
  * reduce launches (0 with atomics: the flush is part of the sweep).  tools/matrix_timing.py reads them. */
 int memo_debug_cooc_times(int32_t on, float *out2);
+/* this THREAD's later memo_tracks_dev calls put an event pair around their launch (on = 1) or do not (0); out1 (may be NULL)
+ * receives the device milliseconds of the last timed call's kernel (the upload of the edges is not in them).
+ * tools/tracks_timing.py reads them. */
+int memo_debug_tracks_times(int32_t on, float *out1);
 /* this THREAD's later memo_maxk_rows_dev calls: how the rows' bounds reach the cells: 0 (the default, the product's way) =
  * wave-aggregated: a segmented min over the lanes that hit the same cell leaves one atomic min per run of equal cells and wave,
  * 1 = one atomic min per row (the A/B of DESIGN.md 10.5).  The cells are the same either way. */

@@ -20,6 +20,8 @@ Layout (only what the path needs):
   matrix_cli.py    `memo matrix`: flags, usage, counts or Jaccard distances as tab-separated text
   collect.py       `memo collect`: core and covered k-mer curves over genome orders, reduced on the GPU, a window's in slices
   collect_cli.py   `memo collect`: flags, usage, the curve, the band over random orders or every order as tab-separated text
+  tracks.py        `memo tracks`: every genome's k-mer presence per bin along the pivot, counted on the GPU, a window's in slices
+  tracks_cli.py    `memo tracks`: flags, usage, counts or fractions as tab-separated text, or the heat map (matplotlib)
   maxk.py          `memo maxk`: the longest shared k per position, all k in one pass over the rows, a window's from a Parquet index
   maxk_cli.py      `memo maxk`: flags, usage, one integer per line
   lengths.py       `memo lengths`: every genome's match length per position from a membership index, and the T-th largest, in slices
@@ -46,6 +48,7 @@ _LAZY = {
     "runs": "regions", "membership_runs": "regions", "region_runs": "regions",
     "cooccurrence": "matrix", "region_matrix": "matrix",
     "region_curves": "collect",
+    "bin_tracks": "tracks", "region_tracks": "tracks",
     "region_maxk": "maxk", "index_maxk": "maxk",          # (maxk.maxk keeps its module's name: memo_amd.maxk is the module)
     "region_planes": "lengths", "region_kth": "lengths",
     "region_exact": "spectrum",
@@ -61,7 +64,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

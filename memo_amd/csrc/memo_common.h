@@ -45,6 +45,8 @@ extern thread_local int g_maxk_timed;     // ... memo_debug_maxk_times: event pa
 extern thread_local float g_maxk_ms[5];
 extern thread_local int g_collect_timed;  // memo_collect.hip (AB library, memo_debug_collect_times: event pairs around the launches of memo_collect_dev)
 extern thread_local float g_collect_ms[2];
+extern thread_local int g_tracks_timed;  // memo_tracks.hip (AB library, memo_debug_tracks_times: an event pair around the launch of memo_tracks_dev)
+extern thread_local float g_tracks_ms;
 extern thread_local int g_lengths_timed;  // memo_lengths.hip (AB library, memo_debug_lengths_times: event pairs around the launches of the memo_lengths_*_dev calls)
 extern thread_local float g_lengths_ms[7];
 extern thread_local int g_spectrum_timed;  // memo_spectrum.hip (AB library, memo_debug_spectrum_times: bit 0 event pairs around the launches, bit 1 the global atomics counted)

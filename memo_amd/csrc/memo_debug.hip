@@ -175,6 +175,12 @@ int memo_debug_cooc_times(int32_t on, float *out2) {
     return MEMO_OK;
 }
 
+int memo_debug_tracks_times(int32_t on, float *out1) {
+    g_tracks_timed = on ? 1 : 0;
+    if (out1) out1[0] = g_tracks_ms;
+    return MEMO_OK;
+}
+
 int memo_debug_maxk_rows(int32_t way) {
     if (way < 0 || way > 1) return fail(MEMO_EINVAL, "maxk row pass: 0 wave-aggregated atomics, 1 one atomic per row");
     g_maxk_rows_way = way;
