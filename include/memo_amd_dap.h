@@ -331,6 +331,31 @@ size_t memo_emit_u32_rows(const uint32_t *planes, int64_t L, int64_t pitch, int3
  * MEMO_EMIT_THREADS, read per call; 0 for an empty text), for tests that want the threaded path and must know that they got it */
 int32_t memo_emit_u32_rows_threads(int64_t L, int32_t n);
 
+/* ---- `memo mems`: the maximal shared matches of a window, compacted on the device (no counterpart in the reference) -------------------
+ * (Declared here, beside the `memo lengths` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * From finished lengths that are still on the device (memo_amd/csrc/memo_mems.hip): d_cells is uint32 [planes][pitch] on `device`, L
+ * cells per plane read -- the planes of the memo_lengths_*_dev calls; the cells of the memo_maxk_*_dev calls and the output of
+ * memo_lengths_select_dev are one plane.  With v the cells of one plane, a cap CAP in [1, 2^31 - 1] and min_len in [1, CAP]:
+ *   key 1  cell i is reported when v[i] >= min_len and (i == 0 ? halo == 0 : v[i - 1] < v[i] || (v[i - 1] == v[i] && v[i] < CAP)):
+ *          the matches that start in the plane, a run at CAP once, at its first cell.  halo = 0: cell 0 is position 0 of its record;
+ *          halo = 1: cell 0 is only the neighbour of cell 1 and is never reported.  d_starts[r] = i, d_lengths[r] = v[i].
+ *   key 2  the cells at which v[i] >= min_len changes, the cell before cell 0 counting as false: d_starts alone (d_lengths may be NULL
+ *          and is set to NULL); in a plane 2j opens an interval, 2j + 1 closes it, an odd count leaves the last to end at L.  halo is 0.
+ * The entries are plane-major and ascending within a plane; counts[pl] (a HOST array of `planes` entries) receives plane pl's number
+ * of them.  *d_starts and *d_lengths are allocated on `device` to exactly the total (memo_dev_free; NULL where the total is 0); an
+ * allocation that fails is MEMO_EHIP with the bytes asked for, and nothing stays allocated.  MEMO_EINVAL before anything is launched: a
+ * key other than 1 or 2, a halo other than 0 or 1 or a halo with key 2, planes < 0, L < 0 or above 2^31, pitch < L, pitch % 4 != 0, CAP
+ * or min_len outside their ranges, cells that are not 16-byte aligned, more than 2^31 - 1 tiles, an output that is NULL.  L == 0 or
+ * planes == 0 launches nothing.  Nothing outside [0, L) of a plane is read: the cells [L, pitch) never are.  Blocking. */
+int memo_mems_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t planes, uint32_t cap, uint32_t min_len, int32_t key,
+                  int32_t halo, uint32_t **d_starts, uint32_t **d_lengths, uint64_t *counts, int32_t device, void *stream);
+/* cells per tile of the passes (a tile never crosses a plane), for tests that want lengths around it */
+int32_t memo_mems_tile(void);
+/* the text of `memo mems`: per entry record '\t' start '\t' end, and '\t' genome[i] where genome is not NULL, then '\n'; no entries is no
+ * text at all.  Returns the number of bytes the text needs; it is written only if it fits in cap (nothing is written past cap). */
+size_t memo_emit_intervals(const char *record, const int64_t *starts, const int64_t *ends, const int32_t *genome, uint64_t entries,
+                           char *buf, size_t cap);
+
 /* ---- `memo spectrum`: the conservation histogram of a window at every k, one pass (no counterpart in the reference) -----------------
  * (Declared here, beside the `memo lengths` block: memo_amd.h keeps to the query path's 44 entry points.)
  * From the finished planes of the memo_lengths_*_dev calls, run with cap = KMAX (memo_amd/csrc/memo_spectrum.hip): d_cells is uint32

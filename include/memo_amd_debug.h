@@ -140,6 +140,10 @@ int memo_debug_lengths_times(int32_t on, float *out7);
  * last add of this thread accumulated in the workgroup-private table in LDS (1) or merged equal updates per wave before global atomics
  * (0; -1: no add yet); *atomics (may be NULL) the global atomics the last counted add issued.  tools/spectrum_timing.py reads them. */
 int memo_debug_spectrum_times(int32_t on, float *out2, int32_t *private_table, uint64_t *atomics);
+/* this THREAD's later memo_mems_dev calls put event pairs around their launches (on = 1; each launch is then waited for) or do not
+ * (0); out3 (may be NULL) receives the device milliseconds of the last timed call: [0] the count pass, [1] the scan and the gather of
+ * the plane bases, [2] the scatter pass.  tools/mems_timing.py reads them. */
+int memo_debug_mems_times(int32_t on, float *out3);
 
 #ifdef __cplusplus
 }

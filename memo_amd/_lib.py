@@ -138,6 +138,9 @@ SYMBOLS = {
     "memo_lengths_select_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, _I32, _P, _I32, _P]),
     "memo_lengths_tile": (_I32, []),
     "memo_lengths_select_tile": (_I32, [_I32]),
+    "memo_mems_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, C.c_uint32, _I32, _I32, C.POINTER(_P), C.POINTER(_P), _P, _I32, _P]),
+    "memo_mems_tile": (_I32, []),
+    "memo_emit_intervals": (_SZ, [C.c_char_p, _P, _P, _P, _U64, _P, _SZ]),
     "memo_spectrum_scratch_bytes": (_SZ, [_I32, _I32]),
     "memo_spectrum_begin_dev": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "memo_spectrum_add_dev": (C.c_int, [_P, _I64, _I64, _I32, _I32, _I32, _P, _I32, _P]),
@@ -224,6 +227,7 @@ DEBUG_SYMBOLS = {
     "memo_debug_collect_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_lengths_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_spectrum_times": (C.c_int, [_I32, C.POINTER(C.c_float), C.POINTER(_I32), C.POINTER(_U64)]),
+    "memo_debug_mems_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_ms_piece_text": (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _I64, C.POINTER(_I64)]),
 }
 

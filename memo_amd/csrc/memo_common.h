@@ -49,6 +49,8 @@ extern thread_local int g_tracks_timed;  // memo_tracks.hip (AB library, memo_de
 extern thread_local float g_tracks_ms;
 extern thread_local int g_lengths_timed;  // memo_lengths.hip (AB library, memo_debug_lengths_times: event pairs around the launches of the memo_lengths_*_dev calls)
 extern thread_local float g_lengths_ms[7];
+extern thread_local int g_mems_timed;  // memo_mems.hip (AB library, memo_debug_mems_times: event pairs around the launches of memo_mems_dev)
+extern thread_local float g_mems_ms[3];
 extern thread_local int g_spectrum_timed;  // memo_spectrum.hip (AB library, memo_debug_spectrum_times: bit 0 event pairs around the launches, bit 1 the global atomics counted)
 extern thread_local float g_spectrum_ms[2];
 extern thread_local int g_spectrum_private;

@@ -215,4 +215,11 @@ int memo_debug_spectrum_times(int32_t on, float *out2, int32_t *private_table, u
     return MEMO_OK;
 }
 
+int memo_debug_mems_times(int32_t on, float *out3) {
+    g_mems_timed = on ? 1 : 0;
+    if (out3)
+        for (int i = 0; i < 3; ++i) out3[i] = g_mems_ms[i];
+    return MEMO_OK;
+}
+
 }  // extern "C"

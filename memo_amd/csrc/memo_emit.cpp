@@ -282,6 +282,28 @@ size_t memo_emit_u32(const uint32_t *vec, int64_t L, char *buf, size_t cap) {
                       });
 }
 
+// ---- `memo mems`: REC start end [genome] per entry (include/memo_amd_dap.h); no line at all for no entries ----
+size_t memo_emit_intervals(const char *record, const int64_t *starts, const int64_t *ends, const int32_t *genome, uint64_t entries,
+                           char *buf, size_t cap) {
+    const size_t rlen = strlen(record);
+    return emit_lines((int64_t)entries, 1 << 17, buf, cap,
+                      [&](int64_t i) { return rlen + digits(starts[i]) + digits(ends[i]) + 3 + (genome ? 1 + digits(genome[i]) : 0); },
+                      [&](char *p, int64_t i) {
+                          memcpy(p, record, rlen);
+                          p += rlen;
+                          *p++ = '\t';
+                          p = put(p, starts[i]);
+                          *p++ = '\t';
+                          p = put(p, ends[i]);
+                          if (genome) {
+                              *p++ = '\t';
+                              p = put(p, genome[i]);
+                          }
+                          *p++ = '\n';
+                          return p;
+                      });
+}
+
 // ---- `memo lengths -a`: n unsigned integers per line out of genome-major planes (include/memo_amd_dap.h).  A thread walks its lines in
 // blocks of kBlock positions, genome by genome inside a block, so that every plane is read in runs of kBlock values ----
 int32_t memo_emit_u32_rows_threads(int64_t L, int32_t n) { return L <= 0 || n <= 0 ? 0 : (int32_t)emit_threads(L * (int64_t)n, 1 << 20); }

@@ -87,34 +87,40 @@ class _DevBuffer:
         self.close()
 
 
-def _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions):
+def _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0):
     """Yields (a, b, d_cells, pitch) for every slice [a, b) of the window, from the right, its planes finished on the device (they
     are the next slice's cells once the consumer comes back).  feed(lo, hi) yields (d_start, d_end, d_annot, rows) chunks of device
-    columns that hold at least the rows with lo < start < hi."""
+    columns that hold at least the rows with lo < start < hi.  halo=1: every slice with a > 0 has one more cell on its left, the
+    true lengths of position a - 1 (its planes begin at a - 1: the slice is begun there and fed the rows a - 1 < start <= b, the carry
+    still takes the rows a < start <= b); a slice at a = 0 has nothing on its left and none."""
+    if halo not in (0, 1):
+        raise ValueError("halo must be 0 or 1")
     qe = qs + L
     slices = _slices(qs, L, n_docs, slice_positions)
     if not slices:
         return
     L_ = lib()
-    longest = max(b - a for a, b in slices)
+    longest = max(b - a for a, b in slices) + halo
     with _DevBuffer(device, 4 * n_docs * _pitch(longest)) as cells, _DevBuffer(device, 8 * n_docs if len(slices) > 1 else 0) as carry:
         reach = min(qe + cap, 2 ** 62)
         if len(slices) == 1:            # the whole window: the row pass itself takes qs < start < qe + cap
-            check(L_.memo_lengths_begin_dev(cells.d, L, _pitch(L), n_docs, cap, qs, None, device, None))
-            for chunk in feed(qs, reach):
-                check(L_.memo_lengths_rows_dev(*chunk, qs, L, _pitch(L), n_docs, cap, cells.d, device, None))
-            check(L_.memo_lengths_finish_dev(cells.d, L, _pitch(L), n_docs, cap, device, None))
-            yield qs, qe, cells.d, _pitch(L)
+            h = halo if qs > 0 else 0
+            check(L_.memo_lengths_begin_dev(cells.d, L + h, _pitch(L + h), n_docs, cap, qs - h, None, device, None))
+            for chunk in feed(qs - h, reach):
+                check(L_.memo_lengths_rows_dev(*chunk, qs - h, L + h, _pitch(L + h), n_docs, cap, cells.d, device, None))
+            check(L_.memo_lengths_finish_dev(cells.d, L + h, _pitch(L + h), n_docs, cap, device, None))
+            yield qs, qe, cells.d, _pitch(L + h)
             return
         none = np.full(n_docs, _NO_CARRY, np.int64)
         check(L_.memo_dev_upload(device, carry.d, none.ctypes.data, none.nbytes, None))
         for chunk in feed(qe, reach):   # the tail: the rows right of the window
             check(L_.memo_lengths_carry_dev(*chunk, qe, reach, n_docs, carry.d, device, None))
         for a, b in slices:             # before [a, b) the carry holds the rows with b < start < qe + cap
-            Ls, pitch = b - a, _pitch(b - a)
-            check(L_.memo_lengths_begin_dev(cells.d, Ls, pitch, n_docs, cap, a, carry.d, device, None))
-            for chunk in feed(a, b + 1):
-                check(L_.memo_lengths_rows_dev(*chunk, a, Ls, pitch, n_docs, cap, cells.d, device, None))
+            h = halo if a > 0 else 0
+            Ls, pitch = b - a + h, _pitch(b - a + h)
+            check(L_.memo_lengths_begin_dev(cells.d, Ls, pitch, n_docs, cap, a - h, carry.d, device, None))
+            for chunk in feed(a - h, b + 1):
+                check(L_.memo_lengths_rows_dev(*chunk, a - h, Ls, pitch, n_docs, cap, cells.d, device, None))
                 check(L_.memo_lengths_carry_dev(*chunk, a, b + 1, n_docs, carry.d, device, None))
             check(L_.memo_lengths_finish_dev(cells.d, Ls, pitch, n_docs, cap, device, None))
             yield a, b, cells.d, pitch
@@ -231,17 +237,19 @@ def _region(region, cap):
     return (record, *_window(qs, qe, cap))
 
 
-def region_slices(index_path, region, n_docs, cap=CAP_MAX, device=0, slice_positions=None):
-    """The planes of a window of a Parquet membership index, slice by slice FROM THE RIGHT: yields (a, b, uint32 [n_docs, b - a]).
+def region_slices(index_path, region, n_docs, cap=CAP_MAX, device=0, slice_positions=None, halo=0):
+    """The planes of a window of a Parquet membership index, slice by slice FROM THE RIGHT: yields (a, b, uint32 [n_docs, b - a]);
+    with halo=1 a slice with a > 0 has the lengths of position a - 1 as one more column on its left.
     The rows stream out of the file row group by row group (memo_query.region_chunks: first the tail qe < start < qe + cap, then
     every slice's own rows), each chunk through one reused device buffer.  No sidecar cache is read or built."""
     n_docs = _docs(n_docs)
     record, qs, L, cap = _region(region, cap)
     feed, buf = _region_feed(index_path, record, device)
     with buf:
-        for a, b, d_cells, pitch in _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions):
-            part = np.empty((n_docs, b - a), np.uint32)
-            _download_planes(part, a, a, b, d_cells, pitch, n_docs, device)
+        for a, b, d_cells, pitch in _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo):
+            h = halo if a > 0 else 0
+            part = np.empty((n_docs, b - a + h), np.uint32)
+            _download_planes(part, a - h, a - h, b, d_cells, pitch, n_docs, device)
             yield a, b, part
 
 
