@@ -3,6 +3,9 @@
 Layout (only what the path needs):
   csrc/            HIP kernels for gfx950 + the C ABI (include/memo_amd*.h)
   _lib.py          ctypes binding of libmemo_amd.so -- raises if the library is missing
+  _device.py       for the drivers below: DevBuffer, the one owner of a device allocation; RowBuffer; on_device; emit_text
+  _window.py       for the drivers below: parse_region (CHR:START-END), membership_slices (a window swept slice by slice)
+  _cli.py          for the NAME_cli.py below: usage, refusals, the flags, the device, the error tail, the output file
   index.py         DeviceIndex: an index chromosome resident in HBM; IndexBuilder; sweep launches
   memo_query.py    host-side mirror of the reference's src/memo_query.py (same function
                    names and argument meaning: filter_pq, memo_init, memo_query, print_res)
@@ -67,7 +70,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

@@ -29,7 +29,7 @@ import re
 import numpy as np
 
 from ._lib import MemoError, check, lib
-from .convert import L_MAX, _Builders, _dap, _docs, _record_rows, _same_file, _setting, check_rows, record_length, scan_index
+from .convert import L_MAX, Builders, check_rows, dap_of, docs, record_length, record_rows, same_file, scan_index, setting
 
 N_MAX = 2048                 # genomes after the addition, the pivot included
 HOLD_BYTES = 2 << 30         # new genomes whose FASTA files are larger together are read twice: once to refuse, once to add
@@ -49,7 +49,7 @@ def _sizes(n_docs, new):
         raise ValueError("no new genome: needs the pivot and at least one new genome")
     if n_docs + new > N_MAX:
         raise ValueError(f"{n_docs} genomes and {new} new ones are {n_docs + new}: the limit is {N_MAX}")
-    return _docs(n_docs), new
+    return docs(n_docs), new
 
 
 def _add_genomes(ms, genomes, piece_bytes, label=lambda j: f"new genome {j}"):
@@ -66,14 +66,14 @@ def _add_genomes(ms, genomes, piece_bytes, label=lambda j: f"new genome {j}"):
 
 
 def _grown_rows(ms, base, feed, length, n_docs, builders, device, slice_positions, batch_positions):
-    """_record_rows of one record whose first position is `base` in the pivot of `ms`, the new columns beside the old"""
+    """record_rows of one record whose first position is `base` in the pivot of `ms`, the new columns beside the old"""
     L_, new = lib(), ms.columns
 
     def matrix(d_cells, pitch, at, first, positions, remaining, d_dap):
         d_new = C.c_void_p()
         check(L_.memo_ms_rows_dev(ms._h, base + at, positions, C.byref(d_new)))
         check(L_.memo_add_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_new, new, d_dap, device, None))
-    return _record_rows([(feed, n_docs)], length, builders, device, slice_positions, batch_positions, n_docs - 1 + new, matrix)
+    return record_rows([(feed, n_docs)], length, builders, device, slice_positions, batch_positions, n_docs - 1 + new, matrix)
 
 
 def rows(start, end, annot, n_docs, record, genomes, *, order=True, device=0, slice_positions=None, batch_positions=None,
@@ -83,7 +83,7 @@ def rows(start, end, annot, n_docs, record, genomes, *, order=True, device=0, sl
     of record sequences (bytes).  Returns the (start, end, annot) int64 columns of the record's rows in the index of n_docs +
     len(genomes) genomes: the conservation rows (order=True) or the membership rows in canonical form (order=False)."""
     from .build_index import MatchingStatistics, pivot_layout
-    from .lengths import _host_feed
+    from .lengths import host_feed
     genomes = [[("", bytes(s)) for s in g] for g in genomes]
     n_docs, new = _sizes(n_docs, len(genomes))
     cols = [np.ascontiguousarray(c, np.int64) for c in (start, end, annot)]
@@ -96,13 +96,13 @@ def rows(start, end, annot, n_docs, record, genomes, *, order=True, device=0, sl
     _names, pivot, rec_begin = pivot_layout([("record", bytes(record))])
     if L != len(pivot):
         raise ValueError(f"the largest row start is {L}, the record has {len(pivot)} positions")
-    slice_positions = _setting(slice_positions, "MEMO_ADD_SLICE", "slice_positions")
-    batch_positions = _setting(batch_positions, "MEMO_ADD_BATCH", "batch_positions")
+    slice_positions = setting(slice_positions, "MEMO_ADD_SLICE", "slice_positions")
+    batch_positions = setting(batch_positions, "MEMO_ADD_BATCH", "batch_positions")
     out = [[np.empty(0, np.int64)] for _ in range(3)]
-    feed, buf = _host_feed(*cols, None, device, (0, L + min(L, L_MAX)))
+    feed, buf = host_feed(*cols, None, device, (0, L + min(L, L_MAX)))
     with buf, MatchingStatistics(pivot, rec_begin, new, device, 0, layout, walk_budget) as ms:
         _add_genomes(ms, genomes, piece_bytes)
-        with _Builders(n_docs - 1 + new, rec_begin, [order], device) as builders:
+        with Builders(n_docs - 1 + new, rec_begin, [order], device) as builders:
             for ((_rec, s, e, a),) in _grown_rows(ms, 0, feed, L, n_docs, builders, device, slice_positions, batch_positions):
                 for column, part in zip(out, (s, e, a)):
                     column.append(part.astype(np.int64))
@@ -124,7 +124,7 @@ def dap(planes, new, first, positions, remaining, device=0, pitch=None):
 
     def call(d_cells, pitch, d_new, first, positions, remaining, d_out):
         return lib().memo_add_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_new, m, d_out, device, None)
-    return _dap(call, n_docs - 1 + m, planes, first, positions, remaining, device, pitch, new)
+    return dap_of(call, n_docs - 1 + m, planes, first, positions, remaining, device, pitch, new)
 
 
 def _match_pivot(in_path, n_docs, pivot_path):
@@ -158,8 +158,8 @@ def add_index(in_path, genome_list, n_docs, out_path=None, cons_path=None, devic
     Returns {"positions", "new", "rows": [per output, -o first]}."""
     from .build_index import MatchingStatistics, _layout_number, read_fasta, read_genome_list
     from .dap_to_bed import RowWriter
-    from .lengths import _region_feed
-    from .view_cli import _replace_all_into
+    from ._cli import replace_all_into
+    from .lengths import region_feed
     outputs = [(path, order) for path, order in ((out_path, False), (cons_path, True)) if path]
     if not outputs:
         raise ValueError("no output: give the membership index's path, the conservation index's, or both")
@@ -167,12 +167,12 @@ def add_index(in_path, genome_list, n_docs, out_path=None, cons_path=None, devic
     n_docs, new = _sizes(n_docs, len(paths) - 1)
     _layout_number(layout)
     for path, _ in outputs:
-        if _same_file(in_path, path):
+        if same_file(in_path, path):
             raise ValueError(f"{path} is the input file")
-    if len(outputs) == 2 and _same_file(outputs[0][0], outputs[1][0]):
+    if len(outputs) == 2 and same_file(outputs[0][0], outputs[1][0]):
         raise ValueError(f"{outputs[0][0]} is named for both outputs")
-    slice_positions = _setting(None, "MEMO_ADD_SLICE", "MEMO_ADD_SLICE")
-    batch_positions = _setting(None, "MEMO_ADD_BATCH", "MEMO_ADD_BATCH")
+    slice_positions = setting(None, "MEMO_ADD_SLICE", "MEMO_ADD_SLICE")
+    batch_positions = setting(None, "MEMO_ADD_BATCH", "MEMO_ADD_BATCH")
     names, pivot, rec_begin = _match_pivot(in_path, n_docs, paths[0])
     hold = sum(os.path.getsize(p) for p in paths[1:]) <= HOLD_BYTES
     held = []
@@ -191,9 +191,9 @@ def add_index(in_path, genome_list, n_docs, out_path=None, cons_path=None, devic
             ms = stack.enter_context(MatchingStatistics(pivot, rec_begin, new, device, 0, layout, walk_budget))
             _add_genomes(ms, genomes(), piece_bytes, lambda j: paths[1 + j])
             writers = [stack.enter_context(RowWriter(tmp)) for tmp in tmps]
-            builders = stack.enter_context(_Builders(n_docs - 1 + new, rec_begin, [order for _, order in outputs], device))
+            builders = stack.enter_context(Builders(n_docs - 1 + new, rec_begin, [order for _, order in outputs], device))
             for r, name in enumerate(names):                           # in FASTA order
-                feed, buf = _region_feed(in_path, name, device)
+                feed, buf = region_feed(in_path, name, device)
                 with buf:
                     for parts in _grown_rows(ms, int(rec_begin[r]), feed, int(rec_begin[r + 1] - rec_begin[r]), n_docs, builders, device,
                                              slice_positions, batch_positions):
@@ -203,5 +203,5 @@ def add_index(in_path, genome_list, n_docs, out_path=None, cons_path=None, devic
         return [w.rows for w in writers]
 
     written = []
-    _replace_all_into([path for path, _ in outputs], lambda tmps: written.extend(write(tmps)))
+    replace_all_into([path for path, _ in outputs], lambda tmps: written.extend(write(tmps)))
     return {"positions": int(rec_begin[-1]), "new": new, "rows": written}

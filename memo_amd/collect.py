@@ -16,9 +16,10 @@ import ctypes as C
 
 import numpy as np
 
+from ._device import DevBuffer, on_device
 from ._lib import check, lib
+from ._window import membership_slices, parse_region
 from .index import words
-from .regions import _on_device
 
 
 def tile(words_per_position=1):
@@ -49,27 +50,12 @@ def _as_orders(order_rows):
     return np.ascontiguousarray(rows, np.uint16)
 
 
-def _curve_on_device(shape, start, device):
-    """a device array uint64 [P, M] holding `start` (None: zeros)"""
+def _curve(shape, start):
+    """`start` as a host array uint64 [P, M] (None: zeros)"""
     host = np.zeros(shape, np.uint64) if start is None else np.ascontiguousarray(start, np.uint64)
     if host.shape != tuple(shape):
         raise ValueError(f"a starting curve must be {list(shape)}")
-    d = C.c_void_p()
-    check(lib().memo_dev_malloc(device, max(host.nbytes, 8), C.byref(d)))
-    try:
-        if host.nbytes:
-            check(lib().memo_dev_upload(device, d, host.ctypes.data, host.nbytes, None))
-    except BaseException:
-        lib().memo_dev_free(device, d)
-        raise
-    return d
-
-
-def _curve_to_host(d_curve, shape, device):
-    out = np.empty(shape, np.uint64)
-    if out.nbytes:
-        check(lib().memo_dev_download(device, out.ctypes.data, d_curve, out.nbytes, None))
-    return out
+    return host
 
 
 def _accumulate(d_bits, L, num_docs, order_rows, d_core, d_covered, device, stream=None):
@@ -87,30 +73,10 @@ def curves(bits, num_docs, orders, core=None, covered=None, device=0, stream=Non
     rows = _as_orders(orders)
     if not isinstance(bits, tuple):
         bits = np.ascontiguousarray(bits, np.uint32).reshape(-1, W)
-    d_core = _curve_on_device(rows.shape, core, device)
-    try:
-        d_covered = _curve_on_device(rows.shape, covered, device)
-        try:
-            d_bits, L, tmp = _on_device(bits, np.uint32, device)
-            try:
-                _accumulate(d_bits, L, num_docs, rows, d_core, d_covered, device, stream)
-            finally:
-                if tmp is not None:
-                    lib().memo_dev_free(device, tmp)
-            return _curve_to_host(d_core, rows.shape, device), _curve_to_host(d_covered, rows.shape, device)
-        finally:
-            lib().memo_dev_free(device, d_covered)
-    finally:
-        lib().memo_dev_free(device, d_core)
-
-
-def parse_region(region):
-    """(record, start, end) of CHR:START-END as `memo query -r` takes it; what is wrong with it raises what memo_query.main raises"""
-    record, start_end = region.split(':')                  # exactly one ':' and one '-'
-    qs, qe = map(int, start_end.split('-'))
-    if qe < qs:
-        raise ValueError("negative dimensions are not allowed")          # np.zeros of memo_init, as `memo query` raises it
-    return record, qs, qe
+    with DevBuffer.of(_curve(rows.shape, core), device) as d_core, DevBuffer.of(_curve(rows.shape, covered), device) as d_covered, \
+            on_device(bits, np.uint32, device) as (d_bits, L):
+        _accumulate(d_bits, L, num_docs, rows, d_core.d, d_covered.d, device, stream)
+        return d_core.to_host(rows.shape, np.uint64), d_covered.to_host(rows.shape, np.uint64)
 
 
 def region_curves(index_path, region, k, n_docs, orders, device=0, slice_positions=1 << 24):
@@ -120,34 +86,15 @@ def region_curves(index_path, region, k, n_docs, orders, device=0, slice_positio
     the slices.  One device.  Returns (core, covered), uint64 [P, M] each; orders without a step (N = 1) or without a row touch no
     device."""
     from . import memo_query
-    if slice_positions < 1:
-        raise ValueError("slice_positions must be at least 1")
     record, qs, qe = parse_region(region)
     rows = _as_orders(orders)
     if not rows.size:
         return np.zeros(rows.shape, np.uint64), np.zeros(rows.shape, np.uint64)
     index = memo_query.region_index(index_path, record, qs, qe + k, device=device, k=k, num_docs=n_docs, membership=True)
-    with index:
-        step = min(int(slice_positions), max(qe - qs, 1))
-        d_core = _curve_on_device(rows.shape, None, device)
-        try:
-            d_covered = _curve_on_device(rows.shape, None, device)
-            try:
-                d_bits = C.c_void_p()
-                check(lib().memo_dev_malloc(device, step * 4 * words(n_docs), C.byref(d_bits)))
-                try:
-                    for s in range(qs, qe, step):
-                        e = min(s + step, qe)
-                        index.membership_slice_dev(qs, qe, s, e, k, n_docs, d_bits.value)
-                        index.check()
-                        _accumulate(d_bits, e - s, n_docs, rows, d_core, d_covered, device)
-                finally:
-                    lib().memo_dev_free(device, d_bits)
-                return _curve_to_host(d_core, rows.shape, device), _curve_to_host(d_covered, rows.shape, device)
-            finally:
-                lib().memo_dev_free(device, d_covered)
-        finally:
-            lib().memo_dev_free(device, d_core)
+    with index, DevBuffer.of(_curve(rows.shape, None), device) as d_core, DevBuffer.of(_curve(rows.shape, None), device) as d_covered:
+        for d_bits, s, e in membership_slices(index, qs, qe, k, n_docs, slice_positions, device):
+            _accumulate(d_bits, e - s, n_docs, rows, d_core.d, d_covered.d, device)
+        return d_core.to_host(rows.shape, np.uint64), d_covered.to_host(rows.shape, np.uint64)
 
 
 def format_curves(L, core, covered, form="curve", orders=None, labels=None):

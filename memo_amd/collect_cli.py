@@ -6,11 +6,7 @@ them -- for the index order 1 .. N - 1, or with -p over random orders, as a band
 order.  The window is swept as `memo query -m` sweeps it, in slices, each slice is reduced where it lies (memo_amd/collect.py,
 memo_amd/csrc/memo_collect.hip), and only the curves leave the device.  One GPU.
 """
-import getopt
-import os
-import sys
-
-from .matrix_cli import label_of
+from . import _cli
 
 USAGE = """
 MEMO collect - core and covered k-mers of a pivot genome region as genomes are added (collector's curve)
@@ -29,52 +25,17 @@ Basic options:
 
 """
 
-
-def usage():
-    sys.stdout.write(USAGE)
-    sys.exit(0)
-
-
-def refuse(message, status=1):
-    sys.stderr.write(f"memo collect: {message}\n")
-    sys.exit(status)
-
-
-def read_labels(path, n_docs):
-    try:
-        with open(path) as fh:
-            lines = [ln.strip() for ln in fh if ln.strip()]
-    except OSError as exc:
-        refuse(f"cannot read the genome list {path}: {exc.strerror}")
-    if len(lines) != n_docs:
-        refuse(f"-g {path} names {len(lines)} genomes, -n says {n_docs}")
-    return [label_of(ln) for ln in lines]
+cli = _cli.Cli("collect", USAGE, "b:k:n:r:o:p:s:ag:", {"-k": "31", "-p": "0", "-s": "0"})
+refuse, read_labels = cli.refuse, cli.read_labels
 
 
 def main(argv):
     """bin/memo collect [options]: usage handling as the other sub-commands (getopts messages on stderr, then the usage, exit 0)"""
-    if not argv or argv[0] == "-h":
-        usage()
-    try:
-        opts, _ = getopt.getopt(argv, "b:k:n:r:o:p:s:ag:")
-    except getopt.GetoptError as exc:
-        what = "option requires an argument" if "requires argument" in exc.msg else "illegal option"
-        sys.stderr.write(f"{sys.argv[0]}: {what} -- {exc.opt}\n")
-        usage()
-    val = {"-k": "31", "-p": "0", "-s": "0"}
-    for o, a in opts:
-        val[o] = a
-    print("MEMO - collect", flush=True)
+    val = cli.parse(argv)
     # everything that can be refused is refused before the device is touched
-    missing = [f for f in ("-b", "-r", "-n", "-o") if val.get(f, "") == ""]
-    if missing:
-        refuse(f"{', '.join(missing)} required", 2)
-    if int(os.environ.get("WORLD_SIZE", "1") or "1") > 1 or os.environ.get("MEMO_FORCE_SHARDED"):
-        refuse("one GPU only: a sharded launch (WORLD_SIZE > 1, MEMO_FORCE_SHARDED) is not supported")
-    try:
-        n_docs, k, perms, seed = int(val["-n"]), int(val["-k"]), int(val["-p"]), int(val["-s"])
-    except ValueError as exc:
-        refuse(str(exc))
+    cli.require(val, ("-b", "-r", "-n", "-o"))
+    cli.one_gpu_only()
+    n_docs, k, perms, seed = cli.integers(val, "-n", "-k", "-p", "-s")
     if perms < 0:
         refuse(f"-p {perms}: the number of random orders cannot be negative")
     form = "curve" if perms == 0 else "long" if "-a" in val else "band"
@@ -82,20 +43,11 @@ def main(argv):
         refuse("-g names the genome a line adds: a band over random orders (-p without -a) has none")
     labels = read_labels(val["-g"], n_docs) if "-g" in val else None
     from . import collect
-    from ._lib import MemoError
-    from .view_cli import _replace_into
-    try:
-        device = int(os.environ.get("MEMO_DEVICE", "0"))   # as `memo query` chooses its GPU
+
+    def run():
+        device = _cli.device()
         _, qs, qe = collect.parse_region(val["-r"])
         order_rows = collect.orders(n_docs, perms, seed)
         core, covered = collect.region_curves(val["-b"], val["-r"], k, n_docs, order_rows, device)
-        text = collect.format_curves(qe - qs, core, covered, form, order_rows, labels)
-
-        def write(tmp):
-            with open(tmp, "w") as fh:
-                fh.write(text)
-        _replace_into(val["-o"], write)
-    # a window or a Parquet file that is refused (pyarrow's errors are ValueErrors and OSErrors), the sweep's own IndexError
-    # (index.check), a record that is not there.  Anything else is a defect and leaves as a traceback, as from `memo query`.
-    except (MemoError, OSError, LookupError, ValueError) as exc:
-        refuse(f"{type(exc).__name__}: {exc}" if isinstance(exc, LookupError) else str(exc))
+        _cli.write_text(val["-o"], collect.format_curves(qe - qs, core, covered, form, order_rows, labels))
+    cli.guarded(run)

@@ -40,7 +40,8 @@ def tile():
     return int(lib().memo_convert_tile())
 
 
-def _docs(n_docs):
+def docs(n_docs):
+    """n_docs as an integer of [2, N_MAX]"""
     n_docs = int(n_docs)
     if not 2 <= n_docs <= N_MAX:
         raise ValueError(f"n_docs must be in [2, {N_MAX}] (got {n_docs})")
@@ -52,7 +53,7 @@ def default_batch_positions(n_docs):
     return max(BATCH_BYTES // (4 * (int(n_docs) - 1)), 1)
 
 
-def _setting(value, env, what):
+def setting(value, env, what):
     """a slice or batch length: the argument, else the environment's (the tests force small ones; the result depends on neither), else None"""
     if value is None and os.environ.get(env):
         value = os.environ[env]
@@ -100,7 +101,7 @@ def slice_carries(start, end, annot, length, n_docs, step):
     """Pass A's bookkeeping on the host, for the tests: {(a, b): int64 [N]} -- for every slice [a, b) of [0, length) cut at multiples
     of `step`, the smallest end per genome among the rows with b < start (INT64_MAX: none), found from the right as the device finds
     it: the carry is saved, then the slice's rows a < start < b + 1 enter it."""
-    from .lengths import _slices
+    from .lengths import window_slices
     start, end, annot = (np.asarray(c, np.int64) for c in (start, end, annot))
     known = (annot >= 0) & (annot < n_docs)
     carry = np.full(n_docs, _NO_CARRY, np.int64)
@@ -110,7 +111,7 @@ def slice_carries(start, end, annot, length, n_docs, step):
         np.minimum.at(carry, annot[take], end[take])
     enter(length, length + min(length, L_MAX))
     out = {}
-    for a, b in _slices(0, length, n_docs, step):
+    for a, b in window_slices(0, length, n_docs, step):
         out[(a, b)] = carry.copy()
         enter(a, b + 1)
     return out
@@ -138,7 +139,7 @@ class _RowBuilder:
         self._conv.close()
 
 
-class _Builders:
+class Builders:
     """one row builder per requested output, all fed the same matrix"""
 
     def __init__(self, columns, rec_begin, orders, device):
@@ -159,13 +160,14 @@ class _Builders:
         self._stack.close()
 
 
-def _same_file(a, b):
+def same_file(a, b):
+    """whether two paths name one file, existing or not"""
     if os.path.exists(a) and os.path.exists(b):
         return os.path.samefile(a, b)
     return os.path.abspath(a) == os.path.abspath(b)
 
 
-def _record_rows(sources, length, builder, device, slice_positions, batch_positions, columns, matrix):
+def record_rows(sources, length, builder, device, slice_positions, batch_positions, columns, matrix):
     """Yields what builder.push_dev(d_dap, positions) returns for one record of `length` positions, batch by batch, in the index's
     order.  sources = [(feed, n_docs), ...]: feed(lo, hi) yields (d_start, d_end, d_annot, rows) chunks of device columns that hold at
     least that source's rows with lo < start < hi.  The sources' planes lie stacked in one buffer with one pitch, source s in planes
@@ -173,18 +175,19 @@ def _record_rows(sources, length, builder, device, slice_positions, batch_positi
     The step that makes a batch's matrix is the caller's: `columns`, the matrix's width, and matrix(d_cells, pitch, at, first,
     positions, remaining, d_dap), which writes int32 [positions][columns] at d_dap from positions [first, first + positions) of the
     slice's stack; `at` is the batch's first position in the record."""
-    from .lengths import _DevBuffer, _pitch, _slices
+    from ._device import DevBuffer
+    from .lengths import pitch_of, window_slices
     L_ = lib()
     sizes = [n for _, n in sources]
     total = sum(sizes)
     bases = np.concatenate([[0], np.cumsum(sizes)]).tolist()
     cap = min(length, L_MAX)
     reach = length + cap
-    slices = _slices(0, length, total, slice_positions)               # from the right; cut for the whole stack
+    slices = window_slices(0, length, total, slice_positions)               # from the right; cut for the whole stack
     batch = default_batch_positions(columns + 1) if batch_positions is None else batch_positions
     longest = max(b - a for a, b in slices)
-    with _DevBuffer(device, 4 * total * _pitch(longest)) as cells, _DevBuffer(device, 8 * total if len(slices) > 1 else 0) as carry, \
-            _DevBuffer(device, 4 * columns * min(batch, longest)) as d_dap:
+    with DevBuffer(device, 4 * total * pitch_of(longest)) as cells, DevBuffer(device, 8 * total if len(slices) > 1 else 0) as carry, \
+            DevBuffer(device, 4 * columns * min(batch, longest)) as d_dap:
         saved = {}
         if len(slices) > 1:                                            # pass A: every slice's carry, from the right, source by source
             for s, (feed, n) in enumerate(sources):
@@ -200,7 +203,7 @@ def _record_rows(sources, length, builder, device, slice_positions, batch_positi
                         for chunk in feed(a, b + 1):
                             check(L_.memo_lengths_carry_dev(*chunk, a, b + 1, n, d_carry, device, None))
         for a, b in slices[::-1]:                                      # pass B: the planes, left to right
-            Ls, pitch = b - a, _pitch(b - a)
+            Ls, pitch = b - a, pitch_of(b - a)
             for s, (feed, n) in enumerate(sources):
                 block = cells.at(4 * bases[s] * pitch)                 # (pitch % 4 == 0: every block is 16-byte aligned)
                 if len(slices) > 1:
@@ -221,17 +224,17 @@ def _record_rows(sources, length, builder, device, slice_positions, batch_positi
 
 
 def _converted_rows(feed, length, n_docs, builder, device, slice_positions, batch_positions):
-    """_record_rows of one source, its N - 1 columns as they lie (convert_dap_kernel)"""
+    """record_rows of one source, its N - 1 columns as they lie (convert_dap_kernel)"""
     def matrix(d_cells, pitch, at, first, positions, remaining, d_dap):
         check(lib().memo_convert_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_dap, device, None))
-    return _record_rows([(feed, n_docs)], length, builder, device, slice_positions, batch_positions, n_docs - 1, matrix)
+    return record_rows([(feed, n_docs)], length, builder, device, slice_positions, batch_positions, n_docs - 1, matrix)
 
 
-def _dap(call, width, planes, first, positions, remaining, device, pitch, side=None):
+def dap_of(call, width, planes, first, positions, remaining, device, pitch, side=None):
     """One planes-to-matrix kernel alone on host values: the uint32 planes [P, L], padded to `pitch` (default: L rounded up to 4), and
     the kernel's other host array `side` (or None) go up, call(d_cells, pitch, d_side, first, positions, remaining, d_out) runs, and
     int32 [positions, width] comes back."""
-    from .lengths import _DevBuffer
+    from ._device import DevBuffer
     count, L = planes.shape
     pitch = (L + 3) & ~3 if pitch is None else int(pitch)
     if pitch < L:
@@ -240,8 +243,8 @@ def _dap(call, width, planes, first, positions, remaining, device, pitch, side=N
     padded[:, :L] = planes
     positions = int(positions)
     out = np.empty((max(positions, 0), width), np.int32)
-    with _DevBuffer(device, max(padded.nbytes, 16)) as cells, _DevBuffer(device, 0 if side is None else max(side.nbytes, 16)) as d_side, \
-            _DevBuffer(device, max(out.nbytes, 16)) as d_out:
+    with DevBuffer(device, max(padded.nbytes, 16)) as cells, DevBuffer(device, 0 if side is None else max(side.nbytes, 16)) as d_side, \
+            DevBuffer(device, max(out.nbytes, 16)) as d_out:
         for d, host in ((cells, padded), (d_side, side)):
             if host is not None and host.nbytes:
                 check(lib().memo_dev_upload(device, d.d, host.ctypes.data, host.nbytes, None))
@@ -255,18 +258,18 @@ def rows(start, end, annot, n_docs, *, length=None, order=True, device=0, slice_
     """One record's host columns (any order), converted: the (start, end, annot) int64 columns of its conservation rows (order=True) or
     of its membership rows in canonical form (order=False).  length: the record's length where it is not the largest start.  The result
     depends neither on slice_positions nor on batch_positions."""
-    n_docs = _docs(n_docs)
+    n_docs = docs(n_docs)
     cols = [np.ascontiguousarray(c, np.int64) for c in (start, end, annot)]
     if len({len(c) for c in cols}) != 1:
         raise ValueError("start, end and annot differ in length")
     check_rows(*cols, n_docs)
     L = record_length(cols[0].max() if len(cols[0]) else 0, length)
-    slice_positions = _setting(slice_positions, "MEMO_CONVERT_SLICE", "slice_positions")
-    batch_positions = _setting(batch_positions, "MEMO_CONVERT_BATCH", "batch_positions")
+    slice_positions = setting(slice_positions, "MEMO_CONVERT_SLICE", "slice_positions")
+    batch_positions = setting(batch_positions, "MEMO_CONVERT_BATCH", "batch_positions")
     out = [[np.empty(0, np.int64)] for _ in range(3)]
     if L:
-        from .lengths import _host_feed
-        feed, buf = _host_feed(*cols, None, device, (0, L + min(L, L_MAX)))
+        from .lengths import host_feed
+        feed, buf = host_feed(*cols, None, device, (0, L + min(L, L_MAX)))
         with buf, _RowBuilder(n_docs - 1, [0, L], order, device) as builder:
             for _rec, s, e, a in _converted_rows(feed, L, n_docs, builder, device, slice_positions, batch_positions):
                 for column, part in zip(out, (s, e, a)):
@@ -280,18 +283,18 @@ def dap(planes, first, positions, remaining, device=0, pitch=None):
     planes = np.asarray(planes, np.uint32)
     if planes.ndim != 2:
         raise ValueError("planes must be [n_docs, positions]")
-    n_docs = _docs(planes.shape[0])
+    n_docs = docs(planes.shape[0])
 
     def call(d_cells, pitch, _d_side, first, positions, remaining, d_out):
         return lib().memo_convert_dap_dev(d_cells, pitch, n_docs, first, positions, remaining, d_out, device, None)
-    return _dap(call, n_docs - 1, planes, first, positions, remaining, device, pitch)
+    return dap_of(call, n_docs - 1, planes, first, positions, remaining, device, pitch)
 
 
 def scan_index(in_path, n_docs, fai=None):
     """The records of a Parquet index in order of first appearance with their lengths, after every row has passed check_rows:
     ([name, ...], [Lrec, ...]).  Host only."""
     import pyarrow.parquet as pq
-    n_docs = _docs(n_docs)
+    n_docs = docs(n_docs)
     lengths = None
     if fai is not None:
         from .dap_to_bed import parse_fai
@@ -324,20 +327,20 @@ def convert_index(in_path, out_path, n_docs, order=True, fai=None, device=0, log
     .fai, for records longer than their largest row start.  Everything that is refused is refused before out_path is touched; the file
     is written beside its name and renamed.  Returns the number of rows written."""
     from . import dap_to_bed
-    from .lengths import _region_feed
-    from .view_cli import _replace_into
-    n_docs = _docs(n_docs)
+    from ._cli import replace_into
+    from .lengths import region_feed
+    n_docs = docs(n_docs)
     if os.path.exists(out_path) and os.path.samefile(in_path, out_path):
         raise ValueError(f"{out_path} is the input file")
-    slice_positions = _setting(None, "MEMO_CONVERT_SLICE", "MEMO_CONVERT_SLICE")
-    batch_positions = _setting(None, "MEMO_CONVERT_BATCH", "MEMO_CONVERT_BATCH")
+    slice_positions = setting(None, "MEMO_CONVERT_SLICE", "MEMO_CONVERT_SLICE")
+    batch_positions = setting(None, "MEMO_CONVERT_BATCH", "MEMO_CONVERT_BATCH")
     names, lengths = scan_index(in_path, n_docs, fai)
     kept = [(name, L) for name, L in zip(names, lengths) if L]          # (a record whose rows all start at 0 has no position)
     names = [name for name, _ in kept]
 
     def batches(builder):
         for name, L in kept:
-            feed, buf = _region_feed(in_path, name, device)
+            feed, buf = region_feed(in_path, name, device)
             with buf:
                 for part in _converted_rows(feed, L, n_docs, builder, device, slice_positions, batch_positions):
                     yield names, part
@@ -350,5 +353,5 @@ def convert_index(in_path, out_path, n_docs, order=True, fai=None, device=0, log
         with _RowBuilder(n_docs - 1, rec_begin, order, device) as builder:
             return dap_to_bed.write_parquet(tmp, batches(builder))
     written = []
-    _replace_into(out_path, lambda tmp: written.append(write(tmp)))
+    replace_into(out_path, lambda tmp: written.append(write(tmp)))
     return written[0]

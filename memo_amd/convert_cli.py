@@ -6,9 +6,7 @@ membership index still holds them: this reads every genome's match lengths back 
 answer from it as from any other); with -m it is the membership index in canonical form, the row builder run without --order
 (memo_amd/convert.py, memo_amd/csrc/memo_convert.hip).  One GPU.
 """
-import getopt
-import os
-import sys
+from . import _cli
 
 N_MAX = 2048
 
@@ -26,48 +24,18 @@ Basic options:
 """
 
 
-def usage():
-    sys.stdout.write(USAGE)
-    sys.exit(0)
-
-
-def refuse(message, status=1):
-    sys.stderr.write(f"memo convert: {message}\n")
-    sys.exit(status)
+cli = _cli.Cli("convert", USAGE, "b:n:o:mf:")
 
 
 def main(argv):
     """bin/memo convert [options]: usage handling as the other sub-commands (getopts messages on stderr, then the usage, exit 0)"""
-    if not argv or argv[0] == "-h":
-        usage()
-    try:
-        opts, _ = getopt.getopt(argv, "b:n:o:mf:")
-    except getopt.GetoptError as exc:
-        what = "option requires an argument" if "requires argument" in exc.msg else "illegal option"
-        sys.stderr.write(f"{sys.argv[0]}: {what} -- {exc.opt}\n")
-        usage()
-    val = {}
-    for o, a in opts:
-        val[o] = a
-    print("MEMO - convert", flush=True)
+    val = cli.parse(argv)
     # everything that can be refused is refused before the device is touched and before anything is written
-    missing = [f for f in ("-b", "-n", "-o") if val.get(f, "") == ""]
-    if missing:
-        refuse(f"{', '.join(missing)} required", 2)
-    if int(os.environ.get("WORLD_SIZE", "1") or "1") > 1 or os.environ.get("MEMO_FORCE_SHARDED"):
-        refuse("one GPU only: a sharded launch (WORLD_SIZE > 1, MEMO_FORCE_SHARDED) is not supported")
-    try:
-        n_docs = int(val["-n"])
-    except ValueError as exc:
-        refuse(str(exc))
+    cli.require(val, ("-b", "-n", "-o"))
+    cli.one_gpu_only()
+    n_docs, = cli.integers(val, "-n")
     if not 2 <= n_docs <= N_MAX:
-        refuse(f"-n must be in [2, {N_MAX}] (got {n_docs})")
+        cli.refuse(f"-n must be in [2, {N_MAX}] (got {n_docs})")
     from . import convert
-    from ._lib import MemoError
-    try:
-        device = int(os.environ.get("MEMO_DEVICE", "0"))   # as `memo query` chooses its GPU
-        convert.convert_index(val["-b"], val["-o"], n_docs, order="-m" not in val, fai=val.get("-f"), device=device, log=lambda line: None)
-    # an index or a .fai that is refused (pyarrow's errors are ValueErrors and OSErrors), a device call that fails.
-    # Anything else is a defect and leaves as a traceback, as from `memo query`.
-    except (MemoError, OSError, LookupError, ValueError) as exc:
-        refuse(f"{type(exc).__name__}: {exc}" if isinstance(exc, LookupError) else str(exc))
+    cli.guarded(lambda: convert.convert_index(val["-b"], val["-o"], n_docs, order="-m" not in val, fai=val.get("-f"),
+                                              device=_cli.device(), log=lambda line: None))

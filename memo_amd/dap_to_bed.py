@@ -21,6 +21,7 @@ import sys
 
 import numpy as np
 
+from ._device import emit_text
 from ._lib import check, lib
 
 
@@ -133,10 +134,7 @@ class DapConverter:
 def bed_bytes(names, rec, start, end, annot):
     blob = b"".join(n.encode() + b"\0" for n in names)
     args = (rec.ctypes.data, start.ctypes.data, end.ctypes.data, annot.ctypes.data, len(rec), blob, len(names))
-    need = lib().memo_emit_bed(*args, None, 0)
-    buf = np.empty(need, np.uint8)
-    lib().memo_emit_bed(*args, buf.ctypes.data, need)
-    return buf
+    return emit_text(lambda buf, cap: lib().memo_emit_bed(*args, buf, cap))
 
 
 def convert(dap_path, fai_path, order, overlap, device=0):

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import emit_text
 from ._lib import check, lib
 
 
@@ -353,19 +354,13 @@ def query_multi_dev(shards, qs, qe, k, num_docs, out, root_device=0, stream=None
 def emit_conservation_buffer(vec):
     """the text as a uint8 array (no extra copies; write it with fh.write(memoryview(buf)))"""
     vec = np.ascontiguousarray(vec, np.uint16)
-    need = lib().memo_emit_conservation(vec.ctypes.data, len(vec), None, 0)
-    buf = np.empty(need, np.uint8)
-    lib().memo_emit_conservation(vec.ctypes.data, len(vec), buf.ctypes.data, need)
-    return buf
+    return emit_text(lambda buf, cap: lib().memo_emit_conservation(vec.ctypes.data, len(vec), buf, cap))
 
 
 def emit_membership_buffer(bits, num_docs):
     bits = np.ascontiguousarray(bits, np.uint32)
     L = bits.shape[0] if bits.ndim == 2 else len(bits) // max(words(num_docs), 1)
-    need = lib().memo_emit_membership(bits.ctypes.data, L, num_docs, None, 0)
-    buf = np.empty(need, np.uint8)
-    lib().memo_emit_membership(bits.ctypes.data, L, num_docs, buf.ctypes.data, need)
-    return buf
+    return emit_text(lambda buf, cap: lib().memo_emit_membership(bits.ctypes.data, L, num_docs, buf, cap))
 
 
 def emit_conservation(vec):

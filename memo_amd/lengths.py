@@ -17,12 +17,12 @@ only its own rows, every row is read once, and the result never depends on the s
 window asks the file for the tail and for every slice's rows (a row group that straddles a slice bound is decoded for both
 slices); host columns of a sliced window are sorted by start once and cut at the slice bounds.  The flags are memo_amd/lengths_cli.py.
 """
-import ctypes as C
-
 import numpy as np
 
+from ._device import DevBuffer, RowBuffer, emit_text
 from ._lib import check, lib
-from .maxk import CAP_MAX, _RowBuffer, _window
+from ._window import parse_region
+from .maxk import CAP_MAX, window
 
 N_MAX = 2048
 _NO_CARRY = np.iinfo(np.int64).max
@@ -38,11 +38,13 @@ def select_tile(n_docs):
     return int(lib().memo_lengths_select_tile(int(n_docs)))
 
 
-def _pitch(L):
+def pitch_of(L):
+    """cells per plane of L positions: the next multiple of 4"""
     return (L + 3) & ~3
 
 
-def _docs(n_docs, threshold=None):
+def docs(n_docs, threshold=None):
+    """n_docs as an integer of [1, N_MAX], a threshold checked against it"""
     n_docs = int(n_docs)
     if not 1 <= n_docs <= N_MAX:
         raise ValueError(f"n_docs must be in [1, {N_MAX}]")
@@ -56,7 +58,7 @@ def default_slice_positions(n_docs):
     return max((2 ** 29 // int(n_docs)) & ~3, 4)
 
 
-def _slices(qs, L, n_docs, slice_positions):
+def window_slices(qs, L, n_docs, slice_positions):
     """[(a, b), ...]: the window cut at multiples of the slice length, from the right"""
     step = default_slice_positions(n_docs) if slice_positions is None else int(slice_positions)
     if step < 1:
@@ -64,30 +66,7 @@ def _slices(qs, L, n_docs, slice_positions):
     return [(qs + at, qs + min(at + step, L)) for at in range(0, L, step)][::-1]
 
 
-class _DevBuffer:
-    """one device allocation"""
-
-    def __init__(self, device, nbytes):
-        self.device, self.d = device, C.c_void_p()
-        if nbytes:
-            check(lib().memo_dev_malloc(device, nbytes, C.byref(self.d)))
-
-    def at(self, offset):
-        return C.c_void_p((self.d.value or 0) + offset)
-
-    def close(self):
-        if self.d:
-            lib().memo_dev_free(self.device, self.d)
-            self.d = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-def _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0):
+def finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0):
     """Yields (a, b, d_cells, pitch) for every slice [a, b) of the window, from the right, its planes finished on the device (they
     are the next slice's cells once the consumer comes back).  feed(lo, hi) yields (d_start, d_end, d_annot, rows) chunks of device
     columns that hold at least the rows with lo < start < hi.  halo=1: every slice with a > 0 has one more cell on its left, the
@@ -96,20 +75,20 @@ def _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0):
     if halo not in (0, 1):
         raise ValueError("halo must be 0 or 1")
     qe = qs + L
-    slices = _slices(qs, L, n_docs, slice_positions)
+    slices = window_slices(qs, L, n_docs, slice_positions)
     if not slices:
         return
     L_ = lib()
     longest = max(b - a for a, b in slices) + halo
-    with _DevBuffer(device, 4 * n_docs * _pitch(longest)) as cells, _DevBuffer(device, 8 * n_docs if len(slices) > 1 else 0) as carry:
+    with DevBuffer(device, 4 * n_docs * pitch_of(longest)) as cells, DevBuffer(device, 8 * n_docs if len(slices) > 1 else 0) as carry:
         reach = min(qe + cap, 2 ** 62)
         if len(slices) == 1:            # the whole window: the row pass itself takes qs < start < qe + cap
             h = halo if qs > 0 else 0
-            check(L_.memo_lengths_begin_dev(cells.d, L + h, _pitch(L + h), n_docs, cap, qs - h, None, device, None))
+            check(L_.memo_lengths_begin_dev(cells.d, L + h, pitch_of(L + h), n_docs, cap, qs - h, None, device, None))
             for chunk in feed(qs - h, reach):
-                check(L_.memo_lengths_rows_dev(*chunk, qs - h, L + h, _pitch(L + h), n_docs, cap, cells.d, device, None))
-            check(L_.memo_lengths_finish_dev(cells.d, L + h, _pitch(L + h), n_docs, cap, device, None))
-            yield qs, qe, cells.d, _pitch(L + h)
+                check(L_.memo_lengths_rows_dev(*chunk, qs - h, L + h, pitch_of(L + h), n_docs, cap, cells.d, device, None))
+            check(L_.memo_lengths_finish_dev(cells.d, L + h, pitch_of(L + h), n_docs, cap, device, None))
+            yield qs, qe, cells.d, pitch_of(L + h)
             return
         none = np.full(n_docs, _NO_CARRY, np.int64)
         check(L_.memo_dev_upload(device, carry.d, none.ctypes.data, none.nbytes, None))
@@ -117,7 +96,7 @@ def _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0):
             check(L_.memo_lengths_carry_dev(*chunk, qe, reach, n_docs, carry.d, device, None))
         for a, b in slices:             # before [a, b) the carry holds the rows with b < start < qe + cap
             h = halo if a > 0 else 0
-            Ls, pitch = b - a + h, _pitch(b - a + h)
+            Ls, pitch = b - a + h, pitch_of(b - a + h)
             check(L_.memo_lengths_begin_dev(cells.d, Ls, pitch, n_docs, cap, a - h, carry.d, device, None))
             for chunk in feed(a - h, b + 1):
                 check(L_.memo_lengths_rows_dev(*chunk, a - h, Ls, pitch, n_docs, cap, cells.d, device, None))
@@ -126,7 +105,7 @@ def _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0):
             yield a, b, cells.d, pitch
 
 
-def _host_feed(start, end, annot, chunk_rows, device, whole):
+def host_feed(start, end, annot, chunk_rows, device, whole):
     """(feed, buffer) of host columns.  Asked for `whole` = (qs, qe + cap), the bounds of a window of one slice, the feed hands over
     every row as it lies, in chunks of chunk_rows (the row pass filters; a single chunk is uploaded once).  Asked for anything
     narrower -- the tail or one slice of a sliced window -- it hands over exactly the rows with lo < start < hi: the columns are
@@ -136,7 +115,7 @@ def _host_feed(start, end, annot, chunk_rows, device, whole):
     if len(cols[1]) != n or len(cols[2]) != n:
         raise ValueError("start, end and annot differ in length")
     step = max(n if not chunk_rows else int(chunk_rows), 1)
-    buf = _RowBuffer(device)
+    buf = RowBuffer(device)
     by_start = []
 
     def feed(lo, hi):
@@ -153,9 +132,9 @@ def _host_feed(start, end, annot, chunk_rows, device, whole):
     return feed, buf
 
 
-def _region_feed(index_path, record, device):
+def region_feed(index_path, record, device):
     from . import memo_query
-    buf = _RowBuffer(device)
+    buf = RowBuffer(device)
 
     def feed(lo, hi):
         _, chunks = memo_query.region_chunks(index_path, record, lo, hi)
@@ -173,19 +152,16 @@ def _download_planes(out, qs, a, b, d_cells, pitch, n_docs, device):
 def _planes(feed, buf, qs, L, n_docs, cap, device, slice_positions):
     out = np.empty((n_docs, L), np.uint32)
     with buf:
-        for a, b, d_cells, pitch in _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions):
+        for a, b, d_cells, pitch in finished_slices(feed, qs, L, n_docs, cap, device, slice_positions):
             _download_planes(out, qs, a, b, d_cells, pitch, n_docs, device)
     return out
 
 
 def _kth(feed, buf, qs, L, n_docs, threshold, cap, device, slice_positions):
-    out = np.empty(L, np.uint32)
-    with buf, _DevBuffer(device, 4 * L) as d_out:
-        for a, b, d_cells, pitch in _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions):
+    with buf, DevBuffer(device, 4 * L) as d_out:
+        for a, b, d_cells, pitch in finished_slices(feed, qs, L, n_docs, cap, device, slice_positions):
             check(lib().memo_lengths_select_dev(d_cells, b - a, pitch, n_docs, cap, threshold, d_out.at(4 * (a - qs)), device, None))
-        if L:
-            check(lib().memo_dev_download(device, out.ctypes.data, d_out.d, out.nbytes, None))
-    return out
+        return d_out.to_host(L, np.uint32)
 
 
 def planes(start, end, annot, qs, qe, n_docs, *, cap=CAP_MAX, device=0, chunk_rows=None, slice_positions=None):
@@ -193,18 +169,18 @@ def planes(start, end, annot, qs, qe, n_docs, *, cap=CAP_MAX, device=0, chunk_ro
     qs < start < qe + cap and the annots outside [0, n_docs)).  chunk_rows: feed the rows in calls of that many; slice_positions: take
     the window in slices of that many positions (the result depends on neither; a sliced window sorts a copy of the rows by start
     and gives every slice its own).  Returns uint32 [n_docs, qe - qs]."""
-    n_docs = _docs(n_docs)
-    qs, L, cap = _window(qs, qe, cap)
-    feed, buf = _host_feed(start, end, annot, chunk_rows, device, (qs, min(qs + L + cap, 2 ** 62)))
+    n_docs = docs(n_docs)
+    qs, L, cap = window(qs, qe, cap)
+    feed, buf = host_feed(start, end, annot, chunk_rows, device, (qs, min(qs + L + cap, 2 ** 62)))
     return _planes(feed, buf, qs, L, n_docs, cap, device, slice_positions)
 
 
 def kth(start, end, annot, qs, qe, n_docs, *, threshold, cap=CAP_MAX, device=0, chunk_rows=None, slice_positions=None):
     """The threshold-th largest of the genomes' match lengths per position: the largest k (up to cap) at which at least `threshold`
     genomes hold the k-mer.  The planes stay on the device; 4 (qe - qs) bytes leave it.  Returns uint32 [qe - qs]."""
-    n_docs = _docs(n_docs, threshold)
-    qs, L, cap = _window(qs, qe, cap)
-    feed, buf = _host_feed(start, end, annot, chunk_rows, device, (qs, min(qs + L + cap, 2 ** 62)))
+    n_docs = docs(n_docs, threshold)
+    qs, L, cap = window(qs, qe, cap)
+    feed, buf = host_feed(start, end, annot, chunk_rows, device, (qs, min(qs + L + cap, 2 ** 62)))
     return _kth(feed, buf, qs, L, n_docs, int(threshold), cap, device, slice_positions)
 
 
@@ -214,27 +190,24 @@ def select(planes, threshold, cap=CAP_MAX, device=0):
     planes = np.asarray(planes, np.uint32)
     if planes.ndim != 2:
         raise ValueError("planes must be [n_docs, positions]")
-    n_docs = _docs(planes.shape[0], threshold)
+    n_docs = docs(planes.shape[0], threshold)
     L, cap = planes.shape[1], int(cap)
     if not 1 <= cap <= CAP_MAX:
         raise ValueError(f"cap must be in [1, {CAP_MAX}]")
-    pitch = _pitch(L)
+    pitch = pitch_of(L)
     padded = np.zeros((n_docs, pitch), np.uint32)
     padded[:, :L] = planes
-    out = np.empty(L, np.uint32)
-    with _DevBuffer(device, padded.nbytes) as cells, _DevBuffer(device, 4 * L) as d_out:
+    with DevBuffer(device, padded.nbytes) as cells, DevBuffer(device, 4 * L) as d_out:
         if L:
             check(lib().memo_dev_upload(device, cells.d, padded.ctypes.data, padded.nbytes, None))
         check(lib().memo_lengths_select_dev(cells.d, L, pitch, n_docs, cap, int(threshold), d_out.d, device, None))
-        if L:
-            check(lib().memo_dev_download(device, out.ctypes.data, d_out.d, out.nbytes, None))
-    return out
+        return d_out.to_host(L, np.uint32)
 
 
-def _region(region, cap):
-    record, start_end = region.split(':')                  # exactly one ':' and one '-', as `memo query -r` takes it
-    qs, qe = map(int, start_end.split('-'))
-    return (record, *_window(qs, qe, cap))
+def region_window(region, cap):
+    """(record, qs, L, cap) of CHR:START-END and a cap: parse_region's refusals, then maxk.window's"""
+    record, qs, qe = parse_region(region)
+    return (record, *window(qs, qe, cap))
 
 
 def region_slices(index_path, region, n_docs, cap=CAP_MAX, device=0, slice_positions=None, halo=0):
@@ -242,11 +215,11 @@ def region_slices(index_path, region, n_docs, cap=CAP_MAX, device=0, slice_posit
     with halo=1 a slice with a > 0 has the lengths of position a - 1 as one more column on its left.
     The rows stream out of the file row group by row group (memo_query.region_chunks: first the tail qe < start < qe + cap, then
     every slice's own rows), each chunk through one reused device buffer.  No sidecar cache is read or built."""
-    n_docs = _docs(n_docs)
-    record, qs, L, cap = _region(region, cap)
-    feed, buf = _region_feed(index_path, record, device)
+    n_docs = docs(n_docs)
+    record, qs, L, cap = region_window(region, cap)
+    feed, buf = region_feed(index_path, record, device)
     with buf:
-        for a, b, d_cells, pitch in _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo):
+        for a, b, d_cells, pitch in finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo):
             h = halo if a > 0 else 0
             part = np.empty((n_docs, b - a + h), np.uint32)
             _download_planes(part, a - h, a - h, b, d_cells, pitch, n_docs, device)
@@ -256,9 +229,9 @@ def region_slices(index_path, region, n_docs, cap=CAP_MAX, device=0, slice_posit
 def region_planes(index_path, region, n_docs, cap=CAP_MAX, device=0, slice_positions=None):
     """Every genome's match length per position of a window of a Parquet membership index.  `region` is CHR:START-END as
     `memo query -r` takes it, and what is wrong with it raises what memo_query.main raises.  One device.  Returns uint32 [n_docs, qe - qs]."""
-    n_docs = _docs(n_docs)
-    record, qs, L, cap = _region(region, cap)
-    feed, buf = _region_feed(index_path, record, device)
+    n_docs = docs(n_docs)
+    record, qs, L, cap = region_window(region, cap)
+    feed, buf = region_feed(index_path, record, device)
     return _planes(feed, buf, qs, L, n_docs, cap, device, slice_positions)
 
 
@@ -266,9 +239,9 @@ def region_kth(index_path, region, n_docs, threshold=None, cap=CAP_MAX, device=0
     """The threshold-th largest match length per position of a window of a Parquet membership index (threshold=None: n_docs, held by
     all).  Returns uint32 [qe - qs]."""
     threshold = n_docs if threshold is None else threshold
-    n_docs = _docs(n_docs, threshold)
-    record, qs, L, cap = _region(region, cap)
-    feed, buf = _region_feed(index_path, record, device)
+    n_docs = docs(n_docs, threshold)
+    record, qs, L, cap = region_window(region, cap)
+    feed, buf = region_feed(index_path, record, device)
     return _kth(feed, buf, qs, L, n_docs, int(threshold), cap, device, slice_positions)
 
 
@@ -278,8 +251,4 @@ def emit_rows(planes):
     if planes.ndim != 2:
         raise ValueError("planes must be [n_docs, positions]")
     n, L = planes.shape
-    need = lib().memo_emit_u32_rows(planes.ctypes.data, L, L, n, None, 0)
-    buf = np.empty(need, np.uint8)
-    got = lib().memo_emit_u32_rows(planes.ctypes.data, L, L, n, buf.ctypes.data, need)
-    assert got == need
-    return buf
+    return emit_text(lambda buf, cap: lib().memo_emit_u32_rows(planes.ctypes.data, L, L, n, buf, cap))

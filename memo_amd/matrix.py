@@ -14,9 +14,10 @@ import ctypes as C
 
 import numpy as np
 
+from ._device import DevBuffer, on_device
 from ._lib import check, lib
+from ._window import membership_slices, parse_region
 from .index import words
-from .regions import _on_device
 
 
 def tile(words_per_position=1):
@@ -28,25 +29,12 @@ def _accumulate(d_bits, L, num_docs, d_counts, device, stream=None):
     check(lib().memo_cooccurrence_dev(d_bits, L, num_docs, d_counts, device, None if stream is None else C.c_void_p(int(stream))))
 
 
-def _matrix_on_device(num_docs, counts, device):
-    """a device matrix uint64 [N, N] holding `counts` (None: zeros)"""
+def _matrix(num_docs, counts):
+    """`counts` as a host matrix uint64 [N, N] (None: zeros)"""
     host = np.zeros((num_docs, num_docs), np.uint64) if counts is None else np.ascontiguousarray(counts, np.uint64)
     if host.shape != (num_docs, num_docs):
         raise ValueError(f"counts must be [{num_docs}, {num_docs}]")
-    d = C.c_void_p()
-    check(lib().memo_dev_malloc(device, host.nbytes, C.byref(d)))
-    try:
-        check(lib().memo_dev_upload(device, d, host.ctypes.data, host.nbytes, None))
-    except BaseException:
-        lib().memo_dev_free(device, d)
-        raise
-    return d
-
-
-def _matrix_to_host(d_counts, num_docs, device):
-    out = np.empty((num_docs, num_docs), np.uint64)
-    check(lib().memo_dev_download(device, out.ctypes.data, d_counts, out.nbytes, None))
-    return out
+    return host
 
 
 def cooccurrence(bits, num_docs, counts=None, device=0, stream=None):
@@ -55,17 +43,9 @@ def cooccurrence(bits, num_docs, counts=None, device=0, stream=None):
     W = words(num_docs)
     if not isinstance(bits, tuple):
         bits = np.ascontiguousarray(bits, np.uint32).reshape(-1, W)
-    d_counts = _matrix_on_device(num_docs, counts, device)
-    try:
-        d_bits, L, tmp = _on_device(bits, np.uint32, device)
-        try:
-            _accumulate(d_bits, L, num_docs, d_counts, device, stream)
-        finally:
-            if tmp is not None:
-                lib().memo_dev_free(device, tmp)
-        return _matrix_to_host(d_counts, num_docs, device)
-    finally:
-        lib().memo_dev_free(device, d_counts)
+    with DevBuffer.of(_matrix(num_docs, counts), device) as d_counts, on_device(bits, np.uint32, device) as (d_bits, L):
+        _accumulate(d_bits, L, num_docs, d_counts.d, device, stream)
+        return d_counts.to_host((num_docs, num_docs), np.uint64)
 
 
 def region_matrix(index_path, region, k, n_docs, device=0, slice_positions=1 << 24):
@@ -75,30 +55,12 @@ def region_matrix(index_path, region, k, n_docs, device=0, slice_positions=1 << 
     matrix does not depend on the slices.  `region` is CHR:START-END as `memo query -r` takes it, and what is
     wrong with it raises what memo_query.main raises.  One device.  Returns uint64 [N, N]."""
     from . import memo_query
-    if slice_positions < 1:
-        raise ValueError("slice_positions must be at least 1")
-    record, start_end = region.split(':')                  # exactly one ':' and one '-'
-    qs, qe = map(int, start_end.split('-'))
-    if qe < qs:
-        raise ValueError("negative dimensions are not allowed")          # np.zeros of memo_init, as `memo query` raises it
+    record, qs, qe = parse_region(region)
     index = memo_query.region_index(index_path, record, qs, qe + k, device=device, k=k, num_docs=n_docs, membership=True)
-    with index:
-        step = min(int(slice_positions), max(qe - qs, 1))
-        d_counts = _matrix_on_device(n_docs, None, device)
-        try:
-            d_bits = C.c_void_p()
-            check(lib().memo_dev_malloc(device, step * 4 * words(n_docs), C.byref(d_bits)))
-            try:
-                for s in range(qs, qe, step):
-                    e = min(s + step, qe)
-                    index.membership_slice_dev(qs, qe, s, e, k, n_docs, d_bits.value)
-                    index.check()
-                    _accumulate(d_bits, e - s, n_docs, d_counts, device)
-            finally:
-                lib().memo_dev_free(device, d_bits)
-            return _matrix_to_host(d_counts, n_docs, device)
-        finally:
-            lib().memo_dev_free(device, d_counts)
+    with index, DevBuffer.of(_matrix(n_docs, None), device) as d_counts:
+        for d_bits, s, e in membership_slices(index, qs, qe, k, n_docs, slice_positions, device):
+            _accumulate(d_bits, e - s, n_docs, d_counts.d, device)
+        return d_counts.to_host((n_docs, n_docs), np.uint64)
 
 
 def jaccard(counts):

@@ -14,11 +14,11 @@ memo_amd/csrc/memo_maxk.hip: the cells are filled with the identity, every chunk
 one per run of rows that hit the same cell (any order, any cut into chunks), a reverse min-scan turns them into the result in place; 4 L bytes leave the device.
 The flags are memo_amd/maxk_cli.py.
 """
-import ctypes as C
-
 import numpy as np
 
+from ._device import DevBuffer, RowBuffer, emit_text
 from ._lib import check, lib
+from ._window import parse_region
 
 CAP_MAX = 2 ** 31 - 1
 
@@ -35,7 +35,8 @@ def _predicate(threshold, genome):
     return (0, int(threshold)) if genome is None else (1, int(genome))
 
 
-def _window(qs, qe, cap):
+def window(qs, qe, cap):
+    """(qs, L, cap) as integers, or the ValueError of a reversed window and then of a cap outside [1, CAP_MAX]"""
     qs, qe, cap = int(qs), int(qe), int(cap)
     if qe < qs:
         raise ValueError("negative dimensions are not allowed")          # as `memo query` raises it
@@ -44,19 +45,21 @@ def _window(qs, qe, cap):
     return qs, qe - qs, cap
 
 
-class _Cells:
+class Cells:
     """uint32 [L] on the device between memo_maxk_begin_dev and memo_maxk_finish_dev"""
 
     def __init__(self, qs, L, cap, mode, arg, device):
         self.qs, self.L, self.cap, self.mode, self.arg, self.device = qs, L, cap, mode, arg, device
-        self.d = C.c_void_p()
-        if L:
-            check(lib().memo_dev_malloc(device, 4 * L, C.byref(self.d)))
+        self.buf = DevBuffer(device, 4 * L)
         try:
             check(lib().memo_maxk_begin_dev(self.d, L, cap, device, None))
         except BaseException:
             self.close()
             raise
+
+    @property
+    def d(self):
+        return self.buf.d
 
     def add(self, d_start, d_end, d_annot, rows):
         """one chunk of rows, device columns"""
@@ -66,49 +69,10 @@ class _Cells:
     def finish(self):
         """the result, uint32 [L] on the host"""
         check(lib().memo_maxk_finish_dev(self.d, self.L, self.cap, self.device, None))
-        out = np.empty(self.L, np.uint32)
-        if self.L:
-            check(lib().memo_dev_download(self.device, out.ctypes.data, self.d, out.nbytes, None))
-        return out
+        return self.buf.to_host(self.L, np.uint32)
 
     def close(self):
-        if self.d:
-            lib().memo_dev_free(self.device, self.d)
-            self.d = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class _RowBuffer:
-    """one reused device buffer for a chunk's three int64 columns, each at a 16-byte aligned offset; it grows with the largest chunk"""
-
-    def __init__(self, device):
-        self.device, self.d, self.capacity = device, C.c_void_p(), 0
-
-    def upload(self, start, end, annot):
-        """(d_start, d_end, d_annot, rows) of host columns"""
-        cols = [np.ascontiguousarray(c, np.int64) for c in (start, end, annot)]
-        n = len(cols[0])
-        if len(cols[1]) != n or len(cols[2]) != n:
-            raise ValueError("start, end and annot differ in length")
-        if n > self.capacity:
-            self.close()
-            self.capacity = (n + 1) & ~1
-            check(lib().memo_dev_malloc(self.device, 24 * self.capacity, C.byref(self.d)))
-        ptrs = [C.c_void_p((self.d.value or 0) + 8 * self.capacity * i) for i in range(3)]
-        for p, c in zip(ptrs, cols):
-            if n:
-                check(lib().memo_dev_upload_pipelined(self.device, p, c.ctypes.data, c.nbytes))
-        return (*ptrs, n)
-
-    def close(self):
-        if self.d:
-            lib().memo_dev_free(self.device, self.d)
-        self.d, self.capacity = C.c_void_p(), 0
+        self.buf.close()
 
     def __enter__(self):
         return self
@@ -121,11 +85,11 @@ def maxk(start, end, annot, qs, qe, *, threshold=None, genome=None, cap=CAP_MAX,
     """The longest shared k per position of [qs, qe) from host columns (any order; rows outside qs < start < qe + cap are ignored
     by the kernel).  chunk_rows: feed the rows in calls of that many (the result does not depend on it).  Returns uint32 [qe - qs]."""
     mode, arg = _predicate(threshold, genome)
-    qs, L, cap = _window(qs, qe, cap)
+    qs, L, cap = window(qs, qe, cap)
     cols = [np.ascontiguousarray(c, np.int64) for c in (start, end, annot)]
     n = len(cols[0])
     step = n if not chunk_rows else int(chunk_rows)
-    with _Cells(qs, L, cap, mode, arg, device) as cells, _RowBuffer(device) as buf:
+    with Cells(qs, L, cap, mode, arg, device) as cells, RowBuffer(device) as buf:
         for at in range(0, n, max(step, 1)):
             cells.add(*buf.upload(*(c[at:at + step] for c in cols)))
         return cells.finish()
@@ -136,10 +100,10 @@ def index_maxk(index, qs, qe, *, threshold=None, genome=None, cap=CAP_MAX):
     columns out as writable, which drops what the index derived from them (bucket table, packed rows, views): the index is
     finalized again before this returns, and packs again when it is asked to."""
     mode, arg = _predicate(threshold, genome)
-    qs, L, cap = _window(qs, qe, cap)
+    qs, L, cap = window(qs, qe, cap)
     d_s, d_e, d_o = index.columns()
     try:
-        with _Cells(qs, L, cap, mode, arg, index.device) as cells:
+        with Cells(qs, L, cap, mode, arg, index.device) as cells:
             cells.add(d_s, d_e, d_o, index.rows)
             return cells.finish()
     finally:
@@ -156,10 +120,9 @@ def region_maxk(index_path, region, n_docs, threshold=None, genome=None, cap=CAP
     if threshold is None and genome is None:
         threshold = n_docs
     mode, arg = _predicate(threshold, genome)
-    record, start_end = region.split(':')                  # exactly one ':' and one '-'
-    qs, qe = map(int, start_end.split('-'))
-    qs, L, cap = _window(qs, qe, cap)
-    with _Cells(qs, L, cap, mode, arg, device) as cells, _RowBuffer(device) as buf:
+    record, qs, qe = parse_region(region)
+    qs, L, cap = window(qs, qe, cap)
+    with Cells(qs, L, cap, mode, arg, device) as cells, RowBuffer(device) as buf:
         if L:
             _, chunks = memo_query.region_chunks(index_path, record, qs, min(qe + cap, 2 ** 62))
             for cols in chunks:
@@ -170,8 +133,4 @@ def region_maxk(index_path, region, n_docs, threshold=None, genome=None, cap=CAP
 def emit(vec):
     """the text of a result, one integer per line, as a uint8 array (write it with fh.write(memoryview(buf))); empty for L = 0"""
     vec = np.ascontiguousarray(vec, np.uint32)
-    need = lib().memo_emit_u32(vec.ctypes.data, len(vec), None, 0)
-    buf = np.empty(need, np.uint8)
-    got = lib().memo_emit_u32(vec.ctypes.data, len(vec), buf.ctypes.data, need)
-    assert got == need
-    return buf
+    return emit_text(lambda buf, cap: lib().memo_emit_u32(vec.ctypes.data, len(vec), buf, cap))

@@ -30,9 +30,10 @@ import ctypes as C
 
 import numpy as np
 
+from ._device import DevBuffer, RowBuffer, emit_text
 from ._lib import check, lib
-from .lengths import _DevBuffer, _docs, _finished_slices, _pitch, _region, _region_feed
-from .maxk import CAP_MAX, _Cells, _RowBuffer
+from .lengths import docs, finished_slices, pitch_of, region_feed, region_window
+from .maxk import CAP_MAX, Cells
 
 L_MAX = 2 ** 31 - 1
 
@@ -55,18 +56,9 @@ def of_cells(d_cells, L, pitch, planes=1, *, cap=CAP_MAX, min_len=1, band=False,
     check(lib().memo_mems_dev(C.c_void_p(int(getattr(d_cells, "value", d_cells) or 0)), int(L), int(pitch), int(planes), int(cap), int(min_len),
                               2 if band else 1, int(halo), C.byref(d_starts), None if band else C.byref(d_lengths), counts.ctypes.data,
                               device, None if stream is None else C.c_void_p(int(stream))))
-    out = []
-    try:
-        for d in (d_starts,) if band else (d_starts, d_lengths):
-            host = np.empty(int(counts.sum()), np.uint32)
-            if host.nbytes:
-                check(lib().memo_dev_download(device, host.ctypes.data, d, host.nbytes, None))
-            out.append(host)
-    finally:
-        for d in (d_starts, d_lengths):
-            if d:
-                lib().memo_dev_free(device, d)
-    return out[0], (None if band else out[1]), counts
+    with DevBuffer.adopt(d_starts, device) as starts, DevBuffer.adopt(d_lengths, device) as lengths:
+        entries = int(counts.sum())
+        return starts.to_host(entries, np.uint32), (None if band else lengths.to_host(entries, np.uint32)), counts
 
 
 def merge(begin, end):
@@ -108,7 +100,7 @@ def _plane_lists(d_cells, L, pitch, planes, origin, halo, cap, min_len, union, d
 
 def _check(n_docs, threshold, genome, membership, all_genomes, min_len, cap, union):
     """the mode and its numbers, or a ValueError before any device call"""
-    n_docs = _docs(n_docs)
+    n_docs = docs(n_docs)
     if not membership and (genome is not None or all_genomes):
         raise ValueError("genome and all_genomes are questions to a membership index")
     if genome is not None and all_genomes:
@@ -143,7 +135,7 @@ def region_mems(index_path, region, n_docs, *, threshold=None, genome=None, memb
     index; all_genomes: every genome 1 .. n_docs - 1 of it, one list each.  cap=None: 2^31 - 1.  slice_positions: the planes of
     a membership index are taken in slices of that many positions (the result does not depend on it).  One device."""
     n_docs, threshold, genome, min_len, cap = _check(n_docs, threshold, genome, membership, all_genomes, min_len, cap, union)
-    record, qs, L, cap = _region(region, cap)
+    record, qs, L, cap = region_window(region, cap)
     if qs < 0:
         raise ValueError("the window starts before position 0 of the record")
     if L > L_MAX:
@@ -155,9 +147,9 @@ def region_mems(index_path, region, n_docs, *, threshold=None, genome=None, memb
     lo, Lh = qs - h, L + h
     if all_genomes:
         per_genome = [[] for _ in range(n_docs - 1)]
-        feed, buf = _region_feed(index_path, record, device)
+        feed, buf = region_feed(index_path, record, device)
         with buf:
-            for a, b, d_cells, pitch in _finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0 if union else 1):
+            for a, b, d_cells, pitch in finished_slices(feed, qs, L, n_docs, cap, device, slice_positions, halo=0 if union else 1):
                 hs = 0 if union or a == 0 else 1
                 first = C.c_void_p((d_cells.value or 0) + 4 * pitch)         # plane 1: the pivot's plane is left out
                 lists = _plane_lists(first, b - a + hs, pitch, n_docs - 1, a - hs, hs, cap, min_len, union, device)
@@ -173,21 +165,21 @@ def region_mems(index_path, region, n_docs, *, threshold=None, genome=None, memb
         return Mems(record, np.concatenate(starts), np.concatenate(ends), np.concatenate(who))
     if membership and genome is None:
         # the planes in slices, their threshold-th largest into one whole-window buffer that stays on the device
-        feed, buf = _region_feed(index_path, record, device)
-        pitch = _pitch(Lh)
-        with buf, _DevBuffer(device, 4 * pitch) as sel:
-            for a, b, d_cells, p in _finished_slices(feed, lo, Lh, n_docs, cap, device, slice_positions):
+        feed, buf = region_feed(index_path, record, device)
+        pitch = pitch_of(Lh)
+        with buf, DevBuffer(device, 4 * pitch) as sel:
+            for a, b, d_cells, p in finished_slices(feed, lo, Lh, n_docs, cap, device, slice_positions):
                 check(lib().memo_lengths_select_dev(d_cells, b - a, p, n_docs, cap, threshold, sel.at(4 * (a - lo)), device, None))
             (s, e), = _plane_lists(sel.d, Lh, pitch, 1, lo, h, cap, min_len, union, device)
         return Mems(record, s, e, None)
     from . import memo_query
     mode, arg = (0, threshold) if genome is None else (1, genome)
-    with _Cells(lo, Lh, cap, mode, arg, device) as cells, _RowBuffer(device) as buf:
+    with Cells(lo, Lh, cap, mode, arg, device) as cells, RowBuffer(device) as buf:
         _, chunks = memo_query.region_chunks(index_path, record, lo, min(qs + L + cap, 2 ** 62))
         for cols in chunks:
             cells.add(*buf.upload(*cols))
         check(lib().memo_maxk_finish_dev(cells.d, Lh, cap, device, None))
-        (s, e), = _plane_lists(cells.d, Lh, _pitch(Lh), 1, lo, h, cap, min_len, union, device)
+        (s, e), = _plane_lists(cells.d, Lh, pitch_of(Lh), 1, lo, h, cap, min_len, union, device)
     return Mems(record, s, e, None)
 
 
@@ -199,9 +191,4 @@ def emit(result):
     if len(e) != len(s) or (g is not None and len(g) != len(s)):
         raise ValueError("starts, ends and genome differ in length")
     args = (result.record.encode(), s.ctypes.data, e.ctypes.data, None if g is None else g.ctypes.data, len(s))
-    need = lib().memo_emit_intervals(*args, None, 0)
-    buf = np.empty(need, np.uint8)
-    if need:
-        got = lib().memo_emit_intervals(*args, buf.ctypes.data, need)
-        assert got == need
-    return buf
+    return emit_text(lambda buf, cap: lib().memo_emit_intervals(*args, buf, cap))

@@ -26,7 +26,7 @@ import contextlib
 import numpy as np
 
 from ._lib import check, lib
-from .convert import L_MAX, _Builders, _dap, _docs, _record_rows, _same_file, _setting, check_rows, record_length, scan_index
+from .convert import L_MAX, Builders, check_rows, dap_of, docs, record_length, record_rows, same_file, scan_index, setting
 
 N_MAX = 2048                 # genomes of one input, and of the output, the pivot included
 PLANES_MAX = 65536           # genomes of all inputs together, their pivots included
@@ -74,7 +74,7 @@ def _plan(sizes, selections):
     """([N_s], [chosen annots of s], plane_of int32 [W]) after the checks both the command and the functions make"""
     if not sizes:
         raise ValueError("no input")
-    sizes = [_docs(n) for n in sizes]
+    sizes = [docs(n) for n in sizes]
     if sum(sizes) > PLANES_MAX:
         raise ValueError(f"the inputs hold {sum(sizes)} genomes together: the limit is {PLANES_MAX}")
     chosen = [parse_selection(sel, n) for sel, n in zip(selections, sizes)]
@@ -90,13 +90,13 @@ def _plan(sizes, selections):
 
 @contextlib.contextmanager
 def _mapped(sizes, plane_of, device):
-    """The column map on the device for a run: yields (columns, matrix), _record_rows' batch step through merge_dap_kernel.  sizes: the
+    """The column map on the device for a run: yields (columns, matrix), record_rows' batch step through merge_dap_kernel.  sizes: the
     N_s of the sources whose planes make the stack; plane_of names the plane of every output column in it."""
-    from .lengths import _DevBuffer
+    from ._device import DevBuffer
     L_ = lib()
     total, width = int(sum(sizes)), len(plane_of)
     plane_of = np.ascontiguousarray(plane_of, np.int32)
-    with _DevBuffer(device, 4 * width) as d_map:
+    with DevBuffer(device, 4 * width) as d_map:
         check(L_.memo_dev_upload(device, d_map.d, plane_of.ctypes.data, plane_of.nbytes, None))
 
         def matrix(d_cells, pitch, at, first, positions, remaining, d_dap):
@@ -110,7 +110,7 @@ def rows(sources, length=None, *, order=True, device=0, slice_positions=None, ba
     record's length (default: the largest row start, which must then be the same in every input).  Returns the (start, end, annot)
     int64 columns of the record's rows in the index of the chosen genomes: the conservation rows (order=True) or the membership rows
     in canonical form (order=False).  The result depends neither on slice_positions nor on batch_positions."""
-    from .lengths import _host_feed
+    from .lengths import host_feed
     sources = list(sources)
     sizes, _chosen, plane_of = _plan([src[3] for src in sources], [src[4] for src in sources])
     columns, lengths = [], []
@@ -124,19 +124,19 @@ def rows(sources, length=None, *, order=True, device=0, slice_positions=None, ba
     if len(set(lengths)) != 1:
         raise ValueError(f"the record's largest row starts differ between the inputs ({', '.join(map(str, lengths))}): is this the same pivot?")
     L = lengths[0]
-    slice_positions = _setting(slice_positions, "MEMO_MERGE_SLICE", "slice_positions")
-    batch_positions = _setting(batch_positions, "MEMO_MERGE_BATCH", "batch_positions")
+    slice_positions = setting(slice_positions, "MEMO_MERGE_SLICE", "slice_positions")
+    batch_positions = setting(batch_positions, "MEMO_MERGE_BATCH", "batch_positions")
     out = [[np.empty(0, np.int64)] for _ in range(3)]
     if L:
         with contextlib.ExitStack() as stack:
             feeds = []
             for cols in columns:
-                feed, buf = _host_feed(*cols, None, device, (0, L + min(L, L_MAX)))
+                feed, buf = host_feed(*cols, None, device, (0, L + min(L, L_MAX)))
                 stack.enter_context(buf)
                 feeds.append(feed)
-            builders = stack.enter_context(_Builders(len(plane_of), [0, L], [order], device))
+            builders = stack.enter_context(Builders(len(plane_of), [0, L], [order], device))
             mapped = stack.enter_context(_mapped(sizes, plane_of, device))
-            for ((_rec, s, e, a),) in _record_rows(list(zip(feeds, sizes)), L, builders, device, slice_positions, batch_positions, *mapped):
+            for ((_rec, s, e, a),) in record_rows(list(zip(feeds, sizes)), L, builders, device, slice_positions, batch_positions, *mapped):
                 for column, part in zip(out, (s, e, a)):
                     column.append(part.astype(np.int64))
     return tuple(np.concatenate(column) for column in out)
@@ -161,11 +161,11 @@ def dap(planes, plane_of, first, positions, remaining, device=0, pitch=None):
 
     def call(d_cells, pitch, d_map, first, positions, remaining, d_out):
         return lib().memo_merge_dap_dev(d_cells, pitch, count, d_map, len(plane_of), first, positions, remaining, d_out, device, None)
-    return _dap(call, len(plane_of), planes, first, max(int(positions), 0), remaining, device, pitch, plane_of)
+    return dap_of(call, len(plane_of), planes, first, max(int(positions), 0), remaining, device, pitch, plane_of)
 
 
 def read_list(path, n_docs):
-    """the lines of a genome list as memo_amd/matrix_cli.py reads them (stripped, the empty ones dropped); there must be n_docs"""
+    """the lines of a genome list as memo_amd/_cli.py reads them (stripped, the empty ones dropped); there must be n_docs"""
     try:
         with open(path) as fh:
             lines = [ln.strip() for ln in fh if ln.strip()]
@@ -191,8 +191,8 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
     anything is written; each file is written beside its name and renamed.
     Returns {"positions", "genomes", "rows": [per output, -o first]}."""
     from .dap_to_bed import RowWriter
-    from .lengths import _region_feed
-    from .view_cli import _replace_all_into
+    from ._cli import replace_all_into
+    from .lengths import region_feed
     inputs = [tuple(i) + (None,) * (4 - len(i)) for i in inputs]
     outputs = [(path, order) for path, order in ((out_path, False), (cons_path, True)) if path]
     if not outputs:
@@ -200,19 +200,19 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
     sizes, chosen, plane_of = _plan([i[1] for i in inputs], [i[2] for i in inputs])
     paths = [i[0] for i in inputs]
     for at, path in enumerate(paths):
-        if any(_same_file(path, other) for other in paths[:at]):
+        if any(same_file(path, other) for other in paths[:at]):
             raise ValueError(f"{path} is given as two inputs")
     written_paths = [path for path, _ in outputs] + ([list_out] if list_out else [])
     for path in written_paths:
-        if any(_same_file(path, other) for other in paths) or any(i[3] and _same_file(path, i[3]) for i in inputs):
+        if any(same_file(path, other) for other in paths) or any(i[3] and same_file(path, i[3]) for i in inputs):
             raise ValueError(f"{path} is an input file")
     for at, path in enumerate(written_paths):
-        if any(_same_file(path, other) for other in written_paths[:at]):
+        if any(same_file(path, other) for other in written_paths[:at]):
             raise ValueError(f"{path} is named for two outputs")
     if list_out and not all(i[3] for i in inputs):
         raise ValueError("-G needs the genome list (-g) of every input")
-    slice_positions = _setting(None, "MEMO_MERGE_SLICE", "MEMO_MERGE_SLICE")
-    batch_positions = _setting(None, "MEMO_MERGE_BATCH", "MEMO_MERGE_BATCH")
+    slice_positions = setting(None, "MEMO_MERGE_SLICE", "MEMO_MERGE_SLICE")
+    batch_positions = setting(None, "MEMO_MERGE_BATCH", "MEMO_MERGE_BATCH")
     lists = [read_list(i[3], n) if i[3] else None for i, n in zip(inputs, sizes)]
     found = [scan_index(path, n, fai) for path, n in zip(paths, sizes)]
     names, lengths = found[0]
@@ -235,16 +235,16 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
         with contextlib.ExitStack() as stack:
             writers = [stack.enter_context(RowWriter(tmp)) for tmp in tmps[:len(outputs)]]
             if kept:
-                builders = stack.enter_context(_Builders(len(plane_of), rec_begin, [order for _, order in outputs], device))
+                builders = stack.enter_context(Builders(len(plane_of), rec_begin, [order for _, order in outputs], device))
                 mapped = stack.enter_context(_mapped(sizes, plane_of, device))
             for name, L in kept:
                 with contextlib.ExitStack() as record:
                     feeds = []
                     for path in paths:
-                        feed, buf = _region_feed(path, name, device)
+                        feed, buf = region_feed(path, name, device)
                         record.enter_context(buf)
                         feeds.append(feed)
-                    for parts in _record_rows(list(zip(feeds, sizes)), L, builders, device, slice_positions, batch_positions, *mapped):
+                    for parts in record_rows(list(zip(feeds, sizes)), L, builders, device, slice_positions, batch_positions, *mapped):
                         for writer, part in zip(writers, parts):
                             writer.write(names, part)
                 log(f"{name}: {L} positions")
@@ -254,5 +254,5 @@ def merge_index(inputs, out_path=None, cons_path=None, list_out=None, fai=None, 
         return [w.rows for w in writers]
 
     written = []
-    _replace_all_into(written_paths, lambda tmps: written.extend(write(tmps)))
+    replace_all_into(written_paths, lambda tmps: written.extend(write(tmps)))
     return {"positions": int(rec_begin[-1]), "genomes": len(plane_of) + 1, "rows": written}

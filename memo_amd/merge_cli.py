@@ -7,9 +7,7 @@ to it; the output's genomes are annot 1, 2 ... in command order.  -o is the memb
 form `memo convert -m` writes), -c their conservation index, from the same matrix in the same run (memo_amd/merge.py,
 memo_amd/csrc/memo_merge.hip).  One GPU.
 """
-import getopt
-import os
-import sys
+from . import _cli
 
 N_MAX = 2048
 
@@ -33,14 +31,8 @@ Basic options:
 """
 
 
-def usage():
-    sys.stdout.write(USAGE)
-    sys.exit(0)
-
-
-def refuse(message, status=1):
-    sys.stderr.write(f"memo merge: {message}\n")
-    sys.exit(status)
+cli = _cli.Cli("merge", USAGE, "b:n:s:g:o:c:G:f:")
+refuse = cli.refuse
 
 
 def inputs_of(opts):
@@ -62,15 +54,8 @@ def inputs_of(opts):
 
 def main(argv):
     """bin/memo merge [options]: usage handling as the other sub-commands (getopts messages on stderr, then the usage, exit 0)"""
-    if not argv or argv[0] == "-h":
-        usage()
-    try:
-        opts, _ = getopt.getopt(argv, "b:n:s:g:o:c:G:f:")
-    except getopt.GetoptError as exc:
-        what = "option requires an argument" if "requires argument" in exc.msg else "illegal option"
-        sys.stderr.write(f"{sys.argv[0]}: {what} -- {exc.opt}\n")
-        usage()
-    print("MEMO - merge", flush=True)
+    opts = cli.options(argv)
+    cli.banner()
     # everything that can be refused is refused before the device is touched and before anything is written
     inputs, val = inputs_of(opts)
     if not inputs or any(i["-b"] == "" for i in inputs):
@@ -80,24 +65,13 @@ def main(argv):
             refuse(f"-n required for {i['-b']}", 2)
     if val.get("-o", "") == "" and val.get("-c", "") == "":
         refuse("-o or -c required", 2)
-    if int(os.environ.get("WORLD_SIZE", "1") or "1") > 1 or os.environ.get("MEMO_FORCE_SHARDED"):
-        refuse("one GPU only: a sharded launch (WORLD_SIZE > 1, MEMO_FORCE_SHARDED) is not supported")
+    cli.one_gpu_only()
     sources = []
     for i in inputs:
-        try:
-            n_docs = int(i["-n"])
-        except ValueError as exc:
-            refuse(str(exc))
+        n_docs, = cli.integers(i, "-n")
         if not 2 <= n_docs <= N_MAX:
             refuse(f"-n must be in [2, {N_MAX}] (got {n_docs} for {i['-b']})")
         sources.append((i["-b"], n_docs, i.get("-s"), i.get("-g") or None))
     from . import merge
-    from ._lib import MemoError
-    try:
-        device = int(os.environ.get("MEMO_DEVICE", "0"))   # as `memo query` chooses its GPU
-        merge.merge_index(sources, out_path=val.get("-o") or None, cons_path=val.get("-c") or None, list_out=val.get("-G") or None,
-                          fai=val.get("-f"), device=device, log=lambda line: None)
-    # an index, a list or a .fai that is refused (pyarrow's errors are ValueErrors and OSErrors), a device call that fails.
-    # Anything else is a defect and leaves as a traceback, as from `memo query`.
-    except (MemoError, OSError, LookupError, ValueError) as exc:
-        refuse(f"{type(exc).__name__}: {exc}" if isinstance(exc, LookupError) else str(exc))
+    cli.guarded(lambda: merge.merge_index(sources, out_path=val.get("-o") or None, cons_path=val.get("-c") or None,
+                                          list_out=val.get("-G") or None, fai=val.get("-f"), device=_cli.device(), log=lambda line: None))

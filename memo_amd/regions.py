@@ -17,7 +17,9 @@ import ctypes as C
 
 import numpy as np
 
+from ._device import DevBuffer, emit_text, on_device
 from ._lib import check, lib
+from ._window import parse_region
 from .index import words
 
 Runs = collections.namedtuple("Runs", "record qs L starts values run_bits num_docs")
@@ -30,33 +32,6 @@ def tile(words_per_position=0):
     return int(lib().memo_runs_tile(int(words_per_position)))
 
 
-def _on_device(host_or_pair, dtype, device):
-    """(device pointer, L, buffer to free or None) of a host array, or of a (device pointer, L) pair as it is"""
-    if isinstance(host_or_pair, tuple):
-        return C.c_void_p(int(host_or_pair[0])), int(host_or_pair[1]), None
-    host = np.ascontiguousarray(host_or_pair, dtype)
-    tmp = C.c_void_p()
-    check(lib().memo_dev_malloc(device, host.nbytes, C.byref(tmp)))
-    try:
-        check(lib().memo_dev_upload(device, tmp, host.ctypes.data, host.nbytes, None))
-    except BaseException:
-        lib().memo_dev_free(device, tmp)
-        raise
-    return tmp, len(host), tmp
-
-
-def _download(device, d_ptr, shape, dtype):
-    """a device buffer the runs calls allocated, as a host array; the buffer is freed"""
-    out = np.empty(shape, dtype)
-    try:
-        if d_ptr and out.nbytes:
-            check(lib().memo_dev_download(device, out.ctypes.data, d_ptr, out.nbytes, None))
-    finally:
-        if d_ptr:
-            lib().memo_dev_free(device, d_ptr)
-    return out
-
-
 def runs(vec, mode="value", lo=None, hi=None, device=0, stream=None):
     """Runs of a conservation vector: a host uint16 array, or (device pointer, L).  mode "value": (starts, values); mode
     "band": the boundaries of lo <= value <= hi (one int64 array)."""
@@ -65,22 +40,14 @@ def runs(vec, mode="value", lo=None, hi=None, device=0, stream=None):
     band = mode == "band"
     if band and (lo is None or hi is None):
         raise ValueError("a band needs lo and hi")
-    d_vec, L, tmp = _on_device(vec, np.uint16, device)
     d_starts, d_values, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
-    try:
+    with on_device(vec, np.uint16, device) as (d_vec, L):
         check(lib().memo_runs_conservation_dev(d_vec, L, 1 if band else 0, int(lo) if band else 0, int(hi) if band else 0,
                                                C.byref(d_starts), None if band else C.byref(d_values), C.byref(n), device,
                                                None if stream is None else C.c_void_p(int(stream))))
-    finally:
-        if tmp is not None:
-            lib().memo_dev_free(device, tmp)
-    try:
-        starts = _download(device, d_starts, n.value, np.int64)
-    except BaseException:
-        if d_values:
-            lib().memo_dev_free(device, d_values)
-        raise
-    return starts if band else (starts, _download(device, d_values, n.value, np.uint16))
+    with DevBuffer.adopt(d_starts, device) as b_starts, DevBuffer.adopt(d_values, device) as b_values:
+        starts = b_starts.to_host(n.value, np.int64)
+        return starts if band else (starts, b_values.to_host(n.value, np.uint16))
 
 
 def membership_runs(bits, num_docs, device=0, stream=None):
@@ -88,21 +55,12 @@ def membership_runs(bits, num_docs, device=0, stream=None):
     W = words(num_docs)
     if not isinstance(bits, tuple):
         bits = np.ascontiguousarray(bits, np.uint32).reshape(-1, W)
-    d_bits, L, tmp = _on_device(bits, np.uint32, device)
     d_starts, d_rows, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
-    try:
+    with on_device(bits, np.uint32, device) as (d_bits, L):
         check(lib().memo_runs_membership_dev(d_bits, L, num_docs, C.byref(d_starts), C.byref(d_rows), C.byref(n), device,
                                              None if stream is None else C.c_void_p(int(stream))))
-    finally:
-        if tmp is not None:
-            lib().memo_dev_free(device, tmp)
-    try:
-        starts = _download(device, d_starts, n.value, np.int64)
-    except BaseException:
-        if d_rows:
-            lib().memo_dev_free(device, d_rows)
-        raise
-    return starts, _download(device, d_rows, (n.value, W), np.uint32)
+    with DevBuffer.adopt(d_starts, device) as b_starts, DevBuffer.adopt(d_rows, device) as b_rows:
+        return b_starts.to_host(n.value, np.int64), b_rows.to_host((n.value, W), np.uint32)
 
 
 def band_intervals(boundaries, L):
@@ -127,47 +85,30 @@ def region_runs(index_path, region, k, n_docs, membership=False, lo=None, hi=Non
     from . import memo_query
     if membership and (lo is not None or hi is not None):
         raise ValueError("a band is a question about conservation values, not about membership rows")
-    record, start_end = region.split(':')                  # exactly one ':' and one '-'
-    qs, qe = map(int, start_end.split('-'))
-    if qe < qs:
-        raise ValueError("negative dimensions are not allowed")          # np.zeros of memo_init, as `memo query` raises it
+    record, qs, qe = parse_region(region)
     band = lo is not None or hi is not None
     index = memo_query.region_index(index_path, record, qs, qe + k, device=device, k=k, num_docs=n_docs, membership=membership)
-    with index:
-        L = qe - qs
-        d_vec = C.c_void_p()
-        check(lib().memo_dev_malloc(device, L * (4 * words(n_docs) if membership else 2), C.byref(d_vec)))
-        try:
-            if membership:
-                index.membership_dev(qs, qe, k, n_docs, d_vec.value)
-                index.check()
-                starts, rows = membership_runs((d_vec.value, L), n_docs, device)
-                return Runs(record, qs, L, starts, None, rows, n_docs)
-            index.conservation_dev(qs, qe, k, n_docs, d_vec.value)
+    L = qe - qs
+    with index, DevBuffer(device, max(L * (4 * words(n_docs) if membership else 2), 8)) as vec:       # (an empty window has an address too)
+        if membership:
+            index.membership_dev(qs, qe, k, n_docs, vec.d.value)
             index.check()
-            if band:
-                starts = runs((d_vec.value, L), "band", 0 if lo is None else lo, n_docs if hi is None else hi, device)
-                return Runs(record, qs, L, starts, None, None, n_docs)
-            starts, values = runs((d_vec.value, L), "value", device=device)
-            return Runs(record, qs, L, starts, values, None, n_docs)
-        finally:
-            lib().memo_dev_free(device, d_vec)
-
-
-def _emit(call):
-    """the text as a writable byte buffer: sized by a first call, written by the second"""
-    need = call(None, 0)
-    buf = np.empty(need, np.uint8)
-    if need:
-        call(buf.ctypes.data, need)
-    return buf
+            starts, rows = membership_runs((vec.d.value, L), n_docs, device)
+            return Runs(record, qs, L, starts, None, rows, n_docs)
+        index.conservation_dev(qs, qe, k, n_docs, vec.d.value)
+        index.check()
+        if band:
+            starts = runs((vec.d.value, L), "band", 0 if lo is None else lo, n_docs if hi is None else hi, device)
+            return Runs(record, qs, L, starts, None, None, n_docs)
+        starts, values = runs((vec.d.value, L), "value", device=device)
+        return Runs(record, qs, L, starts, values, None, n_docs)
 
 
 def emit_runs(record, qs, L, starts, values=None):
     """bedGraph lines (values given) or BED3 lines of a band's intervals (values None), as a uint8 array"""
     s = np.ascontiguousarray(starts, np.int64)
     v = None if values is None else np.ascontiguousarray(values, np.uint16)
-    return _emit(lambda buf, cap: lib().memo_emit_runs(record.encode(), qs, L, s.ctypes.data, None if v is None else v.ctypes.data,
+    return emit_text(lambda buf, cap: lib().memo_emit_runs(record.encode(), qs, L, s.ctypes.data, None if v is None else v.ctypes.data,
                                                        len(s), buf, cap))
 
 
@@ -175,7 +116,7 @@ def emit_membership_runs(record, qs, L, starts, run_bits, num_docs):
     """REC start end 0110... lines (num_docs characters, genome 0 first), as a uint8 array"""
     s = np.ascontiguousarray(starts, np.int64)
     b = np.ascontiguousarray(run_bits, np.uint32)
-    return _emit(lambda buf, cap: lib().memo_emit_membership_runs(record.encode(), qs, L, s.ctypes.data, b.ctypes.data, len(s),
+    return emit_text(lambda buf, cap: lib().memo_emit_membership_runs(record.encode(), qs, L, s.ctypes.data, b.ctypes.data, len(s),
                                                                   num_docs, buf, cap))
 
 

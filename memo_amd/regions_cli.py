@@ -5,9 +5,7 @@ of equal values -- a bedGraph for a genome browser, a BED3 of the regions inside
 bedtools, or a BED with one 0/1 character per genome (-m).  The window is swept as `memo query` sweeps it, the result is
 run-coded where it lies (memo_amd/regions.py, memo_amd/csrc/memo_runs.hip), and only the runs leave the device.  One GPU.
 """
-import getopt
-import os
-import sys
+from . import _cli
 
 USAGE = """
 MEMO regions - k-mer conservation or membership of a pivot genome region as intervals
@@ -26,53 +24,25 @@ Basic options:
 """
 
 
-def usage():
-    sys.stdout.write(USAGE)
-    sys.exit(0)
-
-
-def refuse(message, status=1):
-    sys.stderr.write(f"memo regions: {message}\n")
-    sys.exit(status)
+cli = _cli.Cli("regions", USAGE, "b:k:n:r:o:mt:T:", {"-k": "31"})
+refuse = cli.refuse
 
 
 def _bound(flag, text, n_docs):
-    try:
-        value = int(text)
-    except ValueError:
-        value = -1
-    if not 0 <= value <= n_docs:
-        refuse(f"{flag} must be an integer in [0, {n_docs}] (got {text!r})")
-    return value
+    return cli.integer(flag, text, 0, n_docs, f"[0, {n_docs}]")
 
 
 def main(argv):
     """bin/memo regions [options]: usage handling as the other sub-commands (getopts messages on stderr, then the usage, exit 0)"""
-    if not argv or argv[0] == "-h":
-        usage()
-    try:
-        opts, _ = getopt.getopt(argv, "b:k:n:r:o:mt:T:")
-    except getopt.GetoptError as exc:
-        what = "option requires an argument" if "requires argument" in exc.msg else "illegal option"
-        sys.stderr.write(f"{sys.argv[0]}: {what} -- {exc.opt}\n")
-        usage()
-    val = {"-k": "31"}
-    for o, a in opts:
-        val[o] = a
-    print("MEMO - regions", flush=True)
+    val = cli.parse(argv)
     # everything that can be refused is refused before the device is touched
-    missing = [f for f in ("-b", "-r", "-n", "-o") if val.get(f, "") == ""]
-    if missing:
-        refuse(f"{', '.join(missing)} required", 2)
-    if int(os.environ.get("WORLD_SIZE", "1") or "1") > 1 or os.environ.get("MEMO_FORCE_SHARDED"):
+    cli.require(val, ("-b", "-r", "-n", "-o"))
+    if _cli.sharded_launch():
         refuse("one GPU only: a sharded launch (WORLD_SIZE > 1, MEMO_FORCE_SHARDED) is not supported -- use memo query")
     membership, band = "-m" in val, "-t" in val or "-T" in val
     if membership and band:
         refuse("-m cannot be combined with -t / -T: a band is a question about conservation values")
-    try:
-        n_docs, k = int(val["-n"]), int(val["-k"])
-    except ValueError as exc:
-        refuse(str(exc))
+    n_docs, k = cli.integers(val, "-n", "-k")
     lo = hi = None
     if band:
         lo = _bound("-t", val["-t"], n_docs) if "-t" in val else 0
@@ -80,18 +50,8 @@ def main(argv):
         if lo > hi:
             refuse(f"-t {lo} is above -T {hi}: no value lies in that band")
     from . import regions
-    from ._lib import MemoError
-    from .view_cli import _replace_into
-    try:
-        device = int(os.environ.get("MEMO_DEVICE", "0"))   # as `memo query` chooses its GPU
-        result = regions.region_runs(val["-b"], val["-r"], k, n_docs, membership, lo, hi, device)
-        text = regions.emit(result)
 
-        def write(tmp):
-            with open(tmp, "wb") as fh:
-                fh.write(memoryview(text))
-        _replace_into(val["-o"], write)
-    # a window or a Parquet file that is refused (pyarrow's errors are ValueErrors and OSErrors), the sweep's own IndexError
-    # (index.check), a record that is not there.  Anything else is a defect and leaves as a traceback, as from `memo query`.
-    except (MemoError, OSError, LookupError, ValueError) as exc:
-        refuse(f"{type(exc).__name__}: {exc}" if isinstance(exc, LookupError) else str(exc))
+    def run():
+        result = regions.region_runs(val["-b"], val["-r"], k, n_docs, membership, lo, hi, _cli.device())
+        _cli.write_bytes(val["-o"], regions.emit(result))
+    cli.guarded(run)

@@ -11,17 +11,16 @@ No counterpart in the reference.  With N genomes, a window [qs, qe), 1 <= kmax <
 
 For rows with end >= start exact[k] is numpy.bincount of what `memo query -k k` writes for the window on a conservation index, and of
 the one-bit counts of what `memo query -m -k k` writes on a membership index.  Nothing in an index tells the two kinds apart: the
-caller says which it is.  The planes stay on the device, slice by slice (lengths._finished_slices); every slice is added into one table
+caller says which it is.  The planes stay on the device, slice by slice (lengths.finished_slices); every slice is added into one table
 there, and kmax (N + 1) integers leave it.  The result depends neither on the slicing nor on the cut of the rows into chunks.  The
 flags are memo_amd/spectrum_cli.py.
 """
-import ctypes as C
-
 import numpy as np
 
+from ._device import DevBuffer
 from ._lib import check, lib
-from .lengths import N_MAX, _DevBuffer, _docs, _finished_slices, _host_feed, _pitch, _region, _region_feed
-from .maxk import _window
+from .lengths import N_MAX, docs, finished_slices, host_feed, pitch_of, region_feed, region_window
+from .maxk import window
 
 KMAX_MAX = 1024
 
@@ -43,7 +42,7 @@ class _Table:
 
     def __init__(self, n_docs, kmax, membership, device):
         self.n, self.kmax, self.mode, self.device = n_docs, kmax, 1 if membership else 0, device
-        self.scratch = _DevBuffer(device, int(lib().memo_spectrum_scratch_bytes(n_docs, kmax)))
+        self.scratch = DevBuffer(device, int(lib().memo_spectrum_scratch_bytes(n_docs, kmax)))
         try:
             check(lib().memo_spectrum_begin_dev(self.scratch.d, n_docs, kmax, device, None))
         except BaseException:
@@ -54,11 +53,10 @@ class _Table:
         check(lib().memo_spectrum_add_dev(d_cells, L, pitch, self.n, self.kmax, self.mode, self.scratch.d, self.device, None))
 
     def finish(self):
-        out = np.empty((self.kmax, self.n + 1), np.uint64)
-        with _DevBuffer(self.device, out.nbytes) as d_exact:
+        shape = (self.kmax, self.n + 1)
+        with DevBuffer(self.device, 8 * shape[0] * shape[1]) as d_exact:
             check(lib().memo_spectrum_finish_dev(self.scratch.d, self.n, self.kmax, d_exact.d, self.device, None))
-            check(lib().memo_dev_download(self.device, out.ctypes.data, d_exact.d, out.nbytes, None))
-        return out
+            return d_exact.to_host(shape, np.uint64)
 
     def __enter__(self):
         return self
@@ -73,12 +71,12 @@ def table(planes, kmax, membership, device=0):
     planes = np.asarray(planes, np.uint32)
     if planes.ndim != 2:
         raise ValueError("planes must be [n_docs, positions]")
-    n_docs, kmax = _docs(planes.shape[0]), _kmax(kmax)
+    n_docs, kmax = docs(planes.shape[0]), _kmax(kmax)
     L = planes.shape[1]
-    pitch = _pitch(L)
+    pitch = pitch_of(L)
     padded = np.zeros((n_docs, pitch), np.uint32)
     padded[:, :L] = planes
-    with _DevBuffer(device, padded.nbytes) as cells, _Table(n_docs, kmax, membership, device) as tab:
+    with DevBuffer(device, padded.nbytes) as cells, _Table(n_docs, kmax, membership, device) as tab:
         if L:
             check(lib().memo_dev_upload(device, cells.d, padded.ctypes.data, padded.nbytes, None))
         tab.add(cells.d, L, pitch)
@@ -87,7 +85,7 @@ def table(planes, kmax, membership, device=0):
 
 def _exact(feed, buf, qs, L, n_docs, kmax, membership, device, slice_positions):
     with buf, _Table(n_docs, kmax, membership, device) as tab:
-        for a, b, d_cells, pitch in _finished_slices(feed, qs, L, n_docs, kmax, device, slice_positions):
+        for a, b, d_cells, pitch in finished_slices(feed, qs, L, n_docs, kmax, device, slice_positions):
             tab.add(d_cells, b - a, pitch)
         return tab.finish()
 
@@ -96,18 +94,18 @@ def exact(start, end, annot, qs, qe, n_docs, *, kmax, membership, device=0, chun
     """exact[k][v] of the window [qs, qe) from host columns (any order; rows outside qs < start < qe + kmax and annots outside
     [0, n_docs) are ignored).  chunk_rows: feed the rows in calls of that many; slice_positions: take the window in slices of that many
     positions (the result depends on neither).  Returns uint64 [kmax, n_docs + 1]: row k - 1 is exact[k]."""
-    n_docs, kmax = _docs(n_docs), _kmax(kmax)
-    qs, L, _ = _window(qs, qe, kmax)
-    feed, buf = _host_feed(start, end, annot, chunk_rows, device, (qs, min(qs + L + kmax, 2 ** 62)))
+    n_docs, kmax = docs(n_docs), _kmax(kmax)
+    qs, L, _ = window(qs, qe, kmax)
+    feed, buf = host_feed(start, end, annot, chunk_rows, device, (qs, min(qs + L + kmax, 2 ** 62)))
     return _exact(feed, buf, qs, L, n_docs, kmax, membership, device, slice_positions)
 
 
 def region_exact(index_path, region, n_docs, kmax=128, membership=False, device=0, slice_positions=None):
     """exact[k][v] of a window of a Parquet index.  `region` is CHR:START-END as `memo query -r` takes it, and what is wrong with it
     raises what memo_query.main raises.  One device.  Returns uint64 [kmax, n_docs + 1]."""
-    n_docs, kmax = _docs(n_docs), _kmax(kmax)
-    record, qs, L, _ = _region(region, kmax)
-    feed, buf = _region_feed(index_path, record, device)
+    n_docs, kmax = docs(n_docs), _kmax(kmax)
+    record, qs, L, _ = region_window(region, kmax)
+    feed, buf = region_feed(index_path, record, device)
     return _exact(feed, buf, qs, L, n_docs, kmax, membership, device, slice_positions)
 
 

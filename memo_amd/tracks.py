@@ -16,9 +16,10 @@ import ctypes as C
 
 import numpy as np
 
+from ._device import DevBuffer, on_device
 from ._lib import check, lib
+from ._window import membership_slices, parse_region
 from .index import words
-from .regions import _on_device
 from .view import bin_edges
 
 
@@ -39,27 +40,12 @@ def _edges(edges):
     return edges
 
 
-def _table_on_device(num_docs, bins, counts, device):
-    """a device table uint64 [N, B] holding `counts` (None: zeros)"""
+def _table(num_docs, bins, counts):
+    """`counts` as a host table uint64 [N, B] (None: zeros)"""
     host = np.zeros((num_docs, bins), np.uint64) if counts is None else np.ascontiguousarray(counts, np.uint64)
     if host.shape != (num_docs, bins):
         raise ValueError(f"counts must be [{num_docs}, {bins}]")
-    d = C.c_void_p()
-    check(lib().memo_dev_malloc(device, max(host.nbytes, 8), C.byref(d)))
-    try:
-        if host.nbytes:
-            check(lib().memo_dev_upload(device, d, host.ctypes.data, host.nbytes, None))
-    except BaseException:
-        lib().memo_dev_free(device, d)
-        raise
-    return d
-
-
-def _table_to_host(d_counts, num_docs, bins, device):
-    out = np.empty((num_docs, bins), np.uint64)
-    if out.nbytes:
-        check(lib().memo_dev_download(device, out.ctypes.data, d_counts, out.nbytes, None))
-    return out
+    return host
 
 
 def bin_tracks(bits, num_docs, edges, first=0, counts=None, device=0, stream=None):
@@ -71,17 +57,18 @@ def bin_tracks(bits, num_docs, edges, first=0, counts=None, device=0, stream=Non
     if not isinstance(bits, tuple):
         bits = np.ascontiguousarray(bits, np.uint32).reshape(-1, W)
     bins = len(edges) - 1
-    d_counts = _table_on_device(num_docs, bins, counts, device)
-    try:
-        d_bits, L, tmp = _on_device(bits, np.uint32, device)
-        try:
-            _accumulate(d_bits, L, num_docs, int(first), edges, d_counts, device, stream)
-        finally:
-            if tmp is not None:
-                lib().memo_dev_free(device, tmp)
-        return _table_to_host(d_counts, num_docs, bins, device)
-    finally:
-        lib().memo_dev_free(device, d_counts)
+    with DevBuffer.of(_table(num_docs, bins, counts), device) as d_counts, on_device(bits, np.uint32, device) as (d_bits, L):
+        _accumulate(d_bits, L, num_docs, int(first), edges, d_counts.d, device, stream)
+        return d_counts.to_host((num_docs, bins), np.uint64)
+
+
+class Tracks(tuple):
+    """region_tracks' result: the pair (counts, edges), and the window's start as .qs"""
+
+    def __new__(cls, counts, edges, qs):
+        self = super().__new__(cls, (counts, edges))
+        self.qs = qs
+        return self
 
 
 def region_edges(positions, n_bins):
@@ -97,36 +84,19 @@ def region_tracks(index_path, region, k, n_docs, n_bins, device=0, slice_positio
     `slice_positions` into one reused device buffer of slice_positions x W x 4 bytes, each slice is accumulated into one device
     table, and N x B x 8 bytes are downloaded at the end.  A slice is swept as part of its window (membership_slice_dev), so the
     table does not depend on the slices.  `region` is CHR:START-END as `memo query -r` takes it, and what is wrong with it raises
-    what memo_query.main raises.  One device.  Returns (counts uint64 [N, B], edges int64 [B + 1] from the window's start); an
-    empty window gives (uint64 [N, 0], [0])."""
+    what memo_query.main raises.  One device.  Returns Tracks: (counts uint64 [N, B], edges int64 [B + 1] from the window's start),
+    which is .qs; an empty window gives (uint64 [N, 0], [0])."""
     from . import memo_query
-    if slice_positions < 1:
-        raise ValueError("slice_positions must be at least 1")
-    record, start_end = region.split(':')                  # exactly one ':' and one '-'
-    qs, qe = map(int, start_end.split('-'))
-    if qe < qs:
-        raise ValueError("negative dimensions are not allowed")          # np.zeros of memo_init, as `memo query` raises it
+    record, qs, qe = parse_region(region)
     edges = region_edges(qe - qs, n_bins) if qe > qs or n_bins < 1 else np.zeros(1, np.int64)
     index = memo_query.region_index(index_path, record, qs, qe + k, device=device, k=k, num_docs=n_docs, membership=True)
     with index:
         if qe == qs:                                       # (nothing to sweep, as in region_matrix)
-            return np.zeros((n_docs, 0), np.uint64), edges
-        step = min(int(slice_positions), qe - qs)
-        d_counts = _table_on_device(n_docs, n_bins, None, device)
-        try:
-            d_bits = C.c_void_p()
-            check(lib().memo_dev_malloc(device, step * 4 * words(n_docs), C.byref(d_bits)))
-            try:
-                for s in range(qs, qe, step):
-                    e = min(s + step, qe)
-                    index.membership_slice_dev(qs, qe, s, e, k, n_docs, d_bits.value)
-                    index.check()
-                    _accumulate(d_bits, e - s, n_docs, s - qs, edges, d_counts, device)
-            finally:
-                lib().memo_dev_free(device, d_bits)
-            return _table_to_host(d_counts, n_docs, n_bins, device), edges
-        finally:
-            lib().memo_dev_free(device, d_counts)
+            return Tracks(np.zeros((n_docs, 0), np.uint64), edges, qs)
+        with DevBuffer.of(_table(n_docs, n_bins, None), device) as d_counts:
+            for d_bits, s, e in membership_slices(index, qs, qe, k, n_docs, slice_positions, device):
+                _accumulate(d_bits, e - s, n_docs, s - qs, edges, d_counts.d, device)
+            return Tracks(d_counts.to_host((n_docs, n_bins), np.uint64), edges, qs)
 
 
 def fractions(counts, edges):

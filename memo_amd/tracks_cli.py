@@ -8,9 +8,9 @@ each slice is counted where it lies (memo_amd/tracks.py, memo_amd/csrc/memo_trac
 What `-o` is called decides what is written, as for `memo view`: a name ending in `.tsv` gets the table, any other name a
 matplotlib plot.  One GPU.
 """
-import getopt
 import os
-import sys
+
+from . import _cli
 
 USAGE = """
 MEMO tracks - per-genome k-mer presence along a pivot genome region, in bins
@@ -31,27 +31,8 @@ Basic options:
 """
 
 
-def usage():
-    sys.stdout.write(USAGE)
-    sys.exit(0)
-
-
-def refuse(message, status=1):
-    sys.stderr.write(f"memo tracks: {message}\n")
-    sys.exit(status)
-
-
-def read_labels(path, n_docs):
-    """as `memo matrix -g` reads and checks them, refused under this sub-command's name"""
-    from .matrix_cli import label_of
-    try:
-        with open(path) as fh:
-            lines = [ln.strip() for ln in fh if ln.strip()]
-    except OSError as exc:
-        refuse(f"cannot read the genome list {path}: {exc.strerror}")
-    if len(lines) != n_docs:
-        refuse(f"-g {path} names {len(lines)} genomes, -n says {n_docs}")
-    return [label_of(ln) for ln in lines]
+cli = _cli.Cli("tracks", USAGE, "b:k:n:r:o:B:fg:d:", {"-k": "31", "-B": "500", "-d": "600"})
+refuse, read_labels = cli.refuse, cli.read_labels
 
 
 def render(share, qs, edges, path, labels=None, dpi=600):
@@ -61,7 +42,7 @@ def render(share, qs, edges, path, labels=None, dpi=600):
     from matplotlib.backends.backend_agg import FigureCanvasAgg
     from matplotlib.colors import LinearSegmentedColormap, Normalize
     from matplotlib.figure import Figure
-    from .view_cli import HIGH, LOW, _replace_into
+    from .view_cli import HIGH, LOW
     share = np.asarray(share, np.float64)
     n_docs, n_bins = share.shape
     with matplotlib.rc_context({"font.size": 18, "font.family": "sans-serif"}):
@@ -80,33 +61,16 @@ def render(share, qs, edges, path, labels=None, dpi=600):
         fig.tight_layout()
         ext = os.path.splitext(path)[1][1:].lower()
         fmt = ext if ext in canvas.get_supported_filetypes() else "png"
-        _replace_into(path, lambda tmp: fig.savefig(tmp, format=fmt, dpi=dpi))
+        _cli.replace_into(path, lambda tmp: fig.savefig(tmp, format=fmt, dpi=dpi))
 
 
 def main(argv):
     """bin/memo tracks [options]: usage handling as the other sub-commands (getopts messages on stderr, then the usage, exit 0)"""
-    if not argv or argv[0] == "-h":
-        usage()
-    try:
-        opts, _ = getopt.getopt(argv, "b:k:n:r:o:B:fg:d:")
-    except getopt.GetoptError as exc:
-        what = "option requires an argument" if "requires argument" in exc.msg else "illegal option"
-        sys.stderr.write(f"{sys.argv[0]}: {what} -- {exc.opt}\n")
-        usage()
-    val = {"-k": "31", "-B": "500", "-d": "600"}
-    for o, a in opts:
-        val[o] = a
-    print("MEMO - tracks", flush=True)
+    val = cli.parse(argv)
     # everything that can be refused is refused before the device is touched
-    missing = [f for f in ("-b", "-r", "-n", "-o") if val.get(f, "") == ""]
-    if missing:
-        refuse(f"{', '.join(missing)} required", 2)
-    if int(os.environ.get("WORLD_SIZE", "1") or "1") > 1 or os.environ.get("MEMO_FORCE_SHARDED"):
-        refuse("one GPU only: a sharded launch (WORLD_SIZE > 1, MEMO_FORCE_SHARDED) is not supported")
-    try:
-        n_docs, k, n_bins, dpi = (int(val[f]) for f in ("-n", "-k", "-B", "-d"))
-    except ValueError as exc:
-        refuse(str(exc))
+    cli.require(val, ("-b", "-r", "-n", "-o"))
+    cli.one_gpu_only()
+    n_docs, k, n_bins, dpi = cli.integers(val, "-n", "-k", "-B", "-d")
     if n_bins < 1:
         refuse(f"-B {n_bins}: the number of bins must be at least 1")
     labels = read_labels(val["-g"], n_docs) if "-g" in val else None
@@ -117,23 +81,14 @@ def main(argv):
         except ImportError:
             refuse("matplotlib is not installed, so no plot can be drawn -- name the output FILE.tsv (-o) to get the table instead")
     from . import tracks
-    from ._lib import MemoError
-    from .view_cli import _replace_into
-    try:
-        device = int(os.environ.get("MEMO_DEVICE", "0"))   # as `memo query` chooses its GPU
-        counts, edges = tracks.region_tracks(val["-b"], val["-r"], k, n_docs, n_bins, device)
-        qs = int(val["-r"].split(':')[1].split('-')[0])    # (a region that region_tracks took)
-        empty = counts.shape[1] == 0                       # an empty window: an empty file
 
-        def write(tmp):
-            with open(tmp, "w") as fh:
-                if not empty:
-                    fh.write(tracks.format_tracks(tracks.fractions(counts, edges) if "-f" in val else counts, qs, edges, labels))
-        if as_table or empty:
-            _replace_into(val["-o"], write)
+    def run():
+        result = tracks.region_tracks(val["-b"], val["-r"], k, n_docs, n_bins, _cli.device())
+        (counts, edges), qs = result, result.qs
+        if counts.shape[1] == 0:                           # an empty window: an empty file
+            _cli.write_text(val["-o"], "")
+        elif as_table:
+            _cli.write_text(val["-o"], tracks.format_tracks(tracks.fractions(counts, edges) if "-f" in val else counts, qs, edges, labels))
         else:
             render(tracks.fractions(counts, edges), qs, edges, val["-o"], labels, dpi)
-    # a window or a Parquet file that is refused (pyarrow's errors are ValueErrors and OSErrors), more bins than positions, the
-    # sweep's own IndexError (index.check), a record that is not there.  Anything else is a defect and leaves as a traceback.
-    except (MemoError, OSError, LookupError, ValueError) as exc:
-        refuse(f"{type(exc).__name__}: {exc}" if isinstance(exc, LookupError) else str(exc))
+    cli.guarded(run)

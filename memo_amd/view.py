@@ -20,7 +20,9 @@ import os
 
 import numpy as np
 
+from ._device import DevBuffer, on_device
 from ._lib import check, lib
+from ._window import parse_region
 
 
 def bin_edges(positions, n_bins):
@@ -29,22 +31,11 @@ def bin_edges(positions, n_bins):
 
 def bin_counts(vec, n_docs, n_bins, device=0, stream=None):
     """uint64 [n_bins, n_docs + 1] histogram.  vec: host uint16 array, or (device pointer, length)."""
-    if isinstance(vec, tuple):
-        d_vec, L, tmp = C.c_void_p(int(vec[0])), int(vec[1]), None
-    else:
-        host = np.ascontiguousarray(vec, np.uint16)
-        L, tmp = len(host), C.c_void_p()
-        check(lib().memo_dev_malloc(device, host.nbytes, C.byref(tmp)))
-        d_vec = tmp
-        check(lib().memo_dev_upload(device, d_vec, host.ctypes.data, host.nbytes, None))
-    try:
+    with on_device(vec, np.uint16, device) as (d_vec, L):
         edges = bin_edges(L, n_bins)
         counts = np.zeros((n_bins, n_docs + 1), np.uint64)
         check(lib().memo_bin_conservation_dev(d_vec, L, edges.ctypes.data, n_bins, n_docs, counts.ctypes.data,
                                               device, None if stream is None else C.c_void_p(int(stream))))
-    finally:
-        if tmp is not None:
-            lib().memo_dev_free(device, tmp)
     return counts, edges
 
 
@@ -63,12 +54,6 @@ def _read_text_reference(path):
     return np.fromiter((v if 0 <= v < 65535 else 65535 for v in values), np.uint16, len(values))
 
 
-def _dev_buffer(device, nbytes):
-    p = C.c_void_p()
-    check(lib().memo_dev_malloc(device, nbytes, C.byref(p)))
-    return p
-
-
 def read_conservation_text_dev(path, device=0):
     """(device pointer, L, free): the file's L values as uint16 in HBM, free() releases them.  The file is copied to the
     device as it is (memory-mapped, in pieces through the pinned ring) and parsed there; a text outside the device
@@ -76,37 +61,29 @@ def read_conservation_text_dev(path, device=0):
     with open(path, "rb") as fh:
         nbytes = os.fstat(fh.fileno()).st_size
         cap = nbytes // 2 + 1
-        d_vec = _dev_buffer(device, 2 * cap)
+        vec = DevBuffer(device, 2 * cap)
         lines, odd = C.c_int64(0), C.c_int64(-1)
         try:
             if nbytes:
-                d_text = _dev_buffer(device, nbytes)
-                try:
+                with DevBuffer(device, nbytes) as text:
                     with mmap.mmap(fh.fileno(), nbytes, access=mmap.ACCESS_READ) as mm:
                         host = np.frombuffer(mm, np.uint8)
                         try:
-                            check(lib().memo_dev_upload_pipelined(device, d_text, host.ctypes.data, nbytes))
+                            check(lib().memo_dev_upload_pipelined(device, text.d, host.ctypes.data, nbytes))
                         finally:
                             del host                       # (the map cannot close under an exported buffer)
-                    check(lib().memo_parse_conservation_text_dev(d_text, nbytes, d_vec, cap, C.byref(lines), C.byref(odd),
+                    check(lib().memo_parse_conservation_text_dev(text.d, nbytes, vec.d, cap, C.byref(lines), C.byref(odd),
                                                                  device, None))
-                finally:
-                    lib().memo_dev_free(device, d_text)
         except BaseException:
-            lib().memo_dev_free(device, d_vec)
+            vec.close()
             raise
     L = lines.value
     if odd.value >= 0:
-        lib().memo_dev_free(device, d_vec)
+        vec.close()
         values = _read_text_reference(path)                # (or its ValueError)
         L = len(values)
-        d_vec = _dev_buffer(device, values.nbytes)
-        try:
-            check(lib().memo_dev_upload(device, d_vec, values.ctypes.data, values.nbytes, None))
-        except BaseException:
-            lib().memo_dev_free(device, d_vec)
-            raise
-    return int(d_vec.value), L, lambda: lib().memo_dev_free(device, d_vec)
+        vec = DevBuffer.of(values, device)
+    return int(vec.d.value), L, vec.close
 
 
 def _table(counts, edges, n_docs, n_bins):
@@ -140,18 +117,11 @@ def preprocess_region(index_path, region, k, n_docs, n_bins, device=0):
     in HBM and is binned there; only n_bins x (n_docs + 1) counts leave the device.  `region` is CHR:START-END as `memo
     query -r` takes it, and what is wrong with it raises what memo_query.main raises.  One device."""
     from . import memo_query
-    record, start_end = region.split(':')                  # exactly one ':' and one '-'
-    qs, qe = map(int, start_end.split('-'))
-    if qe < qs:
-        raise ValueError("negative dimensions are not allowed")          # np.zeros of memo_init, as `memo query` raises it
+    record, qs, qe = parse_region(region)
     index = memo_query.region_index(index_path, record, qs, qe + k, device=device, k=k, num_docs=n_docs, membership=False)
-    with index:
-        L = qe - qs
-        d_vec = _dev_buffer(device, 2 * L)
-        try:
-            index.conservation_dev(qs, qe, k, n_docs, d_vec.value)
-            index.check()
-            counts, edges = bin_counts((d_vec.value, L), n_docs, n_bins, device)
-        finally:
-            lib().memo_dev_free(device, d_vec)
+    L = qe - qs
+    with index, DevBuffer(device, max(2 * L, 8)) as vec:                          # (an empty window has an address too)
+        index.conservation_dev(qs, qe, k, n_docs, vec.d.value)
+        index.check()
+        counts, edges = bin_counts((vec.d.value, L), n_docs, n_bins, device)
     return _table(counts, edges, n_docs, n_bins)

@@ -10,11 +10,12 @@ not a dependency of this build: the plot is drawn with matplotlib (Agg) after pl
 of width 1, the fill from #000000 to #c6dbef over 1 .. n_docs - 1, y from 0 to 1, the same title and labels, 20 x 4 in --
 and is not byte-compatible with the reference's.
 """
-import getopt
 import os
 import sys
 
 import numpy as np
+
+from . import _cli
 
 USAGE = """
 MEMO query - query k-mer membership or conservation on pivot genome region
@@ -41,32 +42,8 @@ TSV_HEADER = "bin\tNo. Genomes\tvalue\n"
 LOW, HIGH, OUTSIDE = "#000000", "#c6dbef", "#7f7f7f"     # scale_fill_gradient(low, high); ggplot's na.value for what lies outside its limits
 
 
-def usage():
-    sys.stdout.write(USAGE + EXTENSION)
-    sys.exit(0)
-
-
-def _replace_into(path, write):
-    """write(tmp) and then rename: the file is whole or it is not there"""
-    tmp = f"{path}.part{os.getpid()}"
-    try:
-        write(tmp)
-        os.replace(tmp, path)
-    except BaseException:
-        if os.path.exists(tmp):
-            os.unlink(tmp)
-        raise
-
-
-def _replace_all_into(paths, write):
-    """write([tmp, ...]), one beside every path, and then rename from the last to the first: no file is replaced before all are
-    whole, and nothing is left behind"""
-    def nest(at, tmps):
-        if at == len(paths):
-            write(tmps)
-        else:
-            _replace_into(paths[at], lambda tmp: nest(at + 1, tmps + [tmp]))
-    nest(0, [])
+cli = _cli.Cli("view", USAGE + EXTENSION, "i:o:n:b:d:r:k:", {"-b": "500", "-d": "600", "-k": "31"},        # view.sh:9-10; query.sh:7
+               banner="MEMO - plotting sequence conservation")
 
 
 def write_tsv(table, path):
@@ -76,7 +53,7 @@ def write_tsv(table, path):
             fh.write(TSV_HEADER)
             fh.write("".join(f"{int(b)}\t{float(g)!r}\t{float(v)!r}\n"
                              for b, g, v in zip(table["bin"], table["No. Genomes"], table["value"])))
-    _replace_into(path, write)
+    _cli.replace_into(path, write)
 
 
 def fill_colours(n_docs):
@@ -116,23 +93,12 @@ def render(table, n_docs, n_bins, path, dpi=600):
         fig.subplots_adjust(left=0.08, right=1.0, bottom=0.24, top=0.86)
         ext = os.path.splitext(path)[1][1:].lower()
         fmt = ext if ext in canvas.get_supported_filetypes() else "png"
-        _replace_into(path, lambda tmp: fig.savefig(tmp, format=fmt, dpi=dpi))
+        _cli.replace_into(path, lambda tmp: fig.savefig(tmp, format=fmt, dpi=dpi))
 
 
 def main(argv):
     """bin/memo view [options]: usage handling of view.sh (getopts messages on stderr, then the usage, exit 0)"""
-    if not argv or argv[0] == "-h":
-        usage()
-    try:
-        opts, _ = getopt.getopt(argv, "i:o:n:b:d:r:k:")
-    except getopt.GetoptError as exc:
-        what = "option requires an argument" if "requires argument" in exc.msg else "illegal option"
-        sys.stderr.write(f"{sys.argv[0]}: {what} -- {exc.opt}\n")
-        usage()
-    val = {"-b": "500", "-d": "600", "-k": "31"}          # view.sh:9-10; query.sh:7
-    for o, a in opts:
-        val[o] = a
-    print("MEMO - plotting sequence conservation", flush=True)
+    val = cli.parse(argv)
     missing = [f for f in ("-i", "-o", "-n") if val.get(f, "") == ""]
     if missing:                                           # (plot_conservation.py's argparse: required=True, status 2)
         sys.stderr.write(f"memo view: {', '.join(missing)} required\n")
@@ -150,7 +116,7 @@ def main(argv):
         from . import view
         from ._lib import MemoError
         try:
-            device = int(os.environ.get("MEMO_DEVICE", "0"))   # as `memo query` chooses its GPU
+            device = _cli.device()
             if "-r" in val:
                 table = view.preprocess_region(val["-i"], val["-r"], k, n_docs, n_bins, device)
             else:

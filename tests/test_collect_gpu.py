@@ -213,21 +213,17 @@ def test_accumulation(memo, num_docs):
 def _call_on_seeded_outputs(d_bits, L, N, order_rows):
     """memo_collect_dev on outputs that hold 7 and 9: (the error or None, core, covered afterwards)"""
     from memo_amd import collect
-    from memo_amd._lib import MemoError, lib
+    from memo_amd._device import DevBuffer
+    from memo_amd._lib import MemoError
     order_rows = np.ascontiguousarray(order_rows, np.uint16)
     shape = (max(order_rows.shape[0], 1), max(order_rows.shape[1], 1))       # (something to look at, whatever the call's P and M)
-    d_core = collect._curve_on_device(shape, np.full(shape, 7, np.uint64), 0)
-    d_covered = collect._curve_on_device(shape, np.full(shape, 9, np.uint64), 0)
-    try:
+    with DevBuffer.of(np.full(shape, 7, np.uint64), 0) as d_core, DevBuffer.of(np.full(shape, 9, np.uint64), 0) as d_covered:
         error = None
         try:
-            collect._accumulate(C.c_void_p(d_bits), L, N, order_rows, d_core, d_covered, 0)
+            collect._accumulate(C.c_void_p(d_bits), L, N, order_rows, d_core.d, d_covered.d, 0)
         except MemoError as exc:
             error = exc
-        return error, collect._curve_to_host(d_core, shape, 0), collect._curve_to_host(d_covered, shape, 0)
-    finally:
-        lib().memo_dev_free(0, d_core)
-        lib().memo_dev_free(0, d_covered)
+        return error, d_core.to_host(shape, np.uint64), d_covered.to_host(shape, np.uint64)
 
 
 def test_refusals_and_empty_calls_leave_the_outputs_unchanged(memo):

@@ -156,11 +156,11 @@ def main():
                 check(lib().memo_add_dap_dev(d_cells, pitch, n, first, positions, remaining, d_new, 1, d_dap, 0, None))
             kernel.append(timed(call))
             sizes.append(positions)
-        feed, buf = lengths._region_feed(old, names[0], 0)
+        feed, buf = lengths.region_feed(old, names[0], 0)
         t1 = time.perf_counter()
         rows = 0
         with buf, convert._RowBuilder(W, rec_begin, False, 0) as builder:
-            for part in convert._record_rows([(feed, n)], a.length, Push(builder), 0, None, None, W, matrix):
+            for part in convert.record_rows([(feed, n)], a.length, Push(builder), 0, None, None, W, matrix):
                 rows += len(part[0])
         pipe_s = time.perf_counter() - t1
     whole = [i for i, p in enumerate(sizes) if p == max(sizes)]       # the batches of full length

@@ -26,6 +26,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from memo_amd import _lib, collect, synth  # noqa: E402
+from memo_amd._device import DevBuffer  # noqa: E402
 from memo_amd.index import words  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -107,16 +108,12 @@ def one(n):
         for P in map(int, a.orders.split(",")):
             rows = collect.orders(n, 0) if P == 1 else collect.orders(n, P, 1)
             M = rows.shape[1]
-            d_core = collect._curve_on_device(rows.shape, None, 0)
-            d_covered = collect._curve_on_device(rows.shape, None, 0)
-            try:
-                t = collect_times(d_bits, Lw, n, rows, d_core, d_covered)
-                core = collect._curve_to_host(d_core, rows.shape, 0)
+            zeros = np.zeros(rows.shape, np.uint64)
+            with DevBuffer.of(zeros, 0) as d_core, DevBuffer.of(zeros, 0) as d_covered:
+                t = collect_times(d_bits, Lw, n, rows, d_core.d, d_covered.d)
+                core = d_core.to_host(rows.shape, np.uint64)
                 assert not (core % np.uint64(a.warm + a.repeats)).any()
                 core = core // np.uint64(a.warm + a.repeats)
-            finally:
-                lib().memo_dev_free(0, d_core)
-                lib().memo_dev_free(0, d_covered)
             dev = [s + f for s, f, _ in t]
             steps = P * M * (Lw / 32)
             print(f"memo_collect_dev, P = {P} orders of M = {M} steps: device {stats(dev)} = sweep {stats([s for s, _, _ in t])} + reduce "

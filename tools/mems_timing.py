@@ -23,6 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from memo_amd import _lib, lengths, mems, synth  # noqa: E402
+from memo_amd._device import DevBuffer  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--positions", type=int, default=100_000_000)
@@ -158,7 +159,7 @@ def main():
             # -a: one slice of the planes of the same rows read as a membership index
             Ls = min(lengths.default_slice_positions(n), M)
             pitch = (Ls + 3) & ~3
-            with lengths._DevBuffer(0, 4 * n * pitch) as planes:
+            with DevBuffer(0, 4 * n * pitch) as planes:
                 check(lib().memo_lengths_begin_dev(planes.d, Ls, pitch, n, cap, 0, None, 0, None))
                 check(lib().memo_lengths_rows_dev(*cols, rows, 0, Ls, pitch, n, cap, planes.d, 0, None))
                 check(lib().memo_lengths_finish_dev(planes.d, Ls, pitch, n, cap, 0, None))

@@ -109,6 +109,7 @@ def main():
     # ---- the kernel beside convert_dap_kernel
     import torch  # (before the library: both then share one HIP runtime) -- the event pairs, and what the runtime says the device is
     from memo_amd import _lib, convert, lengths, merge
+    from memo_amd._device import DevBuffer
     lib, check = _lib.lib, _lib.check
 
     def timed(call):
@@ -124,13 +125,13 @@ def main():
     n, W, L = a.genomes, others, a.length
     batch = min(convert.default_batch_positions(n), L)
     maps = {"identity": np.arange(1, n, dtype=np.int32), "permutation": np.random.default_rng(a.seed).permutation(np.arange(1, n)).astype(np.int32)}
-    feed, buf = lengths._region_feed(full, "chr1", 0)
+    feed, buf = lengths.region_feed(full, "chr1", 0)
     times = {"convert": [], "identity": [], "permutation": []}
-    with buf, lengths._DevBuffer(0, 4 * W * batch) as d_dap, lengths._DevBuffer(0, 4 * W) as d_identity, lengths._DevBuffer(0, 4 * W) as d_permutation:
+    with buf, DevBuffer(0, 4 * W * batch) as d_dap, DevBuffer(0, 4 * W) as d_identity, DevBuffer(0, 4 * W) as d_permutation:
         d_maps = {"identity": d_identity, "permutation": d_permutation}
         for name, host in maps.items():
             check(lib().memo_dev_upload(0, d_maps[name].d, host.ctypes.data, host.nbytes, None))
-        for lo, hi, d_cells, pitch in lengths._finished_slices(feed, 0, L, n, L, 0, None):
+        for lo, hi, d_cells, pitch in lengths.finished_slices(feed, 0, L, n, L, 0, None):
             assert (lo, hi) == (0, L), "one slice is expected at this size"
             calls = {"convert": lambda: check(lib().memo_convert_dap_dev(d_cells, pitch, n, 0, batch, L, d_dap.d, 0, None)),
                      "identity": lambda: check(lib().memo_merge_dap_dev(d_cells, pitch, n, d_maps["identity"].d, W, 0, batch, L, d_dap.d, 0, None)),
@@ -192,13 +193,13 @@ def main():
         sizes.append(args[6])
         return rc[0]
     sizes_in, chosen, plane_of = merge._plan([1 + half, n - half], [None, None])
-    feeds, bufs = zip(*(lengths._region_feed(path, "chr1", 0) for path in (part_a, part_b)))
+    feeds, bufs = zip(*(lengths.region_feed(path, "chr1", 0) for path in (part_a, part_b)))
     rows = [0, 0]
     t1 = time.perf_counter()
     lib().memo_merge_dap_dev = timed_kernel
     try:
-        with bufs[0], bufs[1], convert._Builders(W, [0, L], [False, True], 0) as builders, merge._mapped(sizes_in, plane_of, 0) as mapped:
-            for parts in convert._record_rows(list(zip(feeds, sizes_in)), L, Push(builders), 0, None, None, *mapped):
+        with bufs[0], bufs[1], convert.Builders(W, [0, L], [False, True], 0) as builders, merge._mapped(sizes_in, plane_of, 0) as mapped:
+            for parts in convert.record_rows(list(zip(feeds, sizes_in)), L, Push(builders), 0, None, None, *mapped):
                 for i, part in enumerate(parts):
                     rows[i] += len(part[0])
     finally:
