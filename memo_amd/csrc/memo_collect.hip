@@ -236,9 +236,8 @@ int memo_collect_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, const 
     int batch = (int)std::min<int64_t>(P, (int64_t)(kScratchCap / (step_bytes * gx)));
     if (batch < P) batch = batch / A.ob * A.ob;  // (at least 256 orders: whole blocks)
 
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // one allocation: the partials (the batches take turns with them in stream order), and behind them the orders
     DevPtr<uint32_t> scratch;
@@ -249,38 +248,21 @@ int memo_collect_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, const 
     uint16_t *d_orders = reinterpret_cast<uint16_t *>(scratch + scratch_n);
     HIP_TRY(hipMemcpyAsync(d_orders, orders_host, orders_n * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     A.partials = scratch;
-    struct Events {  // (timed calls only)
-        hipEvent_t e[3] = {};
-        ~Events() {
-            for (hipEvent_t x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } ev;
-    if (g_collect_timed) {
-        for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
-        g_collect_ms[0] = g_collect_ms[1] = 0.f;
-    }
+    Laps laps(st, g_collect_timed, g_collect_ms);  // (the batches add up)
+    if (g_collect_timed) g_collect_ms[0] = g_collect_ms[1] = 0.f;
+    if (int rc = laps.start()) return rc;
     for (int q0 = 0; q0 < P; q0 += batch) {
         A.P = std::min(batch, P - q0);
         A.orders = d_orders + (size_t)q0 * M;
         A.core = d_core + (size_t)q0 * M;
         A.covered = d_covered + (size_t)q0 * M;
         const int gy = (A.P + A.ob - 1) / A.ob;
-        if (g_collect_timed) HIP_TRY(hipEventRecord(ev.e[0], st));
         if (int rc = pw == 16 ? launch_sweep<16>(A, gx, gy, lds, st) : pw == 8 ? launch_sweep<8>(A, gx, gy, lds, st) : launch_sweep<4>(A, gx, gy, lds, st))
             return rc;
-        if (g_collect_timed) HIP_TRY(hipEventRecord(ev.e[1], st));
+        if (int rc = laps.add(0)) return rc;
         hipLaunchKernelGGL(collect_reduce_kernel, dim3((unsigned)(((int64_t)A.P * M + 15) / 16)), dim3(kThreads), 0, st, A, gx);
         HIP_TRY(hipGetLastError());
-        if (g_collect_timed) {
-            float sweep = 0.f, reduce = 0.f;
-            HIP_TRY(hipEventRecord(ev.e[2], st));
-            HIP_TRY(hipEventSynchronize(ev.e[2]));
-            HIP_TRY(hipEventElapsedTime(&sweep, ev.e[0], ev.e[1]));
-            HIP_TRY(hipEventElapsedTime(&reduce, ev.e[1], ev.e[2]));
-            g_collect_ms[0] += sweep;
-            g_collect_ms[1] += reduce;
-        }
+        if (int rc = laps.add(1)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
     return MEMO_OK;

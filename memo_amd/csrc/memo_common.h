@@ -35,8 +35,10 @@ int ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, in
 // memo_ms.hip: >= 0: the allocations of this thread's later coded columns see this many bytes of free device memory instead of the
 // device's (AB library, memo_debug_ms_free_bytes: the test of a column that does not fit)
 extern thread_local int64_t g_ms_free_bytes;
-// memo_text.hip: exclusive scan of ntiles uint32 tile counts into int64 bases, their sum into *d_total (one workgroup; queued on st)
+// memo_compact.hip: exclusive scan of ntiles uint32 tile counts into int64 bases, their sum into *d_total (one workgroup; queued on st)
 hipError_t scan_tile_counts(const uint32_t *d_counts, int64_t ntiles, int64_t *d_bases, int64_t *d_total, hipStream_t st);
+// ... and d_out[pl] = the base of plane pl's first tile, d_out[planes] = the total: what the host reads of a compaction over planes
+hipError_t plane_bases(const int64_t *d_bases, const int64_t *d_total, int64_t tiles_per_plane, int64_t planes, int64_t *d_out, hipStream_t st);
 extern thread_local int g_cooc_flush;  // memo_cooc.hip (AB library, memo_debug_cooc_flush: 1 = atomics instead of partials)
 extern thread_local int g_cooc_timed;  // ... memo_debug_cooc_times: event pairs around the launches of memo_cooccurrence_dev
 extern thread_local float g_cooc_ms[2];
@@ -61,6 +63,7 @@ struct DeviceGuard {  // the caller (e.g. torch) keeps its own notion of the cur
     int prev = -1;
     bool ok = false;
     explicit DeviceGuard(int dev) {
+        if (dev < 0) return;  // (no device: nothing selected, nothing to restore)
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
     }
@@ -125,6 +128,42 @@ struct BuiltView {
             return memo::fail(MEMO_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(err__),    \
                               __FILE__, __LINE__);                                             \
     } while (0)
+
+namespace memo {
+// The event pair around the launches of a timed call of the AB library (the memo_debug_*_times switches): start() arms it, lap(i)
+// waits for the launches since the last lap, puts their device time into ms[i] (add(i): adds it) and arms it again.  While `timed`
+// is 0 -- the product never sets it -- it creates no event, records nothing and waits for nothing.
+struct Laps {
+    hipEvent_t e[2] = {};
+    hipStream_t st;
+    const int &timed;
+    float *ms;
+    Laps(hipStream_t s, const int &on, float *out) : st(s), timed(on), ms(out) {}
+    Laps(const Laps &) = delete;
+    ~Laps() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    int start() {
+        if (!timed) return MEMO_OK;
+        for (hipEvent_t &x : e)
+            if (!x) HIP_TRY(hipEventCreate(&x));
+        HIP_TRY(hipEventRecord(e[0], st));
+        return MEMO_OK;
+    }
+    int lap(int i, bool adding = false) {
+        if (!timed) return MEMO_OK;
+        float t = 0.f;
+        HIP_TRY(hipEventRecord(e[1], st));
+        HIP_TRY(hipEventSynchronize(e[1]));
+        HIP_TRY(hipEventElapsedTime(&t, e[0], e[1]));
+        ms[i] = adding ? ms[i] + t : t;
+        HIP_TRY(hipEventRecord(e[0], st));
+        return MEMO_OK;
+    }
+    int add(int i) { return lap(i, true); }
+};
+}  // namespace memo
 
 // Kernel-shape choices of one index.  All zero in the product (= the library chooses per query);
 // only libmemo_amd_ab.so (memo_debug.hip, include/memo_amd_debug.h) can set them, for A/B timing and
@@ -325,10 +364,39 @@ enum Level { kLevelColumns, kLevelWords, kLevelDense, kLevelDerived };
 void rows_changed(memo_index *ix, Level at, bool keep_word_buffers = false);
 int need_wide(const memo_index *ix);  // MEMO_OK, or the refusal of an index whose int64 columns memo_index_pack dropped
 int device_ok(int device);            // MEMO_OK, or the refusal of a device number that is not among the visible ones
+// How an entry point gets onto its device: the device_ok refusal first (kSelectOnly: not made -- the entry points that never made it),
+// then the selection, and the caller's device again when it goes.  rc != MEMO_OK: return it.
+struct OnDevice {
+    static constexpr bool kSelectOnly = true;
+    int rc;
+    DeviceGuard guard;
+    explicit OnDevice(int dev, bool select_only = false) : rc(select_only ? MEMO_OK : device_ok(dev)), guard(rc ? -1 : dev) {
+        if (!rc && !guard.ok) rc = fail(MEMO_EHIP, "cannot select HIP device %d", dev);
+    }
+};
 inline uint64_t padded_for(uint64_t rows) { return ((rows + 15) & ~(uint64_t)15) + kPadRows; }
 // The one birth of an index (memo_index.hip): an empty one of `rows` rows on a checked device, with its status and scratch words; the
 // status word's clear is queued on st (the builder's ring stream, which it waits for with its copies), st == nullptr: done on return
 int new_index(uint64_t rows, int device, hipStream_t st, memo_index **out);
+// memo_cells.hip: the passes over planes of uint32 cells [planes][pitch], L of them a plane, that memo_maxk.hip (one plane: the pitch
+// is never used) and memo_lengths.hip share.  The refusals both make, in the two groups in which both make them; the fill of [0, L) of
+// every plane with the identity L - 1 + cap, on at most `most` workgroups a plane; the carries (int64 [planes], INT64_MAX: none) into
+// cell L - 1; and the finish in place -- tile minima into d_mins [planes x cell_tiles(L)], their suffix-min scan, apply -- whose three
+// launches are laps slot, slot + 1, slot + 2 of the caller's timer.  All queued on st; none waits for it outside a timed call.
+constexpr int kCellTile = 2048;
+inline int64_t cell_tiles(int64_t L) { return (L + kCellTile - 1) / kCellTile; }
+struct CellPlanes {
+    uint32_t *cells;
+    int64_t L, pitch;
+    int planes;
+    uint32_t cap;
+    uint32_t ident() const { return (uint32_t)(L - 1 + cap); }
+};
+int check_window(int64_t L, uint32_t cap);
+int check_cell_pointer(const uint32_t *d_cells, int64_t L);
+hipError_t cells_fill(const CellPlanes &P, int64_t most, hipStream_t st);
+hipError_t cells_carry_in(const CellPlanes &P, const int64_t *d_carry, int64_t qs, hipStream_t st);
+int cells_finish(const CellPlanes &P, uint32_t *d_mins, hipStream_t st, Laps &laps, int slot);
 constexpr size_t kMaxTileTables = 64;
 int builder_why(const memo_builder_t *b);  // memo_hostpack.hip: which rows a builder refused with MEMO_EUNPACKABLE (BlockResult::bad bits)
 extern thread_local int g_one_shot_way;     // memo_oneshot.hip (AB library, memo_debug_one_shot_way: 1 = int64 columns, 2 = 4-byte words)

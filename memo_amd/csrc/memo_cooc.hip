@@ -268,9 +268,8 @@ int memo_cooccurrence_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, u
     if (!d_counts || (reinterpret_cast<uintptr_t>(d_counts) & 7)) return fail(MEMO_EINVAL, "d_counts is NULL or not 8-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_bits) & 15) return fail(MEMO_EINVAL, "d_bits must be 16-byte aligned");
     if (!L) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool partials = g_cooc_flush == 0;
     const int W = (num_docs + 31) / 32, cw = W <= kMaxStaged ? W : kMaxStaged / 2, chunks = (W + cw - 1) / cw;
@@ -287,37 +286,20 @@ int memo_cooccurrence_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, u
     if (partials)
         if (hipError_t err = scratch.alloc(scratch_bytes / sizeof(uint32_t)); err != hipSuccess)
             return fail(MEMO_EHIP, "hipMalloc(%zu bytes) for the partial counts of %d genomes: %s", scratch_bytes, num_docs, hipGetErrorString(err));
-    struct Events {  // (timed calls only)
-        hipEvent_t e[3] = {};
-        ~Events() {
-            for (hipEvent_t x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } ev;
-    if (g_cooc_timed) {
-        for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
-        g_cooc_ms[0] = g_cooc_ms[1] = 0.f;
-    }
+    Laps laps(st, g_cooc_timed, g_cooc_ms);  // (the launches add up)
+    if (g_cooc_timed) g_cooc_ms[0] = g_cooc_ms[1] = 0.f;
+    if (int rc = laps.start()) return rc;
     for (Launch &l : launches) {
         l.A.partials = scratch;
-        if (g_cooc_timed) HIP_TRY(hipEventRecord(ev.e[0], st));
         if (l.ku == 1) launch_sweep<1>(l, st);
         else launch_sweep<2>(l, st);
         HIP_TRY(hipGetLastError());
-        if (g_cooc_timed) HIP_TRY(hipEventRecord(ev.e[1], st));
+        if (int rc = laps.add(0)) return rc;
         if (partials) {
             hipLaunchKernelGGL(cooc_reduce_kernel, dim3((unsigned)l.A.units), dim3(kThreads), 0, st, l.A, l.gx, l.slots);
             HIP_TRY(hipGetLastError());
         }
-        if (g_cooc_timed) {
-            float sweep = 0.f, flush = 0.f;
-            HIP_TRY(hipEventRecord(ev.e[2], st));
-            HIP_TRY(hipEventSynchronize(ev.e[2]));
-            HIP_TRY(hipEventElapsedTime(&sweep, ev.e[0], ev.e[1]));
-            HIP_TRY(hipEventElapsedTime(&flush, ev.e[1], ev.e[2]));
-            g_cooc_ms[0] += sweep;
-            g_cooc_ms[1] += flush;
-        }
+        if (int rc = laps.add(1)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
     return MEMO_OK;

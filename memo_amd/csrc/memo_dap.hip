@@ -332,8 +332,8 @@ int memo_dap_create(int32_t columns, const int64_t *rec_begin, int32_t nrec, int
         if (L < 1 || L >= ((int64_t)1 << 30)) return fail(MEMO_EINVAL, "record %d has length %lld (need 1 .. 2^30-1)", r, (long long)L);
     }
     if (rec_begin[0] != 0) return fail(MEMO_EINVAL, "rec_begin[0] must be 0");
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     memo_dap *h = new (std::nothrow) memo_dap();
     if (!h) return fail(MEMO_EHIP, "out of host memory");
     h->device = device;

@@ -115,9 +115,8 @@ int memo_builder_create_rows(uint64_t max_rows, int32_t device, int32_t bucket_s
         return fail(MEMO_EINVAL, "row_format must be MEMO_ROWS_PACKED (0) or MEMO_ROWS_DENSE (1)");
     if (bucket_shift <= 0) bucket_shift = kDefaultBucketShift;
     if (bucket_shift > 8) return fail(MEMO_EINVAL, "bucket_shift must be <= 8 (tile width 256)");
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     memo_builder *b = new (std::nothrow) memo_builder();
     if (!b) return fail(MEMO_EHIP, "out of host memory");
     b->device = device;

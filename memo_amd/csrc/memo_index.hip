@@ -322,9 +322,8 @@ int need_wide(const memo_index *ix) {
 // the life of an index: its one birth, and what a change of its rows makes stale
 // ------------------------------------------------------------------------------------------
 int new_index(uint64_t rows, int device, hipStream_t st, memo_index **out) {
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     memo_index *ix = new (std::nothrow) memo_index();
     if (!ix) return fail(MEMO_EHIP, "out of host memory");
     ix->device = device;
@@ -879,8 +878,8 @@ int memo_bin_conservation_dev(const uint16_t *d_vec, int64_t L, const int64_t *e
     for (int i = 0; i < nbins; ++i)
         if (edges[i] < 0 || edges[i] > edges[i + 1] || edges[i + 1] > L)
             return fail(MEMO_EINVAL, "bin edges must be non-decreasing inside [0, L]");
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int ncols = num_docs + 1;
     const size_t cbytes = (size_t)nbins * ncols * sizeof(uint64_t);
@@ -931,8 +930,8 @@ int memo_bin_conservation_dev(const uint16_t *d_vec, int64_t L, const int64_t *e
 int memo_dev_malloc(int32_t device, size_t bytes, void **out) {
     if (!out) return fail(MEMO_EINVAL, "out is NULL");
     *out = nullptr;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     HIP_TRY(hipMalloc(out, bytes ? bytes : 16));
     return MEMO_OK;
 }

@@ -5,12 +5,11 @@
 // ("up to which k do at least T genomes hold this k-mer").  len[g] is `memo maxk -m -d g` (memo_maxk.hip); the planes,
 // the carry between slices and the selection are new.  No counterpart in the reference.
 //
-// Cells.  uint32 cell[N][pitch], genome-major, relative to qs; pitch >= L, a multiple of 4; the base 16-byte aligned, so every plane
-// is.  The identity is ident = L - 1 + CAP (L <= 2^31 and CAP < 2^31: below 2^32); every value is saturated to [0, ident], which is
-// exact: a bound at or above ident yields CAP at every position.  The cells [L, pitch) of a plane are never read or written.
-//   1. begin   lengths_fill_kernel: [0, L) of every plane = ident, 16-byte stores (pitch % 4 == 0 keeps the planes aligned); with a
-//              carry (int64 [N], INT64_MAX: none) cell[g][L - 1] = clamp(carry[g] - qs)
-//   2. rows    lengths_rows_kernel: streams the three int64 columns as maxk_rows_kernel does (16 bytes a lane and load, kLoads loads of
+// Cells.  uint32 cell[N][pitch], genome-major, relative to qs (memo_cells.h's layout, with its identity ident = L - 1 + CAP); pitch >= L,
+// a multiple of 4; the base 16-byte aligned, so every plane is.  The cells [L, pitch) of a plane are never read or written.
+//   1. begin   memo::cells_fill (memo_cells.hip): [0, L) of every plane = ident, 16-byte stores (pitch % 4 == 0 keeps the planes
+//              aligned); with a carry (int64 [N], INT64_MAX: none) memo::cells_carry_in: cell[g][L - 1] = clamp(carry[g] - qs)
+//   2. rows    lengths_rows_kernel: memo_cells.h's stream_rows over the three int64 columns (16 bytes a lane and load, kLoads loads of
 //              each column in flight) and for every row with 0 <= a < N and qs < s < qe + CAP:
 //              atomicMin(&cell[a][min(s - 1 - qs, L - 1)], clamp(e - qs)), no return value, device scope; a row whose clamp is ident is
 //              the identity and is skipped.  ONE atomic per row: a membership index sorted by start has neighbouring rows in different
@@ -21,9 +20,8 @@
 //              it a long window runs in slices from the right, every row read once: before the slice [a, b) the carry holds the rows
 //              with b < s < qe + CAP and enters cell L - 1 of every plane (begin); it stays int64, because a carry clamped into one
 //              slice's cells would be wrong for rows with e < s that reach across slices.
-//   4. finish  the three launches of memo_maxk.hip with the plane in blockIdx.y (the scan: one workgroup per plane, in blockIdx.x):
-//              lengths_tile_min_kernel, lengths_scan_kernel (mins[g][t] <- min(mins[g][t + 1 ..]), ident for the last tile),
-//              lengths_apply_kernel (reverse inclusive min-scan per tile, then cell > i ? min(cell - i, CAP) : 0 over the cell)
+//   4. finish  memo::cells_finish (memo_cells.hip) on the N planes: the tile minima, their suffix-min scan (one workgroup per plane),
+//              and the apply launch (reverse inclusive min-scan per tile, then cell > i ? min(cell - i, CAP) : 0 over the cell)
 //   5. select  lengths_select_kernel<P>: out[p] = the T-th largest over g of min(cell[g][p], CAP).  A workgroup of 256 lanes takes a tile
 //              of P positions (256, 128 ... 8: the largest whose N rows, with the kernel's 16 static bytes, fit 120 KiB of LDS) and
 //              stages them as [g][stride] (a whole tile with 16-byte loads, eight in flight per lane; the window's last tile cell by
@@ -46,9 +44,7 @@
 //     bytes asked for, and nothing stays allocated
 //   - LDS above 64 KiB is opted into with hipFuncSetAttribute before the launch that needs it
 //   - values are written with vector stores and vector atomics only; there is no inline assembly
-#include <algorithm>
-
-#include "memo_common.h"
+#include "memo_cells.h"
 
 using namespace memo;
 
@@ -59,103 +55,43 @@ thread_local float g_lengths_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // fi
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPerLane = 8;                   // cells a lane of the scan holds: two 16-byte loads
-constexpr int kTile = kThreads * kPerLane;    // cells per tile of the scan
-constexpr int kScanThreads = 1024, kScanPerLane = 4;
-constexpr int kScanRound = kScanThreads * kScanPerLane;  // tile minima one round of the scan takes
-constexpr int kLoads = 4;                     // 16-byte loads of each column a lane has in flight
-constexpr int64_t kPairsPerWg = (int64_t)kThreads * kLoads;  // row pairs a workgroup takes at a time
-constexpr uint32_t kNone = 0xFFFFFFFFu;       // above every cell value; as a cell index: no cell
-constexpr int64_t kMaxL = (int64_t)1 << 31;
-constexpr uint32_t kMaxCap = 0x7FFFFFFFu;
+constexpr int kThreads = kRowThreads;
 constexpr int kMaxDocs = 2048;
 constexpr size_t kSelectLds = 120 << 10;      // of the CU's 160 KiB: the staged values and the kernel's static words together
 constexpr size_t kSelectStatic = (kThreads / 64) * sizeof(uint32_t);  // lengths_select_kernel's wave_max
 constexpr int kCarryWgs = 1024;               // workgroups of the carry pass at most: each ends with up to N global atomics
 
 struct RowArgs {
-    const int64_t *s, *e, *a;
-    uint64_t rows;
-    int64_t head;    // rows before the first 16-byte pair (0 or 1)
-    int64_t npairs;  // 16-byte pairs behind them
-    int64_t qs, s_end, e_hi;  // rows: s_end = qs + L + CAP (a start at or past it is ignored), e_hi = qs + ident; carry: qs = lo, s_end = hi
+    Columns c;
+    RowWindow w;  // carry: qs = lo, s_end = hi
     int64_t n, pitch;
-    uint32_t last, ident;  // last = L - 1
     uint32_t *cell;
     int64_t *carry;
 };
 
-// the cell (inside its plane) and value of a row; cell kNone: the row is ignored
-__device__ __forceinline__ void row_bound(const RowArgs &A, int64_t s, int64_t e, int64_t a, uint32_t &j, uint32_t &v) {
-    j = kNone, v = kNone;
-    if (a < 0 || a >= A.n || s <= A.qs || s >= A.s_end) return;
-    v = e <= A.qs ? 0u : e >= A.e_hi ? A.ident : (uint32_t)(e - A.qs);
-    if (v >= A.ident) return;  // the identity
-    const uint64_t d = (uint64_t)(s - A.qs - 1);
-    j = d < A.last ? (uint32_t)d : A.last;
-}
-
 struct CellMin {  // rows: one atomic min per row into its genome's plane
-    __device__ __forceinline__ void operator()(const RowArgs &A, int64_t s, int64_t e, int64_t a) const {
+    const RowArgs &A;
+    __device__ __forceinline__ void one(int64_t s, int64_t e, int64_t a) const {
         uint32_t j, v;
-        row_bound(A, s, e, a, j, v);
+        row_bound(A.w, a >= 0 && a < A.n, s, e, j, v);
         if (j != kNone) (void)__hip_atomic_fetch_min(A.cell + a * A.pitch + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    __device__ __forceinline__ void pair(const longlong2 &s, const longlong2 &e, const longlong2 &a) const { one(s.x, e.x, a.x), one(s.y, e.y, a.y); }
 };
 
 struct CarryMin {  // carry: the workgroup's minima in LDS
+    const RowArgs &A;
     long long *lds;
-    __device__ __forceinline__ void operator()(const RowArgs &A, int64_t s, int64_t e, int64_t a) const {
-        if (a < 0 || a >= A.n || s <= A.qs || s >= A.s_end) return;
+    __device__ __forceinline__ void one(int64_t s, int64_t e, int64_t a) const {
+        if (a < 0 || a >= A.n || s <= A.w.qs || s >= A.w.s_end) return;
         (void)__hip_atomic_fetch_min(lds + a, (long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
+    __device__ __forceinline__ void pair(const longlong2 &s, const longlong2 &e, const longlong2 &a) const { one(s.x, e.x, a.x), one(s.y, e.y, a.y); }
 };
-
-// every row of the columns to f, once: the pairs grid-strided in chunks of kPairsPerWg, the rows outside the pairs (the first row of
-// columns that start 8 bytes off a 16-byte line, the last odd row) by two lanes of workgroup 0
-template <bool VEC, typename F>
-__device__ __forceinline__ void stream_rows(const RowArgs &A, const F &f) {
-    const int64_t nchunks = (A.npairs + kPairsPerWg - 1) / kPairsPerWg;
-    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int64_t p0 = c * kPairsPerWg + threadIdx.x;
-        longlong2 s[kLoads], e[kLoads], a[kLoads];
-#pragma unroll
-        for (int u = 0; u < kLoads; ++u) {
-            const int64_t p = p0 + (int64_t)u * kThreads, r = A.head + 2 * p;
-            // (a pair past the end: a start that no window takes)
-            s[u] = e[u] = a[u] = make_longlong2(INT64_MIN, INT64_MIN);
-            if (p < A.npairs) {
-                if (VEC) {
-                    s[u] = *reinterpret_cast<const longlong2 *>(A.s + r);
-                    e[u] = *reinterpret_cast<const longlong2 *>(A.e + r);
-                    a[u] = *reinterpret_cast<const longlong2 *>(A.a + r);
-                } else {
-                    s[u] = make_longlong2(A.s[r], A.s[r + 1]);
-                    e[u] = make_longlong2(A.e[r], A.e[r + 1]);
-                    a[u] = make_longlong2(A.a[r], A.a[r + 1]);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kLoads; ++u) {
-            f(A, s[u].x, e[u].x, a[u].x);
-            f(A, s[u].y, e[u].y, a[u].y);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 2) {
-        const uint64_t behind = (uint64_t)(A.head + 2 * A.npairs);
-        const bool first = threadIdx.x == 0;
-        if (first ? A.head == 1 : behind < A.rows) {
-            const uint64_t r = first ? 0 : behind;
-            f(A, A.s[r], A.e[r], A.a[r]);
-        }
-    }
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void lengths_rows_kernel(const RowArgs A) {
-    stream_rows<VEC>(A, CellMin{});
+    stream_rows<VEC>(A.c, CellMin{A});
 }
 
 template <bool VEC>
@@ -163,132 +99,10 @@ __global__ __launch_bounds__(kThreads) void lengths_carry_kernel(const RowArgs A
     __shared__ long long lo[kMaxDocs];
     for (int g = threadIdx.x; g < A.n; g += kThreads) lo[g] = INT64_MAX;
     __syncthreads();
-    stream_rows<VEC>(A, CarryMin{lo});
+    stream_rows<VEC>(A.c, CarryMin{A, lo});
     __syncthreads();
     for (int g = threadIdx.x; g < A.n; g += kThreads)
         if (lo[g] != INT64_MAX) (void)__hip_atomic_fetch_min((long long *)A.carry + g, lo[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// grid (.., N): [0, L) of plane blockIdx.y = ident
-__global__ __launch_bounds__(kThreads) void lengths_fill_kernel(uint32_t *cells, int64_t L, int64_t pitch, uint32_t ident) {
-    uint32_t *cell = cells + (int64_t)blockIdx.y * pitch;
-    const int64_t n4 = L >> 2;
-    const uint4 v = make_uint4(ident, ident, ident, ident);
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kThreads)
-        reinterpret_cast<uint4 *>(cell)[i] = v;
-    if (blockIdx.x == 0 && threadIdx.x < (L & 3)) cell[4 * n4 + threadIdx.x] = ident;
-}
-
-// cell[g][L - 1] = clamp(carry[g] - qs), after the fill (its own launch: the fill's workgroups are not ordered among themselves)
-__global__ __launch_bounds__(kThreads) void lengths_carry_in_kernel(uint32_t *cells, int64_t L, int64_t pitch, int n, uint32_t ident,
-                                                                    const int64_t *carry, int64_t qs) {
-    const int g = blockIdx.x * kThreads + threadIdx.x;
-    if (g >= n) return;
-    const int64_t e = carry[g];
-    if (e == INT64_MAX) return;
-    cells[(int64_t)g * pitch + L - 1] = e <= qs ? 0u : e >= qs + (int64_t)ident ? ident : (uint32_t)(e - qs);  // (|qs| <= 2^61: the sum cannot overflow, e - qs could)
-}
-
-// the kPerLane cells of a lane of tile t, cells at or past L as kNone
-__device__ __forceinline__ void load_cells(const uint32_t *cell, int64_t L, int64_t t, uint32_t (&c)[kPerLane]) {
-    const int64_t i0 = t * kTile + (int64_t)threadIdx.x * kPerLane;
-    if (i0 + kPerLane <= L) {
-        const uint4 lo = *reinterpret_cast<const uint4 *>(cell + i0), hi = *reinterpret_cast<const uint4 *>(cell + i0 + 4);
-        c[0] = lo.x, c[1] = lo.y, c[2] = lo.z, c[3] = lo.w, c[4] = hi.x, c[5] = hi.y, c[6] = hi.z, c[7] = hi.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < kPerLane; ++q) c[q] = i0 + q < L ? cell[i0 + q] : kNone;
-    }
-}
-
-// the minimum over the lanes RIGHT of this one in the workgroup (kNone: none), and the workgroup's minimum.  wave_min: LDS [WAVES];
-// all lanes of the workgroup call it; two barriers
-template <int WAVES>
-__device__ __forceinline__ uint32_t min_right_of(uint32_t mine, uint32_t *wave_min, uint32_t &all) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = mine;  // over this lane and the lanes of the wave right of it
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_down(inc, d);
-        if (lane + d < 64) inc = min(inc, o);
-    }
-    uint32_t right = __shfl_down(inc, 1);
-    if (lane == 63) right = kNone;
-    if (lane == 0) wave_min[wave] = inc;
-    __syncthreads();
-    all = kNone;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const uint32_t m = wave_min[w];
-        all = min(all, m);
-        if (w > wave) right = min(right, m);
-    }
-    __syncthreads();  // (the next call writes wave_min again)
-    return right;
-}
-
-// grid (ntiles, N): the minimum of tile blockIdx.x of plane blockIdx.y
-__global__ __launch_bounds__(kThreads) void lengths_tile_min_kernel(const uint32_t *cells, int64_t L, int64_t pitch, uint32_t *mins) {
-    __shared__ uint32_t wave_min[kThreads / 64];
-    uint32_t c[kPerLane];
-    load_cells(cells + (int64_t)blockIdx.y * pitch, L, blockIdx.x, c);
-    uint32_t m = c[0];
-#pragma unroll
-    for (int q = 1; q < kPerLane; ++q) m = min(m, c[q]);
-    uint32_t all;
-    (void)min_right_of<kThreads / 64>(m, wave_min, all);
-    if (threadIdx.x == 0) mins[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = all;
-}
-
-// grid (N): plane blockIdx.x's mins[t] <- min(mins[t + 1 .. ntiles)), ident for the last tile; rounds of kScanRound tiles from the right
-__global__ __launch_bounds__(kScanThreads) void lengths_scan_kernel(uint32_t *all_mins, int64_t ntiles, uint32_t ident) {
-    __shared__ uint32_t wave_min[kScanThreads / 64];
-    uint32_t *mins = all_mins + (int64_t)blockIdx.x * ntiles;
-    uint32_t carry = ident;  // the minimum of every tile right of this round
-    for (int64_t hi = ntiles; hi > 0; hi -= kScanRound) {
-        const int64_t i0 = hi - kScanRound + (int64_t)threadIdx.x * kScanPerLane;  // (may be negative in the last round)
-        uint32_t m[kScanPerLane];
-#pragma unroll
-        for (int q = 0; q < kScanPerLane; ++q) m[q] = i0 + q >= 0 ? mins[i0 + q] : kNone;
-        uint32_t mine = m[0];
-#pragma unroll
-        for (int q = 1; q < kScanPerLane; ++q) mine = min(mine, m[q]);
-        uint32_t all;
-        uint32_t right = min(min_right_of<kScanThreads / 64>(mine, wave_min, all), carry);
-#pragma unroll
-        for (int q = kScanPerLane - 1; q >= 0; --q) {
-            if (i0 + q >= 0) mins[i0 + q] = right;
-            right = min(right, m[q]);
-        }
-        carry = min(carry, all);
-    }
-}
-
-// grid (ntiles, N)
-__global__ __launch_bounds__(kThreads) void lengths_apply_kernel(uint32_t *cells, int64_t L, int64_t pitch, const uint32_t *carry, uint32_t cap) {
-    __shared__ uint32_t wave_min[kThreads / 64];
-    uint32_t *cell = cells + (int64_t)blockIdx.y * pitch;
-    uint32_t c[kPerLane];
-    load_cells(cell, L, blockIdx.x, c);
-#pragma unroll
-    for (int q = kPerLane - 2; q >= 0; --q) c[q] = min(c[q], c[q + 1]);
-    uint32_t all;
-    const uint32_t right = min(min_right_of<kThreads / 64>(c[0], wave_min, all), carry[(int64_t)blockIdx.y * gridDim.x + blockIdx.x]);
-    const int64_t i0 = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kPerLane;
-    uint32_t out[kPerLane];
-#pragma unroll
-    for (int q = 0; q < kPerLane; ++q) {
-        const uint32_t bound = min(c[q], right), i = (uint32_t)(i0 + q);  // (i < L <= 2^31)
-        out[q] = bound > i ? min(bound - i, cap) : 0u;
-    }
-    if (i0 + kPerLane <= L) {
-        *reinterpret_cast<uint4 *>(cell + i0) = make_uint4(out[0], out[1], out[2], out[3]);
-        *reinterpret_cast<uint4 *>(cell + i0 + 4) = make_uint4(out[4], out[5], out[6], out[7]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < kPerLane; ++q)
-            if (i0 + q < L) cell[i0 + q] = out[q];
-    }
 }
 
 // ---- select -------------------------------------------------------------------------------------------------------------
@@ -390,68 +204,17 @@ int launch_select(const SelectArgs &A, hipStream_t st) {
 // what every entry point that takes the cells refuses before it looks at anything else
 int check_cells(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t n, uint32_t cap) {
     if (n < 1 || n > kMaxDocs) return fail(MEMO_EINVAL, "num_docs must be in [1, %d] (got %d)", kMaxDocs, n);
-    if (L < 0 || L > kMaxL) return fail(MEMO_EINVAL, "a window of %lld positions: L must be in [0, 2^31]", (long long)L);
-    if (cap < 1 || cap > kMaxCap) return fail(MEMO_EINVAL, "cap must be in [1, 2^31 - 1] (got %u)", cap);
+    if (int rc = check_window(L, cap)) return rc;
     if (pitch < L || (pitch & 3)) return fail(MEMO_EINVAL, "pitch %lld: it must be a multiple of 4 and at least L = %lld", (long long)pitch, (long long)L);
     if ((int64_t)n * pitch >= ((int64_t)1 << 32)) return fail(MEMO_EINVAL, "%d planes of pitch %lld: 2^32 cells or more (take the window in slices)", n, (long long)pitch);
-    if (reinterpret_cast<uintptr_t>(d_cells) & 15) return fail(MEMO_EINVAL, "d_cells must be 16-byte aligned");
-    if (L && !d_cells) return fail(MEMO_EINVAL, "d_cells is NULL");
-    return MEMO_OK;
+    return check_cell_pointer(d_cells, L);
 }
-
-int check_columns(const int64_t *d_start, const int64_t *d_end, const int64_t *d_annot, uint64_t rows) {
-    if ((reinterpret_cast<uintptr_t>(d_start) | reinterpret_cast<uintptr_t>(d_end) | reinterpret_cast<uintptr_t>(d_annot)) & 7)
-        return fail(MEMO_EINVAL, "the row columns must be 8-byte aligned");
-    if (rows && (!d_start || !d_end || !d_annot)) return fail(MEMO_EINVAL, "a row column is NULL");
-    return MEMO_OK;
-}
-
-// the columns of a row pass: 16-byte loads when all three have the same alignment mod 16, else 8-byte loads.  Returns the grid.
-unsigned set_columns(RowArgs &A, const int64_t *d_start, const int64_t *d_end, const int64_t *d_annot, uint64_t rows, bool &vec, int64_t most) {
-    A.s = d_start, A.e = d_end, A.a = d_annot;
-    A.rows = rows;
-    const uintptr_t off = reinterpret_cast<uintptr_t>(d_start) & 15;
-    vec = (reinterpret_cast<uintptr_t>(d_end) & 15) == off && (reinterpret_cast<uintptr_t>(d_annot) & 15) == off;
-    A.head = vec && off ? 1 : 0;
-    A.npairs = (int64_t)((rows - (uint64_t)A.head) / 2);
-    const int64_t nchunks = (A.npairs + kPairsPerWg - 1) / kPairsPerWg;
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(nchunks, most));
-}
-
-// event pairs around the launches of a timed call (memo_debug_lengths_times): lap(i) waits for the launches since the last lap
-// and puts their device time into g_lengths_ms[i]
-struct Laps {
-    hipEvent_t e[2] = {};
-    hipStream_t st;
-    explicit Laps(hipStream_t s) : st(s) {}
-    ~Laps() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    int start() {
-        if (!g_lengths_timed) return MEMO_OK;
-        for (hipEvent_t &x : e)
-            if (!x) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(e[0], st));
-        return MEMO_OK;
-    }
-    int lap(int i) {
-        if (!g_lengths_timed) return MEMO_OK;
-        float ms = 0.f;
-        HIP_TRY(hipEventRecord(e[1], st));
-        HIP_TRY(hipEventSynchronize(e[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, e[0], e[1]));
-        g_lengths_ms[i] = ms;
-        HIP_TRY(hipEventRecord(e[0], st));
-        return MEMO_OK;
-    }
-};
 
 }  // namespace
 
 extern "C" {
 
-int32_t memo_lengths_tile(void) { return kTile; }
+int32_t memo_lengths_tile(void) { return kCellTile; }
 
 int32_t memo_lengths_select_tile(int32_t num_docs) { return num_docs < 1 || num_docs > kMaxDocs ? 0 : select_tile(num_docs); }
 
@@ -461,21 +224,14 @@ int memo_lengths_begin_dev(uint32_t *d_cells, int64_t L, int64_t pitch, int32_t 
     if (qs < -kCoordLimit || qs > kCoordLimit) return fail(MEMO_EINVAL, "window start %lld is beyond +-2^61", (long long)qs);
     if (reinterpret_cast<uintptr_t>(d_carry) & 7) return fail(MEMO_EINVAL, "d_carry must be 8-byte aligned");
     if (!L) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    Laps laps(st);
+    Laps laps(st, g_lengths_timed, g_lengths_ms);
     if (int rc = laps.start()) return rc;
-    const uint32_t ident = (uint32_t)(L - 1 + cap);
-    const int64_t wgs = std::max<int64_t>(1, std::min<int64_t>(((L >> 2) + kThreads - 1) / kThreads, 1 << 12));
-    hipLaunchKernelGGL(lengths_fill_kernel, dim3((unsigned)wgs, (unsigned)num_docs), dim3(kThreads), 0, st, d_cells, L, pitch, ident);
-    HIP_TRY(hipGetLastError());
-    if (d_carry) {
-        hipLaunchKernelGGL(lengths_carry_in_kernel, dim3((unsigned)((num_docs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, d_cells, L, pitch,
-                           (int)num_docs, ident, d_carry, qs);
-        HIP_TRY(hipGetLastError());
-    }
+    const CellPlanes P = {d_cells, L, pitch, num_docs, cap};
+    HIP_TRY(cells_fill(P, 1 << 12, st));
+    if (d_carry) HIP_TRY(cells_carry_in(P, d_carry, qs, st));
     if (int rc = laps.lap(0)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return MEMO_OK;
@@ -487,22 +243,17 @@ int memo_lengths_rows_dev(const int64_t *d_start, const int64_t *d_end, const in
     if (qs < -kCoordLimit || qs > kCoordLimit) return fail(MEMO_EINVAL, "window start %lld is beyond +-2^61", (long long)qs);
     if (int rc = check_columns(d_start, d_end, d_annot, rows)) return rc;
     if (!L || !rows) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     RowArgs A = {};
     bool vec;
-    const unsigned grid = set_columns(A, d_start, d_end, d_annot, rows, vec, 1 << 16);
-    A.ident = (uint32_t)(L - 1 + cap);
-    A.last = (uint32_t)(L - 1);
-    A.qs = qs;
-    A.s_end = qs + L + (int64_t)cap;
-    A.e_hi = qs + (int64_t)A.ident;
+    const unsigned grid = set_columns(A.c, d_start, d_end, d_annot, rows, vec, 1 << 16);
+    A.w.set(qs, L, cap);
     A.n = num_docs;
     A.pitch = pitch;
     A.cell = d_cells;
-    Laps laps(st);
+    Laps laps(st, g_lengths_timed, g_lengths_ms);
     if (int rc = laps.start()) return rc;
     if (vec) hipLaunchKernelGGL(lengths_rows_kernel<true>, dim3(grid), dim3(kThreads), 0, st, A);
     else hipLaunchKernelGGL(lengths_rows_kernel<false>, dim3(grid), dim3(kThreads), 0, st, A);
@@ -518,18 +269,17 @@ int memo_lengths_carry_dev(const int64_t *d_start, const int64_t *d_end, const i
     if (int rc = check_columns(d_start, d_end, d_annot, rows)) return rc;
     if (!d_carry || (reinterpret_cast<uintptr_t>(d_carry) & 7)) return fail(MEMO_EINVAL, "d_carry must be 8-byte aligned and not NULL");
     if (!rows || hi <= lo) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     RowArgs A = {};
     bool vec;
-    const unsigned grid = set_columns(A, d_start, d_end, d_annot, rows, vec, kCarryWgs);
-    A.qs = lo;
-    A.s_end = hi;
+    const unsigned grid = set_columns(A.c, d_start, d_end, d_annot, rows, vec, kCarryWgs);
+    A.w.qs = lo;
+    A.w.s_end = hi;
     A.n = num_docs;
     A.carry = d_carry;
-    Laps laps(st);
+    Laps laps(st, g_lengths_timed, g_lengths_ms);
     if (int rc = laps.start()) return rc;
     if (vec) hipLaunchKernelGGL(lengths_carry_kernel<true>, dim3(grid), dim3(kThreads), 0, st, A);
     else hipLaunchKernelGGL(lengths_carry_kernel<false>, dim3(grid), dim3(kThreads), 0, st, A);
@@ -542,27 +292,16 @@ int memo_lengths_carry_dev(const int64_t *d_start, const int64_t *d_end, const i
 int memo_lengths_finish_dev(uint32_t *d_cells, int64_t L, int64_t pitch, int32_t num_docs, uint32_t cap, int32_t device, void *stream) {
     if (int rc = check_cells(d_cells, L, pitch, num_docs, cap)) return rc;
     if (!L) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t ntiles = (L + kTile - 1) / kTile;  // (at most 2^20: fits grid.x; num_docs <= 2048 fits grid.y)
+    const int64_t ntiles = cell_tiles(L);
     DevPtr<uint32_t> mins;
     if (hipError_t err = mins.alloc((size_t)ntiles * num_docs); err != hipSuccess)
         return fail(MEMO_EHIP, "hipMalloc(%zu bytes) for the tile minima of %d planes of %lld positions: %s", (size_t)ntiles * num_docs * sizeof(uint32_t),
                     num_docs, (long long)L, hipGetErrorString(err));
-    const dim3 tiles((unsigned)ntiles, (unsigned)num_docs);
-    Laps laps(st);
-    if (int rc = laps.start()) return rc;
-    hipLaunchKernelGGL(lengths_tile_min_kernel, tiles, dim3(kThreads), 0, st, d_cells, L, pitch, mins.p);
-    HIP_TRY(hipGetLastError());
-    if (int rc = laps.lap(3)) return rc;
-    hipLaunchKernelGGL(lengths_scan_kernel, dim3((unsigned)num_docs), dim3(kScanThreads), 0, st, mins.p, ntiles, (uint32_t)(L - 1 + cap));
-    HIP_TRY(hipGetLastError());
-    if (int rc = laps.lap(4)) return rc;
-    hipLaunchKernelGGL(lengths_apply_kernel, tiles, dim3(kThreads), 0, st, d_cells, L, pitch, mins.p, cap);
-    HIP_TRY(hipGetLastError());
-    if (int rc = laps.lap(5)) return rc;
+    Laps laps(st, g_lengths_timed, g_lengths_ms);
+    if (int rc = cells_finish(CellPlanes{d_cells, L, pitch, num_docs, cap}, mins, st, laps, 3)) return rc;
     HIP_TRY(hipStreamSynchronize(st));  // (the tile minima go with this call)
     return MEMO_OK;
 }
@@ -574,12 +313,11 @@ int memo_lengths_select_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, i
     if (reinterpret_cast<uintptr_t>(d_out) & 3) return fail(MEMO_EINVAL, "d_out must be 4-byte aligned");
     if (L && !d_out) return fail(MEMO_EINVAL, "d_out is NULL");
     if (!L) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     SelectArgs A = {d_cells, d_out, L, pitch, num_docs, threshold, cap};
-    Laps laps(st);
+    Laps laps(st, g_lengths_timed, g_lengths_ms);
     if (int rc = laps.start()) return rc;
     int rc = MEMO_OK;
     switch (select_tile(num_docs)) {

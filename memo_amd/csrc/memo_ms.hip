@@ -1178,8 +1178,8 @@ thread_local int64_t memo::g_ms_free_bytes = -1;
 int memo::ms_piece_text(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_begin, int32_t nrec, int64_t piece_bytes, int32_t piece,
                         uint8_t *out, int64_t out_cap, int64_t *out_n) {
     if (!h || !out_n) return fail(MEMO_EINVAL, "NULL argument");
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
+    OnDevice on(h->device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     hipStream_t st = nullptr;
     std::vector<int32_t> first;
     int rc = prepare_records(h, seq, rec_begin, nrec, piece_bytes, first, st);
@@ -1200,8 +1200,8 @@ int memo_suffix_array(const uint8_t *text, int64_t n, int32_t *sa_out, int32_t d
     if (n < 0 || n >= ((int64_t)1 << 31) - 1) return fail(MEMO_EINVAL, "text length %lld outside [0, 2^31 - 1)", (long long)n);
     if (n == 0) return MEMO_OK;
     if (!text || !sa_out) return fail(MEMO_EINVAL, "NULL argument");
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     int rc = fits((int64_t)sa_bytes(n), "the suffix array");
     if (rc) return rc;
     DevBuf<uint8_t> T;
@@ -1251,8 +1251,8 @@ int memo_ms_create_layout(const uint8_t *pivot, const int64_t *rec_begin, int32_
     if (npos >= ((int64_t)1 << 40)) return fail(MEMO_EINVAL, "pivot of %lld positions is too long", (long long)npos);
     if (chunk <= 0) chunk = 128;
     if (chunk > ((int64_t)1 << 30)) return fail(MEMO_EINVAL, "walk chunk %lld too long", (long long)chunk);
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     // the DAP (dense: the matrix; coded: the scratch column and every column's flags) stays resident; every genome's working set
     // comes on top of it
     size_t free_b = 0, total_b = 0;
@@ -1306,8 +1306,8 @@ int memo_ms_add_genome(memo_ms_t *h, const uint8_t *text, int64_t n, int32_t col
     if (column < 0 || column >= h->C) return fail(MEMO_EINVAL, "column %d outside [0, %d)", column, h->C);
     if (n < 0 || n >= ((int64_t)1 << 31) - 1)
         return fail(MEMO_EINVAL, "genome text of %lld characters: the limit is 2^31 - 2 (int32 suffix array)", (long long)n);
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
+    OnDevice on(h->device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     hipStream_t st = nullptr;
     int rc = begin_add(h, st);
     if (rc) return rc;
@@ -1331,8 +1331,8 @@ int memo_ms_add_records(memo_ms_t *h, const uint8_t *seq, const int64_t *rec_beg
                         int64_t piece_bytes, int32_t *pieces) {
     if (!h) return fail(MEMO_EINVAL, "handle is NULL");
     if (column < 0 || column >= h->C) return fail(MEMO_EINVAL, "column %d outside [0, %d)", column, h->C);
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", h->device);
+    OnDevice on(h->device, OnDevice::kSelectOnly);
+    if (on.rc) return on.rc;
     hipStream_t st = nullptr;
     std::vector<int32_t> first;
     int rc = prepare_records(h, seq, rec_begin, nrec, piece_bytes, first, st);

@@ -162,8 +162,8 @@ int dev_multi(memo_index_t *const *shards, int32_t n, int64_t qs, int64_t qe, in
     thread_local hipEvent_t root_ready[64] = {};
     hipEvent_t ready = nullptr;
     if (root_device >= 0 && root_device < 64) {
-        DeviceGuard root(root_device);
-        if (!root.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", root_device);
+        OnDevice root(root_device, OnDevice::kSelectOnly);
+        if (root.rc) return root.rc;
         if (!root_ready[root_device]) HIP_TRY(hipEventCreateWithFlags(&root_ready[root_device], hipEventDisableTiming));
         ready = root_ready[root_device];
         HIP_TRY(hipEventRecord(ready, rs));
@@ -189,8 +189,8 @@ int dev_multi(memo_index_t *const *shards, int32_t n, int64_t qs, int64_t qe, in
             if (rc) return rc;
             continue;
         }
-        DeviceGuard guard(dev);
-        if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", dev);
+        OnDevice on(dev, OnDevice::kSelectOnly);
+        if (on.rc) return on.rc;
         PeerLane &ln = lanes[(size_t)g];
         const size_t bytes = (size_t)(b - a) * stride;
         if (ln.device != dev || ln.cap < bytes) {

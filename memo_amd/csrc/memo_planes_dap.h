@@ -198,9 +198,8 @@ inline Frame frame(int64_t pitch, int64_t first, int64_t positions, int64_t rema
 
 template <typename Args>
 int launch(void (*kernel)(Args), const Args &A, int32_t device, void *stream) {
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Frame &F = A.f;
     const int64_t ptiles = (F.first + F.positions - 1) / kTP - F.first / kTP + 1;  // (at most 2^24 + 1, times at most 32 column tiles: fits grid.x)

@@ -9,16 +9,13 @@
 //                                              odd count leaves the last interval to end at L
 //   bits    key = the W words of position i    position 0 is a boundary; starts[r] and the W words of the run per run.  Bits at or
 //                                              above num_docs are 0 by the result encoding (include/memo_amd.h: result encodings): whole words compare
-// One code path, a template on the key.  A key owns kPer positions per lane and load: the 16 bytes a lane loads hold 8 uint16
+// Each is a key of memo_compact.h's compaction, on one plane.  A key owns kPer positions per lane and load: the 16 bytes a lane loads hold 8 uint16
 // values, or 4 one-word rows, or 2 two-word rows (PackedKey: an element is an integer); any other W takes one row per lane, its
 // words loaded 4, 2 or 1 at a time as W allows (RowKey: right for every W >= 1, rows of an odd W lie off the 16-byte grid).
 //
-// Three launches, ordered by the stream (the structure of memo_text.hip):
-//   runs_count_kernel    per tile of 256 lanes x 4 loads x kPer positions: its boundaries counted, one uint32 per tile, no atomics
-//   the scan             memo::scan_tile_counts (memo_text.hip's one-workgroup scan): int64 bases and the total
-//   runs_scatter_kernel  the flags recomputed; rank = tile base + the boundaries of the waves before + of the iterations before
-//                        + of the lanes below (ballot / mbcnt); starts[rank] = i and the key's payload
-// The host reads the total between the scan and the scatter and allocates exactly that many entries.
+// Three launches, ordered by the stream (memo_compact.h): the count per tile of 256 lanes x 4 loads x kPer positions, the scan of
+// the tile counts, the scatter of starts[rank] = i and the key's payload.  The host reads the total between the scan and the scatter
+// and allocates exactly that many entries.
 //
 // Conditions the code holds:
 //   - no workgroup waits for another: no look-back, no flag in memory, no cooperative launch
@@ -30,13 +27,13 @@
 //   - a position at or past L never sets a flag, and the scatter writes no rank at or past the total
 #include <type_traits>
 
-#include "memo_common.h"
+#include "memo_compact.h"
 
 using namespace memo;
 
 namespace {
 
-constexpr int kThreads = 256, kIters = 4;  // a wave owns kIters x 64 x kPer positions in a row
+const int kNeverTimed = 0;  // (`memo regions` has no timed form: the compaction's laps stay off)
 
 __device__ __forceinline__ uint32_t shfl_up1(uint32_t x) { return (uint32_t)__shfl_up((int)x, 1, 64); }
 __device__ __forceinline__ uint64_t shfl_up1(uint64_t x) { return (uint64_t)__shfl_up((unsigned long long)x, 1, 64); }
@@ -46,14 +43,18 @@ template <typename E, bool kBand>
 struct PackedKey {
     static constexpr int kPer = 16 / (int)sizeof(E);
     using K = typename std::conditional<(sizeof(E) > 4), uint64_t, uint32_t>::type;  // what is compared and shuffled
+    using Start = int64_t;
     const E *vec;
     E *payload;  // values[] / run_bits[]; nullptr for a band
+    int64_t L;
     uint32_t lo, hi;
+
+    __device__ __forceinline__ void tile_of(int64_t block, int64_t &plane, int64_t &p0) const { plane = 0, p0 = block * tile_positions<PackedKey>(); }
 
     __device__ __forceinline__ K key(E v) const { return kBand ? (K)(lo <= (uint32_t)v && (uint32_t)v <= hi) : (K)v; }
 
     // bit j: position p + j (p a multiple of kPer) is a boundary.  Called by whole waves (it shuffles).
-    __device__ __forceinline__ uint32_t flags(int64_t p, int64_t L) const {
+    __device__ __forceinline__ uint32_t flags(int64_t, int64_t p) const {
         E e[kPer];
         if (p + kPer <= L) {
             const uint4 q = *reinterpret_cast<const uint4 *>(vec + p);
@@ -75,7 +76,7 @@ struct PackedKey {
         return m;
     }
 
-    __device__ __forceinline__ void store(int64_t rank, int64_t i) const {
+    __device__ __forceinline__ void store(int64_t, int64_t rank, int64_t i) const {
         if (!kBand) payload[rank] = vec[i];
     }
 };
@@ -85,11 +86,15 @@ template <int V>
 struct RowKey {
     static constexpr int kPer = 1;
     using Vec = typename std::conditional<V == 4, uint4, typename std::conditional<V == 2, uint2, uint32_t>::type>::type;
+    using Start = int64_t;
     const uint32_t *vec;
     uint32_t *payload;
+    int64_t L;
     int W;
 
-    __device__ __forceinline__ uint32_t flags(int64_t p, int64_t L) const {
+    __device__ __forceinline__ void tile_of(int64_t block, int64_t &plane, int64_t &p0) const { plane = 0, p0 = block * tile_positions<RowKey>(); }
+
+    __device__ __forceinline__ uint32_t flags(int64_t, int64_t p) const {
         const bool valid = p < L, own_prev = (threadIdx.x & 63) == 0 && valid && p > 0;
         bool diff = false;
         for (int c = 0; c < W; c += V) {
@@ -108,89 +113,22 @@ struct RowKey {
         return valid && (p == 0 || diff) ? 1u : 0u;
     }
 
-    __device__ __forceinline__ void store(int64_t rank, int64_t i) const {
+    __device__ __forceinline__ void store(int64_t, int64_t rank, int64_t i) const {
         for (int c = 0; c < W; c += V)
             *reinterpret_cast<Vec *>(payload + rank * W + c) = *reinterpret_cast<const Vec *>(vec + i * W + c);
     }
 };
 
+// count, scan, allocate exactly, scatter.  payload_bytes: of one payload entry per run (0: none).  Blocking.
 template <typename Key>
-constexpr int tile_positions() { return kThreads * kIters * Key::kPer; }
-
-template <typename Key>
-__device__ __forceinline__ int64_t chunk_pos(int64_t tile0, int it) {
-    return tile0 + (int64_t)(((threadIdx.x >> 6) * kIters + it) * 64 + (threadIdx.x & 63)) * Key::kPer;
-}
-
-template <typename Key>
-__global__ __launch_bounds__(kThreads) void runs_count_kernel(Key key, int64_t L, uint32_t *__restrict__ counts) {
-    __shared__ uint32_t wsum[kThreads / 64];
-    const int64_t tile0 = (int64_t)blockIdx.x * tile_positions<Key>();
-    uint32_t n = 0;
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) n += (uint32_t)__popc(key.flags(chunk_pos<Key>(tile0, it), L));
-    for (int off = 32; off; off >>= 1) n += __shfl_xor(n, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-template <typename Key>
-__global__ __launch_bounds__(kThreads) void runs_scatter_kernel(Key key, int64_t L, const int64_t *__restrict__ bases, int64_t total,
-                                                                int64_t *__restrict__ starts) {
-    __shared__ uint32_t wtot[kThreads / 64];
-    const int64_t tile0 = (int64_t)blockIdx.x * tile_positions<Key>();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // rank of a lane's first boundary among its wave's: the lanes below by ballot + mbcnt, the iterations before by a running sum
-    uint32_t mask[kIters], rank[kIters], running = 0;
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-        const uint32_t m = key.flags(chunk_pos<Key>(tile0, it), L);
-        uint32_t below = 0, count = 0;
-#pragma unroll
-        for (int j = 0; j < Key::kPer; ++j) {
-            const unsigned long long bal = __ballot((m >> j) & 1u);
-            below += __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            count += (uint32_t)__popcll(bal);
-        }
-        mask[it] = m;
-        rank[it] = running + below;
-        running += count;
-    }
-    if (lane == 0) wtot[wave] = running;
-    __syncthreads();
-    int64_t base = bases[blockIdx.x];
-    for (int w = 0; w < wave; ++w) base += wtot[w];
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-        int64_t idx = base + rank[it];
-        const int64_t p = chunk_pos<Key>(tile0, it);
-        for (uint32_t m = mask[it]; m; m &= m - 1, ++idx) {
-            if (idx >= total) break;  // (cannot happen while both passes see the same vector: a caller that writes it meanwhile)
-            const int64_t i = p + __builtin_ctz(m);
-            starts[idx] = i;
-            key.store(idx, i);
-        }
-    }
-}
-
-// count, scan, allocate exactly, scatter.  elem_bytes: of one payload entry per run (0: none).  Blocking.
-template <typename Key>
-int compact_runs(Key key, int64_t L, size_t payload_bytes, int64_t **d_starts, void **d_payload, uint64_t *runs, hipStream_t st) {
+int compact_runs(Key key, size_t payload_bytes, int64_t **d_starts, void **d_payload, uint64_t *runs, hipStream_t st) {
     constexpr int64_t T = tile_positions<Key>();
-    const int64_t ntiles = (L + T - 1) / T;
-    if (ntiles > INT32_MAX) return fail(MEMO_EINVAL, "a result of %lld positions is too long", (long long)L);
-    // one allocation: the total, the tiles' bases, their counts
-    DevPtr<int64_t> work;
-    HIP_TRY(work.alloc((size_t)(1 + ntiles + (ntiles + 1) / 2)));
-    int64_t *d_total = work, *d_bases = d_total + 1;
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(d_bases + ntiles);
-    hipLaunchKernelGGL(runs_count_kernel<Key>, dim3((unsigned)ntiles), dim3(kThreads), 0, st, key, L, d_counts);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(scan_tile_counts(d_counts, ntiles, d_bases, d_total, st));
-    int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t ntiles = (key.L + T - 1) / T;
+    if (ntiles > INT32_MAX) return fail(MEMO_EINVAL, "a result of %lld positions is too long", (long long)key.L);
+    Compaction c(st, kNeverTimed, nullptr);
+    HIP_TRY(c.lay_out(ntiles, 0));
+    if (int rc = c.count(key)) return rc;
+    const int64_t total = c.total();
     if (total <= 0) return MEMO_OK;
     DevPtr<int64_t> starts;
     DevPtr<char> payload;
@@ -201,19 +139,17 @@ int compact_runs(Key key, int64_t L, size_t payload_bytes, int64_t **d_starts, v
         if (hipError_t err = payload.alloc(pbytes); err != hipSuccess)
             return fail(MEMO_EHIP, "hipMalloc(%zu bytes) for the values of %lld runs: %s", pbytes, (long long)total, hipGetErrorString(err));
     key.payload = reinterpret_cast<decltype(key.payload)>(payload.p);
-    hipLaunchKernelGGL(runs_scatter_kernel<Key>, dim3((unsigned)ntiles), dim3(kThreads), 0, st, key, L, d_bases, total, starts.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = c.scatter(key, starts.p)) return rc;
     *runs = (uint64_t)total;
     *d_starts = starts.release();
     if (d_payload) *d_payload = payload.release();
     return MEMO_OK;
 }
 
-int runs_device(const void *d_vec, int64_t L, int32_t device) {
+int check_vector(const void *d_vec, int64_t L) {
     if (L < 0 || (L && !d_vec)) return fail(MEMO_EINVAL, "bad result vector (L = %lld)", (long long)L);
     if (reinterpret_cast<uintptr_t>(d_vec) & 15) return fail(MEMO_EINVAL, "d_vec must be 16-byte aligned");
-    return L ? device_ok(device) : MEMO_OK;
+    return MEMO_OK;
 }
 
 }  // namespace
@@ -234,13 +170,13 @@ int memo_runs_conservation_dev(const uint16_t *d_vec, int64_t L, int32_t mode, i
     if (d_values) *d_values = nullptr;
     if (mode != 0 && mode != 1) return fail(MEMO_EINVAL, "mode %d: 0 (value) or 1 (band)", mode);
     if (mode == 1 && (lo < 0 || hi > 65535 || lo > hi)) return fail(MEMO_EINVAL, "band [%d, %d]: 0 <= lo <= hi <= 65535", lo, hi);
-    if (int rc = runs_device(d_vec, L, device)) return rc;
+    if (int rc = check_vector(d_vec, L)) return rc;
     if (!L) return MEMO_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (mode == 1) return compact_runs(PackedKey<uint16_t, true>{d_vec, nullptr, (uint32_t)lo, (uint32_t)hi}, L, 0, d_starts, nullptr, runs, st);
-    return compact_runs(PackedKey<uint16_t, false>{d_vec, nullptr, 0, 0}, L, sizeof(uint16_t), d_starts, reinterpret_cast<void **>(d_values),
+    if (mode == 1) return compact_runs(PackedKey<uint16_t, true>{d_vec, nullptr, L, (uint32_t)lo, (uint32_t)hi}, 0, d_starts, nullptr, runs, st);
+    return compact_runs(PackedKey<uint16_t, false>{d_vec, nullptr, L, 0, 0}, sizeof(uint16_t), d_starts, reinterpret_cast<void **>(d_values),
                         runs, st);
 }
 
@@ -251,20 +187,20 @@ int memo_runs_membership_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs
     *d_run_bits = nullptr;
     *runs = 0;
     if (num_docs < 1) return fail(MEMO_EINVAL, "num_docs must be at least 1");
-    if (int rc = runs_device(d_bits, L, device)) return rc;
+    if (int rc = check_vector(d_bits, L)) return rc;
     if (!L) return MEMO_OK;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int W = (num_docs + 31) / 32;
     void **out = reinterpret_cast<void **>(d_run_bits);
     const size_t row = (size_t)W * sizeof(uint32_t);
-    if (W == 1) return compact_runs(PackedKey<uint32_t, false>{d_bits, nullptr, 0, 0}, L, row, d_starts, out, runs, st);
+    if (W == 1) return compact_runs(PackedKey<uint32_t, false>{d_bits, nullptr, L, 0, 0}, row, d_starts, out, runs, st);
     if (W == 2)
-        return compact_runs(PackedKey<uint64_t, false>{reinterpret_cast<const uint64_t *>(d_bits), nullptr, 0, 0}, L, row, d_starts, out, runs, st);
-    if (W % 4 == 0) return compact_runs(RowKey<4>{d_bits, nullptr, W}, L, row, d_starts, out, runs, st);
-    if (W % 2 == 0) return compact_runs(RowKey<2>{d_bits, nullptr, W}, L, row, d_starts, out, runs, st);
-    return compact_runs(RowKey<1>{d_bits, nullptr, W}, L, row, d_starts, out, runs, st);
+        return compact_runs(PackedKey<uint64_t, false>{reinterpret_cast<const uint64_t *>(d_bits), nullptr, L, 0, 0}, row, d_starts, out, runs, st);
+    if (W % 4 == 0) return compact_runs(RowKey<4>{d_bits, nullptr, L, W}, row, d_starts, out, runs, st);
+    if (W % 2 == 0) return compact_runs(RowKey<2>{d_bits, nullptr, L, W}, row, d_starts, out, runs, st);
+    return compact_runs(RowKey<1>{d_bits, nullptr, L, W}, row, d_starts, out, runs, st);
 }
 
 }  // extern "C"

@@ -300,32 +300,6 @@ int launch(const Args &A, size_t lds, unsigned grid, hipStream_t st) {
     return MEMO_OK;
 }
 
-// event pairs around the launches of a timed call (memo_debug_spectrum_times)
-struct Lap {
-    hipEvent_t e[2] = {};
-    hipStream_t st;
-    explicit Lap(hipStream_t s) : st(s) {}
-    ~Lap() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    int start() {
-        if (!g_spectrum_timed) return MEMO_OK;
-        for (hipEvent_t &x : e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(e[0], st));
-        return MEMO_OK;
-    }
-    int stop(int i) {
-        if (!g_spectrum_timed) return MEMO_OK;
-        float ms = 0.f;
-        HIP_TRY(hipEventRecord(e[1], st));
-        HIP_TRY(hipEventSynchronize(e[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, e[0], e[1]));
-        g_spectrum_ms[i] = ms;
-        return MEMO_OK;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -343,9 +317,8 @@ int32_t memo_spectrum_tile(int32_t num_docs, int32_t kmax, int32_t mode) {
 int memo_spectrum_begin_dev(uint64_t *d_scratch, int32_t num_docs, int32_t kmax, int32_t device, void *stream) {
     if (int rc = check_shape(num_docs, kmax)) return rc;
     if (int rc = check_scratch(d_scratch)) return rc;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(d_scratch, 0, table_cells(num_docs, kmax) * sizeof(uint64_t), st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -364,9 +337,8 @@ int memo_spectrum_add_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int
     if (L && !d_cells) return fail(MEMO_EINVAL, "d_cells is NULL");
     if (int rc = check_scratch(d_scratch)) return rc;
     if (!L) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     Args A = {};
     A.cells = d_cells;
@@ -386,14 +358,14 @@ int memo_spectrum_add_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int
         HIP_TRY(hipMemsetAsync(counted.p, 0, sizeof(unsigned long long), st));
         A.counted = counted.p;
     }
-    Lap lap(st);
-    if (int rc = lap.start()) return rc;
+    Laps laps(st, g_spectrum_timed, g_spectrum_ms);
+    if (int rc = laps.start()) return rc;
     int rc;
     if (mode == 0) rc = priv ? launch<0, true>(A, lds, grid, st) : launch<0, false>(A, lds, grid, st);
     else rc = priv ? launch<1, true>(A, lds, grid, st) : launch<1, false>(A, lds, grid, st);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
-    if (int rc2 = lap.stop(0)) return rc2;
+    if (int rc2 = laps.lap(0)) return rc2;
     HIP_TRY(hipStreamSynchronize(st));
     g_spectrum_private = priv ? 1 : 0;
     if (A.counted) {
@@ -408,16 +380,15 @@ int memo_spectrum_finish_dev(const uint64_t *d_scratch, int32_t num_docs, int32_
     if (int rc = check_shape(num_docs, kmax)) return rc;
     if (int rc = check_scratch(d_scratch)) return rc;
     if (!d_exact || (reinterpret_cast<uintptr_t>(d_exact) & 7)) return fail(MEMO_EINVAL, "d_exact must be 8-byte aligned and not NULL");
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    Lap lap(st);
-    if (int rc = lap.start()) return rc;
+    Laps laps(st, g_spectrum_timed, g_spectrum_ms);
+    if (int rc = laps.start()) return rc;
     hipLaunchKernelGGL(spectrum_finish_kernel, dim3((unsigned)((num_docs + 1 + kFinishV - 1) / kFinishV)), dim3(kFinishV * kFinishParts), 0, st,
                        reinterpret_cast<const unsigned long long *>(d_scratch), reinterpret_cast<unsigned long long *>(d_exact), (int)num_docs, (int)kmax);
     HIP_TRY(hipGetLastError());
-    if (int rc = lap.stop(1)) return rc;
+    if (int rc = laps.lap(1)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return MEMO_OK;
 }

@@ -4,19 +4,21 @@
 //
 // The whole text is resident, so no kernel knows about the pieces it arrived in.  Three passes:
 //   text_count_kernel   per 16 KB tile: its line terminators counted, every byte validated         (reads the text once)
-//   text_scan_kernel    exclusive scan of the tile counts: one workgroup (a 300 MB text has 2 * 10^4 tiles)
+//   the scan            memo::scan_tile_counts (memo_compact.hip): exclusive scan of the tile counts, one workgroup
 //   text_parse_kernel   the tile + a 48-byte left halo staged in LDS; each line is parsed by the lane that owns its terminator,
 //                       reading backwards; line number = tile base + rank of the terminator in the workgroup  (reads it again)
+// The count's tail and the ranks are memo_compact.h's device pieces (store_tile_count, rank_flags).
 // A last line without \n is ended by the end of the text: position nbytes is staged as a \n then, and as it may open a tile of
 // its own the grid is nbytes / 16384 + 1 tiles.  Bytes behind it are staged as 0xFF, which is neither a terminator nor validated.
 // Halo: 32 bytes of line, its \r, the terminator before it -- 34 bytes, rounded up to the 16-byte load.
-#include "memo_common.h"
+#include "memo_compact.h"
 
 using namespace memo;
 
 namespace {
 
 constexpr int kTile = 16384, kHalo = 48, kWaveSpan = kTile / 4, kIterSpan = 1024;  // 256 lanes x 16 B x 4; a wave owns 4 KB in a row
+static_assert(kCompactIters == 4 && kCompactThreads == 256, "the tile is cut as memo_compact.h's device pieces cut theirs");
 constexpr int kMaxLine = 32, kMaxDigits = 9;
 constexpr unsigned long long kNoOdd = ~0ull;
 
@@ -58,7 +60,6 @@ __device__ __forceinline__ void report_odd(unsigned long long odd, unsigned long
 
 __global__ __launch_bounds__(256) void text_count_kernel(const char *__restrict__ text, int64_t nbytes, uint32_t *__restrict__ counts,
                                                          unsigned long long *first_odd) {
-    __shared__ uint32_t wsum[4];
     const int64_t tile0 = (int64_t)blockIdx.x * kTile;
     const bool open_end = open_ended(text, nbytes);
     uint4 v[4];
@@ -81,38 +82,7 @@ __global__ __launch_bounds__(256) void text_count_kernel(const char *__restrict_
         }
     }
     report_odd(odd, first_odd);
-    for (int off = 32; off; off >>= 1) n += __shfl_xor(n, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-__global__ __launch_bounds__(1024) void text_scan_kernel(const uint32_t *__restrict__ counts, int64_t ntiles, int64_t *__restrict__ bases,
-                                                         int64_t *lines) {
-    __shared__ long long wsum[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long carry = 0;
-    for (int64_t c0 = 0; c0 < ntiles; c0 += 1024) {
-        const int64_t i = c0 + threadIdx.x;
-        const long long x = i < ntiles ? (long long)counts[i] : 0;
-        long long s = x;  // inclusive scan inside the wave
-        for (int off = 1; off < 64; off <<= 1) {
-            const long long t = __shfl_up(s, off, 64);
-            if (lane >= off) s += t;
-        }
-        if (lane == 63) wsum[wave] = s;
-        __syncthreads();
-        long long before = 0, total = 0;
-        for (int w = 0; w < 16; ++w) {
-            const long long t = wsum[w];
-            before += w < wave ? t : 0;
-            total += t;
-        }
-        if (i < ntiles) bases[i] = carry + before + s - x;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *lines = carry;
+    store_tile_count(n, counts);
 }
 
 __global__ __launch_bounds__(256) void text_parse_kernel(const char *__restrict__ text, int64_t nbytes, const int64_t *__restrict__ bases,
@@ -123,7 +93,6 @@ __global__ __launch_bounds__(256) void text_parse_kernel(const char *__restrict_
     uint32_t *const wtot = reinterpret_cast<uint32_t *>(staged + (kHalo + kTile) / 16);
     const int64_t tile0 = (int64_t)blockIdx.x * kTile;
     const bool open_end = open_ended(text, nbytes);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (threadIdx.x < kHalo / 16)  // (tile0 <= nbytes: the halo lies inside the text; before the text: its beginning starts a line)
         staged[threadIdx.x] = tile0 ? *reinterpret_cast<const uint4 *>(text + tile0 - kHalo + 16 * threadIdx.x)
                                     : make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
@@ -132,27 +101,16 @@ __global__ __launch_bounds__(256) void text_parse_kernel(const char *__restrict_
     for (int it = 0; it < 4; ++it) v[it] = load_chunk(text, chunk_pos(tile0, it), nbytes, open_end);
 #pragma unroll
     for (int it = 0; it < 4; ++it) staged[(kHalo + chunk_pos(0, it)) / 16] = v[it];
-    // rank of a lane's first terminator among its wave's: the lanes below by ballot + popcount, the iterations before by a running sum
-    uint32_t mask[4], rank[4], running = 0;
+    // the terminators of a lane's loads, and their ranks among the tile's
+    uint32_t mask[4], rank[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-        uint32_t m = 0, below = 0, total = 0;
+        uint32_t m = 0;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const bool term = byte_of(v[it], j) == '\n';
-            m |= (term ? 1u : 0u) << j;
-            const unsigned long long bal = __ballot(term);
-            below += __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            total += (uint32_t)__popcll(bal);
-        }
+        for (int j = 0; j < 16; ++j) m |= (byte_of(v[it], j) == '\n' ? 1u : 0u) << j;
         mask[it] = m;
-        rank[it] = running + below;
-        running += total;
     }
-    if (lane == 0) wtot[wave] = running;
-    __syncthreads();
-    int64_t line = bases[blockIdx.x];
-    for (int w = 0; w < wave; ++w) line += wtot[w];
+    const int64_t line = bases[blockIdx.x] + rank_flags<16>(mask, rank, wtot);
     unsigned long long odd = kNoOdd;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
@@ -181,12 +139,6 @@ __global__ __launch_bounds__(256) void text_parse_kernel(const char *__restrict_
 
 }  // namespace
 
-// the scan, for the other count / scan / scatter pass of the library (memo_runs.hip)
-hipError_t memo::scan_tile_counts(const uint32_t *d_counts, int64_t ntiles, int64_t *d_bases, int64_t *d_total, hipStream_t st) {
-    hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(1024), 0, st, d_counts, ntiles, d_bases, d_total);
-    return hipGetLastError();
-}
-
 extern "C" {
 
 int memo_parse_conservation_text_dev(const char *d_text, int64_t nbytes, uint16_t *d_vec, int64_t cap, int64_t *lines,
@@ -197,9 +149,8 @@ int memo_parse_conservation_text_dev(const char *d_text, int64_t nbytes, uint16_
     if (nbytes < 0 || cap < 0 || (nbytes && !d_text) || (cap && !d_vec)) return fail(MEMO_EINVAL, "bad text arguments");
     if (reinterpret_cast<uintptr_t>(d_text) & 15) return fail(MEMO_EINVAL, "d_text must be 16-byte aligned");
     if (!nbytes) return MEMO_OK;
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t ntiles = nbytes / kTile + 1;
     if (ntiles > INT32_MAX) return fail(MEMO_EINVAL, "a text of %lld bytes is too long", (long long)nbytes);

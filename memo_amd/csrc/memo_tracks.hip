@@ -183,35 +183,21 @@ int memo_tracks_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, int64_t
     std::vector<int64_t> rel((size_t)bins + 1);
     for (int32_t b = 0; b <= bins; ++b) rel[b] = std::min<int64_t>(std::max<int64_t>(edges_host[b] - first, 0), L);
 
-    if (int rc = device_ok(device)) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(MEMO_EHIP, "cannot select HIP device %d", device);
+    OnDevice on(device);
+    if (on.rc) return on.rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     DevPtr<int64_t> d_edges;
     if (hipError_t err = d_edges.alloc(rel.size()); err != hipSuccess)
         return fail(MEMO_EHIP, "hipMalloc(%zu bytes) for the edges of %d bins: %s", rel.size() * sizeof(int64_t), bins, hipGetErrorString(err));
     HIP_TRY(hipMemcpyAsync(d_edges, rel.data(), rel.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     A.edges = d_edges;
-    struct Events {  // (timed calls only)
-        hipEvent_t e[2] = {};
-        ~Events() {
-            for (hipEvent_t x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } ev;
-    if (g_tracks_timed) {
-        for (hipEvent_t &x : ev.e) HIP_TRY(hipEventCreate(&x));
-        HIP_TRY(hipEventRecord(ev.e[0], st));
-    }
+    Laps laps(st, g_tracks_timed, &g_tracks_ms);
+    if (int rc = laps.start()) return rc;
     if (pw == 16) launch_pw<16>(A, gx, st);
     else if (pw == 8) launch_pw<8>(A, gx, st);
     else launch_pw<4>(A, gx, st);
     HIP_TRY(hipGetLastError());
-    if (g_tracks_timed) {
-        HIP_TRY(hipEventRecord(ev.e[1], st));
-        HIP_TRY(hipEventSynchronize(ev.e[1]));
-        HIP_TRY(hipEventElapsedTime(&g_tracks_ms, ev.e[0], ev.e[1]));
-    }
+    if (int rc = laps.lap(0)) return rc;
     HIP_TRY(hipStreamSynchronize(st));  // (rel and d_edges go with this frame)
     return MEMO_OK;
 }

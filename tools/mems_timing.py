@@ -9,7 +9,7 @@ In one process, on the index's own int64 columns (memo_index_columns):
     (4 L bytes) and the starts found with NumPy on the host; its list is compared with the device's;
   - the floor: the bytes the three passes move (the cells are read twice, 8 bytes written per match, the tile counts and bases) over
     8 TB/s;
-  - for comparison, memo_runs_conservation_dev (runs_count_kernel / runs_scatter_kernel) on a uint16 result of the same length, whole
+  - for comparison, memo_runs_conservation_dev (the same count and scatter kernels on its value key) on a uint16 result of the same length, whole
     call on the host clock, against its own bytes;
   - `-a`: the planes 1 .. N - 1 of one slice of the same rows read as a membership index (config 4), memo_lengths_*_dev's cells."""
 import argparse
