@@ -42,6 +42,19 @@ def table(planes, kmax, membership):
     return count(cons(planes, kmax, membership), np.asarray(planes).shape[0])
 
 
+def table_by_rank(planes, kmax, membership):
+    """table() without cons [L, kmax], in O(N L + N kmax): sel_T does not increase in T, so cons(p, k) >= t exactly when sel_t[p] >= k, and
+    atleast[k][t] = #{ p : sel_t[p] >= k } is the count of rank t's values from k up; atleast[k][0] = L, atleast[k][N + 1] = 0, and
+    exact[k][v] = atleast[k][v] - atleast[k][v + 1]"""
+    s = sel(planes, kmax, membership)
+    n, L = s.shape
+    least = np.zeros((kmax, n + 2), np.int64)
+    least[:, 0] = L
+    for t in range(1, n + 1):
+        least[:, t] = np.cumsum(np.bincount(s[t - 1], minlength=kmax + 1)[::-1])[::-1][1:]
+    return (least[:, :-1] - least[:, 1:]).astype(np.uint64)
+
+
 def exact(s, e, a, qs, qe, n_docs, kmax, membership):
     return table(lengths_oracle.planes(s, e, a, qs, qe, kmax, n_docs), kmax, membership)
 

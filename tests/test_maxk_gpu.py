@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "bin", "memo")
-SCAN_ROUND = 4096                       # tile minima one round of scan_tile_mins takes (memo_maxk.hip: kScanRound)
+SCAN_ROUND = 4096                       # tile minima one round of cells_scan_kernel takes (memo_cells.hip: kScanRound)
 CAP_MAX = 2 ** 31 - 1
 N, T = 7, 3                             # the structure tests: annots 0 .. 2 are selected by threshold 3
 ODD_ANNOTS = (-1, N, 2 ** 40)           # never selected by a threshold, whatever it is

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "bin", "memo")
 CAP_MAX = 2 ** 31 - 1
-SCAN_ROUND = 1024                       # tile counts one round of memo::scan_tile_counts takes (memo_text.hip)
+SCAN_ROUND = 1024                       # tile counts one round of memo::scan_tile_counts takes (memo_compact.hip)
 GUARD = 4                               # uint32 words before and behind the cells: the cells stay 16-byte aligned
 
 

@@ -99,6 +99,26 @@ def test_the_oracle_on_a_hand_made_column():
     assert cons[0].tolist() == [1, 0, 1, 2] and cons[1].tolist() == [1, 1, 1, 1] and cons[2].tolist() == [1, 2, 0, 1] and cons[3].tolist() == [2, 1, 0, 1]
 
 
+@pytest.mark.parametrize("n", (1, 2, 5, 33))
+def test_the_table_by_rank_is_the_table(n):
+    """the fast form the many-tile GPU tests compare with (tests/test_many_tiles_gpu.py) against the definition, in both modes"""
+    from tests.test_spectrum_gpu import PATTERNS, pattern_values
+    above = 0
+    for kmax in (1, 2, 31, 256):
+        rng = np.random.default_rng([n, kmax])
+        values = pattern_values(rng, n, 257, kmax, shift=kmax)
+        assert 257 > 2 * PATTERNS                                     # (every pattern, the bit widths above KMAX too, many times)
+        above += int((values > kmax).sum())
+        for membership in (False, True):
+            for L in (0, 1, 257):
+                want = spectrum_oracle.table(values[:, :L], kmax, membership)
+                got = spectrum_oracle.table_by_rank(values[:, :L], kmax, membership)
+                assert got.dtype == want.dtype == np.uint64 and got.shape == want.shape == (kmax, n + 1)
+                assert np.array_equal(got, want), (n, kmax, membership, L)
+                assert (got.sum(axis=1) == L).all()
+    assert above > 50                                                 # (values above KMAX are taken as KMAX by both)
+
+
 # ---------------------------------------------------------------------------------------
 # the command line
 # ---------------------------------------------------------------------------------------
