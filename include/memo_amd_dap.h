@@ -258,6 +258,42 @@ int memo_tracks_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, int64_t
 /* positions per tile at `words` genome words (512 up to 16 words, 256 up to 32, 128 above), for tests that want lengths around it */
 int32_t memo_tracks_tile(int32_t words);
 
+/* ---- `memo features`: per-feature presence and conservation from a BED file (no counterpart in the reference) -----------
+ * (Declared here, beside the `memo tracks` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * Features overlap and nest; the elementary segments between their endpoints do not.  A table is counted per segment -- with a
+ * membership index by memo_tracks_dev, the segment edges as its bins; with a conservation index by memo_segment_conservation_dev --
+ * and memo_feature_sums_dev turns it into the table per feature (memo_amd/csrc/memo_features.hip).
+ *
+ * The sum and the count at or above a threshold of a conservation result that is still on `device`: d_vec is uint16 [L], 16-byte
+ * aligned, read from [0] to [L) and nowhere else, 16 bytes a lane and load; it holds the positions first .. first + L of a window.
+ * edges_host is a HOST pointer, int64 [segs + 1], segment edges in the window's coordinates, non-decreasing (two equal edges are
+ * an empty segment, which counts nothing); the library uploads them itself.
+ *     d_sums[0][s] += sum of v[p - first]                        over p in [first, first + L) with edges[s] <= p < edges[s + 1]
+ *     d_sums[1][s] += #{such p : v[p - first] >= threshold}
+ * uint64 [2][segs] on `device`, ADDED to (the caller zeroes it; the slices of a window accumulate, and the table does not depend
+ * on where the slices are cut).  MEMO_EINVAL before anything is launched: d_vec not 16-byte aligned, d_sums NULL or not 8-byte
+ * aligned, segs outside [1, 2^20 + 1], a threshold outside [0, 65536], edges that decrease somewhere, first < edges[0],
+ * first + L > edges[segs].  L == 0 launches nothing and leaves the table as it was.  Scratch memory on the device: the edges,
+ * (segs + 1) x 8 bytes, freed before the call returns; an allocation that fails returns MEMO_EHIP with the bytes asked for in
+ * memo_last_error and leaves nothing allocated.  Blocking. */
+int memo_segment_conservation_dev(const uint16_t *d_vec, int64_t L, int64_t first, const int64_t *edges_host, int32_t segs,
+                                  int32_t threshold, uint64_t *d_sums, int32_t device, void *stream);
+/* positions per tile (2048), for tests that want lengths around it */
+int32_t memo_segment_conservation_tile(void);
+/* From segments to features: d_sums is uint64 [rows][segs] on `device`, 8-byte aligned, and becomes SCRATCH -- the call overwrites
+ * it with its prefix sums along every row.  lo_host and hi_host are HOST pointers, int32 [features]: feature f is the segments
+ * lo[f] .. hi[f] - 1 (lo == hi: none); the library uploads them itself.
+ *     d_out[f][r] = sum of d_sums[r][s] over lo[f] <= s < hi[f]                    uint64 [features][rows] on `device`, feature-major
+ * modulo 2^64 (a prefix that wraps still gives the exact difference).  MEMO_EINVAL before anything is launched, with d_sums and d_out
+ * as they were: rows outside [1, 2048], segs outside [1, 2^20 + 1], features < 0, a pointer that is NULL or not 8-byte aligned, a
+ * feature with lo < 0, lo > hi or hi > segs.  features == 0 launches nothing and writes nothing.  Scratch memory on the device: lo
+ * and hi, and 8 bytes per row and memo_feature_sums_tile() segments, freed before the call returns; an allocation that fails returns
+ * MEMO_EHIP with the bytes asked for in memo_last_error and leaves nothing allocated.  Blocking. */
+int memo_feature_sums_dev(uint64_t *d_sums, int32_t rows, int32_t segs, const int32_t *lo_host, const int32_t *hi_host, int32_t features,
+                          uint64_t *d_out, int32_t device, void *stream);
+/* segments per tile of the scan (2048), for tests that want segment counts around it */
+int32_t memo_feature_sums_tile(void);
+
 /* ---- `memo maxk`: the longest shared k-mer per position, every k in one pass (no counterpart in the reference) ----------
  * (Declared here, beside the `memo matrix` block: memo_amd.h keeps to the query path's 44 entry points.)
  * For the window [qs, qs + L), a cap CAP in [1, 2^31 - 1] and a row predicate -- mode 0: 0 <= annot < arg ("fewer than arg genomes

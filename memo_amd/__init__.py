@@ -25,6 +25,8 @@ Layout (only what the path needs):
   collect_cli.py   `memo collect`: flags, usage, the curve, the band over random orders or every order as tab-separated text
   tracks.py        `memo tracks`: every genome's k-mer presence per bin along the pivot, counted on the GPU, a window's in slices
   tracks_cli.py    `memo tracks`: flags, usage, counts or fractions as tab-separated text, or the heat map (matplotlib)
+  features.py      `memo features`: a BED file's features from one sweep per record: counted per segment, summed per feature on the GPU
+  features_cli.py  `memo features`: flags, usage, counts, fractions or presence calls per feature as tab-separated text
   maxk.py          `memo maxk`: the longest shared k per position, all k in one pass over the rows, a window's from a Parquet index
   maxk_cli.py      `memo maxk`: flags, usage, one integer per line
   lengths.py       `memo lengths`: every genome's match length per position from a membership index, and the T-th largest, in slices
@@ -54,6 +56,7 @@ _LAZY = {
     "cooccurrence": "matrix", "region_matrix": "matrix",
     "region_curves": "collect",
     "bin_tracks": "tracks", "region_tracks": "tracks",
+    "bed_features": "features", "read_bed": "features",
     "region_maxk": "maxk", "index_maxk": "maxk",          # (maxk.maxk keeps its module's name: memo_amd.maxk is the module)
     "region_planes": "lengths", "region_kth": "lengths",
     "region_mems": "mems",
@@ -70,7 +73,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

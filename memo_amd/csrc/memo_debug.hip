@@ -181,6 +181,12 @@ int memo_debug_tracks_times(int32_t on, float *out1) {
     return MEMO_OK;
 }
 
+int memo_debug_features_times(int32_t on, float *out3) {
+    g_features_timed = on ? 1 : 0;
+    if (out3) out3[0] = g_features_ms[0], out3[1] = g_features_ms[1], out3[2] = g_features_ms[2];
+    return MEMO_OK;
+}
+
 int memo_debug_maxk_rows(int32_t way) {
     if (way < 0 || way > 1) return fail(MEMO_EINVAL, "maxk row pass: 0 wave-aggregated atomics, 1 one atomic per row");
     g_maxk_rows_way = way;
