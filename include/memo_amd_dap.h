@@ -258,6 +258,30 @@ int memo_tracks_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, int64_t
 /* positions per tile at `words` genome words (512 up to 16 words, 256 up to 32, 128 above), for tests that want lengths around it */
 int32_t memo_tracks_tile(int32_t words);
 
+/* ---- `memo breaks`: k-free match starts and length sums per genome and bin (no counterpart in the reference) ------------
+ * (Declared here, beside the `memo tracks` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * From finished lengths that are still on `device` (memo_amd/csrc/memo_breaks.hip): d_cells is uint32 [planes][pitch], 16-byte
+ * aligned, pitch a multiple of 4, L cells per plane read and nothing else -- memo_lengths_finish_dev's layout; memo_maxk_finish_dev's
+ * cells are one plane of it.  halo = 1: cell 0 of every plane is only the left neighbour of cell 1 and is not counted; halo = 0:
+ * cell 0 is position 0 of its record.  The counted cells are halo .. L - 1, counted cell i is position first + i - halo.  edges_host
+ * is a HOST pointer, int64 [bins + 1], bin edges in the same coordinates, non-decreasing (two equal edges are an empty bin), with
+ * edges[0] <= first and first + (L - halo) <= edges[bins]; the library uploads them itself.
+ *     d_table[0][g][b] += #{ counted p in bin b : v[p] >= min_len and p starts a match }
+ *     d_table[1][g][b] += sum of v[p] over the counted p in bin b                                    (min_len plays no part)
+ * uint64 [2][planes][bins] on `device`, ADDED to (the caller zeroes it; the slices of a window accumulate, each with its halo cell,
+ * and the table does not depend on where they are cut).  A cell starts a match by memo_mems_dev's rule: v[p - 1] < v[p], or
+ * v[p - 1] == v[p] < cap, or it is cell 0 with halo = 0 -- so d_table[0][g] is the histogram of the starts memo_mems_dev reports
+ * for plane g.  MEMO_EINVAL before anything is launched, the table as it was: d_cells not 16-byte aligned, pitch not a multiple of 4
+ * or below L, L < 0 or above 2^31, planes outside [0, 2048], bins outside [1, 2^20 + 1], cap outside [1, 2^31 - 1], min_len outside
+ * [1, cap], halo not 0 or 1, edges that are NULL or decrease somewhere, a slice that leaves the edges, a table that is NULL or not
+ * 8-byte aligned.  L - halo <= 0 or planes == 0 launches nothing and leaves the table as it was.  Scratch memory on the device: the
+ * edges, (bins + 1) x 8 bytes, freed before the call returns; an allocation that fails returns MEMO_EHIP with the bytes asked for in
+ * memo_last_error and leaves nothing allocated.  Blocking. */
+int memo_breaks_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t planes, uint32_t cap, uint32_t min_len, int32_t halo,
+                    int64_t first, const int64_t *edges_host, int32_t bins, uint64_t *d_table, int32_t device, void *stream);
+/* cells per tile (1024), for tests that want lengths around it */
+int32_t memo_breaks_tile(void);
+
 /* ---- `memo features`: per-feature presence and conservation from a BED file (no counterpart in the reference) -----------
  * (Declared here, beside the `memo tracks` block: memo_amd.h keeps to the query path's 44 entry points.)
  * Features overlap and nest; the elementary segments between their endpoints do not.  A table is counted per segment -- with a

@@ -117,6 +117,10 @@ int memo_debug_cooc_times(int32_t on, float *out2);
  * receives the device milliseconds of the last timed call's kernel (the upload of the edges is not in them).
  * tools/tracks_timing.py reads them. */
 int memo_debug_tracks_times(int32_t on, float *out1);
+/* this THREAD's later memo_breaks_dev calls put an event pair around their launch (on = 1) or do not (0); out1 (may be NULL)
+ * receives the device milliseconds of the last timed call's kernel (the upload of the edges is not in them).
+ * tools/breaks_timing.py reads them. */
+int memo_debug_breaks_times(int32_t on, float *out1);
 /* this THREAD's later memo_segment_conservation_dev and memo_feature_sums_dev calls put event pairs around their launches (on = 1;
  * each is then waited for) or do not (0); out3 (may be NULL) receives the device milliseconds of the last timed launches: [0] the
  * segment kernel, [1] the three scan launches, [2] the gather (the uploads are not in them).  tools/features_timing.py reads them. */

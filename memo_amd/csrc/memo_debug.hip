@@ -181,6 +181,12 @@ int memo_debug_tracks_times(int32_t on, float *out1) {
     return MEMO_OK;
 }
 
+int memo_debug_breaks_times(int32_t on, float *out1) {
+    g_breaks_timed = on ? 1 : 0;
+    if (out1) out1[0] = g_breaks_ms;
+    return MEMO_OK;
+}
+
 int memo_debug_features_times(int32_t on, float *out3) {
     g_features_timed = on ? 1 : 0;
     if (out3) out3[0] = g_features_ms[0], out3[1] = g_features_ms[1], out3[2] = g_features_ms[2];
