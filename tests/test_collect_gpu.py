@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "bin", "memo")
 DOCS = (2, 3, 32, 33, 34, 65, 100, 130, 500, 513, 1030)          # W = 1, 1, 1, 2, 2, 3, 4, 5, 16, 17 (a tile of 8 words), 33 (of 4)
-LARGEST = (513, 1030)                                           # (L <= 2 T only)
+LARGEST = (513, 1030)                                           # (L <= 2 T only: test_plane_kernels_many_tiles_gpu.py has them
+#                                                                 over more tiles)
 GRID_X = 1024                                                   # workgroups along the positions at most (memo_collect.hip: kMaxGridX)
 
 
@@ -127,7 +128,8 @@ def test_order_shapes(memo, num_docs):
 def test_every_workgroup_more_than_one_tile_and_a_ragged_tail(memo):
     """2050 tiles and 77 positions: 683 workgroups of three tiles and one of one tile and the tail"""
     from memo_amd import collect
-    num_docs = 8                                             # (a question about positions: few genomes keep the oracle quick)
+    num_docs = 8                                             # (a question about positions: few genomes keep the oracle quick;
+    #                                                          many genomes over many tiles: test_plane_kernels_many_tiles_gpu.py)
     T = collect.tile(1)
     L = (2 * GRID_X + 2) * T + 77
     per = -(-(-(-L // T)) // GRID_X)
