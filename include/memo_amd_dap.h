@@ -282,6 +282,31 @@ int memo_breaks_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t p
 /* cells per tile (1024), for tests that want lengths around it */
 int32_t memo_breaks_tile(void);
 
+/* ---- `memo pairs`: k-free pairwise shared match length between genomes (no counterpart in the reference) ----------------
+ * (Declared here, beside the `memo breaks` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * From finished lengths that are still on `device` (memo_amd/csrc/memo_pairs.hip): d_cells is uint32 [planes][pitch], 16-byte
+ * aligned, pitch a multiple of 4, L cells per plane read and nothing else -- memo_lengths_finish_dev's layout, no halo.  With
+ *     w[g][p] = max(0, min(v[g][p], kmax) - (kmin - 1))          the number of k in [kmin, kmax] at which genome g holds the k-mer at p
+ *     d_sums[g][h] += sum over p in [0, L) of min(w[g][p], w[h][p])
+ * uint64 [planes][planes] on `device`, symmetric, ADDED to (the caller zeroes it; the slices of a window accumulate, and the matrix
+ * does not depend on where they are cut).  A cell above kmax counts as kmax.  With kmin == kmax == k it is memo_cooccurrence_dev's
+ * matrix of `memo query -m -k k`, for index rows with end >= start; over [kmin, kmax] the sum of those matrices.  The sums are exact
+ * at every span kmax - kmin + 1: up to memo_pairs_narrow_span() the kernel adds in 32 bits per tile and widens between tiles,
+ * above it in 64 bits.  More than memo_pairs_chunk() planes are taken in chunks, one launch per pair of chunks.  MEMO_EINVAL
+ * before anything is launched, the matrix as it was: d_cells not 16-byte aligned, pitch not a multiple of 4 or below L, L < 0 or
+ * above 2^31, planes outside [0, 2048], kmax outside [1, 2^31 - 1], kmin outside [1, kmax], a matrix that is NULL or not 8-byte
+ * aligned.  L == 0 or planes == 0 launches nothing and leaves the matrix as it was.  Scratch memory on the device: at most 64 MiB,
+ * freed before the call returns; an allocation that fails returns MEMO_EHIP with the bytes asked for in memo_last_error and leaves
+ * nothing allocated.  Blocking. */
+int memo_pairs_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t planes, uint32_t kmin, uint32_t kmax, uint64_t *d_sums,
+                   int32_t device, void *stream);
+/* positions per tile (128), for tests that want lengths around it */
+int32_t memo_pairs_tile(void);
+/* the most planes one launch stages (128): above it the planes come in chunks of half as many */
+int32_t memo_pairs_chunk(void);
+/* the largest span kmax - kmin + 1 that takes the 32-bit form: span x tile < 2^32 */
+uint32_t memo_pairs_narrow_span(void);
+
 /* ---- `memo features`: per-feature presence and conservation from a BED file (no counterpart in the reference) -----------
  * (Declared here, beside the `memo tracks` block: memo_amd.h keeps to the query path's 44 entry points.)
  * Features overlap and nest; the elementary segments between their endpoints do not.  A table is counted per segment -- with a

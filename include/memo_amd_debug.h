@@ -121,6 +121,10 @@ int memo_debug_tracks_times(int32_t on, float *out1);
  * receives the device milliseconds of the last timed call's kernel (the upload of the edges is not in them).
  * tools/breaks_timing.py reads them. */
 int memo_debug_breaks_times(int32_t on, float *out1);
+/* this THREAD's later memo_pairs_dev calls put event pairs around their launches (on = 1; each launch is then waited for) or do not
+ * (0); out2 (may be NULL) receives the device milliseconds of the last timed call: [0] the sweep launches, [1] the reduce launches.
+ * tools/pairs_timing.py reads them. */
+int memo_debug_pairs_times(int32_t on, float *out2);
 /* this THREAD's later memo_segment_conservation_dev and memo_feature_sums_dev calls put event pairs around their launches (on = 1;
  * each is then waited for) or do not (0); out3 (may be NULL) receives the device milliseconds of the last timed launches: [0] the
  * segment kernel, [1] the three scan launches, [2] the gather (the uploads are not in them).  tools/features_timing.py reads them. */

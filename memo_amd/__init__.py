@@ -35,6 +35,8 @@ Layout (only what the path needs):
   mems_cli.py      `memo mems`: flags, usage, one interval per line
   breaks.py        `memo breaks`: match starts and length sums per genome and bin, or per BED feature, counted on the GPU where the lengths lie
   breaks_cli.py    `memo breaks`: flags, usage, counts, sums or their means as tab-separated text
+  pairs.py         `memo pairs`: every pair of genomes' shared match length over a window, reduced on the GPU where the lengths lie
+  pairs_cli.py     `memo pairs`: flags, usage, sums, weighted Jaccard distances or mean lengths as tab-separated text
   spectrum.py      `memo spectrum`: a window's conservation histogram at every k from either kind of index, reduced on the GPU, in slices
   spectrum_cli.py  `memo spectrum`: flags, usage, the table as tab-separated text
   convert.py       `memo convert`: a membership index's lengths fed to the row builder: the conservation index, or the canonical membership index
@@ -63,6 +65,7 @@ _LAZY = {
     "region_planes": "lengths", "region_kth": "lengths",
     "region_mems": "mems",
     "region_breaks": "breaks", "bed_breaks": "breaks", "plane_breaks": "breaks",
+    "region_pairs": "pairs", "plane_sums": "pairs",
     "region_exact": "spectrum",
     "convert_index": "convert",
     "add_index": "add",
@@ -76,7 +79,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "pairs", "pairs_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

@@ -187,6 +187,12 @@ int memo_debug_breaks_times(int32_t on, float *out1) {
     return MEMO_OK;
 }
 
+int memo_debug_pairs_times(int32_t on, float *out2) {
+    g_pairs_timed = on ? 1 : 0;
+    if (out2) out2[0] = g_pairs_ms[0], out2[1] = g_pairs_ms[1];
+    return MEMO_OK;
+}
+
 int memo_debug_features_times(int32_t on, float *out3) {
     g_features_timed = on ? 1 : 0;
     if (out3) out3[0] = g_features_ms[0], out3[1] = g_features_ms[1], out3[2] = g_features_ms[2];
