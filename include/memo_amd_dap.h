@@ -307,6 +307,37 @@ int32_t memo_pairs_chunk(void);
 /* the largest span kmax - kmin + 1 that takes the 32-bit form: span x tile < 2^32 */
 uint32_t memo_pairs_narrow_span(void);
 
+/* ---- `memo nearest`: which genome matches the pivot longest, per position and per bin (no counterpart in the reference) ---
+ * (Declared here, beside the `memo pairs` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * From finished lengths that are still on `device` (memo_amd/csrc/memo_nearest.hip): d_cells is uint32 [planes][pitch], 16-byte
+ * aligned, pitch a multiple of 4, L cells per plane read and nothing else -- memo_lengths_finish_dev's layout, no halo; cell i is
+ * position first + i.  v[g][p] = min(cell, cap).  cand_host is a HOST pointer to 64 words, bit g = genome g is a candidate, or NULL
+ * for 1 .. planes - 1; plane 0 (the pivot) is never a candidate, and neither it nor a plane outside the set is read.  edges_host is a
+ * HOST pointer, int64 [bins + 1], bin edges in the positions' coordinates, non-decreasing (two equal edges are an empty bin), with
+ * edges[0] <= first and first + L <= edges[bins]; the library uploads both itself.  With best[p] = the largest v[g][p] over the
+ * candidates, ok[p] = best[p] >= min_len, att[g][p] = ok[p] and v[g][p] == best[p] (every tied genome attains), sole[g][p] =
+ * att[g][p] and no other genome attains:
+ *     d_wins[0][g][b] += #{ p in bin b : att[g][p] }       g >= 1;     d_wins[0][0][b] += #{ p in bin b : not ok[p] }      ("none")
+ *     d_wins[1][g][b] += #{ p in bin b : sole[g][p] }      g >= 1;     d_wins[1][0][b] += the same "none" count
+ *     d_sums[b]       += sum of best[p] over bin b                                                  (min_len plays no part)
+ *     d_winner[i]      = the smallest g with att[g][i], 0 where not ok[i]                           uint16 [L], WRITTEN
+ * d_wins is uint64 [2][planes][bins] and d_sums uint64 [bins] on `device`, ADDED to (the caller zeroes them; the slices of a window
+ * accumulate, and the tables do not depend on where they are cut); each of the three outputs may be NULL and is then not computed.
+ * With min_len == cap == K row g of d_wins[0] is row g of memo_tracks_dev at k = K.  MEMO_EINVAL before anything is launched, the
+ * outputs as they were: d_cells not 16-byte aligned, pitch not a multiple of 4 or below L, L < 0 or above 2^31, planes outside
+ * [2, 2048], cap outside [1, 2^31 - 1], min_len outside [1, cap], a candidate set that is empty, names bit 0 or names a bit at or
+ * past planes, all three outputs NULL, a table that is not 8-byte aligned, a winner that is not 2-byte aligned; with a table: bins
+ * outside [1, 2^20 + 1], edges that are NULL or decrease somewhere, a slice that leaves the edges; without a table edges may be NULL
+ * with bins == 0.  L == 0 launches nothing and leaves everything as it was.  A workgroup takes a run of tiles, at most 1024 runs a
+ * call.  Scratch memory on the device: the edges, (bins + 1) x 8 bytes, and the 64 candidate words, freed before the call returns;
+ * an allocation that fails returns MEMO_EHIP with the bytes asked for in memo_last_error and leaves nothing allocated.  Blocking. */
+int memo_nearest_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t planes, uint32_t cap, uint32_t min_len,
+                     const uint32_t *cand_host, int64_t first, const int64_t *edges_host, int32_t bins, uint64_t *d_wins, uint64_t *d_sums,
+                     uint16_t *d_winner, int32_t device, void *stream);
+/* positions per tile at that many planes (256 up to 67 planes, 128 up to 109, 64 up to 216, 32 up to 415, 16 up to 763, then 8; 0 for planes outside [2, 2048]), for tests that
+ * want lengths around it */
+int32_t memo_nearest_tile(int32_t planes);
+
 /* ---- `memo features`: per-feature presence and conservation from a BED file (no counterpart in the reference) -----------
  * (Declared here, beside the `memo tracks` block: memo_amd.h keeps to the query path's 44 entry points.)
  * Features overlap and nest; the elementary segments between their endpoints do not.  A table is counted per segment -- with a

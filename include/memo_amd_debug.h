@@ -125,6 +125,14 @@ int memo_debug_breaks_times(int32_t on, float *out1);
  * (0); out2 (may be NULL) receives the device milliseconds of the last timed call: [0] the sweep launches, [1] the reduce launches.
  * tools/pairs_timing.py reads them. */
 int memo_debug_pairs_times(int32_t on, float *out2);
+/* this THREAD's later memo_nearest_dev calls put an event pair around their launch (on = 1) or do not (0); out1 (may be NULL)
+ * receives the device milliseconds of the last timed call's kernel (the uploads of the edges and the candidate words are not in
+ * them).  tools/nearest_timing.py reads them. */
+int memo_debug_nearest_times(int32_t on, float *out1);
+/* this THREAD's later memo_nearest_dev and memo_nearest_tile calls: the LDS a workgroup may take, in KiB of [16, 160]; 0 = the
+ * library's 72 (two workgroups per CU).  It decides the positions per tile and how many workgroups share a CU (the A/B of
+ * DESIGN.md 10.17); 2048 planes take their 113 KiB whatever is set.  The results are the same. */
+int memo_debug_nearest_lds(int32_t kib);
 /* this THREAD's later memo_segment_conservation_dev and memo_feature_sums_dev calls put event pairs around their launches (on = 1;
  * each is then waited for) or do not (0); out3 (may be NULL) receives the device milliseconds of the last timed launches: [0] the
  * segment kernel, [1] the three scan launches, [2] the gather (the uploads are not in them).  tools/features_timing.py reads them. */

@@ -37,6 +37,8 @@ Layout (only what the path needs):
   breaks_cli.py    `memo breaks`: flags, usage, counts, sums or their means as tab-separated text
   pairs.py         `memo pairs`: every pair of genomes' shared match length over a window, reduced on the GPU where the lengths lie
   pairs_cli.py     `memo pairs`: flags, usage, sums, weighted Jaccard distances or mean lengths as tab-separated text
+  nearest.py       `memo nearest`: which genome matches the pivot longest, per genome and bin or as runs of the winner, reduced across the planes on the GPU
+  nearest_cli.py   `memo nearest`: flags, usage, wins, sole wins or their shares as tab-separated text, or one interval per run of the winner
   spectrum.py      `memo spectrum`: a window's conservation histogram at every k from either kind of index, reduced on the GPU, in slices
   spectrum_cli.py  `memo spectrum`: flags, usage, the table as tab-separated text
   convert.py       `memo convert`: a membership index's lengths fed to the row builder: the conservation index, or the canonical membership index
@@ -66,6 +68,7 @@ _LAZY = {
     "region_mems": "mems",
     "region_breaks": "breaks", "bed_breaks": "breaks", "plane_breaks": "breaks",
     "region_pairs": "pairs", "plane_sums": "pairs",
+    "region_nearest": "nearest", "region_winners": "nearest", "plane_nearest": "nearest",
     "region_exact": "spectrum",
     "convert_index": "convert",
     "add_index": "add",
@@ -79,7 +82,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "pairs", "pairs_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "pairs", "pairs_cli", "nearest", "nearest_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

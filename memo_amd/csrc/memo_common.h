@@ -53,6 +53,10 @@ extern thread_local int g_breaks_timed;  // memo_breaks.hip (AB library, memo_de
 extern thread_local float g_breaks_ms;
 extern thread_local int g_pairs_timed;  // memo_pairs.hip (AB library, memo_debug_pairs_times: event pairs around the launches of memo_pairs_dev)
 extern thread_local float g_pairs_ms[2];
+extern thread_local int g_nearest_timed;  // memo_nearest.hip (AB library, memo_debug_nearest_times: an event pair around the launch of memo_nearest_dev)
+extern thread_local float g_nearest_ms;
+extern thread_local int g_nearest_lds_kib;  // ... memo_debug_nearest_lds: the LDS a workgroup may take, which decides the tile
+constexpr int kNearestLdsKib = 72;          // ... the product's: two workgroups a CU
 extern thread_local int g_features_timed;  // memo_features.hip (AB library, memo_debug_features_times: event pairs around the launches of its two calls)
 extern thread_local float g_features_ms[3];
 extern thread_local int g_lengths_timed;  // memo_lengths.hip (AB library, memo_debug_lengths_times: event pairs around the launches of the memo_lengths_*_dev calls)

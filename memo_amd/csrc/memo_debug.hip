@@ -193,6 +193,18 @@ int memo_debug_pairs_times(int32_t on, float *out2) {
     return MEMO_OK;
 }
 
+int memo_debug_nearest_times(int32_t on, float *out1) {
+    g_nearest_timed = on ? 1 : 0;
+    if (out1) out1[0] = g_nearest_ms;
+    return MEMO_OK;
+}
+
+int memo_debug_nearest_lds(int32_t kib) {
+    if (kib != 0 && (kib < 16 || kib > 160)) return fail(MEMO_EINVAL, "LDS of a memo_nearest_dev workgroup: 0 (the library's %d) or [16, 160] KiB", kNearestLdsKib);
+    g_nearest_lds_kib = kib ? kib : kNearestLdsKib;
+    return MEMO_OK;
+}
+
 int memo_debug_features_times(int32_t on, float *out3) {
     g_features_timed = on ? 1 : 0;
     if (out3) out3[0] = g_features_ms[0], out3[1] = g_features_ms[1], out3[2] = g_features_ms[2];
