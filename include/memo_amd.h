@@ -221,7 +221,16 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info);  /*
  *                             the flagged view); 0: never (the flagged view stays and is swept with its dead groups masked: the A/B).
  *   MEMO_OPT_WIDE_TILES       1 (default): a six-row view with few rows per tile (a live copy) is swept at k - 1 = 16 .. 31 on radix-4
  *                             level arrays -- three of 1664 cells, tiles of 1568 positions at k = 31 -- (memo_index_info_t.last_tile_width);
- *                             0: on today's five doubling arrays of 1024 cells (928 positions at k = 31), for A/B runs and tests. */
+ *                             0: on today's five doubling arrays of 1024 cells (928 positions at k = 31), for A/B runs and tests.
+ *   MEMO_OPT_VIEW_DECIDING    1 (default): the copy of a placed six-row view without its dead groups (MEMO_OPT_VIEW_LIVE) is copied once more,
+ *                             for ONE k, down to the rows that hold the least (order, slot) at some position they cover -- at k = 31 one
+ *                             row in five of config 3's copy; the minimum over them is the minimum over all rows at that k and no
+ *                             other.  Made by a conservation query once the live copy has answered 32 queries in a row at that k (a
+ *                             query of the class at its other k starts the count again, whatever MEMO_OPT_BUILD_COST_PCT says) and
+ *                             those queries have lost to the rows that decide nothing what the pass costs (MEMO_OPT_BUILD_COST_PCT
+ *                             applies).  Kept beside the live copy, which goes on answering the class's other k; one such copy per
+ *                             class.  Never by memo_index_prepare; 0: never (a copy already made is kept and not read: the A/B).
+ *                             memo_index_export_view keeps handing out the class's own view (the live copy). */
 #define MEMO_OPT_VIEWS 1
 #define MEMO_OPT_VIEW_BUDGET_PCT 2
 #define MEMO_OPT_BUILD_COST_PCT 3
@@ -229,6 +238,7 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info);  /*
 #define MEMO_OPT_VIEW_PLACES 5
 #define MEMO_OPT_VIEW_LIVE 6
 #define MEMO_OPT_WIDE_TILES 7
+#define MEMO_OPT_VIEW_DECIDING 8
 /* Returns the option's PREVIOUS value (>= 0) -- what a caller that changes an option for one pass puts back -- or a negative code. */
 int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value);
 /* Build NOW what queries of one kind would otherwise build on the way: the k-class view of the rows such a query reads (else

@@ -61,6 +61,13 @@ int memo_debug_six_views(int32_t on);
 /* placed six-row views of this index copied without their dead groups so far (MEMO_OPT_VIEW_LIVE; memo_view_build.hip: live_view_copy), and
  * whether the six-row view of k's class is such a copy: 1, or 0 (not a copy, or no six-row view of that class is resident) */
 int memo_debug_view_live(const memo_index_t *ix, int32_t k, uint64_t *copies);
+/* deciding copies this index has made so far (MEMO_OPT_VIEW_DECIDING; memo_view_build.hip: deciding_view_copy), and whether the class of k
+ * holds one for exactly this k: 1, or 0 (none, one for the class's other k, or no live copy of that class is resident) */
+int memo_debug_view_deciding(const memo_index_t *ix, int32_t k, uint64_t *made);
+/* ... and that copy to host memory, as groups of 6 rows that carry their bucket, like memo_index_export_view(..., 6, ...) hands out the
+ * live copy it was made of: *rows: the rows that decide a minimum (0: no such copy is resident for this k), *group_count: its groups,
+ * boff: info.buckets entries in units of padded row numbers.  groups == boff == NULL: the sizes only. */
+int memo_debug_export_deciding(memo_index_t *ix, int32_t k, void *groups, int64_t *boff, uint64_t *rows, uint64_t *group_count);
 /* this THREAD's later calls: every device allocation for a view or a tile table fails (the test of the no-memory path) */
 int memo_debug_fail_side_allocations(int32_t on);
 /* this thread's later memo_index_pack_dense / dense builders keep the rows that can never write at k <= 64 in the dense rows */

@@ -116,8 +116,8 @@ constexpr int kStatusExecNarrow = 4;          // -DMEMO_EXEC_CHECK builds: a bra
 
 // The one-time passes over an index's rows that one rule decides (memo_view.hip: pass_due): a k-class view of the dense rows, of the
 // 4-byte words, a dense view with the places of its rows chosen, the copy of a placed six-row view without its dead groups, the
-// query order of the 4-byte rows
-enum Pass { kPassDenseView, kPassPackedView, kPassPlaces, kPassLiveCopy, kPassRowOrder, kPasses };
+// query order of the 4-byte rows, the copy of a live copy that holds only the rows that decide a minimum at one k - 1
+enum Pass { kPassDenseView, kPassPackedView, kPassPlaces, kPassLiveCopy, kPassRowOrder, kPassDeciding, kPasses };
 
 // What a view pass (memo_view_build.hip) hands back, and the part of a DenseView it fills: the view's rows (dense groups, or 4-byte
 // words), its bucket table (nb entries), the rows of the source it holds, the rows its table counts (slots of six-row groups; five-row
@@ -256,6 +256,18 @@ struct memo_index {
         int live = 0;            // 1: the copy of a placed six-row view without its dead groups (memo_view_build.hip: live_view_copy; dead_groups 0, padded = 6 x its
                                  //   groups, rows still the class's rows: a dead row is answered by a live one that contains it) --
         double dead_lost_ns = 0; //   a third pass, decided like the others: what the queries on the flagged view have lost to its dead groups
+        // The DECIDING copy of a live copy (memo_view_build.hip: deciding_view_copy), kept beside it: for ONE k - 1 of the class (dec_km1)
+        // the rows that hold the least (order, slot) at some position they cover -- the minimum over them is the minimum over all the
+        // rows, at that k - 1 only (dec.rows: the winners, dec.padded: 6 x its groups; none of its groups is flagged, every row writes).
+        // A fourth pass, decided in memo_view.hip (deciding_rows): the live copy must have answered kDecidingAskAfter queries in a row at
+        // one k (dec_run at dec_run_km1) and the ledger dec_lost_ns must be due.
+        memo::BuiltView dec;
+        int dec_km1 = 0;           // the k - 1 `dec` is exact for (dec.p3 != nullptr)
+        int dec_never[2] = {0, 0}; // [cap - km1]: the copy of this k - 1 spared less than a fifth of the groups (or could not be made): not asked for again
+        int dec_run_km1 = 0, dec_run = 0;  // conservation queries in a row the class's live copy (or its deciding copy) has answered at this k - 1
+        double dec_lost_ns = 0;    // what the queries of the run have lost to the rows that decide nothing (estimate)
+        int dec_backoff = 1;       // x 4 after a pass that found no room
+        uint64_t dec_bytes = 0;    // of dec's groups
         uint64_t bytes = 0;      // of the rows' allocation (set where a view is installed: a six-row view is (groups + 64) x 16 B, not
                                  //   what its padded row count makes of five-row groups -- ADVICE r05: the budget charged it a fifth too much)
         float build_ms = 0.f;
@@ -269,6 +281,8 @@ struct memo_index {
     uint64_t view_placings = 0;   // dense views rebuilt with their rows placed (memo_index_info_t.view_placings)
     int view_live = 1;            // memo_index_set_option(MEMO_OPT_VIEW_LIVE): 0 placed six-row views keep their dead groups (flagged, swept with LIVE)
     int wide_tiles = 1;           // memo_index_set_option(MEMO_OPT_WIDE_TILES): 0 six-row views keep the doubling tiles where R4 would apply (A/B)
+    int view_deciding = 1;        // memo_index_set_option(MEMO_OPT_VIEW_DECIDING): 0 a live copy is never copied down to the rows that decide a minimum at the query's k
+    uint64_t view_deciding_copies = 0;  // deciding copies made (memo_debug_view_deciding of the AB library)
     uint64_t view_live_copies = 0;  // placed six-row views copied without their dead groups (memo_debug_view_live_copies of the AB library)
     double pass_ns[memo::kPasses] = {};  // per row of its source, as the index's last pass of each kind measured it (memo::Pass; the copy without
                                          //   dead groups: per group of the flagged view; 0: the calibrated constant, memo_view.hip: kPassNs)

@@ -93,6 +93,31 @@ int memo_debug_view_live(const memo_index_t *ix, int32_t k, uint64_t *copies) {
     return v.p3 && v.live ? 1 : 0;
 }
 
+int memo_debug_view_deciding(const memo_index_t *ix, int32_t k, uint64_t *made) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (made) *made = ix->view_deciding_copies;
+    if (k < 2 || k > 32) return 0;  // (no class)
+    const memo_index::DenseView &v = ix->views6[k / 2 - 1];  // (the class of k - 1: memo_view.hip, dense_rows_for)
+    return v.p3 && v.live && v.dec.p3 && v.dec_km1 == k - 1 ? 1 : 0;
+}
+
+int memo_debug_export_deciding(memo_index_t *ix, int32_t k, void *groups, int64_t *boff, uint64_t *rows, uint64_t *group_count) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (rows) *rows = 0;
+    if (group_count) *group_count = 0;
+    const int km1 = k - 1;
+    if (km1 < 1 || km1 > 31) return MEMO_OK;  // (no class of six-row views: nothing to export)
+    const memo_index::DenseView &v = ix->views6[k / 2 - 1];
+    if (v.state != 1 || !v.live || !v.dec.p3 || v.dec_km1 != km1) return MEMO_OK;  // (not made, or made for the class's other k)
+    const uint64_t ng = v.dec.padded / 6;
+    if (rows) *rows = v.dec.rows;
+    if (group_count) *group_count = ng;
+    if (!groups && !boff) return MEMO_OK;
+    if (!groups || !boff) return fail(MEMO_EINVAL, "groups and boff: both or neither");
+    if (int rc = download_pipelined(ix->device, groups, v.dec.p3, (size_t)ng * 16, nullptr)) return rc;
+    return download_pipelined(ix->device, boff, v.dec.boff, ix->nb * 8, nullptr);
+}
+
 int memo_debug_fail_side_allocations(int32_t on) {
     g_side_alloc_fails = on != 0;
     return MEMO_OK;

@@ -741,6 +741,7 @@ static void fill_info(const memo_index *ix, memo_index_info_t *info) {
     for (bool dense : {true, false})
         each_view(ix, dense, [&](const memo_index::DenseView &v) {
             side += v.p3 ? v.bytes + ix->nb * 8 : 0;
+            side += v.dec.p3 ? v.dec_bytes + ix->nb * 8 : 0;  // (the deciding copy beside a live copy: side bytes, not a view of its own)
             info->views_resident += v.p3 ? 1 : 0;
         });
     for (const memo_index::TileTable &t : ix->ttabs) side += (uint64_t)t.n * 32;
@@ -796,6 +797,7 @@ static const struct {
     {MEMO_OPT_VIEW_PLACES, &memo_index::view_places, 0, 1, 1, "MEMO_OPT_VIEW_PLACES takes 0 or 1"},
     {MEMO_OPT_VIEW_LIVE, &memo_index::view_live, 0, 1, 1, "MEMO_OPT_VIEW_LIVE takes 0 or 1"},  // (a copy already made stays: it answers exactly what the flagged view does)
     {MEMO_OPT_WIDE_TILES, &memo_index::wide_tiles, 0, 1, 1, "MEMO_OPT_WIDE_TILES takes 0 or 1"},
+    {MEMO_OPT_VIEW_DECIDING, &memo_index::view_deciding, 0, 1, 1, "MEMO_OPT_VIEW_DECIDING takes 0 or 1"},  // (a copy already made stays, unread while the option is 0)
     {MEMO_OPT_VIEW_ROWS, &memo_index::view_rows, 0, 5, 6, "MEMO_OPT_VIEW_ROWS takes 0 (the library's choice), 5 or 6"},
 };
 

@@ -17,12 +17,14 @@ extern thread_local bool g_side_alloc_fails;  // (AB library, memo_debug_fail_si
 inline uint64_t dense_view_bytes(uint64_t padded, int rows_per_group) {  // what dense_view_build allocates for a view's rows
     return (rows_per_group == 6 ? padded / 6 + 64 : (padded + 4) / 5 + 64) * 16;
 }
-// The three passes: a source in, a BuiltView (memo_common.h) out.  Each allocates, queues its kernels on `st` and waits for them; kNoRoom when an allocation found no room.
+// The passes: a source in, a BuiltView (memo_common.h) out.  Each allocates, queues its kernels on `st` and waits for them; kNoRoom when an allocation found no room.
 // (hidden: they were file-local before the file was split, and the library exports what it exported)
 #pragma GCC visibility push(hidden)
 int dense_view_build(int device, const uint32_t *src_p3, const int64_t *src_boff, uint64_t rows, uint64_t nb, int cap, int min_tenths,
                      hipStream_t st, int rpg, int colour_km1, BuiltView &out);
 int live_view_copy(int device, const BuiltView &flagged, uint64_t nb, hipStream_t st, BuiltView &out);
+int deciding_view_copy(int device, const BuiltView &live, uint64_t nb, int64_t bbase, int64_t first_start, int64_t last_start, int km1,
+                       hipStream_t st, BuiltView &out);
 int packed_filter(int device, const uint32_t *src, const int64_t *src_boff, uint64_t rows, uint64_t nb, int cap, int min_tenths,
                   hipStream_t st, int len_shift, BuiltView &out);
 #pragma GCC visibility pop

@@ -58,7 +58,7 @@ static int ask_after_step(int x) { return x ? backoff_step(x) : 16; }
 // the tile tables made for a view go with it (a later allocation may land on its address)
 static void retire_tables_of(memo_index *ix, const memo_index::DenseView &v) {
     for (size_t i = 0; i < ix->ttabs.size();) {
-        if (ix->ttabs[i].rows_of == v.p3) {  // (never of a view that was not built: a table is made for rows)
+        if (ix->ttabs[i].rows_of == v.p3 || (v.dec.p3 && ix->ttabs[i].rows_of == v.dec.p3)) {  // (never of a view that was not built: a table is made for rows)
             retire(ix, ix->ttabs[i].d, (uint64_t)ix->ttabs[i].n * 32);
             ix->ttabs.erase(ix->ttabs.begin() + (long)i);
         } else {
@@ -67,9 +67,29 @@ static void retire_tables_of(memo_index *ix, const memo_index::DenseView &v) {
     }
 }
 
+// the deciding copy of a live copy, out of service: with the tile tables made for it; the class's ledgers for it start again
+static void retire_deciding(memo_index *ix, memo_index::DenseView &v) {
+    if (!v.dec.p3) return;
+    for (size_t i = 0; i < ix->ttabs.size();) {
+        if (ix->ttabs[i].rows_of == v.dec.p3) {
+            retire(ix, ix->ttabs[i].d, (uint64_t)ix->ttabs[i].n * 32);
+            ix->ttabs.erase(ix->ttabs.begin() + (long)i);
+        } else {
+            ++i;
+        }
+    }
+    retire(ix, v.dec.p3, v.dec_bytes);
+    retire(ix, v.dec.boff, ix->nb * 8);
+    v.dec = BuiltView();
+    v.dec_km1 = 0;
+    v.dec_bytes = 0;
+}
+
 static void retire_view(memo_index *ix, memo_index::DenseView &v, bool evicted) {
     retire_tables_of(ix, v);
     retire(ix, v.p3, v.bytes);
+    retire(ix, v.dec.p3, v.dec_bytes);  // (the deciding copy goes with the live copy it was made of)
+    if (v.dec.p3) retire(ix, v.dec.boff, ix->nb * 8);
     retire(ix, v.boff, ix->nb * 8);
     const int backoff = evicted ? backoff_step(v.backoff) : v.backoff, ask = evicted ? ask_after_step(v.ask_after) : v.ask_after;
     v = memo_index::DenseView();
@@ -80,6 +100,8 @@ static void retire_view(memo_index *ix, memo_index::DenseView &v, bool evicted) 
 static void free_view(memo_index::DenseView &v) {  // (the caller has the device drained)
     (void)hipFree(v.p3);
     (void)hipFree(v.boff);
+    (void)hipFree(v.dec.p3);
+    (void)hipFree(v.dec.boff);
     v = memo_index::DenseView();
 }
 void drop_dense_views(memo_index *ix) {
@@ -104,7 +126,7 @@ static void keep_views_in_budget(memo_index *ix, const memo_index::DenseView *fr
         memo_index::DenseView *lru = nullptr;
         each_view(ix, dense, [&](memo_index::DenseView &v) {
             if (!v.p3) return;
-            total += v.bytes + ix->nb * 8;
+            total += v.bytes + ix->nb * 8 + (v.dec.p3 ? v.dec_bytes + ix->nb * 8 : 0);
             if (&v != fresh && (!lru || v.stamp < lru->stamp)) lru = &v;
         });
         if (total <= budget || !lru) break;
@@ -135,9 +157,12 @@ constexpr double kPlacedGainPerKm1 = 0.0013;    // what places buy a sweep on th
 constexpr double kPackedViewNsPerRow = 0.03;    // keep, scan, scatter, and the order inside the view's buckets
 constexpr double kOrderNsPerRow = 0.014;        // copy + the order inside the buckets (more on indexes of many rows per start)
 constexpr double kLiveCopyNsPerGroup = 0.008;   // live_view_copy, per group of the flagged view: two reads of it, a write of its live groups
+constexpr double kDecidingNsPerGroup = 0.12;    // deciding_view_copy, per group of the live copy (profiles/deciding_rows.txt: 1.62 ms for config 3's 1.14e7 groups at k = 31)
+constexpr double kDecidingSparedShare = 0.5;    // ... the share of the live copy's slots a deciding copy is assumed to spare a sweep, before one is made
+constexpr int kDecidingAskAfter = 32;           // ... queries in a row at one k the live copy must have answered first (bench.py's warm-up makes 200: <= 64)
 constexpr double kPassFixedNs = 200e3;
 // per unit of every pass (Pass, memo_common.h: a row of its source; the live copy: a group of the flagged view), until the index has measured one
-constexpr double kPassNs[kPasses] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow, kLiveCopyNsPerGroup, kOrderNsPerRow};
+constexpr double kPassNs[kPasses] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow, kLiveCopyNsPerGroup, kOrderNsPerRow, kDecidingNsPerGroup};
 
 static double rows_in_window(const memo_index *ix, double src_rows, int64_t window, int km1) {
     const double span = (double)ix->max_s - (double)ix->min_s + 1.0;
@@ -196,6 +221,73 @@ static bool live_due(memo_index *ix, memo_index::DenseView &v, int64_t window, i
     const double groups = (double)(v.padded / 6), share = (double)v.dead_groups / groups;
     v.dead_lost_ns += rows_in_window(ix, (double)v.padded, window, km1) * share * kSweepNsPerRow;
     return pass_due(ix, v.dead_lost_ns, v.backoff, kPassLiveCopy, groups);
+}
+
+// A live copy that answers a conservation query at k - 1 = km1: the deciding copy of that k - 1 (memo_view_build.hip: deciding_view_copy)
+// in its place, when it exists or is due.  The copy is exact for ONE k - 1, so the library wants evidence that the host stays at this
+// k before it pays the pass: the live copy (or the deciding copy of this k - 1) must have answered kDecidingAskAfter queries in a
+// row at it -- a query of the class at its other k starts the run again, and this holds at MEMO_OPT_BUILD_COST_PCT 0 too -- and
+// the ledger of the run (the slots of the window x an assumed spared share x what a sweep pays per row) must have reached the pass's
+// cost.  Never inside memo_index_prepare.  One deciding copy per class: a copy for the class's other k - 1 stays until this one's
+// is made, and answers again without a pass when the host goes back.  A copy that spares less than a fifth of the groups is
+// dropped and this k - 1 not looked at again (the precedent of state 2); no room: the live copy answers and the back-off grows.
+// src: the live copy's, rewritten for the deciding copy -- every row of which writes at km1 (cap = km1: the launcher drops the test).
+static int deciding_rows(memo_index *ix, memo_index::DenseView &v, int km1, int64_t window, hipStream_t st, uint64_t base_bytes,
+                         RowSource &src) {
+    if (!ix->view_deciding || km1 > v.cap || km1 < v.cap - 1 || km1 > 31) return MEMO_OK;
+    auto hand_out = [&]() {
+        src.p3 = v.dec.p3;
+        src.boff = v.dec.boff;
+        src.rows = v.dec.padded;
+        src.cap = km1;
+        src.dead_share = 0.0;
+    };
+    if (g_prepare_only) {  // (plans on what there is; counts nothing, builds nothing)
+        if (v.dec.p3 && v.dec_km1 == km1) hand_out();
+        return MEMO_OK;
+    }
+    if (v.dec_run_km1 != km1) {
+        v.dec_run_km1 = km1;
+        v.dec_run = 0;
+        v.dec_lost_ns = 0;
+    }
+    const int answered = v.dec_run++;  // queries of this run before this one
+    if (v.dec.p3 && v.dec_km1 == km1) {
+        hand_out();
+        return MEMO_OK;
+    }
+    if (v.dec_never[v.cap - km1] || v.padded < 6) return MEMO_OK;
+    v.dec_lost_ns += rows_in_window(ix, (double)v.padded, window, km1) * kDecidingSparedShare * kSweepNsPerRow;
+    const double groups = (double)(v.padded / 6);
+    if (answered < kDecidingAskAfter || !pass_due(ix, v.dec_lost_ns, v.dec_backoff, kPassDeciding, groups)) return MEMO_OK;
+    DeviceGuard guard(ix->device);
+    BuiltView b;
+    float ms = 0.f;
+    const int rc = build_timed(st, &ms, [&]() {
+        return deciding_view_copy(ix->device, v, ix->nb, ix->bbase, ix->min_s, ix->max_s, km1, st, b);
+    });
+    if (rc && rc != kNoRoom) return rc;
+    v.dec_lost_ns = 0;
+    if (rc == kNoRoom) {  // (the pressure may pass: the run goes on, the threshold is four times as far)
+        v.dec_backoff = backoff_step(v.dec_backoff);
+        return MEMO_OK;
+    }
+    pass_measured(ix, kPassDeciding, ms, groups);
+    if (!b.p3 || b.padded * 5 > v.padded * 4) {  // gave up, or spares less than a fifth: nobody has read it (the pass waited for st)
+        (void)hipFree(b.p3);
+        (void)hipFree(b.boff);
+        v.dec_never[v.cap - km1] = 1;
+        return MEMO_OK;
+    }
+    retire_deciding(ix, v);  // (the class's other k - 1: sweeps queued on other streams may still read it)
+    v.dec = b;
+    v.dec_km1 = km1;
+    v.dec_bytes = dense_view_bytes(b.padded, 6);
+    ++ix->view_deciding_copies;
+    src.build_ms = ms;
+    hand_out();
+    keep_views_in_budget(ix, &v, base_bytes, true);
+    return MEMO_OK;
 }
 
 // The 4-byte rows brought into a query order (memo_interleave.hip: 2 = the conservation order, 3 = the membership order, 0 =
@@ -476,6 +568,7 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, RowS
         src.rpg = rpg;
         src.placed = v.placed;
         src.dead_share = six && v.padded ? 6.0 * (double)v.dead_groups / (double)v.padded : 0.0;
+        if (account && six && v.live && src.build_ms == 0.f) return deciding_rows(ix, v, km1, window, st, base_bytes, src);  // (at most one pass a query)
     }
     return MEMO_OK;
 }

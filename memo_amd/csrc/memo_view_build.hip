@@ -571,6 +571,149 @@ __global__ __launch_bounds__(256) void live_scatter_kernel(const uint4 *__restri
     }
 }
 
+// ======================================================================================================================
+// The DECIDING copy of a live copy (deciding_view_copy): the rows that win a position at ONE k - 1.
+//
+// A slot (start s, overlap ov, order) of a six-row view covers the n = k - 1 - ov cells [s - n, s) (n <= 0: none).  For every cell keep
+// the slot of least (order, slot number) among those that cover it: the minimum over the kept slots is the minimum over all of
+// them, for any window.  (Which slot a cell keeps does not change when every interval is moved alike, so the cells need not be the
+// sweep's own.)  The places a bucket left empty hold a copy of its last row: slots like any other, and when such a copy wins, it is
+// that row which is kept.
+//   1. decide_mark_kernel: a workgroup per run of kDecideW cells [a, a + W), a = run x W.  Its slice, by tile_table_kernel's rule, is
+//      the groups of the buckets a / 32 ... (a + W + k - 2) / 32: at most 32 of them, so a group's bucket -- carried mod 32 -- is known
+//      from the run's first one.  W cells of LDS, all ones; every slot atomicMin-s order << 24 | slot (counted from the slice's first
+//      group: it grows with the global slot number, so the winner is the same whatever the raster) into the cells it covers inside
+//      the run; a cell that differs from its left neighbour's sets its winner's bit in a bitmap of one bit per slot.  A slice of
+//      2^24 slots or more sets flags[0]: the pass gives up.
+//   2. decide_count_kernel: winners per bucket -> groups of six; the scan of dense_view_build; decide_write_kernel: a lane per
+//      bucket packs its winners, in slot order, into groups that carry the bucket and end at its boundary -- the encoding of
+//      view_build_kernel<6>, the places left empty holding a copy of the bucket's last winner, no flag set -- and the copy's table.
+// ======================================================================================================================
+constexpr int kDecideW = 960;  // 30 buckets: with k - 1 <= 31 a run's slice spans at most 32
+
+// slot i of a six-row group as lo | annot << 10  (lo = start mod 32 | overlap << 5; pack_six)
+__device__ __forceinline__ uint32_t six_slot(const uint4 &V, uint32_t i) {
+    switch (i) {
+        case 0: return (V.x & 1023u) | ((V.x >> 24) << 10);
+        case 1: return (V.y & 1023u) | ((V.y >> 24) << 10);
+        case 2: return (V.z & 1023u) | ((V.z >> 24) << 10);
+        case 3: return (V.w & 1023u) | ((V.w >> 24) << 10);
+        case 4: return ((V.x >> 10) & 1023u) | (((V.y >> 10) & 255u) << 10);
+    }
+    return ((V.w >> 10) & 1023u) | (((V.z >> 10) & 255u) << 10);
+}
+
+__device__ __forceinline__ uint4 pack_six_slots(const uint32_t (&r)[6], uint32_t bucket5) {
+    uint32_t lo[6], an[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        lo[i] = r[i] & 1023u;
+        an[i] = (r[i] >> 10) & 255u;
+    }
+    return make_uint4(lo[0] | (lo[4] << 10) | (an[0] << 24), lo[1] | (an[4] << 10) | (an[1] << 24),
+                      lo[2] | (an[5] << 10) | (bucket5 << 18) | (an[2] << 24), lo[3] | (lo[5] << 10) | (an[3] << 24));
+}
+
+// the slice of the run that begins at cell a: the groups [*g0, *g1) of the buckets that hold a start in [a, a + W + km1)
+__device__ __forceinline__ void decide_slice(const int64_t *__restrict__ boff, int64_t nb, int64_t bbase, int64_t a, int km1, uint64_t *g0,
+                                             uint64_t *g1) {
+    const int64_t last = nb - 1;
+    int64_t b0 = (a >> 5) - bbase, b1 = ((a + kDecideW + km1 + 31) >> 5) - bbase;
+    b0 = b0 < 0 ? 0 : (b0 > last ? last : b0);
+    b1 = b1 < 0 ? 0 : (b1 > last ? last : b1);
+    *g0 = (uint64_t)boff[b0] / 6;
+    *g1 = (uint64_t)boff[b1] / 6;
+}
+
+__global__ __launch_bounds__(256) void decide_mark_kernel(const uint4 *__restrict__ groups, const int64_t *__restrict__ boff, int64_t nb,
+                                                          int64_t bbase, int64_t run_lo, int km1, uint32_t *__restrict__ bitmap,
+                                                          uint32_t *__restrict__ flags) {
+    __shared__ uint32_t cell[kDecideW];
+    const int64_t a = (run_lo + (int64_t)blockIdx.x) * kDecideW;
+    uint64_t g0, g1;
+    decide_slice(boff, nb, bbase, a, km1, &g0, &g1);
+    if (g1 <= g0) return;  // (the whole workgroup)
+    if (6 * (g1 - g0) >= 0xFFFFFFull) {
+        if (threadIdx.x == 0) atomicOr(flags, 1u);
+        return;
+    }
+    for (int p = threadIdx.x; p < kDecideW; p += 256) cell[p] = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint32_t fa = (uint32_t)(a >> 5) & 31u;  // the run's first bucket mod 32
+    for (uint64_t g = g0 + threadIdx.x; g < g1; g += 256) {
+        const uint4 V = groups[g];
+        const int base = (int)(((((V.z >> 18) & 31u) - fa) & 31u) * 32u);  // the cell of the group's bucket, from a
+        const uint32_t slot0 = (uint32_t)(6 * (g - g0));
+#pragma unroll
+        for (uint32_t i = 0; i < 6; ++i) {
+            const uint32_t r = six_slot(V, i);
+            const int n = km1 - (int)((r >> 5) & 31u), s = base + (int)(r & 31u);
+            const uint32_t key = ((r >> 10) << 24) | (slot0 + i);
+            const int hi = s < kDecideW ? s : kDecideW;
+            for (int p = s - n < 0 ? 0 : s - n; p < hi; ++p) atomicMin(&cell[p], key);
+        }
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < kDecideW; p += 256) {
+        const uint32_t c = cell[p];
+        if (c == 0xFFFFFFFFu || (p && cell[p - 1] == c)) continue;
+        const uint64_t slot = 6 * g0 + (uint64_t)(c & 0xFFFFFFu);
+        atomicOr(bitmap + (slot >> 5), 1u << (uint32_t)(slot & 31));
+    }
+}
+
+// the winners among the slots [r0, r1): f(slot) for each, in slot order
+template <typename F>
+__device__ __forceinline__ void decide_each_winner(const uint32_t *__restrict__ bitmap, uint64_t r0, uint64_t r1, F f) {
+    if (r1 <= r0) return;
+    const uint64_t w0 = r0 >> 5, w1 = (r1 - 1) >> 5;
+    for (uint64_t w = w0; w <= w1; ++w) {
+        uint32_t m = bitmap[w];
+        if (w == w0) m &= 0xFFFFFFFFu << (uint32_t)(r0 & 31);
+        if (w == w1 && (r1 & 31)) m &= (1u << (uint32_t)(r1 & 31)) - 1u;
+        while (m) {
+            f((w << 5) + (uint64_t)(__ffs((int)m) - 1));
+            m &= m - 1u;
+        }
+    }
+}
+
+__global__ void decide_count_kernel(const int64_t *__restrict__ boff, int64_t nbuckets, const uint32_t *__restrict__ bitmap,
+                                    uint32_t *__restrict__ gcount, unsigned long long *__restrict__ winners) {
+    const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (b >= nbuckets) return;
+    uint32_t c = 0;
+    decide_each_winner(bitmap, (uint64_t)boff[b], (uint64_t)boff[b + 1], [&](uint64_t) { ++c; });
+    gcount[b] = (c + 5u) / 6u;
+    if (c) atomicAdd(winners, (unsigned long long)c);
+}
+
+// glocal / gblock: the scan of gcount (groups of the copy before every bucket); total: all of them; out holds `total` groups
+__global__ void decide_write_kernel(const uint4 *__restrict__ groups, const int64_t *__restrict__ boff, int64_t nbuckets,
+                                    const uint32_t *__restrict__ bitmap, const uint32_t *__restrict__ glocal,
+                                    const uint64_t *__restrict__ gblock, uint64_t total, uint4 *__restrict__ out, int64_t *__restrict__ boffd) {
+    const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (b >= nbuckets) return;
+    uint64_t gout = gblock[b >> 10] + glocal[b];
+    boffd[b] = (int64_t)(6 * gout);
+    if (b == nbuckets - 1) boffd[nbuckets] = (int64_t)(6 * total);
+    uint32_t r[6] = {0, 0, 0, 0, 0, 0}, have = 0, bucket5 = 0;
+    decide_each_winner(bitmap, (uint64_t)boff[b], (uint64_t)boff[b + 1], [&](uint64_t slot) {
+        const uint4 V = groups[slot / 6];
+        bucket5 = (V.z >> 18) & 31u;
+        const uint32_t row = six_slot(V, (uint32_t)(slot % 6));
+#pragma unroll
+        for (uint32_t i = 0; i < 6; ++i)  // (the places behind it: a copy of the last winner so far)
+            if (i >= have) r[i] = row;
+        if (++have == 6) {
+            if (gout < total) out[gout] = pack_six_slots(r, bucket5);
+            ++gout;
+            have = 0;
+        }
+    });
+    if (have && gout < total) out[gout] = pack_six_slots(r, bucket5);
+}
+
 template <int P>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void view_build_kernel(const ViewArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t view_lds[];
@@ -947,6 +1090,54 @@ int live_view_copy(int device, const BuiltView &flagged, uint64_t nb, hipStream_
         return fail(MEMO_EHIP, "live view: %llu live groups, the placing pass counted %llu", (unsigned long long)total, (unsigned long long)nlive);
     // (rows: the flagged view's -- a dead row is answered by a live one that contains it; no group of the copy is flagged)
     out = {reinterpret_cast<uint32_t *>(side.release(outg)), side.release(boff), flagged.rows, 6 * nlive, 0};
+    return MEMO_OK;
+}
+
+// A live copy (`live`: padded / 6 groups, bucket table of nb entries whose first belongs to bucket bbase) down to the slots that
+// decide a minimum at k - 1 = km1 (the kernels above): a new allocation of groups (+ 64 zeroed) and a new bucket table; out.rows: the
+// winners, out.padded: 6 x the groups.  first_start / last_start: the index's least and largest start (the runs that can hold a row).
+// Nothing built (out.p3 stays NULL, MEMO_OK): a slice too long for the 24 slot bits, more runs than a grid holds, no winner at
+// all.  Queued on `st`, waited for twice (the winners decide the allocation).
+int deciding_view_copy(int device, const BuiltView &live, uint64_t nb, int64_t bbase, int64_t first_start, int64_t last_start, int km1,
+                       hipStream_t st, BuiltView &out) {
+    out = BuiltView();
+    const uint64_t ng = live.padded / 6;
+    if (!ng || nb < 2 || km1 < 1 || km1 > 31 || last_start < first_start) return MEMO_OK;
+    auto run_of = [](int64_t x) { return x >= 0 ? x / kDecideW : -((-x + kDecideW - 1) / kDecideW); };
+    const int64_t run_lo = run_of(first_start - 64), nruns = run_of(last_start + 1) - run_lo + 1;
+    if (nruns < 1 || nruns >= ((int64_t)1 << 31) - 1) return MEMO_OK;
+    DeviceGuard guard(device);
+    const uint64_t nbk = nb - 1, nblk6 = (nbk + 1023) >> 10, words = (live.padded >> 5) + 1;
+    Carve tmp_at;
+    const uint64_t o_flags = tmp_at.take(16), o_bits = tmp_at.take(words * 4), o_gcount = tmp_at.take(nbk * 4 + 4),
+                   o_gblock = tmp_at.take((nblk6 + 1) * 8);
+    SideBuffers side("deciding view");
+    char *tmp = nullptr;
+    uint4 *outg = nullptr;
+    int64_t *boffd = nullptr;
+    if (int rc = side.alloc(&tmp, tmp_at.bytes).status()) return rc;
+    uint32_t *flags = reinterpret_cast<uint32_t *>(tmp + o_flags), *bitmap = reinterpret_cast<uint32_t *>(tmp + o_bits);
+    unsigned long long *winners = reinterpret_cast<unsigned long long *>(tmp + o_flags + 8);
+    uint32_t *gcount = reinterpret_cast<uint32_t *>(tmp + o_gcount);
+    uint64_t *gblock = reinterpret_cast<uint64_t *>(tmp + o_gblock);
+    const uint4 *src = reinterpret_cast<const uint4 *>(live.p3);
+    hipError_t err = hipMemsetAsync(tmp, 0, o_gcount, st);  // (the flag, the winners' count, the bitmap)
+    if (err != hipSuccess) return side.failed(err);
+    hipLaunchKernelGGL(decide_mark_kernel, dim3((unsigned)nruns), dim3(256), 0, st, src, live.boff, (int64_t)nb, bbase, run_lo, km1, bitmap, flags);
+    hipLaunchKernelGGL(decide_count_kernel, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, live.boff, (int64_t)nbk, bitmap, gcount, winners);
+    scan_counts(st, gcount, nbk, gblock);
+    uint64_t total6 = 0, nwin = 0, gave_up = 0;
+    err = wait_for(st, {{gblock + nblk6, &total6}, {winners, &nwin}, {flags, &gave_up}});
+    if (err != hipSuccess) return side.failed(err);
+    if ((gave_up & 1) || !total6) return MEMO_OK;
+    if (int rc = side.alloc(&outg, (total6 + 64) * 16).alloc(&boffd, nb * 8).status()) return rc;
+    err = hipMemsetAsync(outg + total6, 0, 64 * 16, st);
+    if (err != hipSuccess) return side.failed(err);
+    hipLaunchKernelGGL(decide_write_kernel, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, st, src, live.boff, (int64_t)nbk, bitmap, gcount,
+                       gblock, total6, outg, boffd);
+    err = wait_for(st, {});
+    if (err != hipSuccess) return side.failed(err);
+    out = {reinterpret_cast<uint32_t *>(side.release(outg)), side.release(boffd), nwin, 6 * total6, 0};
     return MEMO_OK;
 }
 

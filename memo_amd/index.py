@@ -139,7 +139,7 @@ class DeviceIndex:
     def set_option(self, option, value):
         """memo_index_set_option: 1 = MEMO_OPT_VIEWS (0 / 1), 2 = MEMO_OPT_VIEW_BUDGET_PCT, 3 = MEMO_OPT_BUILD_COST_PCT (100: ski rental; 0: the
         first query of a class builds), 4 = MEMO_OPT_VIEW_ROWS (0 / 5 / 6), 5 = MEMO_OPT_VIEW_PLACES (0 / 1), 6 = MEMO_OPT_VIEW_LIVE (0 / 1),
-        7 = MEMO_OPT_WIDE_TILES (0 / 1).  Returns the option's previous value."""
+        7 = MEMO_OPT_WIDE_TILES (0 / 1), 8 = MEMO_OPT_VIEW_DECIDING (0 / 1).  Returns the option's previous value."""
         return check(lib().memo_index_set_option(self._h, int(option), int(value)))     # the option's previous value
 
     # ---- asynchronous launches on device buffers (torch tensors or raw addresses) ----
@@ -176,6 +176,23 @@ class DeviceIndex:
         out = (C.c_int32 * 6)()
         check(lib().memo_debug_last_membership(self._h, out))
         return dict(zip(("algorithm", "tile_width", "threads", "mw", "sk", "slice"), (int(v) for v in out)))
+
+    def export_deciding(self, k):
+        """memo_debug_export_deciding: (groups uint32[4 g], table int64[buckets], rows) of the deciding copy the class of k keeps for
+        exactly this k -- six-row groups that carry their bucket -- or None when there is none (A/B library)"""
+        rows, ng = C.c_uint64(0), C.c_uint64(0)
+        check(lib().memo_debug_export_deciding(self._h, int(k), None, None, C.byref(rows), C.byref(ng)))
+        if not ng.value:
+            return None
+        groups = np.empty(4 * ng.value, np.uint32)
+        table = np.empty(self.info()["buckets"], np.int64)
+        check(lib().memo_debug_export_deciding(self._h, int(k), groups.ctypes.data, table.ctypes.data, C.byref(rows), C.byref(ng)))
+        return groups, table, rows.value
+
+    def debug_view_deciding(self, k):
+        """memo_debug_view_deciding: (whether the class of k holds a deciding copy for exactly this k, deciding copies made so far)"""
+        made = C.c_uint64(0)
+        return bool(check(lib().memo_debug_view_deciding(self._h, int(k), C.byref(made)))), int(made.value)
 
     def debug_last_tiles_per_group(self):
         """memo_debug_last_tiles_per_group: 2 where the wide tiles' pair kernel answered the last conservation sweep, else 1"""
