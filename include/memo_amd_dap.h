@@ -338,6 +338,37 @@ int memo_nearest_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t 
  * want lengths around it */
 int32_t memo_nearest_tile(int32_t planes);
 
+/* ---- `memo mosaic`: the pivot as the fewest pieces copied whole from one genome each (no counterpart in the reference) -------------
+ * (Declared here, beside the `memo nearest` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The greedy parse by longest match (memo_amd/csrc/memo_mosaic.hip), in two calls.  The FOLD takes one slice of finished lengths as
+ * memo_nearest_dev takes it -- d_cells uint32 [planes][pitch], 16-byte aligned, pitch a multiple of 4, L cells a plane read and
+ * nothing else; v[g][p] = min(cell, cap); cand_host a HOST pointer to 64 words, bit g = genome g is a candidate, or NULL for
+ * 1 .. planes - 1; plane 0 and the planes outside the set are never read -- and WRITES, with best, ok and the winner as there (ties to
+ * the lowest annot),
+ *     d_step[i]   = ok[i] ? best[i] : 1        uint32 [L]: a position no candidate reaches at min_len is a literal of one base
+ *     d_winner[i] = the winner, 0 where not ok[i]                                                          uint16 [L]
+ * on `device`; they are a slice's part of the whole window's vectors and may sit at any element offset (4- and 2-byte aligned).
+ * MEMO_EINVAL before anything is launched, the outputs as they were: what memo_nearest_dev refuses of d_cells, pitch, L, planes, cap,
+ * min_len and the candidate words; L above 2^31 - 1; d_step or d_winner NULL or misaligned.  L == 0 launches nothing.  Scratch: the
+ * candidate list, at most 8 KiB.  Blocking. */
+int memo_mosaic_fold_dev(const uint32_t *d_cells, int64_t L, int64_t pitch, int32_t planes, uint32_t cap, uint32_t min_len,
+                         const uint32_t *cand_host, uint32_t *d_step, uint16_t *d_winner, int32_t device, void *stream);
+/* The PARSE of a whole window: d_step uint32 [L] and d_winner uint16 [L] on `device`, both 16-byte aligned.  p_0 = 0, p_{i+1} = p_i +
+ * max(d_step[p_i], 1) while p_i < L are the reached positions (a step of 0 counts as 1, a step above 2^31 - 1 as 2^31 - 1); a reached
+ * p starts a line iff d_winner[p] != 0, or p == 0, or not (p - 1 is reached and d_winner[p - 1] == 0): consecutive phrases of no
+ * genome are one line (the fold gives a position of no genome a step of 1; a caller's own vectors should), adjacent phrases of one
+ * genome stay two.  *d_starts (int64 [*lines], ascending, the first one 0) and
+ * *d_genomes (uint16 [*lines], the winner at each start) are allocated on `device` for exactly *lines entries and are the caller's,
+ * to be freed with memo_dev_free; line r ends where line r + 1 starts, the last one at L.  MEMO_EINVAL before anything is launched,
+ * the outputs as they were: NULL out-pointers, L < 0 or above 2^31 - 1, d_step or d_winner NULL or not 16-byte aligned.  L == 0
+ * launches nothing and returns zero lines and NULL arrays.  Scratch memory on the device: 4 L bytes, one bit a position rounded up to
+ * whole tiles, 4 bytes a tile and the compaction's counts, freed before the call returns; an allocation that fails returns MEMO_EHIP
+ * with the bytes asked for in memo_last_error and leaves nothing allocated.  Blocking. */
+int memo_mosaic_parse_dev(const uint32_t *d_step, const uint16_t *d_winner, int64_t L, int64_t **d_starts, uint16_t **d_genomes,
+                          uint64_t *lines, int32_t device, void *stream);
+/* positions per tile of the parse (32768), for tests that want lengths around it */
+int32_t memo_mosaic_tile(void);
+
 /* ---- `memo features`: per-feature presence and conservation from a BED file (no counterpart in the reference) -----------
  * (Declared here, beside the `memo tracks` block: memo_amd.h keeps to the query path's 44 entry points.)
  * Features overlap and nest; the elementary segments between their endpoints do not.  A table is counted per segment -- with a

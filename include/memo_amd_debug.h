@@ -140,6 +140,14 @@ int memo_debug_nearest_times(int32_t on, float *out1);
  * library's 72 (two workgroups per CU).  It decides the positions per tile and how many workgroups share a CU (the A/B of
  * DESIGN.md 10.17); 2048 planes take their 113 KiB whatever is set.  The results are the same. */
 int memo_debug_nearest_lds(int32_t kib);
+/* this THREAD's later memo_mosaic_fold_dev and memo_mosaic_parse_dev calls put event pairs around their launches (on = 1; each is then
+ * waited for) or do not (0); out5 (may be NULL) receives the device milliseconds of the last timed launches: [0] the fold, [1] the
+ * exits, [2] the walk, [3] the mark, [4] the lines (count, scan and scatter together).  tools/mosaic_timing.py reads them. */
+int memo_debug_mosaic_times(int32_t on, float *out5);
+/* this THREAD's later memo_mosaic_parse_dev and memo_mosaic_tile calls: the positions a tile (4096, 8192, 16384 or 32768; 0 = the
+ * library's 32768) and the mark (1 = one lane walks the staged steps, 2 = the mark rides the pointer doubling; 0 = the library's 2) --
+ * the A/B of DESIGN.md 10.18.  The lines are the same. */
+int memo_debug_mosaic_shape(int32_t tile, int32_t mark);
 /* this THREAD's later memo_segment_conservation_dev and memo_feature_sums_dev calls put event pairs around their launches (on = 1;
  * each is then waited for) or do not (0); out3 (may be NULL) receives the device milliseconds of the last timed launches: [0] the
  * segment kernel, [1] the three scan launches, [2] the gather (the uploads are not in them).  tools/features_timing.py reads them. */

@@ -39,6 +39,8 @@ Layout (only what the path needs):
   pairs_cli.py     `memo pairs`: flags, usage, sums, weighted Jaccard distances or mean lengths as tab-separated text
   nearest.py       `memo nearest`: which genome matches the pivot longest, per genome and bin or as runs of the winner, reduced across the planes on the GPU
   nearest_cli.py   `memo nearest`: flags, usage, wins, sole wins or their shares as tab-separated text, or one interval per run of the winner
+  mosaic.py        `memo mosaic`: the pivot as the fewest pieces copied whole from one genome each, the greedy parse by longest match, on the GPU
+  mosaic_cli.py    `memo mosaic`: flags, usage, one interval per piece or the pieces' bases per genome and bin as tab-separated text
   spectrum.py      `memo spectrum`: a window's conservation histogram at every k from either kind of index, reduced on the GPU, in slices
   spectrum_cli.py  `memo spectrum`: flags, usage, the table as tab-separated text
   convert.py       `memo convert`: a membership index's lengths fed to the row builder: the conservation index, or the canonical membership index
@@ -69,6 +71,7 @@ _LAZY = {
     "region_breaks": "breaks", "bed_breaks": "breaks", "plane_breaks": "breaks",
     "region_pairs": "pairs", "plane_sums": "pairs",
     "region_nearest": "nearest", "region_winners": "nearest", "plane_nearest": "nearest",
+    "region_mosaic": "mosaic", "plane_mosaic": "mosaic", "bin_phrases": "mosaic",
     "region_exact": "spectrum",
     "convert_index": "convert",
     "add_index": "add",
@@ -82,7 +85,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "pairs", "pairs_cli", "nearest", "nearest_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "pairs", "pairs_cli", "nearest", "nearest_cli", "mosaic", "mosaic_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

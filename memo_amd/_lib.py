@@ -134,6 +134,9 @@ SYMBOLS = {
     "memo_pairs_narrow_span": (C.c_uint32, []),
     "memo_nearest_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, C.c_uint32, _P, _I64, _P, _I32, _P, _P, _P, _I32, _P]),
     "memo_nearest_tile": (_I32, [_I32]),
+    "memo_mosaic_fold_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, C.c_uint32, _P, _P, _P, _I32, _P]),
+    "memo_mosaic_parse_dev": (C.c_int, [_P, _P, _I64, C.POINTER(_P), C.POINTER(_P), C.POINTER(_U64), _I32, _P]),
+    "memo_mosaic_tile": (_I32, []),
     "memo_segment_conservation_dev": (C.c_int, [_P, _I64, _I64, _P, _I32, _I32, _P, _I32, _P]),
     "memo_segment_conservation_tile": (_I32, []),
     "memo_feature_sums_dev": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _I32, _P]),
@@ -240,6 +243,8 @@ DEBUG_SYMBOLS = {
     "memo_debug_pairs_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_nearest_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_nearest_lds": (C.c_int, [_I32]),
+    "memo_debug_mosaic_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
+    "memo_debug_mosaic_shape": (C.c_int, [_I32, _I32]),
     "memo_debug_features_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_maxk_rows": (C.c_int, [_I32]),
     "memo_debug_maxk_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),

@@ -57,6 +57,11 @@ extern thread_local int g_nearest_timed;  // memo_nearest.hip (AB library, memo_
 extern thread_local float g_nearest_ms;
 extern thread_local int g_nearest_lds_kib;  // ... memo_debug_nearest_lds: the LDS a workgroup may take, which decides the tile
 constexpr int kNearestLdsKib = 72;          // ... the product's: two workgroups a CU
+extern thread_local int g_mosaic_timed;  // memo_mosaic.hip (AB library, memo_debug_mosaic_times: event pairs around the launches of its two calls)
+extern thread_local float g_mosaic_ms[5];
+extern thread_local int g_mosaic_tile, g_mosaic_mark;  // ... memo_debug_mosaic_shape: the positions a tile of the parse, and which mark it takes
+constexpr int kMosaicTile = 32768;                     // ... the product's
+constexpr int kMosaicMark = 2;                         // ... 1 the serial lane, 2 the doubling mark
 extern thread_local int g_features_timed;  // memo_features.hip (AB library, memo_debug_features_times: event pairs around the launches of its two calls)
 extern thread_local float g_features_ms[3];
 extern thread_local int g_lengths_timed;  // memo_lengths.hip (AB library, memo_debug_lengths_times: event pairs around the launches of the memo_lengths_*_dev calls)

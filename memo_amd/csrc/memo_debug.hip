@@ -230,6 +230,22 @@ int memo_debug_nearest_lds(int32_t kib) {
     return MEMO_OK;
 }
 
+int memo_debug_mosaic_times(int32_t on, float *out5) {
+    g_mosaic_timed = on ? 1 : 0;
+    if (out5)
+        for (int i = 0; i < 5; ++i) out5[i] = g_mosaic_ms[i];
+    return MEMO_OK;
+}
+
+int memo_debug_mosaic_shape(int32_t tile, int32_t mark) {
+    if (tile != 0 && tile != 4096 && tile != 8192 && tile != 16384 && tile != 32768)
+        return fail(MEMO_EINVAL, "positions a tile of memo_mosaic_parse_dev: 0 (the library's %d), 4096, 8192, 16384 or 32768", kMosaicTile);
+    if (mark < 0 || mark > 2) return fail(MEMO_EINVAL, "the mark of memo_mosaic_parse_dev: 0 (the library's %d), 1 (the serial lane) or 2 (doubling)", kMosaicMark);
+    g_mosaic_tile = tile ? tile : kMosaicTile;
+    g_mosaic_mark = mark ? mark : kMosaicMark;
+    return MEMO_OK;
+}
+
 int memo_debug_features_times(int32_t on, float *out3) {
     g_features_timed = on ? 1 : 0;
     if (out3) out3[0] = g_features_ms[0], out3[1] = g_features_ms[1], out3[2] = g_features_ms[2];

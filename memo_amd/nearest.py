@@ -19,8 +19,8 @@ Rows of genomes outside C are zero.  With min_len == cap == K row g of wins[0] i
 position sums is `memo lengths -t 2` where the pivot has no rows and C is everything; wins[1] <= wins[0].  memo_nearest_dev
 (memo_amd/csrc/memo_nearest.hip) reads every candidate plane once, where it lies, slice by slice; 2 x N x B + B integers leave the
 device, or the winner vector's runs (memo_runs_conservation_dev's value mode run-codes the uint16 [L] vector on the device).  The
-flags are memo_amd/nearest_cli.py.  One device; not built: several GPUs, a BED of features, a plot, the greedy minimal mosaic (the
-relative Lempel-Ziv parse), tie-breaking other than the lowest annot, a conservation index.
+flags are memo_amd/nearest_cli.py.  One device; not built: several GPUs, a BED of features, a plot, tie-breaking other than the lowest
+annot, a conservation index.  (The greedy minimal mosaic, the relative Lempel-Ziv parse, is `memo mosaic`: memo_amd/mosaic.py.)
 """
 import ctypes as C
 
