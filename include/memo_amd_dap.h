@@ -239,6 +239,45 @@ int memo_collect_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, const 
 /* positions per tile at `words` genome words (512 up to 16 words, 256 up to 32, 128 above), for tests that want lengths around it */
 int32_t memo_collect_tile(int32_t words);
 
+/* ---- `memo panel`: the genomes that cover the pivot, chosen greedily (no counterpart in the reference) --------------------
+ * (Declared here, beside the `memo collect` block: memo_amd.h keeps to the query path's 44 entry points.)
+ * The greedy set cover of a window's membership bits, one step at a time (memo_amd/csrc/memo_panel.hip).  The window's rows stay on
+ * `device` as genome-major bit planes: plane g is pitch_words uint32 at d_planes + g * pitch_words, and bit p & 31 of its word
+ * p >> 5 is the bit of genome g at window position p.  d_planes is 16-byte aligned and pitch_words a multiple of 4 everywhere below;
+ * the two masks d_core and d_covered are uint32 [words] on `device`, 16-byte aligned, laid out as one plane; `words` is a multiple of
+ * 4, at most pitch_words: the window's ceil(L / 32) words and the pad words up to the next multiple of 4, which hold zeros and are
+ * read.  Nothing at or past pitch_words of a plane is ever read.  All four calls are stateless and blocking; each refuses with
+ * MEMO_EINVAL before anything is launched -- a pointer that is NULL or not 16-byte aligned, a pitch_words that is no positive multiple
+ * of 4, words or a word range that leaves the pitch, a genome id at or above num_docs, num_docs outside [1, 2048] -- and then leaves
+ * planes, masks and outputs as they were.
+ *
+ * memo_panel_planes_dev: one slice's rows d_bits (uint32 [L][W] as memo_cooccurrence_dev takes it: 16-byte aligned, read from [0] to
+ * [L * W) and nowhere else, bits at or above num_docs masked) become the words [word0, word0 + ceil(L / 32)) of the planes
+ * [0, num_docs); the bits at or past L of the last word are written as zeros; no other word of any plane is written.  L == 0
+ * launches nothing. */
+int memo_panel_planes_dev(const uint32_t *d_bits, int64_t L, int32_t num_docs, uint32_t *d_planes, int64_t pitch_words, int64_t word0, int32_t device,
+                          void *stream);
+/* what no slice writes, for a window of L positions: the pad words [ceil(L / 32), the next multiple of 4) of every plane as zeros,
+ * d_core as ones below L (zeros in the last word's tail and in the pad words), d_covered as zeros.  L == 0 launches nothing. */
+int memo_panel_begin_dev(uint32_t *d_planes, int64_t pitch_words, int32_t num_docs, int64_t L, uint32_t *d_core, uint32_t *d_covered, int32_t device,
+                         void *stream);
+/* list_host is a HOST pointer, uint16 [n_list], genome ids below num_docs, repeats legal, n_list in [0, 65535]; scores_host is a HOST
+ * pointer, uint64 [n_list][2], WRITTEN (not added to):
+ *     scores[i][0] = new  = #{bits of plane list[i] & ~covered}        scores[i][1] = kept = #{bits of plane list[i] & core}
+ * over the words [0, words).  The library uploads the list and downloads the scores itself.  Scratch memory on the device: the list,
+ * the scores and at most 64 MiB of partial sums, freed before the call returns; an allocation that fails returns MEMO_EHIP with the
+ * bytes asked for in memo_last_error and leaves nothing allocated.  n_list == 0 launches nothing. */
+int memo_panel_score_dev(const uint32_t *d_planes, int64_t pitch_words, int32_t num_docs, int64_t words, const uint32_t *d_core, const uint32_t *d_covered,
+                         const uint16_t *list_host, int32_t n_list, uint64_t *scores_host, int32_t device, void *stream);
+/* d_core &= plane `genome`, d_covered |= plane `genome`, in place over the words [0, words); counts_host is a HOST pointer, uint64 [2],
+ * written: the bits of the new core, the bits of the new covered.  Scratch as memo_panel_score_dev's. */
+int memo_panel_take_dev(const uint32_t *d_planes, int64_t pitch_words, int32_t num_docs, int64_t words, int32_t genome, uint32_t *d_core, uint32_t *d_covered,
+                        uint64_t *counts_host, int32_t device, void *stream);
+/* positions per tile of memo_panel_planes_dev (1024), and the mask words a workgroup of score and take reads per pass (1024), for
+ * tests that want lengths around them */
+int32_t memo_panel_tile(void);
+int32_t memo_panel_pass_words(void);
+
 /* ---- `memo tracks`: per-genome k-mer presence along the pivot, binned (no counterpart in the reference) -----------------
  * (Declared here, beside the `memo collect` block: memo_amd.h keeps to the query path's 44 entry points.)
  * The presence counts of a membership result that is still on `device` (memo_amd/csrc/memo_tracks.hip): d_bits as

@@ -271,6 +271,13 @@ int memo_debug_collect_times(int32_t on, float *out2) {
     return MEMO_OK;
 }
 
+int memo_debug_panel_times(int32_t on, float *out4) {
+    g_panel_timed = on ? 1 : 0;
+    if (out4)
+        for (int i = 0; i < 4; ++i) out4[i] = g_panel_ms[i];
+    return MEMO_OK;
+}
+
 int memo_debug_lengths_times(int32_t on, float *out7) {
     g_lengths_timed = on ? 1 : 0;
     if (out7)
