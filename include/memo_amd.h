@@ -100,7 +100,8 @@ typedef struct memo_index_info {
                                2 / 3 / 4 per query from k and the overlap lengths of the rows it sampled when the
                                packed rows were made; membership: 6 bit planes on the dense rows, 7 any other */
     int32_t last_variant;   /* of the dense-row sweep: 0 every wave worked its tile out, 2 the tile's rows from the index's tile table, 3 the same
-                               on a k-class view of SIX rows per group (last_view_rows_per_group) */
+                               on a k-class view of SIX rows per group (last_view_rows_per_group), 4 no sweep: the window was decoded
+                               from the run copy of this k (MEMO_OPT_VIEW_RUNS; last_rows_read: the copy's runs) */
     uint64_t dense_row_count; /* rows the dense rows hold (0: none resident): fewer than `rows` when the rows that can never
                                write at k <= 64 (overlap >= 63, or end < start) were left out of them -- they are when more
                                than a tenth of the rows are such rows (none of the synthetic index, 40 % of one built from
@@ -129,7 +130,8 @@ typedef struct memo_index_info {
     int32_t last_view_rows_per_group; /* rows per 16-byte group of the dense rows the last sweep read: 5, or 6 (a view whose groups carry
                                their bucket: 2.67 B per row; last_rows_read then counts the places a bucket leaves empty too) */
     int32_t last_tile_width;  /* positions per tile of the last table-driven sweep (last_variant 2 / 3; 0 otherwise): 1568 at k = 31 on
-                               the radix-4 arrays of a six-row view (MEMO_OPT_WIDE_TILES), 928 on the doubling arrays */
+                               the radix-4 arrays of a six-row view (MEMO_OPT_WIDE_TILES), 928 on the doubling arrays; last_variant 4: the
+                               positions a workgroup decodes */
 } memo_index_info_t;
 
 const char *memo_last_error(void);
@@ -230,7 +232,21 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info);  /*
  *                             those queries have lost to the rows that decide nothing what the pass costs (MEMO_OPT_BUILD_COST_PCT
  *                             applies).  Kept beside the live copy, which goes on answering the class's other k; one such copy per
  *                             class.  Never by memo_index_prepare; 0: never (a copy already made is kept and not read: the A/B).
- *                             memo_index_export_view keeps handing out the class's own view (the live copy). */
+ *                             memo_index_export_view keeps handing out the class's own view (the live copy).
+ *   MEMO_OPT_VIEW_RUNS        1 (default): the deciding copy of a k (MEMO_OPT_VIEW_DECIDING) is resolved once more, into the RUN copy of that k:
+ *                             the results themselves -- per bucket of 32 positions a mask of where a run of equal results starts and
+ *                             the offset of its first value, per run one byte; a third to a half of a byte per position.  A conservation
+ *                             query at that k then decodes its window from the copy instead of sweeping rows
+ *                             (memo_index_info_t.last_variant 4; last_rows_read: the runs of the whole copy).  Made by a conservation
+ *                             query once the deciding copy has answered 32 queries in a row at that k, whatever
+ *                             MEMO_OPT_BUILD_COST_PCT says, and the queries of the run have lost to sweeping what the pass costs
+ *                             (MEMO_OPT_BUILD_COST_PCT applies).  The count starts again with a query of the class at its other k, and
+ *                             with a memo_index_set_option call that changes which rows or which kernel answer (every option but
+ *                             MEMO_OPT_VIEW_BUDGET_PCT and MEMO_OPT_BUILD_COST_PCT): such a host has not settled.  Only on an index
+ *                             whose orders stay below 255, and only where the deciding copy answers: num_docs <= 255 (uint8 or uint16
+ *                             results) and a window that does not begin below 0 -- any other query is swept as before.  Kept beside
+ *                             the deciding copy and dropped with it; one per class.  Never by memo_index_prepare; 0: never (a copy
+ *                             already made is kept and not read: the A/B). */
 #define MEMO_OPT_VIEWS 1
 #define MEMO_OPT_VIEW_BUDGET_PCT 2
 #define MEMO_OPT_BUILD_COST_PCT 3
@@ -239,6 +255,7 @@ int memo_index_get_info_v5(const memo_index_t *ix, memo_index_info_t *info);  /*
 #define MEMO_OPT_VIEW_LIVE 6
 #define MEMO_OPT_WIDE_TILES 7
 #define MEMO_OPT_VIEW_DECIDING 8
+#define MEMO_OPT_VIEW_RUNS 9
 /* Returns the option's PREVIOUS value (>= 0) -- what a caller that changes an option for one pass puts back -- or a negative code. */
 int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value);
 /* Build NOW what queries of one kind would otherwise build on the way: the k-class view of the rows such a query reads (else

@@ -68,6 +68,15 @@ int memo_debug_view_deciding(const memo_index_t *ix, int32_t k, uint64_t *made);
  * live copy it was made of: *rows: the rows that decide a minimum (0: no such copy is resident for this k), *group_count: its groups,
  * boff: info.buckets entries in units of padded row numbers.  groups == boff == NULL: the sizes only. */
 int memo_debug_export_deciding(memo_index_t *ix, int32_t k, void *groups, int64_t *boff, uint64_t *rows, uint64_t *group_count);
+/* run copies this index has made so far (MEMO_OPT_VIEW_RUNS; memo_view_build.hip: run_view_copy), and whether the class of k holds one
+ * for exactly this k: 1, or 0 */
+int memo_debug_view_runs(const memo_index_t *ix, int32_t k, uint64_t *made);
+/* ... and that copy to host memory: *buckets entries of masks (bit i: position i of the bucket starts a run; bit 0 always) and of offsets
+ * (the byte of the bucket's first value; every eighth is a multiple of four), *value_bytes bytes of values (a byte a run, 255: no row; the
+ * bytes between one group of eight buckets' last value and the next group's first are 0), *runs of them runs; *first_bucket: the pivot
+ * bucket of entry 0.  masks == offsets == values == NULL: the sizes only (all 0: no such copy is resident for this k). */
+int memo_debug_export_runs(memo_index_t *ix, int32_t k, uint32_t *masks, uint32_t *offsets, uint8_t *values, uint64_t *buckets,
+                           uint64_t *value_bytes, uint64_t *runs, int64_t *first_bucket);
 /* this THREAD's later calls: every device allocation for a view or a tile table fails (the test of the no-memory path) */
 int memo_debug_fail_side_allocations(int32_t on);
 /* this thread's later memo_index_pack_dense / dense builders keep the rows that can never write at k <= 64 in the dense rows */

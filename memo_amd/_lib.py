@@ -233,6 +233,8 @@ DEBUG_SYMBOLS = {
     "memo_debug_view_live": (C.c_int, [_P, _I32, C.POINTER(_U64)]),
     "memo_debug_view_deciding": (C.c_int, [_P, _I32, C.POINTER(_U64)]),
     "memo_debug_export_deciding": (C.c_int, [_P, _I32, _P, _P, _P, _P]),
+    "memo_debug_view_runs": (C.c_int, [_P, _I32, C.POINTER(_U64)]),
+    "memo_debug_export_runs": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "memo_debug_fail_side_allocations": (C.c_int, [_I32]),
     "memo_debug_dense_keep_all": (C.c_int, [_I32]),
     "memo_debug_one_shot_way": (C.c_int, [_I32]),

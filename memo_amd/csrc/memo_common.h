@@ -123,8 +123,9 @@ constexpr int kStatusExecNarrow = 4;          // -DMEMO_EXEC_CHECK builds: a bra
 
 // The one-time passes over an index's rows that one rule decides (memo_view.hip: pass_due): a k-class view of the dense rows, of the
 // 4-byte words, a dense view with the places of its rows chosen, the copy of a placed six-row view without its dead groups, the
-// query order of the 4-byte rows, the copy of a live copy that holds only the rows that decide a minimum at one k - 1
-enum Pass { kPassDenseView, kPassPackedView, kPassPlaces, kPassLiveCopy, kPassRowOrder, kPassDeciding, kPasses };
+// query order of the 4-byte rows, the copy of a live copy that holds only the rows that decide a minimum at one k - 1, the run copy
+// of a deciding copy (the results of that k - 1 themselves, run-coded; per position of its buckets)
+enum Pass { kPassDenseView, kPassPackedView, kPassPlaces, kPassLiveCopy, kPassRowOrder, kPassDeciding, kPassRuns, kPasses };
 
 // What a view pass (memo_view_build.hip) hands back, and the part of a DenseView it fills: the view's rows (dense groups, or 4-byte
 // words), its bucket table (nb entries), the rows of the source it holds, the rows its table counts (slots of six-row groups; five-row
@@ -275,6 +276,19 @@ struct memo_index {
         double dec_lost_ns = 0;    // what the queries of the run have lost to the rows that decide nothing (estimate)
         int dec_backoff = 1;       // x 4 after a pass that found no room
         uint64_t dec_bytes = 0;    // of dec's groups
+        // The RUN copy of a deciding copy (memo_view_build.hip: run_view_copy), kept beside it under the same k - 1 (dec_km1): the minimum
+        // itself, resolved once -- per bucket of 32 positions a mask of where a run of equal results starts and the offset of the bucket's
+        // first value, and a byte per run (255: no row covers it).  run.p3: the values, run.boff: mask | offset << 32 per bucket, run.rows:
+        // the runs, run.padded: the buckets (whole groups of 8), the first of which is bucket run_b0 of the pivot.  A fifth pass, decided in
+        // memo_view.hip (run_rows): the deciding copy must have answered kRunsAskAfter queries in a row (run_answered) and the ledger
+        // run_lost_ns must be due.  It goes wherever the deciding copy goes.
+        memo::BuiltView run;
+        int64_t run_b0 = 0;
+        int run_answered = 0;      // conservation queries in a row the deciding copy of dec_run_km1 has answered
+        double run_lost_ns = 0;    // what those queries have lost to sweeping where a decode would do (estimate)
+        int run_backoff = 1;       // x 4 after a pass that found no room
+        int run_never[2] = {0, 0}; // [cap - km1]: no run copy at this k - 1 (it could not be made)
+        uint64_t run_bytes = 0;    // of run's values and table
         uint64_t bytes = 0;      // of the rows' allocation (set where a view is installed: a six-row view is (groups + 64) x 16 B, not
                                  //   what its padded row count makes of five-row groups -- ADVICE r05: the budget charged it a fifth too much)
         float build_ms = 0.f;
@@ -290,6 +304,8 @@ struct memo_index {
     int wide_tiles = 1;           // memo_index_set_option(MEMO_OPT_WIDE_TILES): 0 six-row views keep the doubling tiles where R4 would apply (A/B)
     int view_deciding = 1;        // memo_index_set_option(MEMO_OPT_VIEW_DECIDING): 0 a live copy is never copied down to the rows that decide a minimum at the query's k
     uint64_t view_deciding_copies = 0;  // deciding copies made (memo_debug_view_deciding of the AB library)
+    int view_runs = 1;            // memo_index_set_option(MEMO_OPT_VIEW_RUNS): 0 a deciding copy is never resolved into the run copy of its k (one already made stays, unread)
+    uint64_t view_run_copies = 0; // run copies made (memo_debug_view_runs of the AB library)
     uint64_t view_live_copies = 0;  // placed six-row views copied without their dead groups (memo_debug_view_live_copies of the AB library)
     double pass_ns[memo::kPasses] = {};  // per row of its source, as the index's last pass of each kind measured it (memo::Pass; the copy without
                                          //   dead groups: per group of the flagged view; 0: the calibrated constant, memo_view.hip: kPassNs)
@@ -336,7 +352,7 @@ struct memo_index {
     uint64_t retired_bytes = 0;
     int last_sweep = 0;          // level arrays of the last conservation sweep (memo_index_info_t.last_sweep)
     int last_arrays = 0;         // mixed level arrays (last_sweep 4): how many of them the sweep's level plan allocated
-    int last_variant = 0;        // ... 2 table-driven on five-row groups (memo_sweep_cons3t.hip), 3 on a view of six rows per group; 0 no table
+    int last_variant = 0;        // ... 2 table-driven on five-row groups (memo_sweep_cons3t.hip), 3 on a view of six rows per group, 4 decoded from a run copy (memo_sweep_runs.hip); 0 no table
     int last_tiles_per_group = 1;  // tiles a workgroup of the last table-driven sweep did (2: the wide tiles' pair kernel; memo_debug_last_tiles_per_group)
     // what the plan step and the pickers of the last conservation sweep decided (memo_debug_last_pick of the AB library): the template
     // arguments of the kernel launched, as the picker's lambdas saw them.  All int32, in the order memo_amd_debug.h lists; host side
@@ -352,7 +368,7 @@ struct memo_index {
         int32_t out_bytes = 0;  // sizeof(OutT)
         int32_t nlev = 0, aw = 0, sp = 0, six = 0, live = 0, r4 = 0, chain = 0, pairs = 0, a9 = 0;  // the table-driven sweep's (launch_halo3t)
         int32_t halo3 = 0;      // 1: sweep_conservation_halo3_kernel (no table) answered
-        int32_t kernel = 0;     // table-driven: 1 halo3t, 2 wide_args, 3 wide, 4 wide_pair; else 0
+        int32_t kernel = 0;     // table-driven: 1 halo3t, 2 wide_args, 3 wide, 4 wide_pair; 5 the run copy's decode; else 0
     } last_pick;
     int last_tile_w = 0;         // ... and its tile width (info.last_tile_width: 1568 at k = 31 on the radix-4 arrays, 928 on the doubling ones)
     // the plan of the last membership sweep (memo_debug_last_membership of the AB library): the algorithm (2 doubling, 3 runs, 4 planes on the

@@ -118,6 +118,40 @@ int memo_debug_export_deciding(memo_index_t *ix, int32_t k, void *groups, int64_
     return download_pipelined(ix->device, boff, v.dec.boff, ix->nb * 8, nullptr);
 }
 
+int memo_debug_view_runs(const memo_index_t *ix, int32_t k, uint64_t *made) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    if (made) *made = ix->view_run_copies;
+    if (k < 2 || k > 32) return 0;  // (no class)
+    const memo_index::DenseView &v = ix->views6[k / 2 - 1];
+    return v.p3 && v.live && v.dec.p3 && v.dec_km1 == k - 1 && v.run.p3 ? 1 : 0;
+}
+
+int memo_debug_export_runs(memo_index_t *ix, int32_t k, uint32_t *masks, uint32_t *offsets, uint8_t *values, uint64_t *buckets,
+                           uint64_t *value_bytes, uint64_t *runs, int64_t *first_bucket) {
+    if (!ix) return fail(MEMO_EINVAL, "index is NULL");
+    for (uint64_t *p : {buckets, value_bytes, runs})
+        if (p) *p = 0;
+    if (first_bucket) *first_bucket = 0;
+    const int km1 = k - 1;
+    if (km1 < 1 || km1 > 31) return MEMO_OK;  // (no class of six-row views: nothing to export)
+    const memo_index::DenseView &v = ix->views6[k / 2 - 1];
+    if (v.state != 1 || !v.live || !v.dec.p3 || v.dec_km1 != km1 || !v.run.p3) return MEMO_OK;
+    const uint64_t nbk = v.run.padded, vbytes = v.run_bytes - run_view_bytes(nbk, 0);
+    if (buckets) *buckets = nbk;
+    if (value_bytes) *value_bytes = vbytes;
+    if (runs) *runs = v.run.rows;
+    if (first_bucket) *first_bucket = v.run_b0;
+    if (!masks && !offsets && !values) return MEMO_OK;
+    if (!masks || !offsets || !values) return fail(MEMO_EINVAL, "masks, offsets and values: all or none");
+    std::vector<uint64_t> tab(nbk);
+    if (int rc = download_pipelined(ix->device, tab.data(), v.run.boff, (size_t)nbk * 8, nullptr)) return rc;
+    for (uint64_t b = 0; b < nbk; ++b) {
+        masks[b] = (uint32_t)tab[b];
+        offsets[b] = (uint32_t)(tab[b] >> 32);
+    }
+    return download_pipelined(ix->device, values, v.run.p3, (size_t)vbytes, nullptr);
+}
+
 int memo_debug_fail_side_allocations(int32_t on) {
     g_side_alloc_fails = on != 0;
     return MEMO_OK;

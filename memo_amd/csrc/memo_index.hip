@@ -742,6 +742,7 @@ static void fill_info(const memo_index *ix, memo_index_info_t *info) {
         each_view(ix, dense, [&](const memo_index::DenseView &v) {
             side += v.p3 ? v.bytes + ix->nb * 8 : 0;
             side += v.dec.p3 ? v.dec_bytes + ix->nb * 8 : 0;  // (the deciding copy beside a live copy: side bytes, not a view of its own)
+            side += v.run_bytes;                              // (... and the run copy beside that)
             info->views_resident += v.p3 ? 1 : 0;
         });
     for (const memo_index::TileTable &t : ix->ttabs) side += (uint64_t)t.n * 32;
@@ -798,6 +799,7 @@ static const struct {
     {MEMO_OPT_VIEW_LIVE, &memo_index::view_live, 0, 1, 1, "MEMO_OPT_VIEW_LIVE takes 0 or 1"},  // (a copy already made stays: it answers exactly what the flagged view does)
     {MEMO_OPT_WIDE_TILES, &memo_index::wide_tiles, 0, 1, 1, "MEMO_OPT_WIDE_TILES takes 0 or 1"},
     {MEMO_OPT_VIEW_DECIDING, &memo_index::view_deciding, 0, 1, 1, "MEMO_OPT_VIEW_DECIDING takes 0 or 1"},  // (a copy already made stays, unread while the option is 0)
+    {MEMO_OPT_VIEW_RUNS, &memo_index::view_runs, 0, 1, 1, "MEMO_OPT_VIEW_RUNS takes 0 or 1"},  // (a copy already made stays, unread while the option is 0)
     {MEMO_OPT_VIEW_ROWS, &memo_index::view_rows, 0, 5, 6, "MEMO_OPT_VIEW_ROWS takes 0 (the library's choice), 5 or 6"},
 };
 
@@ -808,6 +810,10 @@ int memo_index_set_option(memo_index_t *ix, int32_t option, int64_t value) {
         if (value != o.lo && (value < o.first || value > o.hi)) return fail(MEMO_EINVAL, "%s", o.takes);
         const int before = ix->*o.field;
         ix->*o.field = (int)value;
+        // (the run copies want a host that has settled -- memo_view.hip, run_rows: one that changes, between its queries, which rows or
+        // which kernel answer them has not; the budget and the cost share change neither)
+        if (option != MEMO_OPT_VIEW_BUDGET_PCT && option != MEMO_OPT_BUILD_COST_PCT)
+            for (memo_index::DenseView &v : ix->views6) v.run_answered = 0;
         if (option == MEMO_OPT_VIEWS && !value) {
             DeviceGuard guard(ix->device);
             HIP_TRY(hipDeviceSynchronize());

@@ -640,6 +640,8 @@ constexpr double kLiveMinShare = 0.25;
 constexpr double kR4MaxGroups = 543.0;
 int launch_halo3t(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, hipStream_t st, bool annot9 = false, bool all_write = false,
                   bool six = false, bool live = false);
+// memo_sweep_runs.hip: the window's results decoded from the run copy of this k - 1 (src.run_tab, memo_view.h), in the sweep's place
+int launch_runs_decode(memo_index *ix, const SweepArgs &A, const RowSource &src, int elem_bytes, hipStream_t st);
 int pick_rows(const memo_index *ix, int32_t k, int &fmt);
 int check_query_args(const memo_index *ix, int64_t qs, int64_t qe, int32_t k, int32_t num_docs,
                      const void *d_out);

@@ -912,7 +912,8 @@ static LevelTile level_tile(int bw, int km1, int fmt, int64_t len, int tile_w, i
 // unclipped doubling tile in A.  Views of six rows per group are for the table-driven kernel alone: a query it cannot take (a
 // negative window start, no room for the tile table) asks again for five-row groups.  The table-driven kernel sweeps the dense
 // rows wherever the query fits it; only the debug row sources 5 and 10 (tune.persistent == 1) keep them on
-// sweep_conservation_halo3_kernel.  *variant: 2 / 3 when the table-driven kernel answered on five- / six-row groups; 0: A holds
+// sweep_conservation_halo3_kernel.  *variant: 2 / 3 when the table-driven kernel answered on five- / six-row groups, 4 when the run copy
+// of this k - 1 was decoded in the sweep's place; 0: A holds
 // five-row groups for sweep_conservation_halo3_kernel.
 static int sweep_dense_rows(memo_index *ix, SweepArgs &A, int tw, int elem_bytes, bool top8, bool top9, hipStream_t st,
                             int *variant) {
@@ -926,6 +927,11 @@ static int sweep_dense_rows(memo_index *ix, SweepArgs &A, int tw, int elem_bytes
         A.p3 = src.p3;
         A.boff = src.boff;
         note_dense_rows_read(ix, src);
+        if (src.run_tab) {  // the run copy of this k - 1 answers: results are decoded, no row is swept (memo_sweep_runs.hip)
+            if (int rc = launch_runs_decode(ix, A, src, elem_bytes, st)) return rc;
+            *variant = 4;
+            return MEMO_OK;
+        }
         if (table) {
             // the tile's row slice from a table built once per (index, k): memo_sweep_cons3t.hip; 1 = does not fit
             // (a view whose cap is k - 1 holds exactly the rows that write at this k: the table-driven kernel's row blocks drop their test)

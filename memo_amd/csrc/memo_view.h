@@ -17,6 +17,10 @@ extern thread_local bool g_side_alloc_fails;  // (AB library, memo_debug_fail_si
 inline uint64_t dense_view_bytes(uint64_t padded, int rows_per_group) {  // what dense_view_build allocates for a view's rows
     return (rows_per_group == 6 ? padded / 6 + 64 : (padded + 4) / 5 + 64) * 16;
 }
+constexpr int kRunGroup = 8;  // buckets per group of a run copy: 256 positions, whose values begin at a multiple of four bytes
+inline uint64_t run_view_bytes(uint64_t buckets, uint64_t value_bytes) {  // what run_view_copy allocates for a copy's table and values
+    return buckets * 8 + value_bytes + 512;
+}
 // The passes: a source in, a BuiltView (memo_common.h) out.  Each allocates, queues its kernels on `st` and waits for them; kNoRoom when an allocation found no room.
 // (hidden: they were file-local before the file was split, and the library exports what it exported)
 #pragma GCC visibility push(hidden)
@@ -25,6 +29,10 @@ int dense_view_build(int device, const uint32_t *src_p3, const int64_t *src_boff
 int live_view_copy(int device, const BuiltView &flagged, uint64_t nb, hipStream_t st, BuiltView &out);
 int deciding_view_copy(int device, const BuiltView &live, uint64_t nb, int64_t bbase, int64_t first_start, int64_t last_start, int km1,
                        hipStream_t st, BuiltView &out);
+// (dec: a deciding copy of k - 1 = km1; out.p3: the run values, out.boff: mask | offset << 32 per bucket, out.rows: the runs, out.padded:
+// the buckets; *first_bucket: the pivot bucket of the first, *value_bytes: of the values, every group's padded to dwords)
+int run_view_copy(int device, const BuiltView &dec, uint64_t nb, int64_t bbase, int64_t first_start, int64_t last_start, int km1,
+                  hipStream_t st, BuiltView &out, int64_t *first_bucket, uint64_t *value_bytes);
 int packed_filter(int device, const uint32_t *src, const int64_t *src_boff, uint64_t rows, uint64_t nb, int cap, int min_tenths,
                   hipStream_t st, int len_shift, BuiltView &out);
 #pragma GCC visibility pop
@@ -42,6 +50,11 @@ struct RowSource {
     int placed = 0;          // the view's rows have their places chosen
     double dead_share = 0;   // ... the share of its groups flagged dead (the sweep skips them where it pays)
     float build_ms = 0.f;    // device time of the view's pass, when this call ran it (else 0)
+    // the run copy of this k - 1, where one answers in the rows' place (run_tab != nullptr; memo_sweep_runs.hip decodes it):
+    const uint32_t *run_vals = nullptr;  // a byte per run, 255: no row covers it
+    const int64_t *run_tab = nullptr;    // per bucket: start mask | offset of its first value << 32
+    int64_t run_b0 = 0;                  // the pivot bucket of the table's first entry
+    uint64_t run_buckets = 0, runs = 0;
 };
 inline void note_dense_rows_read(memo_index *ix, const RowSource &src) {
     ix->last_rows_read = src.rows;

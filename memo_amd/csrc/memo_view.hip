@@ -67,8 +67,21 @@ static void retire_tables_of(memo_index *ix, const memo_index::DenseView &v) {
     }
 }
 
+// the run copy of a deciding copy, out of service; its count and ledger start again
+static void retire_runs(memo_index *ix, memo_index::DenseView &v) {
+    if (v.run.p3) {
+        retire(ix, v.run.p3, v.run_bytes - v.run.padded * 8);
+        retire(ix, v.run.boff, v.run.padded * 8);
+    }
+    v.run = BuiltView();
+    v.run_bytes = 0;
+    v.run_answered = 0;
+    v.run_lost_ns = 0;
+}
+
 // the deciding copy of a live copy, out of service: with the tile tables made for it; the class's ledgers for it start again
 static void retire_deciding(memo_index *ix, memo_index::DenseView &v) {
+    retire_runs(ix, v);  // (it is the deciding copy's k - 1 resolved: it goes where that goes)
     if (!v.dec.p3) return;
     for (size_t i = 0; i < ix->ttabs.size();) {
         if (ix->ttabs[i].rows_of == v.dec.p3) {
@@ -87,6 +100,7 @@ static void retire_deciding(memo_index *ix, memo_index::DenseView &v) {
 
 static void retire_view(memo_index *ix, memo_index::DenseView &v, bool evicted) {
     retire_tables_of(ix, v);
+    retire_runs(ix, v);
     retire(ix, v.p3, v.bytes);
     retire(ix, v.dec.p3, v.dec_bytes);  // (the deciding copy goes with the live copy it was made of)
     if (v.dec.p3) retire(ix, v.dec.boff, ix->nb * 8);
@@ -102,6 +116,8 @@ static void free_view(memo_index::DenseView &v) {  // (the caller has the device
     (void)hipFree(v.boff);
     (void)hipFree(v.dec.p3);
     (void)hipFree(v.dec.boff);
+    (void)hipFree(v.run.p3);
+    (void)hipFree(v.run.boff);
     v = memo_index::DenseView();
 }
 void drop_dense_views(memo_index *ix) {
@@ -126,7 +142,7 @@ static void keep_views_in_budget(memo_index *ix, const memo_index::DenseView *fr
         memo_index::DenseView *lru = nullptr;
         each_view(ix, dense, [&](memo_index::DenseView &v) {
             if (!v.p3) return;
-            total += v.bytes + ix->nb * 8 + (v.dec.p3 ? v.dec_bytes + ix->nb * 8 : 0);
+            total += v.bytes + ix->nb * 8 + (v.dec.p3 ? v.dec_bytes + ix->nb * 8 : 0) + v.run_bytes;
             if (&v != fresh && (!lru || v.stamp < lru->stamp)) lru = &v;
         });
         if (total <= budget || !lru) break;
@@ -160,9 +176,12 @@ constexpr double kLiveCopyNsPerGroup = 0.008;   // live_view_copy, per group of 
 constexpr double kDecidingNsPerGroup = 0.12;    // deciding_view_copy, per group of the live copy (profiles/deciding_rows.txt: 1.62 ms for config 3's 1.14e7 groups at k = 31)
 constexpr double kDecidingSparedShare = 0.5;    // ... the share of the live copy's slots a deciding copy is assumed to spare a sweep, before one is made
 constexpr int kDecidingAskAfter = 32;           // ... queries in a row at one k the live copy must have answered first (bench.py's warm-up makes 200: <= 64)
+constexpr double kRunsNsPerPosition = 0.011;    // run_view_copy, per position of the copy's buckets (profiles/run_copy.txt: 1.3 ms for config 3's 10^8 positions at k = 31)
+constexpr double kDecodeSparedNsPerPosition = 0.00013;  // ... what a decode spares a sweep of the deciding copy, per position of the window (62.7 -> 49.3 us for 10^8 at k = 31; 67.7 -> 50.7 at k = 17)
+constexpr int kRunsAskAfter = 32;               // ... queries in a row the deciding copy must have answered first (above the 15 tests/test_deciding_rows_gpu.py asks of one)
 constexpr double kPassFixedNs = 200e3;
 // per unit of every pass (Pass, memo_common.h: a row of its source; the live copy: a group of the flagged view), until the index has measured one
-constexpr double kPassNs[kPasses] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow, kLiveCopyNsPerGroup, kOrderNsPerRow, kDecidingNsPerGroup};
+constexpr double kPassNs[kPasses] = {kDenseViewNsPerRow, kPackedViewNsPerRow, kPlacedViewNsPerRow, kLiveCopyNsPerGroup, kOrderNsPerRow, kDecidingNsPerGroup, kRunsNsPerPosition};
 
 static double rows_in_window(const memo_index *ix, double src_rows, int64_t window, int km1) {
     const double span = (double)ix->max_s - (double)ix->min_s + 1.0;
@@ -250,8 +269,12 @@ static int deciding_rows(memo_index *ix, memo_index::DenseView &v, int km1, int6
         v.dec_run_km1 = km1;
         v.dec_run = 0;
         v.dec_lost_ns = 0;
+        v.run_answered = 0;  // (run_rows: its count is of this run)
+        v.run_lost_ns = 0;
     }
     const int answered = v.dec_run++;  // queries of this run before this one
+    // (the run copy's ledger, run_rows: every query of the run loses at least what a decode spares a sweep of the deciding copy)
+    if (ix->view_runs && !v.run.p3) v.run_lost_ns += (double)window * kDecodeSparedNsPerPosition;
     if (v.dec.p3 && v.dec_km1 == km1) {
         hand_out();
         return MEMO_OK;
@@ -279,11 +302,78 @@ static int deciding_rows(memo_index *ix, memo_index::DenseView &v, int km1, int6
         v.dec_never[v.cap - km1] = 1;
         return MEMO_OK;
     }
+    const double run_lost_ns = v.run_lost_ns;
     retire_deciding(ix, v);  // (the class's other k - 1: sweeps queued on other streams may still read it)
+    v.run_lost_ns = run_lost_ns;  // (of this run: it goes on)
     v.dec = b;
     v.dec_km1 = km1;
     v.dec_bytes = dense_view_bytes(b.padded, 6);
     ++ix->view_deciding_copies;
+    src.build_ms = ms;
+    hand_out();
+    keep_views_in_budget(ix, &v, base_bytes, true);
+    return MEMO_OK;
+}
+
+// A deciding copy that answers a conservation query at its k - 1 = km1 (src: as deciding_rows left it): the RUN copy of that k - 1
+// (memo_view_build.hip: run_view_copy) in its place, when it exists or is due -- the sweep's launcher then decodes results instead of
+// sweeping rows (src.run_tab; memo_sweep_runs.hip).  Every row of the deciding copy wins somewhere, but the rows still overlap, and a
+// sweep learns again with every query which of them wins where; for one k that never changes.  The same bargain as the deciding copy's,
+// under the same two conditions: the deciding copy must have answered kRunsAskAfter queries in a row at this k - 1 (a query at the class's
+// other k starts the count again, and so does memo_index_set_option with an option that changes which rows or which kernel answer
+// -- all but the budget and the cost share: a host that switches those between its queries, as every A/B of the sweep kernels does, has
+// not settled; at MEMO_OPT_BUILD_COST_PCT 0 too) and the ledger -- the window's positions x what a decode spares a
+// sweep per position, over every query of the run at this k - 1 (deciding_rows adds it: the queries the live copy answered lost no
+// less) -- must have reached the pass's cost.  Never inside memo_index_prepare; only where every order is below 255 (the
+// byte that says "no row").  One per class, retired with its deciding copy; no room: the deciding copy answers and the back-off grows;
+// a copy of half a value per position or more (its bytes come to three quarters of the result's: the decode was never measured there) is
+// dropped and this k - 1 not looked at again.
+static int run_rows(memo_index *ix, memo_index::DenseView &v, int km1, int64_t window, hipStream_t st, uint64_t base_bytes, RowSource &src) {
+    if (!ix->view_runs || ix->max_annot > 254 || !v.dec.p3 || v.dec_km1 != km1 || src.p3 != v.dec.p3) return MEMO_OK;
+    auto hand_out = [&]() {
+        src.run_vals = v.run.p3;
+        src.run_tab = v.run.boff;
+        src.run_b0 = v.run_b0;
+        src.run_buckets = v.run.padded;
+        src.runs = v.run.rows;
+    };
+    if (g_prepare_only) {  // (plans on what there is; counts nothing, builds nothing)
+        if (v.run.p3) hand_out();
+        return MEMO_OK;
+    }
+    const int answered = v.run_answered++;  // queries the deciding copy of this run has answered before this one
+    if (v.run.p3) {
+        hand_out();
+        return MEMO_OK;
+    }
+    if (src.build_ms != 0.f || v.run_never[v.cap - km1]) return MEMO_OK;  // (at most one pass a query)
+    const double cells = 32.0 * (double)((ix->max_s >> 5) - (ix->min_s >> 5) + 2);
+    if (answered < kRunsAskAfter || !pass_due(ix, v.run_lost_ns, v.run_backoff, kPassRuns, cells)) return MEMO_OK;
+    DeviceGuard guard(ix->device);
+    BuiltView b;
+    int64_t b0 = 0;
+    uint64_t value_bytes = 0;
+    float ms = 0.f;
+    const int rc = build_timed(st, &ms, [&]() {
+        return run_view_copy(ix->device, v.dec, ix->nb, ix->bbase, ix->min_s, ix->max_s, km1, st, b, &b0, &value_bytes);
+    });
+    if (rc && rc != kNoRoom) return rc;
+    v.run_lost_ns = 0;
+    if (rc == kNoRoom) {  // (the pressure may pass: the count goes on, the threshold is four times as far)
+        v.run_backoff = backoff_step(v.run_backoff);
+        return MEMO_OK;
+    }
+    pass_measured(ix, kPassRuns, ms, cells);
+    if (!b.p3 || b.rows * 2 >= b.padded * 32) {  // gave up, or too many runs: nobody has read it (the pass waited for st)
+        (void)hipFree(b.p3);
+        (void)hipFree(b.boff);
+        v.run_never[v.cap - km1] = 1;
+        return MEMO_OK;
+    }
+    v.run = b;
+    v.run_b0 = b0;
+    v.run_bytes = run_view_bytes(b.padded, value_bytes);
+    ++ix->view_run_copies;
     src.build_ms = ms;
     hand_out();
     keep_views_in_budget(ix, &v, base_bytes, true);
@@ -568,7 +658,10 @@ int dense_rows_for(memo_index *ix, int km1, int64_t window, hipStream_t st, RowS
         src.rpg = rpg;
         src.placed = v.placed;
         src.dead_share = six && v.padded ? 6.0 * (double)v.dead_groups / (double)v.padded : 0.0;
-        if (account && six && v.live && src.build_ms == 0.f) return deciding_rows(ix, v, km1, window, st, base_bytes, src);  // (at most one pass a query)
+        if (account && six && v.live && src.build_ms == 0.f) {  // (at most one pass a query)
+            if ((rc = deciding_rows(ix, v, km1, window, st, base_bytes, src))) return rc;
+            return run_rows(ix, v, km1, window, st, base_bytes, src);
+        }
     }
     return MEMO_OK;
 }

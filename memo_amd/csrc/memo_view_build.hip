@@ -714,6 +714,105 @@ __global__ void decide_write_kernel(const uint4 *__restrict__ groups, const int6
     if (have && gout < total) out[gout] = pack_six_slots(r, bucket5);
 }
 
+// ======================================================================================================================
+// The RUN copy of a deciding copy (run_view_copy): the minimum of ONE k - 1 itself, resolved once and run-coded.
+//
+// The copy's buckets are the pivot buckets b0 ... b0 + buckets - 1 (b0: one below the index's first -- a row reaches back k - 1 <= 31
+// positions; whole groups of kRunGroup).  Per bucket a start mask -- bit i: result[i] differs from result[i - 1]; bit 0 always -- and the
+// byte offset of its first value; per run a byte, the least order that covers it, 255: none.  A group's values begin at a multiple of four.
+//   1. runs_mark_kernel: decide_mark_kernel's sibling, on the same slices and runs of kDecideW cells: every slot atomicMin-s its order into
+//      the cells it covers, and the cells go out as a byte each into `res` (ncells bytes from position p0 = 32 b0; all 255 before).
+//   2. runs_count_kernel: a lane per bucket -> the values of its group in dwords, and all the runs; the scan of dense_view_build;
+//      runs_write_kernel: a lane per bucket stores its table entry and its values.  (Counting inside the mark kernel instead -- a
+//      wave's ballot over 64 cells, an atomic a bucket -- was measured: the marking went from 0.38 to 1.29 ms on 10^8 positions, more
+//      than the 0.59 ms of the count kernel it replaced: profiles/run_copy.txt.)
+// ======================================================================================================================
+__global__ __launch_bounds__(256) void runs_mark_kernel(const uint4 *__restrict__ groups, const int64_t *__restrict__ boff, int64_t nb,
+                                                        int64_t bbase, int64_t run_lo, int km1, int64_t p0, int64_t ncells,
+                                                        uint32_t *__restrict__ res) {
+    __shared__ uint32_t cell[kDecideW];
+    const int64_t a = (run_lo + (int64_t)blockIdx.x) * kDecideW;
+    uint64_t g0, g1;
+    decide_slice(boff, nb, bbase, a, km1, &g0, &g1);
+    if (g1 <= g0) return;  // (the whole workgroup: its cells stay 255)
+    for (int p = threadIdx.x; p < kDecideW; p += 256) cell[p] = 255u;
+    __syncthreads();
+    const uint32_t fa = (uint32_t)(a >> 5) & 31u;  // the run's first bucket mod 32
+    for (uint64_t g = g0 + threadIdx.x; g < g1; g += 256) {
+        const uint4 V = groups[g];
+        const int base = (int)(((((V.z >> 18) & 31u) - fa) & 31u) * 32u);  // the cell of the group's bucket, from a
+#pragma unroll
+        for (uint32_t i = 0; i < 6; ++i) {
+            const uint32_t r = six_slot(V, i);
+            const int n = km1 - (int)((r >> 5) & 31u), s = base + (int)(r & 31u);
+            const int hi = s < kDecideW ? s : kDecideW;
+            for (int p = s - n < 0 ? 0 : s - n; p < hi; ++p) atomicMin(&cell[p], r >> 10);
+        }
+    }
+    __syncthreads();
+    // four cells a lane, one dword: a and p0 are multiples of 32, ncells of 256
+    for (int q = threadIdx.x; q < kDecideW / 4; q += 256) {
+        const int64_t at = a - p0 + 4 * q;
+        if (at < 0 || at + 4 > ncells) continue;
+        res[at >> 2] = cell[4 * q] | (cell[4 * q + 1] << 8) | (cell[4 * q + 2] << 16) | (cell[4 * q + 3] << 24);
+    }
+}
+
+// the start mask of the bucket whose 32 results are the bytes of A (positions 0 .. 15) and B (16 .. 31)
+__device__ __forceinline__ uint32_t runs_mask(const uint4 &A, const uint4 &B) {
+    const uint32_t w[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
+    uint32_t m = 1u;
+#pragma unroll
+    for (int i = 1; i < 32; ++i) {
+        const uint32_t cur = (w[i >> 2] >> (8 * (i & 3))) & 255u, prev = (w[(i - 1) >> 2] >> (8 * ((i - 1) & 3))) & 255u;
+        m |= (cur != prev ? 1u : 0u) << i;
+    }
+    return m;
+}
+
+// (whole waves: the grid covers `buckets`, a multiple of kRunGroup, rounded up to workgroups; a lane past the end counts nothing)
+__global__ __launch_bounds__(256) void runs_count_kernel(const uint4 *__restrict__ res, int64_t buckets, uint32_t *__restrict__ gcount,
+                                                         unsigned long long *__restrict__ runs) {
+    const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    uint32_t c = 0;
+    if (b < buckets) c = (uint32_t)__popc(runs_mask(res[2 * b], res[2 * b + 1]));
+    c += __shfl_xor(c, 1);
+    c += __shfl_xor(c, 2);
+    c += __shfl_xor(c, 4);
+    if (b < buckets && !(b & (kRunGroup - 1))) gcount[b / kRunGroup] = (c + 3u) >> 2;
+    c += __shfl_xor(c, 8);
+    c += __shfl_xor(c, 16);
+    c += __shfl_xor(c, 32);
+    if (!(threadIdx.x & 63) && c) atomicAdd(runs, (unsigned long long)c);
+}
+
+// glocal / gblock: the scan of gcount (dwords of values before every group); tab: an entry per bucket; vals: the values' bytes (zeroed)
+__global__ __launch_bounds__(256) void runs_write_kernel(const uint4 *__restrict__ res, int64_t buckets, const uint32_t *__restrict__ glocal,
+                                                         const uint64_t *__restrict__ gblock, uint64_t value_bytes, uint2 *__restrict__ tab,
+                                                         uint8_t *__restrict__ vals) {
+    const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const bool in = b < buckets;
+    uint4 A = make_uint4(0, 0, 0, 0), B = A;
+    if (in) A = res[2 * b], B = res[2 * b + 1];
+    const uint32_t m = in ? runs_mask(A, B) : 0u, c = (uint32_t)__popc(m), sub = threadIdx.x & (kRunGroup - 1);
+    uint32_t upto = c;  // inclusive, over the group's buckets so far
+    for (uint32_t d = 1; d < (uint32_t)kRunGroup; d <<= 1) {
+        const uint32_t t = __shfl_up(upto, d);
+        if (sub >= d) upto += t;
+    }
+    if (!in) return;
+    const int64_t g = b / kRunGroup;
+    uint64_t at = 4 * (gblock[g >> 10] + glocal[g]) + (upto - c);
+    tab[b] = make_uint2(m, (uint32_t)at);
+    const uint32_t w[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+        if ((m >> i) & 1u) {
+            if (at < value_bytes) vals[at] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+            ++at;
+        }
+}
+
 template <int P>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void view_build_kernel(const ViewArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t view_lds[];
@@ -1138,6 +1237,60 @@ int deciding_view_copy(int device, const BuiltView &live, uint64_t nb, int64_t b
     err = wait_for(st, {});
     if (err != hipSuccess) return side.failed(err);
     out = {reinterpret_cast<uint32_t *>(side.release(outg)), side.release(boffd), nwin, 6 * total6, 0};
+    return MEMO_OK;
+}
+
+// A deciding copy (`dec`: padded / 6 groups, bucket table of nb entries whose first belongs to bucket bbase; exact for k - 1 = km1, orders
+// <= 254) resolved into the run copy of that k - 1 (the kernels above): a new allocation of values (+ 512 zeroed bytes: a wave loads 64
+// dwords from a group's first) and a table entry per bucket; out.rows: the runs, out.padded: the buckets, *first_bucket: the pivot
+// bucket of the first.  The minima are staged as a byte per position in a buffer that is freed before the call returns: the write
+// kernel that reads them takes 0.04 ms on 10^8 positions, a second run of runs_mark_kernel in their place would take its 0.38 ms.  Nothing built (out.p3 stays NULL, MEMO_OK): more runs than a
+// grid holds, values past 2^32 bytes.  Queued on `st`, waited for twice (the runs decide the allocation).
+int run_view_copy(int device, const BuiltView &dec, uint64_t nb, int64_t bbase, int64_t first_start, int64_t last_start, int km1,
+                  hipStream_t st, BuiltView &out, int64_t *first_bucket, uint64_t *value_bytes_out) {
+    out = BuiltView();
+    const uint64_t ng = dec.padded / 6;
+    if (!ng || nb < 2 || km1 < 1 || km1 > 31 || last_start < first_start) return MEMO_OK;
+    auto run_of = [](int64_t x) { return x >= 0 ? x / kDecideW : -((-x + kDecideW - 1) / kDecideW); };
+    const int64_t run_lo = run_of(first_start - 64), nruns = run_of(last_start + 1) - run_lo + 1;
+    if (nruns < 1 || nruns >= ((int64_t)1 << 31) - 1) return MEMO_OK;
+    const int64_t b0 = (first_start >> 5) - 1;
+    const uint64_t buckets = ((uint64_t)((last_start >> 5) - b0 + 1) + kRunGroup - 1) / kRunGroup * kRunGroup, ngroups = buckets / kRunGroup;
+    const uint64_t ncells = buckets * 32, nblk = (ngroups + 1023) >> 10;
+    if ((buckets + 255) / 256 >= ((uint64_t)1 << 31)) return MEMO_OK;
+    DeviceGuard guard(device);
+    Carve tmp_at;
+    const uint64_t o_runs = tmp_at.take(16), o_gcount = tmp_at.take(ngroups * 4 + 4), o_gblock = tmp_at.take((nblk + 1) * 8), o_res = tmp_at.take(ncells);
+    SideBuffers side("run copy");
+    char *tmp = nullptr, *vals = nullptr;
+    int64_t *tab = nullptr;
+    if (int rc = side.alloc(&tmp, tmp_at.bytes).status()) return rc;
+    unsigned long long *runs = reinterpret_cast<unsigned long long *>(tmp + o_runs);
+    uint32_t *gcount = reinterpret_cast<uint32_t *>(tmp + o_gcount);
+    uint64_t *gblock = reinterpret_cast<uint64_t *>(tmp + o_gblock);
+    hipError_t err = hipMemsetAsync(tmp, 0, o_res, st);
+    if (err == hipSuccess) err = hipMemsetAsync(tmp + o_res, 0xFF, ncells, st);
+    if (err != hipSuccess) return side.failed(err);
+    const unsigned grid = (unsigned)((buckets + 255) / 256);
+    hipLaunchKernelGGL(runs_mark_kernel, dim3((unsigned)nruns), dim3(256), 0, st, reinterpret_cast<const uint4 *>(dec.p3), dec.boff, (int64_t)nb,
+                       bbase, run_lo, km1, b0 * 32, (int64_t)ncells, reinterpret_cast<uint32_t *>(tmp + o_res));
+    hipLaunchKernelGGL(runs_count_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint4 *>(tmp + o_res), (int64_t)buckets, gcount, runs);
+    scan_counts(st, gcount, ngroups, gblock);
+    uint64_t dwords = 0, nrun = 0;
+    err = wait_for(st, {{gblock + nblk, &dwords}, {runs, &nrun}});
+    if (err != hipSuccess) return side.failed(err);
+    if (!nrun || dwords >= ((uint64_t)1 << 30)) return MEMO_OK;
+    const uint64_t value_bytes = dwords * 4;
+    if (int rc = side.alloc(&vals, value_bytes + 512).alloc(&tab, buckets * 8).status()) return rc;
+    err = hipMemsetAsync(vals, 0, value_bytes + 512, st);
+    if (err != hipSuccess) return side.failed(err);
+    hipLaunchKernelGGL(runs_write_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint4 *>(tmp + o_res), (int64_t)buckets, gcount, gblock,
+                       value_bytes, reinterpret_cast<uint2 *>(tab), reinterpret_cast<uint8_t *>(vals));
+    err = wait_for(st, {});
+    if (err != hipSuccess) return side.failed(err);
+    out = {reinterpret_cast<uint32_t *>(side.release(vals)), side.release(tab), nrun, buckets, 0};
+    *first_bucket = b0;
+    *value_bytes_out = value_bytes;
     return MEMO_OK;
 }
 

@@ -139,7 +139,7 @@ class DeviceIndex:
     def set_option(self, option, value):
         """memo_index_set_option: 1 = MEMO_OPT_VIEWS (0 / 1), 2 = MEMO_OPT_VIEW_BUDGET_PCT, 3 = MEMO_OPT_BUILD_COST_PCT (100: ski rental; 0: the
         first query of a class builds), 4 = MEMO_OPT_VIEW_ROWS (0 / 5 / 6), 5 = MEMO_OPT_VIEW_PLACES (0 / 1), 6 = MEMO_OPT_VIEW_LIVE (0 / 1),
-        7 = MEMO_OPT_WIDE_TILES (0 / 1), 8 = MEMO_OPT_VIEW_DECIDING (0 / 1).  Returns the option's previous value."""
+        7 = MEMO_OPT_WIDE_TILES (0 / 1), 8 = MEMO_OPT_VIEW_DECIDING (0 / 1), 9 = MEMO_OPT_VIEW_RUNS (0 / 1).  Returns the option's previous value."""
         return check(lib().memo_index_set_option(self._h, int(option), int(value)))     # the option's previous value
 
     # ---- asynchronous launches on device buffers (torch tensors or raw addresses) ----
@@ -193,6 +193,24 @@ class DeviceIndex:
         """memo_debug_view_deciding: (whether the class of k holds a deciding copy for exactly this k, deciding copies made so far)"""
         made = C.c_uint64(0)
         return bool(check(lib().memo_debug_view_deciding(self._h, int(k), C.byref(made)))), int(made.value)
+
+    def debug_view_runs(self, k):
+        """memo_debug_view_runs: (whether the class of k holds a run copy for exactly this k, run copies made so far)"""
+        made = C.c_uint64(0)
+        return bool(check(lib().memo_debug_view_runs(self._h, int(k), C.byref(made)))), int(made.value)
+
+    def export_runs(self, k):
+        """memo_debug_export_runs: (masks uint32[buckets], offsets uint32[buckets], values uint8[value bytes], runs, first bucket) of
+        the run copy the class of k keeps for exactly this k, or None when there is none (A/B library)"""
+        nbk, vbytes, runs, b0 = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_int64(0)
+        sizes = (C.byref(nbk), C.byref(vbytes), C.byref(runs), C.byref(b0))
+        check(lib().memo_debug_export_runs(self._h, int(k), None, None, None, *sizes))
+        if not nbk.value:
+            return None
+        masks, offsets = np.empty(nbk.value, np.uint32), np.empty(nbk.value, np.uint32)
+        values = np.empty(vbytes.value, np.uint8)
+        check(lib().memo_debug_export_runs(self._h, int(k), masks.ctypes.data, offsets.ctypes.data, values.ctypes.data, *sizes))
+        return masks, offsets, values, int(runs.value), int(b0.value)
 
     def debug_last_tiles_per_group(self):
         """memo_debug_last_tiles_per_group: 2 where the wide tiles' pair kernel answered the last conservation sweep, else 1"""
