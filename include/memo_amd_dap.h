@@ -278,6 +278,47 @@ int memo_panel_take_dev(const uint32_t *d_planes, int64_t pitch_words, int32_t n
 int32_t memo_panel_tile(void);
 int32_t memo_panel_pass_words(void);
 
+/* ---- `memo cover`: the genomes that cover the pivot's matches, at every k (no counterpart in the reference) -------------------
+ * `memo panel` summed over every k of [kmin, kmax], one step at a time (memo_amd/csrc/memo_cover.hip).  With span = kmax - kmin + 1
+ * and w[g][p] = max(0, min(len[g][p], kmax) - (kmin - 1)) -- memo_pairs_dev's weights of memo_lengths' cells -- the window stays on
+ * `device` as weight planes of the genomes a caller names: plane i is `pitch` cells of cell_bytes = 2 (span <= 65535) or 4 bytes at
+ * d_weights + i * pitch * cell_bytes.  d_weights is 16-byte aligned and pitch a multiple of a quad, 16 / cell_bytes cells, everywhere
+ * below; the two masks d_core and d_covered are [cells] cells on `device`, 16-byte aligned, laid out as one plane; `cells` is a
+ * multiple of a quad, at most pitch: the window's L cells and the pad cells up to the next multiple of a quad, which hold zeros and
+ * are read.  Nothing at or past `pitch` of a plane is ever read.  All calls are stateless and blocking; each refuses with MEMO_EINVAL
+ * before anything is launched -- a pointer that is NULL or not 16-byte aligned, a pitch that is no positive multiple of a quad, cells
+ * or a cell range that leaves the pitch, a cell_bytes other than 2 or 4, a span that does not fit the cell, a list entry out of range,
+ * n_list outside [0, 65535], num_docs or num_planes outside [1, 2048] -- and then leaves planes, masks and outputs as they were.
+ * Every sum is exact for any cell values, spans up to 2^31 - 1 and up to 2^31 - 1 cells.
+ *
+ * memo_cover_weights_dev: one finished slice of memo_lengths_*_dev, d_lengths (uint32 [num_docs][pitch_src] on `device`, 16-byte
+ * aligned, pitch_src a multiple of 4 and at least Ls; the cells [0, Ls) of the planes the list names are read and nothing else),
+ * becomes the cells [cell0, cell0 + Ls) of the planes [0, n_list): plane i receives w[list_host[i]], a length above kmax counting
+ * as kmax.  list_host is a HOST pointer, uint16 [n_list], genome ids below num_docs, repeats legal.  cell0 is a multiple of 8.  No
+ * other cell of any plane is written.  Ls == 0 or n_list == 0 launches nothing. */
+int memo_cover_weights_dev(const uint32_t *d_lengths, int64_t Ls, int64_t pitch_src, int32_t num_docs, uint32_t kmin, uint32_t kmax, const uint16_t *list_host,
+                           int32_t n_list, void *d_weights, int64_t pitch, int32_t cell_bytes, int64_t cell0, int32_t device, void *stream);
+/* what no slice writes, for a window of L positions: the pad cells [L, the next multiple of a quad) of every plane as zeros, d_core
+ * as span below L and zeros in the pad cells, d_covered as zeros.  L == 0 launches nothing. */
+int memo_cover_begin_dev(void *d_weights, int64_t pitch, int32_t num_planes, int32_t cell_bytes, int64_t L, uint32_t span, void *d_core, void *d_covered,
+                         int32_t device, void *stream);
+/* list_host is a HOST pointer, uint16 [n_list], plane numbers below num_planes, repeats legal, n_list in [0, 65535]; scores_host is a
+ * HOST pointer, uint64 [n_list][2], WRITTEN (not added to):
+ *     scores[i][0] = new  = sum of max(0, w - covered)        scores[i][1] = kept = sum of min(w, core)        w: plane list[i]
+ * over the cells [0, cells), literally, whatever the cells hold.  The library uploads the list and downloads the scores itself.
+ * Scratch memory on the device: the list, the scores and at most 64 MiB of partial sums (128 MiB for lists past 32767 on masks past
+ * 2^30 cells of 2 bytes), freed before the call returns; an allocation that fails returns MEMO_EHIP with the bytes asked for in
+ * memo_last_error and leaves nothing allocated.  n_list == 0 launches nothing. */
+int memo_cover_score_dev(const void *d_weights, int64_t pitch, int32_t num_planes, int32_t cell_bytes, int64_t cells, const void *d_core, const void *d_covered,
+                         const uint16_t *list_host, int32_t n_list, uint64_t *scores_host, int32_t device, void *stream);
+/* d_core = min(d_core, plane), d_covered = max(d_covered, plane), cell by cell in place over the cells [0, cells); sums_host is a HOST
+ * pointer, uint64 [2], written: the sum of the new core, the sum of the new covered.  Scratch as memo_cover_score_dev's. */
+int memo_cover_take_dev(const void *d_weights, int64_t pitch, int32_t num_planes, int32_t cell_bytes, int64_t cells, int32_t plane, void *d_core, void *d_covered,
+                        uint64_t *sums_host, int32_t device, void *stream);
+/* the cells a workgroup of score and take reads per pass (2048 of 2 bytes, 1024 of 4; 0 for any other cell_bytes), for tests that want
+ * lengths around it */
+int32_t memo_cover_pass_cells(int32_t cell_bytes);
+
 /* ---- `memo tracks`: per-genome k-mer presence along the pivot, binned (no counterpart in the reference) -----------------
  * (Declared here, beside the `memo collect` block: memo_amd.h keeps to the query path's 44 entry points.)
  * The presence counts of a membership result that is still on `device` (memo_amd/csrc/memo_tracks.hip): d_bits as

@@ -177,6 +177,10 @@ int memo_debug_collect_times(int32_t on, float *out2);
  * is then waited for) or do not (0); out4 (may be NULL) receives the device milliseconds of the last timed call of each kind: [0] the
  * planes launch, [1] the score sweep, [2] its reduce launch, [3] the take launch with its reduce.  tools/panel_timing.py reads them. */
 int memo_debug_panel_times(int32_t on, float *out4);
+/* this THREAD's later memo_cover_weights_dev / _score_dev / _take_dev calls put event pairs around their launches (on = 1; each launch
+ * is then waited for) or do not (0); out4 (may be NULL) receives the device milliseconds of the last timed call of each kind: [0] the
+ * weights launch, [1] the score sweep, [2] its reduce launch, [3] the take launch with its reduce.  tools/cover_timing.py reads them. */
+int memo_debug_cover_times(int32_t on, float *out4);
 /* this THREAD's later memo_lengths_*_dev calls put event pairs around their launches (on = 1; each launch is then waited for) or do
  * not (0); out7 (may be NULL) receives the device milliseconds of the last timed launch of each kind: [0] the fill of begin (with the
  * carry's cells), [1] the row pass, [2] the carry pass, [3] the tile minima, [4] their scan, [5] the apply launch of finish, [6] the

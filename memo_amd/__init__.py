@@ -25,6 +25,8 @@ Layout (only what the path needs):
   collect_cli.py   `memo collect`: flags, usage, the curve, the band over random orders or every order as tab-separated text
   panel.py         `memo panel`: the greedy set cover of a window's membership bits, on per-genome bit planes that stay on the GPU
   panel_cli.py     `memo panel`: flags, usage, the curve of the chosen order with the genome each line adds
+  cover.py         `memo cover`: `memo panel` summed over every k, the greedy choice on per-genome weight planes that stay on the GPU
+  cover_cli.py     `memo cover`: flags, usage, the curve of the chosen order over every k with the genome each line adds
   tracks.py        `memo tracks`: every genome's k-mer presence per bin along the pivot, counted on the GPU, a window's in slices
   tracks_cli.py    `memo tracks`: flags, usage, counts or fractions as tab-separated text, or the heat map (matplotlib)
   features.py      `memo features`: a BED file's features from one sweep per record: counted per segment, summed per feature on the GPU
@@ -66,6 +68,7 @@ _LAZY = {
     "cooccurrence": "matrix", "region_matrix": "matrix",
     "region_curves": "collect",
     "region_panel": "panel", "index_panel": "panel",
+    "region_cover": "cover",
     "bin_tracks": "tracks", "region_tracks": "tracks",
     "bed_features": "features", "read_bed": "features",
     "region_maxk": "maxk", "index_maxk": "maxk",          # (maxk.maxk keeps its module's name: memo_amd.maxk is the module)
@@ -88,7 +91,7 @@ def __getattr__(name):
         value = getattr(importlib.import_module("." + _LAZY[name], __name__), name)
         globals()[name] = value
         return value
-    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "panel", "panel_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "pairs", "pairs_cli", "nearest", "nearest_cli", "mosaic", "mosaic_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
+    if name in ("_lib", "_device", "_window", "_cli", "index", "memo_query", "cache", "synth", "shard", "view", "view_cli", "regions", "regions_cli", "matrix", "matrix_cli", "collect", "collect_cli", "panel", "panel_cli", "cover", "cover_cli", "tracks", "tracks_cli", "features", "features_cli", "maxk", "maxk_cli", "lengths", "lengths_cli", "mems", "mems_cli", "breaks", "breaks_cli", "pairs", "pairs_cli", "nearest", "nearest_cli", "mosaic", "mosaic_cli", "spectrum", "spectrum_cli", "convert", "convert_cli", "add", "add_cli", "merge", "merge_cli", "dap_to_bed", "build_index", "_fastquery"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

@@ -130,6 +130,11 @@ SYMBOLS = {
     "memo_panel_take_dev": (C.c_int, [_P, _I64, _I32, _I64, _I32, _P, _P, _P, _I32, _P]),
     "memo_panel_tile": (_I32, []),
     "memo_panel_pass_words": (_I32, []),
+    "memo_cover_weights_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, C.c_uint32, _P, _I32, _P, _I64, _I32, _I64, _I32, _P]),
+    "memo_cover_begin_dev": (C.c_int, [_P, _I64, _I32, _I32, _I64, C.c_uint32, _P, _P, _I32, _P]),
+    "memo_cover_score_dev": (C.c_int, [_P, _I64, _I32, _I32, _I64, _P, _P, _P, _I32, _P, _I32, _P]),
+    "memo_cover_take_dev": (C.c_int, [_P, _I64, _I32, _I32, _I64, _I32, _P, _P, _P, _I32, _P]),
+    "memo_cover_pass_cells": (_I32, [_I32]),
     "memo_tracks_dev": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _P, _I32, _P]),
     "memo_tracks_tile": (_I32, [_I32]),
     "memo_breaks_dev": (C.c_int, [_P, _I64, _I64, _I32, C.c_uint32, C.c_uint32, _I32, _I64, _P, _I32, _P, _I32, _P]),
@@ -258,6 +263,7 @@ DEBUG_SYMBOLS = {
     "memo_debug_maxk_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_collect_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_panel_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
+    "memo_debug_cover_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_lengths_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),
     "memo_debug_spectrum_times": (C.c_int, [_I32, C.POINTER(C.c_float), C.POINTER(_I32), C.POINTER(_U64)]),
     "memo_debug_mems_times": (C.c_int, [_I32, C.POINTER(C.c_float)]),

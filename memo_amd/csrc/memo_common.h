@@ -49,6 +49,8 @@ extern thread_local int g_collect_timed;  // memo_collect.hip (AB library, memo_
 extern thread_local float g_collect_ms[2];
 extern thread_local int g_panel_timed;  // memo_panel.hip (AB library, memo_debug_panel_times: event pairs around the launches of the memo_panel_*_dev calls)
 extern thread_local float g_panel_ms[4];
+extern thread_local int g_cover_timed;  // memo_cover.hip (AB library, memo_debug_cover_times: event pairs around the launches of the memo_cover_*_dev calls)
+extern thread_local float g_cover_ms[4];
 extern thread_local int g_tracks_timed;  // memo_tracks.hip (AB library, memo_debug_tracks_times: an event pair around the launch of memo_tracks_dev)
 extern thread_local float g_tracks_ms;
 extern thread_local int g_breaks_timed;  // memo_breaks.hip (AB library, memo_debug_breaks_times: an event pair around the launch of memo_breaks_dev)

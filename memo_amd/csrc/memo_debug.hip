@@ -312,6 +312,13 @@ int memo_debug_panel_times(int32_t on, float *out4) {
     return MEMO_OK;
 }
 
+int memo_debug_cover_times(int32_t on, float *out4) {
+    g_cover_timed = on ? 1 : 0;
+    if (out4)
+        for (int i = 0; i < 4; ++i) out4[i] = g_cover_ms[i];
+    return MEMO_OK;
+}
+
 int memo_debug_lengths_times(int32_t on, float *out7) {
     g_lengths_timed = on ? 1 : 0;
     if (out7)
