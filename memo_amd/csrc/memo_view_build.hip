@@ -1241,11 +1241,15 @@ int deciding_view_copy(int device, const BuiltView &live, uint64_t nb, int64_t b
 }
 
 // A deciding copy (`dec`: padded / 6 groups, bucket table of nb entries whose first belongs to bucket bbase; exact for k - 1 = km1, orders
-// <= 254) resolved into the run copy of that k - 1 (the kernels above): a new allocation of values (+ 512 zeroed bytes: a wave loads 64
-// dwords from a group's first) and a table entry per bucket; out.rows: the runs, out.padded: the buckets, *first_bucket: the pivot
-// bucket of the first.  The minima are staged as a byte per position in a buffer that is freed before the call returns: the write
-// kernel that reads them takes 0.04 ms on 10^8 positions, a second run of runs_mark_kernel in their place would take its 0.38 ms.  Nothing built (out.p3 stays NULL, MEMO_OK): more runs than a
-// grid holds, values past 2^32 bytes.  Queued on `st`, waited for twice (the runs decide the allocation).
+// <= 254) resolved into the run copy of that k - 1 (the kernels above): a new allocation of values and a table entry per bucket;
+// out.rows: the runs, out.padded: the buckets, *first_bucket: the pivot bucket of the first.
+// The values are followed by 512 zeroed bytes.  What needs them: a lane of the decode (memo_runs_decode.h) reads whole dwords from the
+// one that holds its first byte A on, bytes [A & ~3, (A & ~3) + P + 4) for P positions a lane, A < value_bytes -- at most P bytes past
+// value_bytes, 8 as memo_sweep_runs.hip is built.
+// The minima are staged as a byte per position in a buffer that is freed before the call returns: the write kernel that reads them
+// takes 0.04 ms on 10^8 positions, a second run of runs_mark_kernel in their place would take its 0.38 ms.  Nothing built (out.p3
+// stays NULL, MEMO_OK): more runs than a grid holds, values past 2^32 bytes.  Queued on `st`, waited for twice (the runs decide the
+// allocation).
 int run_view_copy(int device, const BuiltView &dec, uint64_t nb, int64_t bbase, int64_t first_start, int64_t last_start, int km1,
                   hipStream_t st, BuiltView &out, int64_t *first_bucket, uint64_t *value_bytes_out) {
     out = BuiltView();
